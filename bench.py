@@ -200,6 +200,34 @@ class Workload:
         self.raster = None
 
 
+DUMP_SAMPLE = 65536          # --dump-outputs: Gaussians in the fixed sample of the per-Gaussian arrays
+DUMP_IMAGE_FLOATS = 8 << 20  # ... and the most image values written (32 MB); a larger image keeps every k-th row
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs: what a caller of the timed path received in the LAST timed step, as float32 .npy files -- the image, and
+    radii + every input gradient on a fixed, seeded sample of DUMP_SAMPLE Gaussians (the whole SH gradient of C2 alone is 192 MB;
+    gaussian_index.npy holds the sample, exactly, in float64).  An image of more than DUMP_IMAGE_FLOATS values (C4) keeps every k-th
+    row (color_row_index.npy).  Under 64 MB in all.  Two builds run with the same arguments see identical inputs."""
+    os.makedirs(out_dir, exist_ok=True)
+    color = wl.state["color"]
+    H = color.shape[1]
+    rows = torch.arange(0, H, -(-color.numel() // DUMP_IMAGE_FLOATS), device=color.device)
+    P = wl.means3D.shape[0]
+    idx = np.sort(np.random.default_rng(0).choice(P, size=min(P, DUMP_SAMPLE), replace=False)) if P > DUMP_SAMPLE else np.arange(P)
+    idx_t = torch.from_numpy(idx).to(wl.dev)
+    arrays = {"color": color if rows.numel() == H else color.index_select(1, rows), "gaussian_index": torch.from_numpy(idx.astype(np.float64)),
+              "radii": wl.state["radii"].index_select(0, idx_t)}
+    if rows.numel() != H:
+        arrays["color_row_index"] = rows.double()
+    for name, x in zip(("means3D", "means2D", "opacity", "shs", "scales", "rotations"), wl.tensors()):
+        if x is not None and x.grad is not None:
+            arrays["dL_d" + name] = x.grad.index_select(0, idx_t)
+    for name, a in arrays.items():
+        a = a.detach().cpu()
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy() if a.dtype == torch.float64 else a.float().numpy())
+
+
 def timed_region(wl, steps, warmup, prewarm_seconds, barrier, per_step=False):
     """W untimed warm-up steps, then EXACTLY `steps` steps between two barriers (+ device synchronisation).  Returns wall
     seconds, the library's per-stage hipEvent means over the region, and the per-step intervals between hipEvents recorded on
@@ -770,6 +798,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the image, radii and input gradients of the last timed step to DIR/<name>.npy (float32; "
+                         "per-Gaussian arrays on a fixed, seeded sample of Gaussians; under 64 MB)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="C2", choices=["C1", "C2", "C3", "C4", "C5", "L1", "C2L", "C2H"])
     ap.add_argument("--variant", default="full", choices=["full", "min"])
@@ -801,6 +832,8 @@ def main():
                     help="self-test of the N > 1 code path on a box with ONE GPU: every rank uses cuda:0 and the process group is gloo (host-staged "
                          "exchange); the numbers mean nothing")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     t_start = time.perf_counter()
 
     # stdout carries exactly ONE line, the result of rank 0.  Libraries write there too (RCCL prints a five-line version
@@ -981,6 +1014,8 @@ def main():
                 if rank == 0:
                     out["tile_shard"] = {"error": repr(ex)[:300]}
             watchdog.cancel()
+    if args.dump_outputs and rank == 0 and wl is not None:
+        dump_outputs(wl, args.dump_outputs)
     side = None
     if wl is not None:
         scene, sdict, es, gy = wl.scene, wl.sdict, wl.es, wl.gy

@@ -103,3 +103,37 @@ def test_bench_prints_one_bounded_line_at_n1():
     _check_line(d, lines[0])
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
     assert "[bench detail] {" in p.stderr
+
+
+def test_dump_outputs_writes_the_last_step_within_the_cap(tmp_path):
+    """--dump-outputs: float32/float64 .npy files only, under 64 MB for a C4-sized frame, the per-Gaussian
+    arrays on the same fixed sample from run to run, the image rows of an oversized frame subsampled with their index written."""
+    import types
+
+    import numpy as np
+    import torch
+
+    P, H, W = 200_000, 2160, 3840
+    leaves = [torch.zeros(P, 3), torch.zeros(P, 3), torch.zeros(P, 1), torch.zeros(P, 16, 3), torch.zeros(P, 3), torch.zeros(P, 4)]
+    for i, x in enumerate(leaves):
+        x.grad = torch.full_like(x, float(i + 1))
+    color = torch.arange(H, dtype=torch.float32).view(1, H, 1).expand(3, H, W).contiguous()
+    radii = torch.arange(P, dtype=torch.int32)
+    wl = types.SimpleNamespace(state={"color": color, "radii": radii}, means3D=leaves[0], dev=torch.device("cpu"),
+                               tensors=lambda: tuple(leaves))
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        bench.dump_outputs(wl, str(d))
+        runs.append({f.name: np.load(f) for f in d.iterdir()})
+        assert sum(f.stat().st_size for f in d.iterdir()) < 64 << 20
+    a, b = runs
+    assert a.keys() == b.keys() == {"color.npy", "color_row_index.npy", "gaussian_index.npy", "radii.npy", "dL_dmeans3D.npy", "dL_dmeans2D.npy",
+                                    "dL_dopacity.npy", "dL_dshs.npy", "dL_dscales.npy", "dL_drotations.npy"}
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    idx = a["gaussian_index.npy"].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE and np.array_equal(a["radii.npy"], idx.astype(np.float32))
+    assert a["dL_dshs.npy"].shape == (bench.DUMP_SAMPLE, 16, 3) and np.all(a["dL_dshs.npy"] == 4.0)
+    rows = a["color_row_index.npy"].astype(np.int64)
+    assert np.array_equal(a["color.npy"][0, :, 0], rows.astype(np.float32)) and a["color.npy"].size <= bench.DUMP_IMAGE_FLOATS
