@@ -53,14 +53,7 @@ struct RenderArgs {
 // ones and halve the log); a tile whose list is longer than LOG_MAX_LIST is flagged like a log overflow.
 typedef uint16_t log_t;
 constexpr int LOG_MAX_LIST = 65535;
-#ifndef STP_LOG_PACK
-#define STP_LOG_PACK 0 // 1: two records per 32-bit store, layout [tile][wave][record / 2][lane] of u32 (measured in round 2, see profiles/EXPERIMENTS.md;
-                       // written for the [record][lane] layout of rounds 1-5 and not carried over to the blocked layout)
-#endif
-#if STP_LOG_PACK
-#error "STP_LOG_PACK addressed the [record][lane] log of rounds 1-5; the blocked layout (LOG_BLOCK) keeps a lane's records side by side already"
-#endif
-// Depth of the log = records per pixel it can hold (2 B each; + one spare row, STP_LOG_UNCOND): a RUN-TIME value since round 4
+// Depth of the log = records per pixel it can hold (2 B each; + spare rows, see below): a RUN-TIME value since round 4
 // (RenderArgs::log_depth), chosen per frame by the host from the blends per pixel the previous recording forwards of the same kind
 // needed (stp_api.hip: log_depth_for) -- C2 blends at most 114 entries per pixel, C3 155, C5 195 (profiles/r03_log_depth_stats.txt), so
 // one fixed depth either wastes memory or sends tiles to the re-sorting fallback, and ONE such tile costs 1.25 ms (profiles/r04_log_depth_ab.txt).
@@ -69,11 +62,6 @@ constexpr int LOG_MAX_LIST = 65535;
 #define STP_LOG_DEPTH 192
 #endif
 constexpr int BLEND_LOG_DEPTH = STP_LOG_DEPTH, BLEND_LOG_DEPTH_MIN = 32, BLEND_LOG_DEPTH_MAX = 512;
-#ifndef STP_LOG_UNCOND
-#define STP_LOG_UNCOND 1 // 1: the hierarchical recording forward stores a record in EVERY head step, without a branch -- a step that does
-                         // not blend writes into the slot of the lane's next record, which the next blend overwrites -- and only the
-                         // cursor's advance is conditional.  Needs one spare row per wave for the stores behind the last record.
-#endif
 // Layout of one wave's slice.  TWO layouts since round 6, by sort mode (log_blocked()):
 //   rows    [record][lane]                 hierarchical mode (rounds 1-5: every mode).  Its lanes blend nearly in step: a store instruction
 //                                          of the wave fills (most of) ONE 128-byte row.
@@ -89,38 +77,30 @@ constexpr int BLEND_LOG_DEPTH = STP_LOG_DEPTH, BLEND_LOG_DEPTH_MIN = 32, BLEND_L
 // MEASURED the other way round too (one box, alternating, profiles/r06_experiments/log_layout_ab.txt): blocked in the hierarchical kernel costs
 // three more address instructions per head step and eight lines per store instead of one -- C2-full forward 0.861 -> 0.884 ms, C5 unchanged,
 // replay +1 % everywhere: rows stay there.  The replay reads record k of lane l through the same function (template argument by mode).
-// A slice holds depth records per lane (a multiple of 8) + 8 spare rows (the hierarchical kernel's unconditional stores behind the last
-// record land in the first of them).
-#ifndef STP_LOG_BLOCK
-#define STP_LOG_BLOCK 4 // MEASURED (one box, alternating, C3 forward / replay ms): 2: 2.237 / 1.554, 4: 2.135 / 1.544, 8: 2.162 / 1.561, 16: 2.39 / 1.66, 32: 3.08 / 1.86
-#endif
-constexpr int LOG_BLOCK = STP_LOG_BLOCK;                       // blocked layout: records of one lane side by side
-static_assert(LOG_BLOCK == 2 || LOG_BLOCK == 4 || LOG_BLOCK == 8 || LOG_BLOCK == 16 || LOG_BLOCK == 32, "blocks of 2 .. 32 two-byte records");
-constexpr int LOG_PIECE_SHIFT = LOG_BLOCK == 2 ? 2 : LOG_BLOCK == 4 ? 3 : LOG_BLOCK == 8 ? 4 : LOG_BLOCK == 16 ? 5 : 6; // a lane's piece of a block starts at lane << LOG_PIECE_SHIFT
-constexpr int BLEND_LOG_SPARE = LOG_BLOCK < 8 ? 8 : LOG_BLOCK;                     // record rows (64 records = 128 B) of one wave's slice = depth + BLEND_LOG_SPARE
+// A slice holds depth records per lane (a multiple of 8) + 8 spare rows (the hierarchical kernel stores a record in every head step, without
+// a branch: its stores behind the last record land in the first of them).
+// blocked layout: records of one lane side by side.  MEASURED (one box, alternating, C3 forward / replay ms): 2: 2.237 / 1.554, 4: 2.135 / 1.544,
+// 8: 2.162 / 1.561, 16: 2.39 / 1.66, 32: 3.08 / 1.86
+constexpr int LOG_BLOCK = 4;
+constexpr int LOG_PIECE_SHIFT = 3;  // a lane's 8-byte piece of a block starts at lane << LOG_PIECE_SHIFT
+constexpr int BLEND_LOG_SPARE = 8;  // record rows (64 records = 128 B) of one wave's slice = depth + BLEND_LOG_SPARE
 __host__ __device__ __forceinline__ size_t log_wave_bytes(int depth) { return (size_t)(depth + BLEND_LOG_SPARE) * 64 * sizeof(uint16_t); }
 __device__ __forceinline__ char* log_wave_slice(uint32_t* blend_log, int tile, int wave, int depth)
 {
     return reinterpret_cast<char*>(blend_log) + (size_t)(tile * 4 + wave) * log_wave_bytes(depth);
 }
 inline bool log_blocked(const StpSettings& s) { return s.sort_mode == 2; } // (MODE_KBUFFER, stp_internal.h)
-#ifndef STP_LOG_LAYOUT
-#define STP_LOG_LAYOUT 0 // A/B builds: 1 = rows everywhere (rounds 1-5), 2 = blocked everywhere
-#endif
 // byte offset, inside the wave's slice, of record k of the lane whose blocked piece starts at lane16 = 16 * lane; j2 = 2 * k (what the
 // recording forwards keep as their cursor).  Blocked: ((j2 << 6) & ~(block bytes - 1)) | piece | (j2 & (piece bytes - 2)) -- v_lshlrev, v_and_or, v_and_or.
 template <bool BLOCKED> __device__ __forceinline__ uint32_t log_record_offset(uint32_t j2, uint32_t lane16) // lane16 = lane << LOG_PIECE_SHIFT
 {
-    if constexpr ((BLOCKED && STP_LOG_LAYOUT != 1) || STP_LOG_LAYOUT == 2) return (((j2 << 6) & ~(128u * LOG_BLOCK - 1u)) | lane16) | (j2 & (2u * LOG_BLOCK - 2u));
+    if constexpr (BLOCKED) return (((j2 << 6) & ~(128u * LOG_BLOCK - 1u)) | lane16) | (j2 & (2u * LOG_BLOCK - 2u));
     else return (j2 << 6) | (lane16 >> (LOG_PIECE_SHIFT - 1));
 }
 // The k-buffer forwards' log cursor (blocked layout).  A lane's four consecutive records are ONE 8-byte piece: they are collected in two registers -- a
 // 64-bit shift register, the newest record enters at the top -- and stored as a whole piece when the fourth has arrived: a quarter of the store
 // instructions, every one a complete piece, a 128-byte line complete after sixteen of them.  MEASURED (round 6, one box, alternating, C3): forward
 // 2.02-2.11 -> 1.91-1.94 ms, 1.78 -> 1.24 GB written per launch (2-byte stores from the blending lanes: the line of a piece was dirtied four times).
-#ifndef STP_KB_LOG_PIECES
-#define STP_KB_LOG_PIECES (STP_LOG_BLOCK == 4 && STP_LOG_LAYOUT != 1)
-#endif
 struct BlockedLogCursor {
     char* wave;          // the wave's slice
     uint32_t cap2;       // 2 * depth: cursor of the first record that does not fit
@@ -129,27 +109,21 @@ struct BlockedLogCursor {
     uint32_t lo = 0u, hi = 0u;
     __device__ __forceinline__ void append(bool upd, int pay)
     {
-#if STP_KB_LOG_PIECES
         if (upd) {
             lo = __builtin_amdgcn_alignbit(hi, lo, 16);            // {hi, lo} >> 16
             hi = __builtin_amdgcn_alignbit((uint32_t)pay, hi, 16); // ... and the record into the top 16 bits
             if ((j2 & 6u) == 6u && j2 < cap2) *reinterpret_cast<uint2*>(wave + log_record_offset<true>(j2 & ~6u, piece)) = make_uint2(lo, hi);
         }
-#else
-        if (upd && j2 < cap2) *reinterpret_cast<log_t*>(wave + log_record_offset<true>(j2, piece)) = (log_t)pay;
-#endif
         j2 += upd ? 2u : 0u;
     }
     __device__ __forceinline__ int records() const { return (int)(j2 >> 1); }
     __device__ __forceinline__ void flush() // the last, incomplete piece: its records sit at the TOP of the shift register
     {
-#if STP_KB_LOG_PIECES
         const uint32_t have = (j2 >> 1) & 3u;
         if (have != 0u && (j2 & ~6u) < cap2) { // (the piece starts below the cap: depths are multiples of eight, a piece never straddles it)
             const unsigned long long acc = ((((unsigned long long)hi) << 32) | lo) >> (16u * (4u - have));
             *reinterpret_cast<uint2*>(wave + log_record_offset<true>(j2 & ~6u, piece)) = make_uint2((uint32_t)acc, (uint32_t)(acc >> 32));
         }
-#endif
     }
 };
 

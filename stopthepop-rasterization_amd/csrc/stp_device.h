@@ -274,41 +274,6 @@ template <int I, bool FAST = false> __device__ __forceinline__ float depth_along
     return num * rcp;
 }
 
-// ---- the same contraction on the MATRIX pipe -----------------------------------------------------------------------------
-// v_mfma_f32_4x4x1_16b_f32 is sixteen independent 4x4 outer products D[r][j] = A[r] * B[j] + C[r][j], one block per aligned
-// group of four lanes: lane (quad b, j) supplies A = "its" row value and B = its column value and receives, in the four
-// registers of D, row r = 0..3 of ITS column -- i.e. with A = the record word that lane r of the quad fetched and B = my pixel's
-// ray component, D[r] = (entry r's word) * (my ray component) + C[r]: the quad broadcast and the multiply-add of
-// depth_along_ray_quad_ent() for all four candidates of a head group in ONE instruction that issues beside the VALU stream.
-// Every element is an fmaf (one rounding; tools/mfma_probe.hip checks layout and bits on the device), and the three chained
-// instructions of a dot product are exactly fma(c, z, fma(b, y, a * x)) -- the canonical order of depth_along_ray().
-typedef float stp_f4 __attribute__((ext_vector_type(4)));
-struct QuadDepthTerms { stp_f4 a0, a1, a2, num; }; // [r]: candidate r of the quad, at my pixel
-__device__ __forceinline__ QuadDepthTerms depth_terms_quad_mfma(float4 A, float4 B, float4 C, float3 v)
-{
-    const stp_f4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-    QuadDepthTerms t;
-    t.a0 = __builtin_amdgcn_mfma_f32_4x4x1f32(A.x, v.x, z, 0, 0, 0);
-    t.a1 = __builtin_amdgcn_mfma_f32_4x4x1f32(A.y, v.x, z, 0, 0, 0);
-    t.a2 = __builtin_amdgcn_mfma_f32_4x4x1f32(A.z, v.x, z, 0, 0, 0);
-    t.num = __builtin_amdgcn_mfma_f32_4x4x1f32(B.z, v.x, z, 0, 0, 0);
-    t.a0 = __builtin_amdgcn_mfma_f32_4x4x1f32(A.y, v.y, t.a0, 0, 0, 0);
-    t.a1 = __builtin_amdgcn_mfma_f32_4x4x1f32(A.w, v.y, t.a1, 0, 0, 0);
-    t.a2 = __builtin_amdgcn_mfma_f32_4x4x1f32(B.x, v.y, t.a2, 0, 0, 0);
-    t.num = __builtin_amdgcn_mfma_f32_4x4x1f32(B.w, v.y, t.num, 0, 0, 0);
-    t.a0 = __builtin_amdgcn_mfma_f32_4x4x1f32(A.z, v.z, t.a0, 0, 0, 0);
-    t.a1 = __builtin_amdgcn_mfma_f32_4x4x1f32(B.x, v.z, t.a1, 0, 0, 0);
-    t.a2 = __builtin_amdgcn_mfma_f32_4x4x1f32(B.y, v.z, t.a2, 0, 0, 0);
-    t.num = __builtin_amdgcn_mfma_f32_4x4x1f32(C.x, v.z, t.num, 0, 0, 0);
-    return t;
-}
-template <int I, bool FAST = false> __device__ __forceinline__ float depth_from_terms(const QuadDepthTerms& t, float3 v)
-{
-    const float den = fmaf(t.a2[I], v.z, fmaf(t.a1[I], v.y, t.a0[I] * v.x));
-    const float rcp = rcp_ieee<FAST>(fmaxf(0.00001f, den));
-    return t.num[I] * rcp;
-}
-
 // The same for an entry record (BinningState: A = (S00 S01 S02 S11), B = (S12 S22 q.x q.y), C = (q.z . . .)).
 template <int I, bool FAST = false> __device__ __forceinline__ float depth_along_ray_quad_ent(float4 A, float4 B, float4 C, float3 v)
 {

@@ -68,46 +68,12 @@ namespace {
 constexpr int BWD_WIN = STP_BWD_WIN;   // slots of the workgroup's on-chip gradient window (power of two, >= 256)
 constexpr int BWD_RING = STP_BWD_RING; // list positions whose Gaussian id / slot the workgroup keeps in LDS (power of two)
 
-#ifndef STP_FRESH_NOCULL
-#define STP_FRESH_NOCULL 0 // 1: the fresh lane views also without 4x4 culling (measured: see STP_FWD_WAVES)
-#endif
 #ifndef STP_FIFO_GROUPS
 #define STP_FIFO_GROUPS 4
 #endif
 constexpr int FIFO_GROUPS = STP_FIFO_GROUPS; // emitted-but-not-yet-consumed groups of 16 a sub-tile may hold (power of two, >= 4)
-#ifndef STP_HEAD_FILTER
-#define STP_HEAD_FILTER 1 // forward passes: quad-level pre-test + FIFO in front of the head level (see filter_push)
-#endif
-#ifndef STP_TAIL_ONE
-#define STP_TAIL_ONE 1 // tail merge: batches in which no sub-tile of the wave keeps more than sixteen candidates rank one candidate per lane only (see merge_batch)
-#endif
-#ifndef STP_TAIL_SEARCH
-#define STP_TAIL_SEARCH 1 // tail merge: old-entry counts by search + histogram instead of all-pairs counting (see merge_batch)
-#endif
 #ifndef STP_HF_CAP
 #define STP_HF_CAP 32
-#endif
-#ifndef STP_HEAD_MFMA
-#define STP_HEAD_MFMA 0 // 1: the head level's depth dot products on the matrix pipe (stp_device.h: depth_terms_quad_mfma)
-#endif
-#if STP_HEAD_MFMA && !STP_IEEE_DEPTH
-#define STP_HEAD_DEPTH(I) depth_from_terms<I, FRCP>(qdt, pix_dir)
-#else
-#define STP_HEAD_DEPTH(I) depth_along_ray_quad_ent<I, FRCP>(eAq, eBq, eCq, pix_dir)
-#endif
-#ifndef STP_HEAD_LDSB
-#define STP_HEAD_LDSB 0 // forward head level: the four candidates' entry records of a group step go through a per-wave LDS slab (lane q writes
-                        // entry q's rows once, every lane of the quad reads candidate I's rows back with a quad-uniform address), so that the
-                        // candidate evaluation's products take PLAIN operands (2.3 cycles) instead of DPP quad_perm operands (4.4 cycles,
-                        // tools/valu_rate_bench.hip).  1: rows A, B, C (Sigma^-1 pack, mean) through LDS -- row A aliased onto the wave's batch
-                        // staging area, so that with STP_FIFO_GROUPS=4 four workgroups per CU still fit -- D (conic, opacity) stays a DPP
-                        // operand; 2: all four rows in a 16 KB slab (three workgroups per CU).  Measured in round 5, logs bit-identical:
-                        // -10 % issue cycles per group step by tools/isa_cost.py and the kernel is SLOWER, +0.7 % at four workgroups per CU
-                        // (0.9123 -> 0.9187 ms), +2.3 .. 3.0 % at three against the same occupancy (profiles/r05_experiments/head_ldsb_ab.txt):
-                        // the write -> read round trip sits in every group step's dependent chain.  Off.
-#endif
-#ifndef STP_LDS_PAD
-#define STP_LDS_PAD 0 // bytes of unused LDS per workgroup (occupancy experiments)
 #endif
 constexpr int HF_CAP = STP_HF_CAP; // head-level FIFO: list positions a quad may hold (power of two, >= 32: one consumption round adds up to 16)
 
@@ -134,9 +100,7 @@ struct HierLds { // dynamic-LDS carve, per workgroup (16 sub-tiles)
     static __host__ __device__ constexpr size_t ring(int MID) { return dirty(MID) + (size_t)BWD_WIN * 4; }
     static __host__ __device__ constexpr size_t ring_cs(int MID) { return ring(MID) + (size_t)BWD_RING * 4; }
     static __host__ __device__ constexpr size_t wave_mask(int MID) { return ring_cs(MID) + (size_t)BWD_RING * 4; }
-    // forward passes, STP_HEAD_LDSB: float4 [4 waves][4 rows A..D][64 lanes] -- the entry records of the group step in flight
-    static __host__ __device__ constexpr size_t slab(int MID) { return hfifo(MID) + 64 * (size_t)HF_CAP * 4; }
-    static __host__ __device__ constexpr size_t total(int MID, int mode) { return mode == 1 ? wave_mask(MID) + 16 : slab(MID) + (STP_HEAD_LDSB == 0 ? 0 : STP_HEAD_LDSB == 1 ? 4 * 2 * 64 * 16 : 4 * 4 * 64 * 16) + STP_LDS_PAD; }
+    static __host__ __device__ constexpr size_t total(int MID, int mode) { return mode == 1 ? wave_mask(MID) + 16 : hfifo(MID) + 64 * (size_t)HF_CAP * 4; }
 };
 
 __device__ __forceinline__ int hier_remap_tile(int wg, int n_wg)
@@ -157,7 +121,7 @@ template <int HEAD, int MID, bool CULL, int MODE, bool FRCP>
 __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD == 4 && MID == 8 && FRCP) ? STP_FWD_WAVES : 4) render_hier_kernel(const RenderArgs a)
 {
     // (the mid level's lane views from a fresh lane id: only where the register budget needs it -- five waves per SIMD WITH 4x4 culling, see STP_FWD_WAVES)
-    constexpr bool FRESH_QUAD = MODE != MODE_BWD && HEAD == 4 && MID == 8 && FRCP && STP_FWD_WAVES >= 5 && (CULL || STP_FRESH_NOCULL);
+    constexpr bool FRESH_QUAD = MODE != MODE_BWD && HEAD == 4 && MID == 8 && FRCP && STP_FWD_WAVES >= 5 && CULL;
     constexpr bool BACKWARD = MODE == MODE_BWD;
     constexpr bool RECORD = MODE == MODE_FWD_RECORD;
     constexpr bool DEPTHVIZ = MODE == MODE_FWD_DEPTH; // accumulate depth * alpha * T instead of colour (reference :1005-1008, stopthepop_common.cuh:264-282)
@@ -326,30 +290,11 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     const uint32_t log_lane16 = (uint32_t)lane << LOG_PIECE_SHIFT;
     uint32_t log_j2 = 0u;
     auto log_append = [&](bool upd, int pay) __attribute__((always_inline)) {
-#if STP_LOG_UNCOND == 2
-        // the store from the lanes that blend ONLY, without a branch: the exec mask is narrowed around ONE instruction by hand (the compiler's
-        // own `if` brings an s_cbranch_execz and a split loop body: C2-full forward 0.88 -> 1.41 ms, C5 2.03 -> 3.33)
-        {
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(upd && log_j2 < log_cap2);
-            const uint32_t off = log_record_offset<false>(log_j2, log_lane16);
-            unsigned long long saved;
-            asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_short %2, %3, %4\n\ts_mov_b64 exec, %0"
-                         : "=&s"(saved) : "s"(m), "v"(off), "v"(pay), "s"(log_wave) : "memory");
-        }
-        log_j2 += upd ? 2u : 0u;
-        return;
-#elif STP_LOG_UNCOND
         // no branch: the record goes to the lane's current slot whether or not the step blends (a later blend overwrites it; behind
-        // the log's depth everything lands in the first spare row), only the cursor's advance depends on `upd`
+        // the log's depth everything lands in the first spare row), only the cursor's advance depends on `upd`.  (A conditional store
+        // brings an s_cbranch_execz and a split loop body: C2-full forward 0.88 -> 1.41 ms; non-temporal stores 1.9 -> 3.1 ms, the
+        // partial lines then go to HBM one by one.)
         *reinterpret_cast<log_t*>(log_wave + log_record_offset<false>(min(log_j2, log_cap2), log_lane16)) = (log_t)pay;
-        log_j2 += upd ? 2u : 0u;
-        return;
-#endif
-#if !(defined(STP_ABLATE) && STP_ABLATE == 5) // (5: timing experiment without the log stores; the backward then reads garbage)
-        if (upd && log_j2 < log_cap2) {
-            *reinterpret_cast<log_t*>(log_wave + log_record_offset<false>(log_j2, log_lane16)) = (log_t)pay; // (non-temporal stores: 1.9 -> 3.1 ms, the partial lines then go to HBM one by one)
-        }
-#endif
         log_j2 += upd ? 2u : 0u;
     };
     auto log_records = [&]() __attribute__((always_inline)) -> int { return (int)(log_j2 >> 1); };
@@ -406,10 +351,6 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         float g[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) g[k] = g_in[k];
-#if defined(STP_ABLATE) && STP_ABLATE == 4
-        if (g[0] == 1.2345f) atomicAdd(grad_slot(a, id, 0), g[1] + g[2] + g[3] + g[4] + g[5] + g[6] + g[7] + g[8]); // keep the terms live
-        return; // ablation: no accumulation (wrong results)
-#endif
         const unsigned long long here = __ballot(1);
         bool mine = true; // do I write to LDS / memory?
         if (((here >> (lane & ~3)) & 0xFull) == 0xFull) {
@@ -565,63 +506,20 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
             pf = min(max(fid, 0), list_last); // (clamped from above too: depth keys that are NaN -- an overflowing Sigma^-1 -- break the counting ranks, and a stale slot must not become a wild address)
             eAq = ent_row(eA, pf); eBq = ent_row(eB, pf); eCq = ent_row(eC, pf); eDq = ent_row(eD, pf);
         }
-        // (STP_HEAD_LDSB == 0: unused, the compiler drops them)
-#if STP_HEAD_LDSB == 1
-        // compact layout (four workgroups per CU still fit): row A lives in the wave's batch-staging area, which is dead between two batches
-        // (lanes 0..31 in its keys, 512 B, lanes 32..63 in its payloads), rows B and C in a slab of 2 KB per wave
-        char* const rowA = smem + (lane < 32 ? HierLds::new_key() : HierLds::new_id() - 512) + (size_t)w * 512;
-        char* const slab_a = rowA + ((uint32_t)lane << 4);
-        const char* const slab_ra = rowA + ((uint32_t)(lane & ~3) << 4);
-        char* const slab_w = smem + HierLds::slab(MID) + (size_t)w * 2048 + ((uint32_t)lane << 4) - 1024;        // (+ 1024: my slot of row B, + 2048: of row C)
-        const char* const slab_r = smem + HierLds::slab(MID) + (size_t)w * 2048 + ((uint32_t)(lane & ~3) << 4) - 1024;
-#else
-        char* const slab_w = smem + HierLds::slab(MID) + (size_t)w * 4096 + ((uint32_t)lane << 4);        // my slot of row A (rows are 1 KB apart)
-        const char* const slab_r = smem + HierLds::slab(MID) + (size_t)w * 4096 + ((uint32_t)(lane & ~3) << 4); // my quad's slot 0 of row A
-        char* const slab_a = slab_w;
-        const char* const slab_ra = slab_r;
-#endif
-#if STP_HEAD_MFMA
-        QuadDepthTerms qdt{};
-        if constexpr (!BACKWARD && !STP_IEEE_DEPTH) qdt = depth_terms_quad_mfma(eAq, eBq, eCq, pix_dir); // all four candidates' dot products, on the matrix pipe
-#endif
+// (candidate I's rows as DPP quad_perm operands: staging them through a per-wave LDS slab for plain operands cuts issue cycles but puts
+// an LDS round trip into every group step's chain -- measured slower, profiles/EXPERIMENTS.md, round 5)
 #define STP_FEED(I)                                                                                                     \
     {                                                                                                                   \
         /* pop before the candidate is looked at */                                                                    \
         if constexpr (BACKWARD) { if (head.num >= HEAD) blend_front(); }                                                \
         else pop_forward();                                                                                             \
         const int cid = quad_bcast_i<I>(BACKWARD ? fid : pf);                                                           \
-        if constexpr (!BACKWARD && STP_HEAD_LDSB != 0) { /* candidate I's rows come back from the wave's LDS slab: plain operands */ \
-            if constexpr (I == 0) { /* (after the pop: the wait for the four loads stays behind it) */                  \
-                eDq.w = fid < 0 ? 0.0f : eDq.w;                                                                         \
-                wave_sync(); /* the previous group's reads are done */                                                  \
-                *reinterpret_cast<float4*>(slab_a) = eAq; *reinterpret_cast<float4*>(slab_w + 1024) = eBq;              \
-                *reinterpret_cast<float4*>(slab_w + 2048) = eCq;                                                        \
-                if constexpr (STP_HEAD_LDSB >= 2) *reinterpret_cast<float4*>(slab_w + 3072) = eDq;                      \
-                else dpp_hazard_guard_on(eDq.w);                                                                        \
-                wave_sync();                                                                                            \
-            } else if constexpr (STP_HEAD_LDSB < 2) dpp_hazard_guard();                                                 \
-            const float4 rA = *reinterpret_cast<const float4*>(slab_ra + 16 * I);                                       \
-            const float4 rB = *reinterpret_cast<const float4*>(slab_r + 16 * I + 1024);                                 \
-            const float4 rC = *reinterpret_cast<const float4*>(slab_r + 16 * I + 2048);                                 \
-            const float depth = depth_along_ray_ent<FRCP>(rA, rB, rC, pix_dir);                                         \
-            const float dx = rC.y - (float)px, dy = rC.z - (float)py;                                                   \
-            float power, alpha;                                                                                         \
-            if constexpr (STP_HEAD_LDSB >= 2) {                                                                         \
-                const float4 rD = *reinterpret_cast<const float4*>(slab_r + 16 * I + 3072);                             \
-                power = blend_power(dx, dy, rD);                                                                        \
-                alpha = fminf(0.99f, rD.w * exp_blend(power));                                                          \
-            } else {                                                                                                    \
-                power = blend_power_quad<I>(dx, dy, eDq);                                                               \
-                alpha = min_099(quad_mul<I>(eDq.w, exp_blend(power)));                                                  \
-            }                                                                                                           \
-            const bool pass = active && !(depth < 0.0f) && !(power > 0.0f) && !(alpha < ALPHA_THRESHOLD);      \
-            head.replace_front(pass, pass ? depth : -FLT_MAX, cid, alpha);                                              \
-        } else if constexpr (!BACKWARD) { /* straight-line evaluation, broadcast operands folded into the arithmetic */ \
+        if constexpr (!BACKWARD) { /* straight-line evaluation, broadcast operands folded into the arithmetic */         \
             if constexpr (I == 0) { /* (after the pop: the wait for the four loads stays behind it) */                  \
                 eDq.w = fid < 0 ? 0.0f : eDq.w;                                                                         \
                 dpp_hazard_guard_on(eDq.w); /* a VALU result that DPP operands read below */                            \
             } else dpp_hazard_guard();                                                                                  \
-            const float depth = STP_HEAD_DEPTH(I);                                                                      \
+            const float depth = depth_along_ray_quad_ent<I, FRCP>(eAq, eBq, eCq, pix_dir);                              \
             const float dx = quad_sub<I>(eCq.y, (float)px), dy = quad_sub<I>(eCq.z, (float)py);                         \
             const float power = blend_power_quad<I>(dx, dy, eDq);                                                       \
             const float alpha = min_099(quad_mul<I>(eDq.w, exp_blend(power)));                                          \
@@ -656,7 +554,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     // order, in the quad's FIFO.
     // Head steps then run on groups of four parked candidates with all 64 lanes of the wave taking part, as often as
     // the fullest quad of the wave needs; the exact per-pixel tests are unchanged.
-    constexpr bool HEAD_FILTER = !BACKWARD && (STP_HEAD_FILTER != 0);
+    constexpr bool HEAD_FILTER = !BACKWARD;
     int hf_head = 0, hf_cnt = 0; // (quad-uniform)
     constexpr int HF_REJECT = 0x40000000; // payload flag in the mid queue: no pixel of this quad can blend the entry (a pad, -1, carries it too)
     // lane-local: can the entry with record rows C (mean in .yz) and D (conic, opacity) reach 1/255 at any of the four
@@ -722,23 +620,15 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         feed4_from(fid);
         return true;
     };
-#ifndef STP_HEAD_UNROLL
-#define STP_HEAD_UNROLL 2
-#endif
     auto head_rounds = [&](const bool force) __attribute__((always_inline)) {
 #pragma unroll 1
         for (;;) {
             if (!head_round(force)) break;
-#if STP_HEAD_UNROLL >= 2
             if (!head_round(force)) break; // (a second copy of the group step: half as many register shuffles at the loop's back edge)
-#endif
         }
     };
     // feed the four front mid entries mk/mi[0..3] to the quad's four head queues (reference :421-536).
     auto feed4 = [&](const QuadView& qv) __attribute__((always_inline)) {
-#if defined(STP_ABLATE) && STP_ABLATE == 1
-        return; // ablation: no head level
-#endif
         if constexpr (HEAD_FILTER) filter_push(qv);
         else {
             const unsigned long long act = __ballot(active);
@@ -828,9 +718,6 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     // Push up to 16 entries (payloads src[0..cnt)) through the mid level as groups of 4; a short last group is
     // padded with (FLT_MAX,-1) (only while draining), cnt == 0 emits one all-pad group that flushes the mid queue.
     auto process16 = [&](const int* src, int cnt) __attribute__((always_inline)) {
-#if defined(STP_ABLATE) && STP_ABLATE == 2
-        mid_pending = 0; return; // ablation: tail level only (wrong results)
-#endif
         for (int k = 0; k < 4; k++) {
             if (4 * k >= cnt && !(k == 0 && cnt == 0)) break;
             STP_QUAD_VIEW(FRESH_QUAD ? fresh_lane() : lane)
@@ -890,7 +777,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
             float4 enC = make_float4(0, 0, 0, 0);
             if constexpr (!BACKWARD) enC = ent_row(eC, ep); // unit-stride loads: the 32 lanes of a half read 32 consecutive records
             if constexpr (CULL) { // reference :722-743
-                if constexpr (!BACKWARD && STP_CULL_MASK) {
+                if constexpr (!BACKWARD) {
                     // the sixteen sub-tile decisions of this entry were made by the entry gather (stp_tilesort.hip: subtile_cull_mask,
                     // the same functions on the same operands) and sit in the spare word of its colour record
                     const uint32_t mask = __float_as_uint(*reinterpret_cast<const float*>(reinterpret_cast<const char*>(eF) + ((uint32_t)ep << 4) + 12));
@@ -960,9 +847,6 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     // rank my sub-tile's 32 staged candidates and merge them into the sorted tail (old before new on
     // equal keys; candidates among themselves by list position).  Reference :774-825, :24-70, :158-192.
     auto merge_batch = [&](int batch_base) __attribute__((always_inline)) { // batch_base: list index of the batch's first entry
-#if defined(STP_ABLATE) && STP_ABLATE == 3
-        n_tail = 0; return; // ablation: staging only (wrong results)
-#endif
         const int lane_m = fresh_lane();
         const int s_m = lane_m >> 4;
         const int n_new = __popc((unsigned int)(((s_m & 1) ? balB : balA) >> (32 * (s_m >> 1)))); // my sub-tile's survivors
@@ -972,7 +856,6 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         const bool va = x < n_new, vb = x + 16 < n_new;     // my (up to) two new entries
         float ka = va ? nk[x] : 0.0f, kb = vb ? nk[x + 16] : 0.0f;
         int ia = va ? ni[x] : -1, ib = vb ? ni[x + 16] : -1;
-#if STP_TAIL_SEARCH
         // Counting every candidate against every old entry and every old entry against every candidate costs two slow VALU
         // instructions per pair -- 2 x (32 + 32) pairs per lane at full queues, a quarter of the kernel.  The old entries are
         // SORTED, so (a) a candidate's number of old entries in front of it (c = #old <= key) is a six-probe search of the
@@ -988,7 +871,6 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         int ca = 0, cb = 0; // upper bounds in tk[0..32): five halving probes over slots 0..30, then slot 31
         // (strict compares only: candidates with EQUAL keys -- a handful of batches per frame -- collide on one rank, which
         // is how they are found below; such a batch is redone with the reference's network anyway)
-#if STP_TAIL_ONE
         // A batch leaves a sub-tile eleven candidates on average (C2-full): where no row of the wave has more than sixteen, no lane holds a
         // second candidate and everything computed for it -- half of the counting loop's compares, half of the probes -- is dropped.
         if (__all(n_new <= 16)) { // (wave-uniform; rows without candidates have left)
@@ -997,9 +879,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
 #pragma unroll
             for (int step = 16; step >= 1; step >>= 1) ca += tk[ca + step - 1] <= ka ? step : 0;
             ca += (int)(last <= ka);
-        } else
-#endif
-        {
+        } else {
             for (int j = 0; j < n_new; j++) {
                 const float kj = nk[j];
                 ra += (int)(kj < ka);
@@ -1041,36 +921,6 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         if (ovb) { tk[pb_old] = okb; ti[pb_old] = oib; }
         n_tail = n_old + n_new;
         wave_sync();
-#else
-        const bool ova = x < n_old, ovb = x + 16 < n_old;   // my (up to) two old entries
-        const float oka = tk[x], okb = tk[x + 16];
-        const int oia = ti[x], oib = ti[x + 16];
-        int ra = 0, rb = 0, oa = 0, ob = 0, ca = 0, cb = 0;
-        // (strict compares only: candidates with EQUAL keys -- a handful of batches per frame -- collide on one rank, which
-        // is how they are found below; such a batch is redone with the reference's network anyway)
-        for (int j = 0; j < n_new; j++) {
-            const float kj = nk[j];
-            ra += (int)(kj < ka);
-            rb += (int)(kj < kb);
-            oa += (int)(kj < oka);
-            ob += (int)(kj < okb);
-        }
-        for (int i = 0; i < n_old; i++) {
-            const float ki = tk[i];
-            ca += (int)(ki <= ka);
-            cb += (int)(ki <= kb);
-        }
-        wave_sync(); // all reads done
-        float* const nkw = nk;
-        int* const niw = ni;
-        const int fa = ra + ca, fb = rb + cb, pa_old = x + oa, pb_old = x + 16 + ob;
-        if (va) { tk[fa] = ka; ti[fa] = ia; }
-        if (vb) { tk[fb] = kb; ti[fb] = ib; }
-        if (ova) { tk[pa_old] = oka; ti[pa_old] = oia; }
-        if (ovb) { tk[pb_old] = okb; ti[pb_old] = oib; }
-        n_tail = n_old + n_new;
-        wave_sync();
-#endif
         // Exact ties among the batch's candidates.  The reference sorts the 32 slots of a batch with a Batcher odd-even
         // merge network (:158-192), which is not stable -- where two candidates of a sub-tile have bit-identical depths (a
         // handful of batches per C2 frame) its result depends on the slots the two sit in.  The strict ranks above give

@@ -122,11 +122,6 @@ __global__ void __launch_bounds__(256, kb_waves<WIN>()) render_kbuffer_wave_kern
     const float4* const eF = a.entF + range.x;
     const int list_last = max(total - 1, 0);
     auto ent_row = [&](const float4* base, int pos) __attribute__((always_inline)) -> float4 { // SGPR base + 32-bit offset
-#if defined(STP_KB_ENT_NT) && STP_KB_ENT_NT   // experiment: the entry records as non-temporal loads (they stream through; the log's lines should stay in the L2)
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(reinterpret_cast<const char*>(base) + ((uint32_t)pos << 4)));
-        return make_float4(v.x, v.y, v.z, v.w);
-#endif
         return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + ((uint32_t)pos << 4));
     };
 
@@ -248,24 +243,11 @@ __global__ void __launch_bounds__(256, kb_waves<WIN>()) render_kbuffer_wave_kern
         const int ep = base + e;
         bool keepA = false, keepB = false;
         if (ep < total) {
-#if STP_CULL_MASK
             // (the sixteen sub-tile verdicts of this entry were computed by the entry gather, stp_tilesort.hip: subtile_keep_mask_kbuffer)
             const uint32_t mask = __float_as_uint(*reinterpret_cast<const float*>(reinterpret_cast<const char*>(eF) + ((uint32_t)ep << 4) + 12));
             const uint32_t mine = mask >> (4 * w + 2 * half);
             keepA = (mine & 1u) != 0u;
             keepB = (mine & 2u) != 0u;
-#else
-            const float4 C = ent_row(eC, ep), D = ent_row(eD, ep);
-            const float x0A = sxA - C.y, x0B = sxB - C.y, y0 = syf - C.z;
-            const float pA = min_power_rect(D, x0A, x0A + 3.0f, y0, y0 + 3.0f);
-            const float pB = min_power_rect(D, x0B, x0B + 3.0f, y0, y0 + 3.0f);
-            // rounding of the per-pixel exponent against this one: at most a few ulp of the form's terms, all below T * far^2
-            const float T3 = fabsf(D.x) + fabsf(D.y) + fabsf(D.z);
-            const float fy = fmaxf(fabsf(y0), fabsf(y0 + 3.0f));
-            const float fA = fmaxf(fmaxf(fabsf(x0A), fabsf(x0A + 3.0f)), fy), fB = fmaxf(fmaxf(fabsf(x0B), fabsf(x0B + 3.0f)), fy);
-            keepA = !(D.w * __builtin_amdgcn_exp2f(fmaf(T3 * fA * fA, 2.0e-6f, -pA) * 1.44269502162933349609375f) < ALPHA_THRESHOLD * 0.9999f);
-            keepB = !(D.w * __builtin_amdgcn_exp2f(fmaf(T3 * fB * fB, 2.0e-6f, -pB) * 1.44269502162933349609375f) < ALPHA_THRESHOLD * 0.9999f);
-#endif
         }
         const unsigned long long balA = __ballot(keepA), balB = __ballot(keepB);
         const unsigned int mA = (unsigned int)(balA >> (32 * half)), mB = (unsigned int)(balB >> (32 * half));
@@ -394,26 +376,13 @@ __global__ void __launch_bounds__(256, kb_ring_waves<WIN>()) render_kbuffer_ring
     const float4* const eF = a.entF + range.x;
     const int list_last = max(total - 1, 0);
     auto ent_row = [&](const float4* base, int pos) __attribute__((always_inline)) -> float4 { // SGPR base + 32-bit offset
-#if defined(STP_KB_ENT_NT) && STP_KB_ENT_NT   // experiment: the entry records as non-temporal loads (they stream through; the log's lines should stay in the L2)
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(reinterpret_cast<const char*>(base) + ((uint32_t)pos << 4)));
-        return make_float4(v.x, v.y, v.z, v.w);
-#endif
         return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + ((uint32_t)pos << 4));
     };
 
     // blend log (recording forward): blocked layout, whole pieces from blending lanes only (stp_blend.h: BlockedLogCursor)
     BlockedLogCursor logc{RECORD ? log_wave_slice(a.blend_log, tile, w, a.log_depth) : nullptr, 2u * (uint32_t)a.log_depth, (uint32_t)lane << LOG_PIECE_SHIFT};
     auto log_append = [&](bool upd, int pay) __attribute__((always_inline)) {
-#if defined(STP_KB_LOG_ABLATE) && STP_KB_LOG_ABLATE == 1   // timing experiment (log WRONG): every store of the wave into its first block -- same instructions, few lines
-        *reinterpret_cast<log_t*>(logc.wave + logc.piece) = (log_t)pay; logc.j2 += upd ? 2u : 0u;
-#elif defined(STP_KB_LOG_ABLATE) && STP_KB_LOG_ABLATE == 2 // ... no store at all
-        logc.j2 += upd ? 2u : 0u;
-#elif defined(STP_KB_LOG_ABLATE) && STP_KB_LOG_ABLATE == 4 // ... the unconditional 2-byte store of rounds 4-5 (into the slot of the lane's next record, or the spare block)
-        *reinterpret_cast<log_t*>(logc.wave + log_record_offset<true>(min(logc.j2, logc.cap2), logc.piece)) = (log_t)pay; logc.j2 += upd ? 2u : 0u;
-#else
         logc.append(upd, pay);
-#endif
     };
     auto log_records = [&]() __attribute__((always_inline)) -> int { return logc.records(); };
     auto log_flush = [&]() __attribute__((always_inline)) { logc.flush(); };
@@ -596,15 +565,9 @@ __global__ void __launch_bounds__(256, kb_ring_waves<WIN>()) render_kbuffer_ring
     int* const stA = s_stage + (w * 4 + 2 * half) * 32;
     const int* const st_row = s_stage + (w * 4 + s) * 32;
     const float qxc = (float)(px - (q & 1)) + 0.5f, qyc = (float)(py - (q >> 1)) + 0.5f;
-#ifndef STP_KB_SYNC
-#define STP_KB_SYNC 0 // experiment: the four waves of the tile meet at a workgroup barrier every STP_KB_SYNC entries of the list (every wave the same number
-                      // of times, also one that has left the loop): keeps their reads of the entry records inside one stretch of the list
-#endif
-    int sync_at = 0; // (list position of my next barrier)
 #pragma unroll 1
     for (int base = 0; base < total; base += 32) {
         if (!__any(active)) break;
-        if (STP_KB_SYNC && base >= sync_at) { __builtin_amdgcn_s_barrier(); sync_at += STP_KB_SYNC; }
         const int ep = base + e;
         bool keepA = false, keepB = false;
         if (ep < total) {
@@ -644,7 +607,6 @@ __global__ void __launch_bounds__(256, kb_ring_waves<WIN>()) render_kbuffer_ring
             head_rounds(false);
         }
     }
-    if (STP_KB_SYNC) for (; sync_at < total; sync_at += STP_KB_SYNC) __builtin_amdgcn_s_barrier(); // (the barriers I did not reach: my siblings count on them)
     head_rounds(true);
     // drain: what is left in the window, front first.  Only a pop of a FULL window can be the reference's pop "in front of the next entry"
     if (rn != WIN) cfull = total;
@@ -704,7 +666,7 @@ hipError_t launch_kbuffer_wave(int mode, const FrameParams& f, const RenderArgs&
     *handled = true;
     // windows of 8 .. 16 entries: the ring-in-LDS kernel (STP_KBUFFER=wave keeps the register window for them too)
     static const char* const kb_env = std::getenv("STP_KBUFFER");
-    static const bool ring = !STP_LOG_PACK && !(kb_env && std::strcmp(kb_env, "wave") == 0); // (the ring kernel writes the plain log layout only)
+    static const bool ring = !(kb_env && std::strcmp(kb_env, "wave") == 0);
 #define STP_KBW(WIN) return mode == KBW_RECORD ? launch_kb_win<WIN, KBW_RECORD>(f, a, st) : mode == KBW_DEPTH ? launch_kb_win<WIN, KBW_DEPTH>(f, a, st) : launch_kb_win<WIN, KBW_FWD>(f, a, st)
 #define STP_KBR(WIN) return mode == KBW_RECORD ? launch_kb_ring<WIN, KBW_RECORD>(f, a, st) : mode == KBW_DEPTH ? launch_kb_ring<WIN, KBW_DEPTH>(f, a, st) : launch_kb_ring<WIN, KBW_FWD>(f, a, st)
     if (w <= 1) STP_KBW(1);

@@ -43,7 +43,7 @@ for k in ("list", "keys", "color", "final_T", "n", "flags"):
     print(f"{k:8s} identical: {same}")
 # the log is only defined where records were written: record k of a pixel for k < n (layout [tile][wave][record][lane])
 T = ((sc.W + 15) // 16) * ((sc.H + 15) // 16)
-la, lb = a["log"].view(T, 4, -1, 64), b["log"].view(T, 4, -1, 64)   # (rows per wave: 256, or 257 in a build with STP_LOG_UNCOND)
+la, lb = a["log"].view(T, 4, -1, 64), b["log"].view(T, 4, -1, 64)   # (rows per wave: the log depth plus the spare rows)
 gx = (sc.W + 15) // 16
 py, px = torch.meshgrid(torch.arange(sc.H, device=dev), torch.arange(sc.W, device=dev), indexing="ij")
 tile = (py // 16) * gx + (px // 16)
