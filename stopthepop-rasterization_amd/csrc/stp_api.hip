@@ -754,6 +754,13 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
     static const char* const sort_env = std::getenv("STP_SORT");
     static const bool tile_local_sort = !(sort_env && std::strcmp(sort_env, "radix") == 0);
     static const bool atomic_bin = sort_env && std::strcmp(sort_env, "counters") == 0;
+    // The tile sort + entry gather of lists up to TS_SMALL entries runs inside the hierarchical forward's workgroups, in front of rendering the
+    // tile, instead of in a launch of its own: the render's other workgroups on the CU hide the gather's memory latency.
+    // Not in STP_SORT=counters (segments not in id order), STP_SORT=radix, the k-buffer and GLOBAL modes or the debug depth forward.
+    // STP_FUSED_GATHER=0: the separate launch (read once, like STP_SORT).
+    static const char* const fused_env = std::getenv("STP_FUSED_GATHER");
+    static const bool fused_gather = !(fused_env && fused_env[0] == '0');
+    f.fused_gather = fused_gather && tile_local_sort && !atomic_bin && f.s.sort_mode == MODE_HIER && f.s.debug_visualization != STP_DEBUG_DEPTH ? 1 : 0;
 
     // STP_SCAN=rocprim: the device-wide scan of round 1-2 (rocPRIM inclusive_scan + a one-thread mailbox kernel) instead of the two-level scan
     // folded into preprocess_kernel / duplicate_kernel (read once, like the other path switches)

@@ -155,6 +155,7 @@ struct FrameParams {
     uint32_t* log_need;  // forward: device word the recording kernels report their largest blend count per pixel to (or nullptr)
     uint32_t log_tag;    // ... tagged with 16 bits of the frame's kind
     int split_launch = 0; // this FrameParams describes ONE of the two render launches of a split forward (stp_set_forward_split): no tile order of the whole window
+    int fused_gather = 0; // forward: the hierarchical render kernel sorts and gathers the tiles of up to TS_SMALL entries itself (RenderArgs::fused_gather), tile_sort_gather_kernel only the longer ones
     int wild_cov; // forward, after the status read-back: some visible Gaussian has a Sigma^-1 entry >= 1e36 or not finite (depth keys then take the reciprocal with its domain check)
 };
 

@@ -164,6 +164,18 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
             return;
         }
     }
+    if constexpr (MODE == MODE_FWD || MODE == MODE_FWD_RECORD) {
+        // Fused entry gather (RenderArgs::fused_gather): the workgroup sorts its tile's list and writes keys, list and entry records itself --
+        // what tile_sort_gather_kernel<TS_SMALL> did in a launch of its own in front of this one, whose memory latency lay on the critical
+        // path.  Here the other workgroups on the CU, busy blending, hide it.  The keys take the first 8 KB of the LDS carve, which nothing
+        // holds yet; the hand-off to the render body below is the gather kernel's own between its passes.  Longer lists stay that kernel's.
+        const int n = (int)(range.y - range.x); // (>= 1 here)
+        if (a.fused_gather && n <= TS_SMALL) {
+            tile_sort_gather_lds(a.gather, reinterpret_cast<uint64_t*>(smem), tile_y * a.gx + tile_x, range, n, (int)threadIdx.x);
+            __threadfence_block();
+            __syncthreads();
+        }
+    }
 
     const int st = w * 4 + s;
     // Register budget.  What the TAIL level needs of the lane's identity -- its sub-tile's tail / staging / FIFO areas, its

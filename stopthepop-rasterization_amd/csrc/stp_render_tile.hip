@@ -417,6 +417,10 @@ static RenderArgs make_args(const FrameParams& f, const GeometryState& g, const 
     a.tile_order = (tile_order_used(f) && !counters && !f.split_launch) ? img.tile_cursor + f.gx * f.ty0 : nullptr;
     a.log_depth = img.log_depth; a.log_need = f.log_need; a.log_tag = f.log_tag;
     a.debug_depth = f.s.debug_visualization == STP_DEBUG_DEPTH ? 1 : 0; a.means3D = f.means3D;
+    a.fused_gather = 0; // (launch_render_forward: the hierarchical forwards)
+    a.gather.keys = b.keys; a.gather.point_list = b.point_list; a.gather.gpack = g.gpack; a.gather.features = a.features;
+    a.gather.gx = f.gx; a.gather.cull_mask = subtile_mask_kind(f.s);
+    a.gather.entA = b.entA; a.gather.entB = b.entB; a.gather.entC = b.entC; a.gather.entD = b.entD; a.gather.entF = b.entF;
     return a;
 }
 
@@ -474,6 +478,7 @@ hipError_t launch_render_forward(const FrameParams& f, const GeometryState& g, c
     case MODE_FULL: return launch_full_fwd(f, a, st);
     case MODE_HIER:
         if (a.debug_depth) return launch_hier_dbg(f, a, st, err);
+        a.fused_gather = f.fused_gather; // (the forward and recording forward sort + gather their tiles of up to TS_SMALL entries themselves)
         return uses_blend_log(f.s) ? launch_hier_rec(f, a, st, err) : launch_hier_fwd(f, a, st, err);
     default: if (err) *err = "invalid sort mode"; return hipErrorInvalidValue;
     }

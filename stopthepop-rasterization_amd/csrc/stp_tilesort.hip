@@ -11,8 +11,11 @@
 // another pass over the list to build.  Segments longer than TS_CAP entries are sorted by the workgroup with stable
 // 8-bit counting passes (id bytes first when the segment is not in id order yet, then the four depth bytes) through the
 // otherwise unused unsorted arrays.  Same sorted list, bit for bit.
+// The short-segment path (the bitonic network and the gather behind it) is tile_sort_gather_small() of stp_tilesort.h: the hierarchical forwards
+// run it themselves, in front of rendering the tile (RenderArgs::fused_gather), and this file's SMALL instantiation is then not launched.
 #include "stp_internal.h"
 #include "stp_device.h"
+#include "stp_tilesort.h"
 #include <rocprim/block/block_radix_sort.hpp>
 
 namespace stp {
@@ -22,7 +25,7 @@ namespace {
 // Entries a workgroup sorts in LDS: two instantiations, launched back to back -- SMALL (8 KB of LDS: the latency-bound
 // gather wants many workgroups per CU) takes the tiles with up to TS_SMALL entries and leaves at once on the others,
 // LARGE (32 KB) takes the rest, up to TS_CAP in LDS and beyond that through the counting passes.
-constexpr int TS_SMALL = 1024, TS_CAP = 4096;
+constexpr int TS_CAP = 4096; // (TS_SMALL: stp_tilesort.h)
 #ifndef STP_GATHER_WAVES
 #define STP_GATHER_WAVES 6 // waves per SIMD the small instantiation is compiled for: 80 VGPRs as the compiler likes it = 6.  MEASURED (round 5, after the
                            // hierarchical forward gained 7 % from a fifth wave): 8 waves = 64 VGPRs + 32 B of scratch: sort stage 0.3157 / 0.3151 / 0.3161 -> 0.3180 / 0.3201 / 0.3204 ms
@@ -30,35 +33,13 @@ constexpr int TS_SMALL = 1024, TS_CAP = 4096;
 
 struct TileSortArgs {
     const uint2* ranges;
-    uint64_t* keys;           // in: grouped by tile, out: sorted
-    uint32_t* point_list;     // likewise
     uint64_t* keys_scratch;   // the unsorted arrays: scratch of the long-segment path
     uint32_t* list_scratch;
-    const float4* gpack;      // nullptr: no entry records (GLOBAL mode)
-    const float* features;
     int id_passes;            // long segments: counting passes on the id bytes before the depth passes (0: already in id order)
-    int gx;                   // tiles per row
     int tile0;                // first tile of the frame's tile-row window (the grid covers the window's tiles)
     const uint32_t* tile_order; // nullptr, or workgroup j takes tile tile0 + tile_order[j] (longest list first: tile_order_kernel)
-    int cull_mask;            // leave every entry's 16-bit sub-tile mask in entF.w (see write_entry): 1 = hierarchical mode's 4x4 culling, 2 = the k-buffer kernel's sub-tile pre-test
-    float4* entA; float4* entB; float4* entC; float4* entD; float4* entF;
+    EntryGather e;            // keys, list, entry records (stp_tilesort.h)
 };
-
-// What the gather costs (round 4, C2-full, sort stage 0.330 ms, timing ablations, two alternating rounds): the sub-tile masks 15 us, the
-// colour read 22, the entry stores 48 (240 MB: the HBM floor of that part), the bitonic network 37; the rest is key / list / gpack IO.
-__device__ __forceinline__ void write_entry(const TileSortArgs& a, size_t i, int id, int tile)
-{
-    const float4* __restrict__ gp = a.gpack + 4 * (size_t)id; // one 64-byte line written by preprocess_kernel
-    const float4 pa = gp[0], pb = gp[1], pc = gp[2], pd = gp[3];
-    const float3 col = make_float3(a.features[3 * (size_t)id], a.features[3 * (size_t)id + 1], a.features[3 * (size_t)id + 2]);
-    a.entA[i] = pa;
-    a.entB[i] = pb;
-    a.entC[i] = make_float4(pc.x, pc.y, pc.z, __int_as_float(id));
-    a.entD[i] = pd;
-    float spare = 0.0f;
-    if (a.cull_mask) spare = __uint_as_float(subtile_mask(a.cull_mask, pd, make_float2(pc.y, pc.z), tile % a.gx, tile / a.gx)); // (stp_device.h)
-    a.entF[i] = make_float4(col.x, col.y, col.z, spare);
-}
 
 // Segments of 1025 .. 4096 entries that arrive in Gaussian-id order (the tile-bit radix sort is stable): a stable sort on the
 // 32 depth bits alone leaves equal depths in id order, i.e. IS the (depth, id) order -- rocPRIM's workgroup radix sort, four
@@ -111,49 +92,19 @@ __global__ void __launch_bounds__(256, (CAP == TS_SMALL ? STP_GATHER_WAVES : 4))
     const uint2 range = a.ranges[tile];
     const int n = (int)(range.y - range.x);
     if (n <= MIN_N || (CAP == TS_SMALL && n > TS_SMALL)) return; // empty, or the other instantiation's tile
-    uint64_t* const keys = a.keys + range.x;
-    uint32_t* const list = a.point_list + range.x;
+    uint64_t* const keys = a.e.keys + range.x;
+    uint32_t* const list = a.e.point_list + range.x;
 
     if constexpr (CAP == TS_CAP) {
         if (n <= CAP && a.id_passes == 0) { // (segments in id order: always, unless the list was binned through atomic cursors)
-            auto we = [&](int i, int id) __attribute__((always_inline)) { if (a.gpack) write_entry(a, (size_t)range.x + i, id, tile); };
+            auto we = [&](int i, int id) __attribute__((always_inline)) { if (a.e.gpack) write_entry(a.e, (size_t)range.x + i, id, tile); };
             if (n <= 2048) Radix8::run(*reinterpret_cast<typename Radix8::Sort::storage_type*>(s_raw), keys, list, n, tid, we);
             else Radix16::run(*reinterpret_cast<typename Radix16::Sort::storage_type*>(s_raw), keys, list, n, tid, we);
             return;
         }
     }
-    if (n <= CAP) {
-        int m = 2;
-        while (m < n) m <<= 1;
-        const uint64_t tile_bits = keys[0] & 0xFFFFFFFF00000000ull;
-        for (int i = tid; i < m; i += 256) {
-            s_key[i] = i < n ? ((keys[i] << 32) | list[i]) : ~0ull;
-        }
-        __syncthreads();
-        // A stage with partner distance j <= 64 keeps every wave inside its own 128 keys (the 64 consecutive comparators c of a wave cover keys
-        // [128 (c / 64), 128 (c / 64) + 128)): between two such stages the wave's own LDS order is all the synchronisation there is to need --
-        // a workgroup barrier only around the stages that cross waves (3 of the 45 stages of a 512-key network, 6 of 55 at 1024 keys).
-        for (int k = 2; k <= m; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int c = tid; c < (m >> 1); c += 256) {
-                    const int lo = ((c & ~(j - 1)) << 1) | (c & (j - 1));
-                    const int hi = lo | j;
-                    const bool up = (lo & k) == 0;
-                    const uint64_t x = s_key[lo], y = s_key[hi];
-                    if ((x > y) == up) { s_key[lo] = y; s_key[hi] = x; }
-                }
-                const int j_next = j > 1 ? (j >> 1) : k; // (the first distance of the next merge; behind the last stage: the read-out, which crosses waves)
-                const bool last = j == 1 && k == m;
-                if (j > 64 || j_next > 64 || last) __syncthreads();
-                else wave_sync();
-            }
-        for (int i = tid; i < n; i += 256) {
-            const uint64_t k = s_key[i];
-            const int id = (int)(uint32_t)k;
-            keys[i] = tile_bits | (k >> 32);
-            list[i] = (uint32_t)id;
-            if (a.gpack) write_entry(a, (size_t)range.x + i, id, tile);
-        }
+    if (n <= CAP) { // bitonic network on (depth bits, id) in LDS, then keys, list and entry records (stp_tilesort.h)
+        tile_sort_gather_lds(a.e, s_key, tile, range, n, tid);
         return;
     }
 
@@ -280,9 +231,9 @@ __global__ void __launch_bounds__(256, (CAP == TS_SMALL ? STP_GATHER_WAVES : 4))
         __threadfence_block();
         __syncthreads();
     }
-    if (a.gpack) {
+    if (a.e.gpack) {
 #pragma unroll 4
-        for (int i = tid; i < n; i += 256) write_entry(a, (size_t)range.x + i, (int)list[i], tile);
+        for (int i = tid; i < n; i += 256) write_entry(a.e, (size_t)range.x + i, (int)list[i], tile);
     }
 }
 
@@ -295,20 +246,20 @@ hipError_t launch_tile_sort_gather(const FrameParams& f, const GeometryState& g,
     a.id_passes = 0;
     if (unordered) // segments filled through atomic cursors: not in id order
         for (unsigned int top = (unsigned int)(f.P > 1 ? f.P - 1 : 1); top; top >>= 8) a.id_passes++;
-    a.ranges = img.ranges; a.keys = b.keys; a.point_list = b.point_list; a.keys_scratch = b.keys_unsorted; a.list_scratch = b.point_list_unsorted;
+    a.ranges = img.ranges; a.e.keys = b.keys; a.e.point_list = b.point_list; a.keys_scratch = b.keys_unsorted; a.list_scratch = b.point_list_unsorted;
     const bool entries = f.s.sort_mode == MODE_HIER || f.s.sort_mode == MODE_KBUFFER;
-    a.gpack = entries ? g.gpack : nullptr;
-    a.features = f.colors_precomp ? f.colors_precomp : g.rgb;
-    a.gx = f.gx;
+    a.e.gpack = entries ? g.gpack : nullptr;
+    a.e.features = f.colors_precomp ? f.colors_precomp : g.rgb;
+    a.e.gx = f.gx;
     a.tile0 = f.gx * f.ty0;
-    a.cull_mask = subtile_mask_kind(f.s);
+    a.e.cull_mask = subtile_mask_kind(f.s);
     // (STP_GATHER_ORDER: 0 = default: spatial, 1: longest first inside every XCD's contiguous run, 2: longest first over the frame -- tile_order_kernel, measured there)
     const int gmode = (tile_order_used(f) && !unordered) ? gather_order_mode() : 0;
     a.tile_order = gmode == 1 ? img.tile_counts + f.gx * f.ty0 : gmode == 2 ? img.tile_cursor + f.gx * f.ty0 : nullptr;
-    a.entA = b.entA; a.entB = b.entB; a.entC = b.entC; a.entD = b.entD; a.entF = b.entF;
+    a.e.entA = b.entA; a.e.entB = b.entB; a.e.entC = b.entC; a.e.entD = b.entD; a.e.entF = b.entF;
     const int n_tiles = f.gx * (f.ty1 - f.ty0);
     if (n_tiles <= 0) return hipSuccess;
-    hipLaunchKernelGGL((tile_sort_gather_kernel<TS_SMALL, 0>), dim3(n_tiles), dim3(256), 0, st, a);
+    if (!f.fused_gather) hipLaunchKernelGGL((tile_sort_gather_kernel<TS_SMALL, 0>), dim3(n_tiles), dim3(256), 0, st, a); // (else the render kernel's prologue)
     hipLaunchKernelGGL((tile_sort_gather_kernel<TS_CAP, TS_SMALL>), dim3(n_tiles), dim3(256), 0, st, a);
     return hipGetLastError();
 }
