@@ -12,13 +12,16 @@ Rank 0 prints ONE JSON line (contract in the task statement / DESIGN.md section 
 
 N > 1: the north star's tile-row mode is the headline -- ONE frame partitioned by screen-tile row over the N ranks, image
 strips sent to rank 0 over RCCL, per-Gaussian gradient records all-reduced: `"scaling": "strong"`, `value` = frames/s of
-that one frame stream (`--shard tilerows`, the default for every workload).  The same run then also times the
-frame-sharded mode (every rank its own frame, no data-path collective, weak scaling) and reports it in the
-`frame_shard` object of the JSON line (`--no-frame-shard-probe` leaves it out); `--shard frames` swaps the two.
+that one frame stream (`--shard tilerows`, the default for every workload).  With `--full` the same run also times the
+frame-sharded mode (every rank its own frame, no data-path collective, weak scaling) first, as the fallback line, and
+reports it in the `frame_shard` object of the JSON line (`--no-frame-shard-probe` leaves it out); `--shard frames` swaps the two.
 `rccl_ranks` is what the first collective of the run saw.
 
-The `cpu_baseline` leg (rank 0, N == 1 only) times the CPU oracle on a bounded sample of the same frame:
-it is a reported, non-target baseline.
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` and prints the line: a few seconds besides
+its steps.  `--full` adds every other leg: `hbm_measured`, the `cpu_baseline` leg (rank 0, N == 1 only: the CPU
+oracle timed on a bounded sample of the same frame, a reported, non-target baseline), the parity checks against the
+oracle and the reference's kernels, `other_workloads` (N == 1), and at N > 1 the side measurement of the other
+sharding mode; `--detail` (implies `--full`) adds the side legs of rounds 3-5.  About a minute at N == 1.
 """
 from __future__ import annotations
 
@@ -807,10 +810,13 @@ def main():
     ap.add_argument("--shard", default=None, choices=["tilerows", "frames"],
                     help="N > 1: what the ranks share.  Default: tilerows (north star: ONE frame partitioned by screen-tile row, strips "
                          "gathered over RCCL, strong scaling); frames = every rank renders its own frame, no collective, weak scaling")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline: hbm_measured, the CPU baseline, parity against the oracle and the reference's "
+                         "kernels, other_workloads (N == 1), the other sharding mode (N > 1); about a minute at N == 1")
     ap.add_argument("--no-frame-shard-probe", action="store_true",
-                    help="N > 1 with --shard tilerows: do NOT additionally time the frame-sharded mode (the \"frame_shard\" object of the JSON line)")
+                    help="N > 1 with --full and --shard tilerows: do NOT additionally time the frame-sharded mode (the \"frame_shard\" object of the JSON line)")
     ap.add_argument("--tile-shard-probe", action="store_true", help="(accepted, no effect)")
-    ap.add_argument("--no-tile-shard-probe", action="store_true", help="(accepted; N > 1 with --shard frames: no tile-row side measurement)")
+    ap.add_argument("--no-tile-shard-probe", action="store_true", help="(accepted; N > 1 with --full and --shard frames: no tile-row side measurement)")
     ap.add_argument("--probe-timeout", type=float, default=120.0, help="seconds the side measurement may take before the headline is printed without it")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload (debug only; invalidates the headline number)")
     ap.add_argument("--fwd-only", action="store_true")
@@ -818,12 +824,13 @@ def main():
                     help="the step also computes a weighted-sum loss with torch ((image * w).sum().backward(), the step of rounds 1-2) instead of "
                          "handing dL/dimage, resident in HBM, to the rasterizer's backward")
     ap.add_argument("--prewarm-seconds", type=float, default=0.5, help="untimed steps before the W warm-up steps (device clock ramp)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and the parity checks")
     ap.add_argument("--detail", action="store_true",
-                    help="also run the side legs of rounds 3-5 (libstp_raster_fma.so parity + speed, the reference's default-contraction build, the "
+                    help="--full, and also the side legs of rounds 3-5 (libstp_raster_fma.so parity + speed, the reference's default-contraction build, the "
                          "reference's kernels timed on this GPU, the step with a torch loss): minutes of checker time, all of it in bench_detail.json")
-    ap.add_argument("--no-other-workloads", action="store_true", help="N == 1: leave out the other_workloads object (C2-min, C3, C4 on one GPU, C5; 10 steps each)")
-    ap.add_argument("--cpu-rows", type=int, default=0, help="tile rows in the CPU-baseline sample (0 = auto)")
+    ap.add_argument("--no-other-workloads", action="store_true",
+                    help="with --full at N == 1: leave out the other_workloads object (C2-min, C3, C4 on one GPU, C5; 10 steps each)")
+    ap.add_argument("--cpu-rows", type=int, default=0, help="with --full: tile rows in the CPU-baseline sample (0 = auto)")
     ap.add_argument("--train-forward-only", action="store_true",
                     help="debug: forward passes that expect a backward (recording forward) without running it; read stage_ms only")
     ap.add_argument("--per-step", action="store_true", help="debug: print cumulative wall time after each timed step")
@@ -834,6 +841,7 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    args.full = args.full or args.detail
     t_start = time.perf_counter()
 
     # stdout carries exactly ONE line, the result of rank 0.  Libraries write there too (RCCL prints a five-line version
@@ -952,12 +960,12 @@ def main():
     def summary(o):
         return {k: o[k] for k in ("value", "unit", "ms_per_step", "steps", "scaling", "stage_ms") if k in o} | {"parallelism": o["config"]["parallelism"]}
 
-    # N == 1 (or one explicitly chosen mode): one measurement.  N > 1 with the tile-row headline: the mode WITHOUT a data-path
-    # collective -- every rank its own frame -- is measured FIRST and kept as the fallback line; the tile-row exchange (never run by us
-    # on more than one RCCL rank) then runs under a watchdog: should it hang or fail, the fallback line is printed with an error field
+    # N == 1, a plain run (or one explicitly chosen mode): one measurement.  N > 1 with --full and the tile-row headline: the mode WITHOUT
+    # a data-path collective -- every rank its own frame -- is measured FIRST and kept as the fallback line; the tile-row exchange (never run
+    # by us on more than one RCCL rank) then runs under a watchdog: should it hang or fail, the fallback line is printed with an error field
     # instead of nothing.
     out, wl = None, None
-    side_first = world > 1 and ((sharded and not args.no_frame_shard_probe) or (not sharded and not args.no_tile_shard_probe))
+    side_first = world > 1 and args.full and ((sharded and not args.no_frame_shard_probe) or (not sharded and not args.no_tile_shard_probe))
     fallback = None
     if side_first and sharded:
         wl_f, dt_f, stage_f, stats_f = measure(False, args.steps, args.warmup, args.prewarm_seconds)
@@ -1027,18 +1035,18 @@ def main():
                                           "backward: all-reduce of 36 B per Gaussian between the two halves; the per-Gaussian stages run replicated "
                                           "(DESIGN.md section 7 gives the Amdahl ceiling per N)")
         legs = {"headline": round(time.perf_counter() - t_start, 1)}
-        if world == 1:
+        if world == 1 and args.full:
             t_leg = time.perf_counter()
             out["hbm_measured"] = hbm_ceilings(dev)
             legs["hbm_measured"] = round(time.perf_counter() - t_leg, 1)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             t_leg = time.perf_counter()
             checker = checker_legs(scene, sdict, gy, fwd_only, args.cpu_rows, wl.state, wl.leaves,
                                    raster_factory=lambda e: __import__("diff_gaussian_rasterization").GaussianRasterizer(wl.rs._replace(settings=e)),
                                    es=es, tensors=wl.tensors(), w_img=wl.w_img, wl=wl, dev=dev, detail=args.detail)
             out.update(checker)
             legs["cpu_baseline_and_parity"] = round(time.perf_counter() - t_leg, 1)
-        if world == 1 and not args.no_other_workloads and args.workload == "C2" and args.variant == "full" \
+        if world == 1 and args.full and not args.no_other_workloads and args.workload == "C2" and args.variant == "full" \
                 and not args.fwd_only and not args.train_forward_only:
             if not wl.loss and args.detail:
                 # the same workload with the step definition of rounds 1-2 (a torch loss inside the step), for continuity

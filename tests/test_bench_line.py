@@ -3,11 +3,13 @@
 
   * CPU: `bench.compact_line` on the committed full record of round 5 (`profiles/r05_bench_full.json`, the 24.7 KB line the driver could not
     parse) and on a record padded far beyond it;
-  * GPU (-m gpu): `bench.py --scale 0.05` at N = 1 as the driver runs it, every leg on (CPU baseline, parity, other workloads)."""
+  * GPU (-m gpu): `bench.py --full --scale 0.05` at N = 1, every leg on (CPU baseline, parity, other workloads); the plain flagship run
+    `bench.py --gpus 1 --steps 20 --warmup 5`, which times the headline alone and spends at most 30 s besides its steps."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -94,7 +96,7 @@ def test_the_committed_round_6_line_is_what_the_driver_can_parse():
 @pytest.mark.gpu
 def test_bench_prints_one_bounded_line_at_n1():
     env = dict(os.environ, TMPDIR=os.environ.get("TMPDIR", "/tmp"))
-    p = subprocess.run([sys.executable, os.path.join(conftest.ROOT, "bench.py"), "--scale", "0.05", "--steps", "3", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(conftest.ROOT, "bench.py"), "--full", "--scale", "0.05", "--steps", "3", "--warmup", "1"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = p.stdout.splitlines()
@@ -103,6 +105,29 @@ def test_bench_prints_one_bounded_line_at_n1():
     _check_line(d, lines[0])
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
     assert "[bench detail] {" in p.stderr
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_headline_alone(tmp_path):
+    """Without --full: the flagship's line with the contract's keys and the roofline of the timed steps, the dumped outputs, none of the
+    other legs, and at most 30 s of the whole process's wall time outside the warm-up and timed steps."""
+    steps, warmup = 20, 5
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, os.path.join(conftest.ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(tmp_path / "out")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = p.stdout.splitlines()
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert len(lines[0]) < bench.LINE_CAP_BYTES and CONTRACT_KEYS <= set(d) and ROOFLINE_KEYS <= set(d["roofline"])
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup and d["value"] > 0 and d["unit"] == "frames/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["config"]["P"] == 1_000_000
+    assert not {"cpu_baseline", "parity", "hbm_measured", "other_workloads", "fma_depth_build", "with_torch_loss"} & set(d), sorted(d)
+    assert set(d["leg_seconds"]) == {"headline", "total"}
+    assert {"color.npy", "radii.npy", "dL_dmeans3D.npy"} <= {f.name for f in (tmp_path / "out").iterdir()}
+    outside = wall - (steps + warmup) * d["ms_per_step"] / 1000.0
+    assert outside < 30.0, (wall, d["ms_per_step"], d["leg_seconds"])
 
 
 def test_dump_outputs_writes_the_last_step_within_the_cap(tmp_path):

@@ -49,8 +49,8 @@ def test_two_ranks_two_gpus_rccl():
 
 def _bench_two_ranks(extra):
     """bench.py as the driver launches it for N = 2 (one process per rank, rendezvous on 127.0.0.1), in its one-GPU self-test mode
-    (`--test-one-gpu`: both ranks on cuda:0, gloo process group): exercises the N > 1 code path -- fallback measurement first, tile-row
-    headline under the watchdog, the JSON line -- on the 1-GPU box.  The numbers mean nothing; the shape of the line does."""
+    (`--test-one-gpu`: both ranks on cuda:0, gloo process group): exercises the N > 1 code path -- with `--full`, fallback measurement first,
+    tile-row headline under the watchdog; the JSON line -- on the 1-GPU box.  The numbers mean nothing; the shape of the line does."""
     import json
     port = _free_port()
     procs = []
@@ -67,8 +67,15 @@ def _bench_two_ranks(extra):
     return json.loads(lines[0])
 
 
-def test_bench_n2_tile_row_headline_with_frame_shard_side_object():
+def test_bench_n2_plain_run_times_the_tile_row_headline_alone():
     d = _bench_two_ranks([])
+    assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["parallelism"] == "tilerows2", d
+    assert d["rccl_ranks"]["world_size"] == 2 and d["rccl_ranks"]["all_reduce_of_ones"] == 2 and d["value"] > 0
+    assert "frame_shard" not in d and "tile_shard" not in d and "hbm_measured" not in d
+
+
+def test_bench_n2_tile_row_headline_with_frame_shard_side_object():
+    d = _bench_two_ranks(["--full"])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["parallelism"] == "tilerows2", d
     assert d["rccl_ranks"]["world_size"] == 2 and d["rccl_ranks"]["all_reduce_of_ones"] == 2
     assert d["value"] > 0 and d["frame_shard"]["scaling"] == "weak" and d["frame_shard"]["value"] > 0
@@ -76,7 +83,7 @@ def test_bench_n2_tile_row_headline_with_frame_shard_side_object():
 
 
 def test_bench_n2_frames_headline_keeps_the_tile_row_side_object():
-    d = _bench_two_ranks(["--shard", "frames"])
+    d = _bench_two_ranks(["--full", "--shard", "frames"])
     assert d["scaling"] == "weak" and d["config"]["parallelism"] == "frames2" and d["tile_shard"]["scaling"] == "strong" and d["tile_shard"]["value"] > 0
 
 

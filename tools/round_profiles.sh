@@ -8,7 +8,7 @@ tag=${1:-rXX}
 out=gpurun_out/${tag}
 mkdir -p $out
 B="timeout -k 5 600 python bench.py"
-$B > $out/bench_full.json 2> $out/bench_full.err   # (the driver's line: headline + checker legs + other_workloads)
+$B --full > $out/bench_full.json 2> $out/bench_full.err   # (the full run: headline + checker legs + other_workloads)
 cp bench_detail.json $out/bench_full_detail.json 2>/dev/null
 $B --variant min --no-cpu-baseline --no-other-workloads > $out/bench_min.json 2>/dev/null
 $B --fwd-only --no-cpu-baseline --no-other-workloads > $out/bench_full_fwd.json 2>/dev/null
