@@ -173,6 +173,27 @@ int stp_backward_phases(int phases, int P, int D, int M, int R,
                         float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                         int debug, void* stream);
 
+/* Extension (not in the reference): gradients with respect to the camera, for pose refinement and tracking.  The NEXT stp_backward or
+   stp_backward_phases of the calling thread that runs the per-Gaussian half (phases bit 1) also writes
+       dL_dviewmatrix (16 floats), dL_dprojmatrix (16 floats), dL_dcampos (3 floats)
+   in full (device pointers; the caller does no zero-fill), in the matrix layout above: element [i][j] (p_view = [p 1] @ V) is m[4*i+j].
+   The three inputs are differentiated as independent inputs, as the forward reads them (it never checks that projmatrix = viewmatrix @ P
+   or that cam_pos is the camera centre); a caller who builds all three from one pose gets the total derivative by the chain rule.
+   Differentiated: viewmatrix -> view-space mean -> the EWA Jacobian and the rotation of the covariance projection (with the same
+   1.3 * tan_fov clamp masks and, under proper_ewa_scaling, the same opacity factor as dL_dmean3D), projmatrix -> the 2D mean, cam_pos ->
+   the SH view direction (zero with colors_precomp).  They are sums over the visible Gaussians of the intermediates dL_dmean3D is made of.
+   Not differentiated (zero by definition, as for the Gaussians): culling, the near plane, tile binning, every sort key and depth along the
+   ray.  Entries the forward never reads are 0: column 3 of viewmatrix, column 2 of projmatrix.  inv_viewprojmatrix, tan_fovx / tan_fovy
+   (the intrinsics) and the background get no gradient.
+   `workspace` is a 16-byte aligned device buffer of at least stp_camera_grad_workspace_bytes(P) bytes, used until the call's kernels have
+   run.  The sums run in a fixed order without float atomics: equal per-Gaussian gradients give bit-equal camera gradients.  Every other output
+   of the call is bit-identical to that of a call without the request.
+   A NULL output pointer clears a pending request.  STP_ERR_INVALID_ARGUMENT: a workspace that is too small or misaligned, or a chunked
+   per-Gaussian half (phases bits 8-23).  The request is consumed by that call whatever its outcome; a render-only call (phases = 1) leaves
+   it pending. */
+size_t stp_camera_grad_workspace_bytes(int P);
+void stp_set_backward_camera_grads(float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* workspace, size_t workspace_bytes);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:188-193, rasterizer_impl.cu:161-173).
    `present` is P bytes (bool). */
 int stp_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

@@ -64,6 +64,9 @@ struct Api {
     decltype(&stp_abi_version) abi_version = nullptr;
     decltype(&stp_forget_buffer) forget_buffer = nullptr;
     decltype(&stp_set_forward_split) set_forward_split = nullptr;
+    // optional (an older library without them still loads; asking it for camera gradients raises)
+    decltype(&stp_camera_grad_workspace_bytes) camera_grad_workspace_bytes = nullptr;
+    decltype(&stp_set_backward_camera_grads) set_backward_camera_grads = nullptr;
 } g_api;
 
 int load_library(const std::string& path)
@@ -81,6 +84,8 @@ int load_library(const std::string& path)
     a.set_forward_split = reinterpret_cast<decltype(a.set_forward_split)>(dlsym(h, "stp_set_forward_split"));
     if (!a.set_forward_split || !a.forget_buffer || !a.forward || !a.backward_phases || !a.mark_visible || !a.last_error || !a.abi_version)
         throw std::runtime_error(path + " does not export the C ABI of include/stp_raster.h");
+    a.camera_grad_workspace_bytes = reinterpret_cast<decltype(a.camera_grad_workspace_bytes)>(dlsym(h, "stp_camera_grad_workspace_bytes"));
+    a.set_backward_camera_grads = reinterpret_cast<decltype(a.set_backward_camera_grads)>(dlsym(h, "stp_set_backward_camera_grads"));
     if (a.abi_version() != STP_ABI_VERSION) throw std::runtime_error(path + ": ABI version mismatch");
     g_api = a; // (a previously loaded library stays mapped: buffers of its forwards may still be in flight)
     return a.abi_version();
@@ -303,6 +308,8 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
 // phases / partial: extension for tile-row sharding (include/stp_raster.h, stp_backward_phases): phases = 1 runs only the
 // render half and returns the (P,16) gradient records; phases = 2 takes the records (after the caller's all-reduce) and
 // runs the per-Gaussian half.
+// camera_grads (extension, include/stp_raster.h: stp_set_backward_camera_grads): the per-Gaussian half also returns dL/dviewmatrix,
+// dL/dprojmatrix and dL/dcampos, appended to the eight gradients in the shapes of the three inputs.
 std::vector<torch::Tensor>
 rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& opacities,
                              const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
@@ -311,10 +318,16 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
                              const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                              const py::dict& settings, const bool debug, const bool record_log, const int phases, const c10::optional<torch::Tensor>& partial,
-                             const c10::optional<std::vector<torch::Tensor>>& outputs)
+                             const c10::optional<std::vector<torch::Tensor>>& outputs, const bool camera_grads)
 {
     need_library();
     TORCH_CHECK(means3D.is_cuda(), "diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
+    if (camera_grads) {
+        if (!g_api.set_backward_camera_grads || !g_api.camera_grad_workspace_bytes)
+            throw std::runtime_error(std::string("camera gradients: the loaded libstp_raster.so does not export ") +
+                                     (g_api.set_backward_camera_grads ? "stp_camera_grad_workspace_bytes" : "stp_set_backward_camera_grads") + "; rebuild it");
+        TORCH_CHECK(phases & 2, "camera gradients come from the per-Gaussian half (phases bit 1)");
+    }
     const torch::Device dev = means3D.device();
     const int P = (int)means3D.size(0);
     const int H = (int)dL_dout_color.size(1), W = (int)dL_dout_color.size(2);
@@ -356,6 +369,24 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         dL_drotations = have_scales ? torch::empty({P, 4}, fopt) : torch::zeros({P, 4}, fopt);
     }
     const StpSettings s = settings_from_dict(settings, record_log);
+    torch::Tensor dL_dview, dL_dproj, dL_dcam, cam_ws;
+    if (camera_grads) { // written in full by the library (no zero-fill); the workspace holds one row per 256 Gaussians and the partial sums
+        dL_dview = torch::empty(viewmatrix.sizes(), fopt); dL_dproj = torch::empty(projmatrix.sizes(), fopt); dL_dcam = torch::empty(campos.sizes(), fopt);
+        TORCH_CHECK(dL_dview.numel() == 16 && dL_dproj.numel() == 16 && dL_dcam.numel() == 3, "camera gradients: viewmatrix and projmatrix must have 16 elements, campos 3");
+        cam_ws = torch::empty({(int64_t)g_api.camera_grad_workspace_bytes(P)}, means3D.options().dtype(torch::kByte));
+    }
+    auto request_camera_grads = [&] {
+        if (camera_grads) g_api.set_backward_camera_grads(dL_dview.data_ptr<float>(), dL_dproj.data_ptr<float>(), dL_dcam.data_ptr<float>(), cam_ws.data_ptr(), (size_t)cam_ws.numel());
+    };
+    if (P == 0 && camera_grads) { // nothing to differentiate: the library writes the zeros
+        const c10::hip::HIPGuard guard(dev.index());
+        hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+        request_camera_grads();
+        const int rc = g_api.backward_phases(phases, 0, degree, M, R, nullptr, W, H, &s, nullptr, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr,
+                                           nullptr, nullptr, nullptr, nullptr, nullptr, tan_fovx, tan_fovy, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, debug ? 1 : 0, (void*)stream);
+        if (rc < 0) raise_last(rc);
+    }
     if (P != 0) {
         const torch::Tensor bg_ = prep(background, dev), m3_ = prep(means3D, dev), sh_ = prep(sh, dev), col_ = prep(colors, dev), op_ = prep(opacities, dev),
                             sc_ = prep(scales, dev), ro_ = prep(rotations, dev), c3_ = prep(cov3D_precomp, dev), vm_ = prep(viewmatrix, dev),
@@ -368,6 +399,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
         forget_unless_same_storage(binningBuffer); // (a clone, a copy or a recycled address: the library then reads the buffer's own header)
         forget_unless_same_storage(imageBuffer);
+        request_camera_grads(); // (consumed by the call below, on this thread)
         const int rc = g_api.backward_phases(keep_records ? (phases | 8) : phases, P, degree, M, R, fptr(bg_), W, H, &s, fptr(m3_), fptr(sh_), fptr(op_), fptr(col_), fptr(sc_),
                                            scale_modifier, fptr(ro_), fptr(c3_), fptr(vm_), fptr(pm_), fptr(inv_), fptr(cam_), tan_fovx, tan_fovy,
                                            fptr(pix_), radii_.numel() ? radii_.data_ptr<int>() : nullptr, optb(geomBuffer), optb(binningBuffer),
@@ -381,6 +413,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         }
     }
     if ((phases & 3) == 1) return {records};
+    if (camera_grads) return {dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview, dL_dproj, dL_dcam};
     return {dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations};
 }
 

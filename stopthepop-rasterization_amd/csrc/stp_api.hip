@@ -992,6 +992,16 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
     return R;
 }
 
+// stp_set_backward_camera_grads: the request of the calling thread for its NEXT backward that runs the per-Gaussian half (consumed there)
+thread_local CameraGradRequest t_camera_grads;
+size_t stp_camera_grad_workspace_bytes(int P) { return camera_grad_workspace_bytes(P); }
+void stp_set_backward_camera_grads(float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* workspace, size_t workspace_bytes)
+{
+    t_camera_grads = CameraGradRequest{};
+    if (!dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos) return; // (clears a pending request)
+    t_camera_grads = CameraGradRequest{dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, workspace, workspace_bytes};
+}
+
 int stp_backward_phases(int phases, int P, int D, int M, int R, const float* background, int width, int height, const StpSettings* settings,
                  const float* means3D, const float* shs, const float* opacities, const float* colors_precomp, const float* scales,
                  float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
@@ -1001,8 +1011,22 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
                  float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug, void* stream)
 {
     hipStream_t st = (hipStream_t)stream;
+    CameraGradRequest cam;
+    if (phases & 2) { // (one per-Gaussian half per request, whatever its outcome)
+        cam = t_camera_grads;
+        t_camera_grads = CameraGradRequest{};
+    }
+    if (cam.dL_dview) {
+        if (!cam.workspace || (reinterpret_cast<uintptr_t>(cam.workspace) & 15) != 0 || cam.workspace_bytes < camera_grad_workspace_bytes(P))
+            return fail(STP_ERR_INVALID_ARGUMENT, "camera gradients: the workspace is null, not 16-byte aligned or smaller than stp_camera_grad_workspace_bytes(P)");
+        if (((phases >> 8) & 0xFF) > 1)
+            return fail(STP_ERR_INVALID_ARGUMENT, "camera gradients are not available from a chunked per-Gaussian half (phases bits 8-23)");
+    }
     if (!settings) return fail(STP_ERR_INVALID_ARGUMENT, "null settings");
-    if (P == 0) return 0; // reference rasterize_points.cu:191
+    if (P == 0) { // reference rasterize_points.cu:191 (a camera request still gets its outputs: zeros)
+        if (cam.dL_dview) STP_TRY(launch_camera_grad_finalize(0, cam, st), "camera gradient launch");
+        return 0;
+    }
     if (int rc = check_settings(*settings, true)) return rc;
     if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)) return fail(STP_ERR_INVALID_ARGUMENT, "null scratch buffer");
     if (!grad_records) return fail(STP_ERR_INVALID_ARGUMENT, "null gradient record buffer");
@@ -1024,6 +1048,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     if (!radii) radii = g.internal_radii;
 
     BackwardParams bw;
+    bw.cam = cam;
     bw.pixel_colors = pixel_colors; bw.dL_dpix = dL_dpix; bw.dL_dmean2D = dL_dmean2D; bw.grad_rec = grad_records;
     bw.grad_stride = (phases & 4) ? STP_GRAD_RECORD_USED : STP_GRAD_RECORD_FLOATS;
     bw.clear_rec = (phases & 8) ? 1 : 0;

@@ -42,15 +42,42 @@ struct BwdPreArgs {
     float* dL_dsh;
     float* dL_dscale;
     float* dL_drot;
+    float* cam_rows;       // CAM only: one kCamRow-float row of camera-gradient partial sums per workgroup (camera_grad_* below)
 };
+
+// Camera-gradient contributions of one Gaussian (CAM instantiation), in the order of a workspace row:
+//   [0..11]  dL/dviewmatrix[i][j], i = 0..3 (world axis; 3 = translation), j = 0..2 (view axis) at 3*i + j  (column 3 is never read)
+//   [12..23] dL/dprojmatrix[i][j], i = 0..3, j = 0, 1, 3 at 12 + 3*i + (0, 1, 2)                           (column 2 is never read)
+//   [24..26] dL/dcampos
+// Matrices in the row-vector layout of stp_raster.h: element [i][j] is view[4*i + j].
+constexpr int kCamTerms = 27;
+constexpr int kCamRow = 32;
+
+// An opaque copy: the compiler cannot see that it equals its input, so no expression built on it is merged with one built on the input.
+__device__ __forceinline__ float opaque(float v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
 
 // Everything for one visible Gaussian.  sh_row / dsh_row: this Gaussian's 3M SH coefficients and their gradient,
 // both in the SAME LDS row (the kernel stages them, see below): each channel reads what it needs before it writes.
-__device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, float* sh_row)
+// TERMS = true: the same chain rule evaluated for this Gaussian's camera terms only (cg[kCamTerms]): nothing is stored, and every input is
+// read through opaque(), so none of its arithmetic is shared with -- or changes the instruction selection of -- the TERMS = false pass that
+// writes the Gaussian's gradients (bit-identical with and without a camera request).
+template <bool TERMS>
+__device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, float* sh_row, float* cg)
 {
     const float* __restrict__ view = a.view;
     const float* __restrict__ proj = a.proj;
-    const float3 mean = make_float3(a.means3D[3 * (size_t)idx], a.means3D[3 * (size_t)idx + 1], a.means3D[3 * (size_t)idx + 2]);
+    float view_t[TERMS ? 16 : 1], proj_t[TERMS ? 16 : 1];
+    if constexpr (TERMS) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) { view_t[k] = opaque(a.view[k]); proj_t[k] = opaque(a.proj[k]); }
+        view = view_t; proj = proj_t;
+    }
+    float3 mean = make_float3(a.means3D[3 * (size_t)idx], a.means3D[3 * (size_t)idx + 1], a.means3D[3 * (size_t)idx + 2]);
+    if constexpr (TERMS) mean = make_float3(opaque(mean.x), opaque(mean.y), opaque(mean.z));
     float3 dmean;
     // the render half's sums: one 64-byte record, two 16-byte loads and a scalar
     float4 rec0, rec1; // colour r g b, mean2D x | mean2D y, conic xx xy yy
@@ -65,7 +92,12 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         rec1 = make_float4(r[4], r[5], r[6], r[7]);
         rec_op = r[8];
     }
-    if (a.clear_rec) { // only records of visible Gaussians are ever written by the render half, and all of those pass through here
+    if constexpr (TERMS) {
+        rec0 = make_float4(opaque(rec0.x), opaque(rec0.y), opaque(rec0.z), opaque(rec0.w));
+        rec1 = make_float4(opaque(rec1.x), opaque(rec1.y), opaque(rec1.z), opaque(rec1.w));
+        rec_op = opaque(rec_op);
+    }
+    if (!TERMS && a.clear_rec) { // only records of visible Gaussians are ever written by the render half, and all of those pass through here
         float* const r = const_cast<float*>(a.grad_rec) + (size_t)a.grad_stride * idx;
         if (a.grad_stride == 16) {
             const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -75,12 +107,20 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
             for (int k = 0; k < 9; k++) r[k] = 0.0f;
         }
     }
-    a.dL_dcolor[3 * (size_t)idx] = rec0.x; a.dL_dcolor[3 * (size_t)idx + 1] = rec0.y; a.dL_dcolor[3 * (size_t)idx + 2] = rec0.z;
-    a.dL_dmean2D[3 * (size_t)idx] = rec0.w; a.dL_dmean2D[3 * (size_t)idx + 1] = rec1.x;
+    if constexpr (!TERMS) {
+        a.dL_dcolor[3 * (size_t)idx] = rec0.x; a.dL_dcolor[3 * (size_t)idx + 1] = rec0.y; a.dL_dcolor[3 * (size_t)idx + 2] = rec0.z;
+        a.dL_dmean2D[3 * (size_t)idx] = rec0.w; a.dL_dmean2D[3 * (size_t)idx + 1] = rec1.x;
+    }
 
     // ---- dL/dconic -> dL/dcov2D -> dL/dcov3D and dL/dmean (covariance path) ----
     {
         const float* cov3D = a.cov3Ds + 6 * (size_t)idx;
+        float cov3D_t[TERMS ? 6 : 1];
+        if constexpr (TERMS) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) cov3D_t[k] = opaque(cov3D[k]);
+            cov3D = cov3D_t;
+        }
         const float dcx = rec1.y, dcy = rec1.z, dcz = rec1.w;
         float3 t;
         t.x = view[0] * mean.x + view[4] * mean.y + view[8] * mean.z + view[12];
@@ -117,8 +157,8 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
             const float det_plus = c_xx * c_yy - c_xy * c_xy;
             const float h_scal = sqrtf(fmaxf(0.000025f, det_cov_orig / det_plus));
             const float dL_dop_v = rec_op;
-            const float d_h_scal = dL_dop_v * a.opacities[idx];
-            a.dL_dopacity[idx] = dL_dop_v * h_scal;
+            const float d_h_scal = dL_dop_v * (TERMS ? opaque(a.opacities[idx]) : a.opacities[idx]);
+            if constexpr (!TERMS) a.dL_dopacity[idx] = dL_dop_v * h_scal;
             const float d_inside_root = (det_cov_orig / det_plus) <= 0.000025f ? 0.f : d_h_scal / (2 * h_scal);
             const float x = c_xx, y = c_yy, z = c_xy, w = h_var;
             const float qd = w * w + w * (x + y) + x * y - z * z;
@@ -126,7 +166,7 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
             dL_dc_xx = w * (w * y + y * y + z * z) * denom_f;
             dL_dc_yy = w * (w * x + x * x + z * z) * denom_f;
             dL_dc_xy = -2.f * w * z * (w + x + y) * denom_f;
-        } else {
+        } else if constexpr (!TERMS) {
             a.dL_dopacity[idx] = rec_op;
         }
         const float denom = c_xx * c_yy - c_xy * c_xy;
@@ -147,7 +187,7 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
             for (int i = 0; i < 6; i++) dcov[i] = 0;
         }
 #pragma unroll
-        for (int i = 0; i < 6; i++) a.dL_dcov3D[6 * (size_t)idx + i] = dcov[i];
+        for (int i = 0; i < 6; i++) if constexpr (!TERMS) a.dL_dcov3D[6 * (size_t)idx + i] = dcov[i];
 
         const float dL_dT00 = 2 * (T.m[0][0] * Vrk.m[0][0] + T.m[0][1] * Vrk.m[0][1] + T.m[0][2] * Vrk.m[0][2]) * dL_dc_xx +
                               (T.m[1][0] * Vrk.m[0][0] + T.m[1][1] * Vrk.m[0][1] + T.m[1][2] * Vrk.m[0][2]) * dL_dc_xy;
@@ -172,6 +212,20 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         dmean.x = view[0] * dL_dtx + view[1] * dL_dty + view[2] * dL_dtz;
         dmean.y = view[4] * dL_dtx + view[5] * dL_dty + view[6] * dL_dtz;
         dmean.z = view[8] * dL_dtx + view[9] * dL_dty + view[10] * dL_dtz;
+        if constexpr (TERMS) {
+            // t = mean @ view (+ translation row): dL/dview[i][j] = mean_i dL/dt_j.  T = J Wm with Wm.m[k][c] = view[4c + k]:
+            // dL/dWm.m[k][c] = sum_r J.m[r][k] dL/dT_rc -- the transpose of the dL/dJ chain above.
+            const float dt[3] = {dL_dtx, dL_dty, dL_dtz};
+            const float mu[3] = {mean.x, mean.y, mean.z};
+            const float dT0[3] = {dL_dT00, dL_dT01, dL_dT02}, dT1[3] = {dL_dT10, dL_dT11, dL_dT12};
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                cg[3 * c + 0] = mu[c] * dt[0] + J.m[0][0] * dT0[c];
+                cg[3 * c + 1] = mu[c] * dt[1] + J.m[1][1] * dT1[c];
+                cg[3 * c + 2] = mu[c] * dt[2] + J.m[0][2] * dT0[c] + J.m[1][2] * dT1[c];
+            }
+            cg[9] = dt[0]; cg[10] = dt[1]; cg[11] = dt[2];
+        }
     }
 
     // ---- projection path of dL/dmean (reference backward.cu:408-425) ----
@@ -184,18 +238,27 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         dmean.x += (proj[0] * m_w - proj[3] * mul1) * gx + (proj[1] * m_w - proj[3] * mul2) * gy;
         dmean.y += (proj[4] * m_w - proj[7] * mul1) * gx + (proj[5] * m_w - proj[7] * mul2) * gy;
         dmean.z += (proj[8] * m_w - proj[11] * mul1) * gx + (proj[9] * m_w - proj[11] * mul2) * gy;
+        if constexpr (TERMS) { // p_hom = [mean 1] @ proj: dL/dproj[i][j] = mean_h_i dL/dp_hom_j
+            const float dp[3] = {gx * m_w, gy * m_w, -(gx * mul1 + gy * mul2)}; // columns 0, 1, 3
+            const float mh[4] = {mean.x, mean.y, mean.z, 1.0f};
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 3; j++) cg[12 + 3 * i + j] = mh[i] * dp[j];
+        }
     }
 
     // ---- SH colour backward, including the view-direction dependence on the mean ----
     if (a.shs != nullptr) {
-        const float3 cam = make_float3(a.cam[0], a.cam[1], a.cam[2]);
+        float3 cam = make_float3(a.cam[0], a.cam[1], a.cam[2]);
+        if constexpr (TERMS) cam = make_float3(opaque(cam.x), opaque(cam.y), opaque(cam.z));
         const float3 v = make_float3(mean.x - cam.x, mean.y - cam.y, mean.z - cam.z);
         const float len = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z);
         const float x = v.x / len, y = v.y / len, z = v.z / len;
         float* const dsh = sh_row; // in place: gradient row over coefficient row
         float dRGB[3];
 #pragma unroll
-        for (int ch = 0; ch < 3; ch++) dRGB[ch] = (ch == 0 ? rec0.x : ch == 1 ? rec0.y : rec0.z) * (a.clamped[3 * (size_t)idx + ch] ? 0.0f : 1.0f);
+        for (int ch = 0; ch < 3; ch++) dRGB[ch] = (ch == 0 ? rec0.x : ch == 1 ? rec0.y : rec0.z) * (TERMS ? opaque(a.clamped[3 * (size_t)idx + ch] ? 0.0f : 1.0f) : (a.clamped[3 * (size_t)idx + ch] ? 0.0f : 1.0f));
         float ddir[3] = {0, 0, 0};
         const int D = a.D;
 #pragma unroll
@@ -205,24 +268,30 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
             // the coefficients this channel's direction derivative needs, read before their slots are overwritten
             float sh[16];
 #pragma unroll
-            for (int k = 1; k < 16; k++) sh[k] = (k < a.M && k < (D + 1) * (D + 1)) ? sh_row[3 * k + ch] : 0.0f;
-            for (int k = (D + 1) * (D + 1); k < a.M; k++) dsh[3 * k + ch] = 0.0f; // coefficients above the active degree
-            dsh[ch] = kSH_C0 * g;
+            for (int k = 1; k < 16; k++) sh[k] = (k < a.M && k < (D + 1) * (D + 1)) ? (TERMS ? opaque(sh_row[3 * k + ch]) : sh_row[3 * k + ch]) : 0.0f;
+            if constexpr (!TERMS) {
+                for (int k = (D + 1) * (D + 1); k < a.M; k++) dsh[3 * k + ch] = 0.0f; // coefficients above the active degree
+                dsh[ch] = kSH_C0 * g;
+            }
             if (D > 0) {
-                dsh[3 + ch] = (-kSH_C1 * y) * g; dsh[6 + ch] = (kSH_C1 * z) * g; dsh[9 + ch] = (-kSH_C1 * x) * g;
+                if constexpr (!TERMS) { dsh[3 + ch] = (-kSH_C1 * y) * g; dsh[6 + ch] = (kSH_C1 * z) * g; dsh[9 + ch] = (-kSH_C1 * x) * g; }
                 dx = -kSH_C1 * sh[3]; dy = -kSH_C1 * sh[1]; dz = kSH_C1 * sh[2];
                 if (D > 1) {
                     const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                    dsh[12 + ch] = (kSH_C2[0] * xy) * g; dsh[15 + ch] = (kSH_C2[1] * yz) * g; dsh[18 + ch] = (kSH_C2[2] * (2.f * zz - xx - yy)) * g;
-                    dsh[21 + ch] = (kSH_C2[3] * xz) * g; dsh[24 + ch] = (kSH_C2[4] * (xx - yy)) * g;
+                    if constexpr (!TERMS) {
+                        dsh[12 + ch] = (kSH_C2[0] * xy) * g; dsh[15 + ch] = (kSH_C2[1] * yz) * g; dsh[18 + ch] = (kSH_C2[2] * (2.f * zz - xx - yy)) * g;
+                        dsh[21 + ch] = (kSH_C2[3] * xz) * g; dsh[24 + ch] = (kSH_C2[4] * (xx - yy)) * g;
+                    }
                     dx += kSH_C2[0] * y * sh[4] + kSH_C2[2] * 2.f * -x * sh[6] + kSH_C2[3] * z * sh[7] + kSH_C2[4] * 2.f * x * sh[8];
                     dy += kSH_C2[0] * x * sh[4] + kSH_C2[1] * z * sh[5] + kSH_C2[2] * 2.f * -y * sh[6] + kSH_C2[4] * 2.f * -y * sh[8];
                     dz += kSH_C2[1] * y * sh[5] + kSH_C2[2] * 2.f * 2.f * z * sh[6] + kSH_C2[3] * x * sh[7];
                     if (D > 2) {
-                        dsh[27 + ch] = (kSH_C3[0] * y * (3.f * xx - yy)) * g; dsh[30 + ch] = (kSH_C3[1] * xy * z) * g;
-                        dsh[33 + ch] = (kSH_C3[2] * y * (4.f * zz - xx - yy)) * g; dsh[36 + ch] = (kSH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy)) * g;
-                        dsh[39 + ch] = (kSH_C3[4] * x * (4.f * zz - xx - yy)) * g; dsh[42 + ch] = (kSH_C3[5] * z * (xx - yy)) * g;
-                        dsh[45 + ch] = (kSH_C3[6] * x * (xx - 3.f * yy)) * g;
+                        if constexpr (!TERMS) {
+                            dsh[27 + ch] = (kSH_C3[0] * y * (3.f * xx - yy)) * g; dsh[30 + ch] = (kSH_C3[1] * xy * z) * g;
+                            dsh[33 + ch] = (kSH_C3[2] * y * (4.f * zz - xx - yy)) * g; dsh[36 + ch] = (kSH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy)) * g;
+                            dsh[39 + ch] = (kSH_C3[4] * x * (4.f * zz - xx - yy)) * g; dsh[42 + ch] = (kSH_C3[5] * z * (xx - yy)) * g;
+                            dsh[45 + ch] = (kSH_C3[6] * x * (xx - 3.f * yy)) * g;
+                        }
                         dx += (kSH_C3[0] * sh[9] * 3.f * 2.f * xy + kSH_C3[1] * sh[10] * yz + kSH_C3[2] * sh[11] * -2.f * xy +
                                kSH_C3[3] * sh[12] * -3.f * 2.f * xz + kSH_C3[4] * sh[13] * (-3.f * xx + 4.f * zz - yy) +
                                kSH_C3[5] * sh[14] * 2.f * xz + kSH_C3[6] * sh[15] * 3.f * (xx - yy));
@@ -242,7 +311,15 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         dmean.x += ((+sum2 - v.x * v.x) * ddir[0] - v.y * v.x * ddir[1] - v.z * v.x * ddir[2]) * invsum32;
         dmean.y += (-v.x * v.y * ddir[0] + (sum2 - v.y * v.y) * ddir[1] - v.z * v.y * ddir[2]) * invsum32;
         dmean.z += (-v.x * v.z * ddir[0] - v.y * v.z * ddir[1] + (sum2 - v.z * v.z) * ddir[2]) * invsum32;
+        if constexpr (TERMS) { // v = mean - campos: the negated normalisation terms above
+            cg[24] = -(((+sum2 - v.x * v.x) * ddir[0] - v.y * v.x * ddir[1] - v.z * v.x * ddir[2]) * invsum32);
+            cg[25] = -((-v.x * v.y * ddir[0] + (sum2 - v.y * v.y) * ddir[1] - v.z * v.y * ddir[2]) * invsum32);
+            cg[26] = -((-v.x * v.z * ddir[0] - v.y * v.z * ddir[1] + (sum2 - v.z * v.z) * ddir[2]) * invsum32);
+        }
+    } else if constexpr (TERMS) {
+        cg[24] = 0.0f; cg[25] = 0.0f; cg[26] = 0.0f; // precomputed colours: no view direction
     }
+    if constexpr (TERMS) return; // (camera terms complete)
     a.dL_dmean3D[3 * (size_t)idx + 0] = dmean.x;
     a.dL_dmean3D[3 * (size_t)idx + 1] = dmean.y;
     a.dL_dmean3D[3 * (size_t)idx + 2] = dmean.z;
@@ -288,6 +365,28 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
 // 16-byte loads of the whole 256 x 3M block, rows padded to 3M+1 words (conflict-free row access), the gradient
 // written over the coefficients in place, coalesced stores back.  Every output row of every Gaussian is written
 // (zeros for the invisible ones), so none of the dL_d* outputs needs a zero-fill by the caller.
+//
+// CAM = true (camera gradients requested, stp_set_backward_camera_grads): each thread also forms its Gaussian's kCamTerms
+// camera terms (zeros when invisible); the workgroup sums them -- over each wave with DPP / cross-lane adds, then over its
+// four waves in LDS in wave order -- and writes one kCamRow-float row to a.cam_rows[blockIdx.x] with vector stores.  No
+// float atomics: camera_grad_partial_kernel / camera_grad_final_kernel sum the rows in a fixed order.
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v)
+{
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float wave_sum(float v) // every lane ends with the sum of all 64 (lane 0's value is the one used)
+{
+    v += dpp_mov<0xB1>(v);  // quad_perm [1,0,3,2]
+    v += dpp_mov<0x4E>(v);  // quad_perm [2,3,0,1]
+    v += dpp_mov<0x141>(v); // row_half_mirror: the other quad of the 8
+    v += dpp_mov<0x140>(v); // row_mirror: the other 8 of the row
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    return v;
+}
+
+template <bool CAM>
 __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreArgs a)
 {
     extern __shared__ float s_rows[]; // [256][3M + 1]
@@ -297,6 +396,11 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreAr
     const int rows = min(256, a.P - base);
     const int row_len = 3 * a.M, row_stride = row_len + 1;
     const bool have_sh = a.shs != nullptr && a.M > 0;
+    float cg[CAM ? kCamTerms : 1];
+    if constexpr (CAM) {
+#pragma unroll
+        for (int k = 0; k < kCamTerms; k++) cg[k] = 0.0f;
+    }
     if (have_sh) {
         const float* __restrict__ src = a.shs + (size_t)base * row_len;
         const int total = rows * row_len;
@@ -319,7 +423,14 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreAr
     }
     if (idx < a.P) {
         if (a.radii[idx] > 0) {
-            gaussian_backward(a, idx, s_rows + tid * row_stride);
+            if constexpr (CAM) {
+                // the camera terms first (they read the SH coefficients the gradient pass overwrites), in a block of their own behind an
+                // opaque branch: the gradient pass below is the CAM = false kernel's, arithmetic for arithmetic
+                int go = 1;
+                asm volatile("" : "+s"(go));
+                if (go) gaussian_backward<true>(a, idx, s_rows + tid * row_stride, cg);
+            }
+            gaussian_backward<false>(a, idx, s_rows + tid * row_stride, cg);
         } else { // invisible: all gradients are zero
             a.dL_dcolor[3 * (size_t)idx] = 0.0f; a.dL_dcolor[3 * (size_t)idx + 1] = 0.0f; a.dL_dcolor[3 * (size_t)idx + 2] = 0.0f;
             a.dL_dmean2D[3 * (size_t)idx] = 0.0f; a.dL_dmean2D[3 * (size_t)idx + 1] = 0.0f;
@@ -356,12 +467,100 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreAr
             }
         }
     }
+    if constexpr (CAM) {
+        __shared__ float s_cam[4][kCamRow]; // per-wave sums
+        const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+        for (int k = 0; k < kCamTerms; k++) {
+            const float s = wave_sum(cg[k]);
+            if (lane == 0) s_cam[wave][k] = s;
+        }
+        __syncthreads();
+        if (tid < kCamRow / 4) { // 8 threads, 4 columns each: the four waves in order, one 16-byte store
+            float o[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int k = 4 * tid + q;
+                o[q] = k < kCamTerms ? ((s_cam[0][k] + s_cam[1][k]) + s_cam[2][k]) + s_cam[3][k] : 0.0f;
+            }
+            reinterpret_cast<float4*>(a.cam_rows + (size_t)blockIdx.x * kCamRow)[tid] = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    }
 }
+
+// Sum of the per-workgroup rows, in two fixed-order steps (no atomics: the result depends only on the rows and their count).
+// Step 1: block g of `parts` sums rows [g * n / parts, (g + 1) * n / parts) in double -- 32 groups of 32 lanes, lane = column, group r
+// takes every 32nd row -- and writes one row of kCamRow doubles.  Step 2: one block sums the `parts` rows and writes the three outputs
+// in full, the entries the forward never reads as zeros.
+__global__ void __launch_bounds__(1024) camera_grad_partial_kernel(const float* __restrict__ rows, int n_rows, int parts, double* __restrict__ partial)
+{
+    __shared__ double s[32][kCamRow];
+    const int c = (int)threadIdx.x & 31, grp = (int)threadIdx.x >> 5;
+    const int r0 = (int)((long long)n_rows * blockIdx.x / parts), r1 = (int)((long long)n_rows * (blockIdx.x + 1) / parts);
+    double acc = 0.0;
+    for (int r = r0 + grp; r < r1; r += 32) acc += (double)rows[(size_t)r * kCamRow + c];
+    s[grp][c] = acc;
+    __syncthreads();
+    if (grp == 0) {
+        double t = 0.0;
+        for (int k = 0; k < 32; k++) t += s[k][c];
+        partial[(size_t)blockIdx.x * kCamRow + c] = t;
+    }
+}
+
+__global__ void __launch_bounds__(1024) camera_grad_final_kernel(const double* __restrict__ partial, int parts, float* __restrict__ dview,
+                                                                 float* __restrict__ dproj, float* __restrict__ dcam)
+{
+    __shared__ double s[32][kCamRow];
+    const int tid = (int)threadIdx.x, c = tid & 31, grp = tid >> 5;
+    double acc = 0.0;
+    for (int g = grp; g < parts; g += 32) acc += partial[(size_t)g * kCamRow + c];
+    s[grp][c] = acc;
+    __syncthreads();
+    if (grp == 0) {
+        double t = 0.0;
+        for (int k = 0; k < 32; k++) t += s[k][c];
+        s[0][c] = t; // (each lane reads its own column above and writes it here: no other lane reads s[0][c] before the barrier)
+    }
+    __syncthreads();
+    if (tid < 16) { // view[i][j]: column 3 is never read
+        const int i = tid >> 2, j = tid & 3;
+        dview[tid] = j == 3 ? 0.0f : (float)s[0][3 * i + j];
+    } else if (tid < 32) { // proj[i][j]: column 2 is never read
+        const int i = (tid - 16) >> 2, j = (tid - 16) & 3;
+        dproj[tid - 16] = j == 2 ? 0.0f : (float)s[0][12 + 3 * i + (j == 3 ? 2 : j)];
+    } else if (tid < 35) {
+        dcam[tid - 32] = (float)s[0][24 + tid - 32];
+    }
+}
+
+constexpr int kCamMaxParts = 256;
+int camera_grad_parts(int n_rows) { return max(1, min(kCamMaxParts, (n_rows + 191) / 192)); }
 
 } // namespace
 
+size_t camera_grad_workspace_bytes(int P)
+{
+    const size_t n_rows = (size_t)(P > 0 ? (P + 255) / 256 : 0);
+    return n_rows * kCamRow * sizeof(float) + (size_t)kCamMaxParts * kCamRow * sizeof(double);
+}
+
+hipError_t launch_camera_grad_finalize(int P, const CameraGradRequest& cam, hipStream_t st)
+{
+    const int n_rows = P > 0 ? (P + 255) / 256 : 0;
+    const int parts = camera_grad_parts(n_rows);
+    const float* rows = reinterpret_cast<const float*>(cam.workspace);
+    double* partial = reinterpret_cast<double*>(static_cast<char*>(cam.workspace) + (size_t)n_rows * kCamRow * sizeof(float));
+    hipLaunchKernelGGL(camera_grad_partial_kernel, dim3(parts), dim3(1024), 0, st, rows, n_rows, parts, partial);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(camera_grad_final_kernel, dim3(1), dim3(1024), 0, st, (const double*)partial, parts, cam.dL_dview, cam.dL_dproj, cam.dL_dcam);
+    return hipGetLastError();
+}
+
 hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState& g, const int* radii, const BackwardParams& bw, hipStream_t st)
 {
+    const bool cam = bw.cam.dL_dview != nullptr; // (the caller has refused a chunked half with a request)
     BwdPreArgs a;
     a.P = f.P; a.D = f.D; a.M = f.M; a.proper_ewa_scaling = f.s.proper_ewa_scaling;
     a.h_x = f.focal_x; a.h_y = f.focal_y; a.tan_fovx = f.tan_fovx; a.tan_fovy = f.tan_fovy; a.scale_modifier = f.scale_modifier;
@@ -370,9 +569,11 @@ hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState&
     a.view = f.viewmatrix; a.proj = f.projmatrix; a.cam = f.cam_pos;
     a.dL_dmean2D = bw.dL_dmean2D; a.grad_rec = bw.grad_rec; a.grad_stride = bw.grad_stride; a.clear_rec = bw.clear_rec; a.dL_dopacity = bw.dL_dopacity; a.dL_dcolor = bw.dL_dcolor;
     a.dL_dmean3D = bw.dL_dmean3D; a.dL_dcov3D = bw.dL_dcov3D; a.dL_dsh = bw.dL_dsh; a.dL_dscale = bw.dL_dscale; a.dL_drot = bw.dL_drot;
+    a.cam_rows = cam ? reinterpret_cast<float*>(bw.cam.workspace) : nullptr;
+    const void* kernel = cam ? reinterpret_cast<const void*>(preprocess_backward_kernel<true>) : reinterpret_cast<const void*>(preprocess_backward_kernel<false>);
     const size_t lds = (a.shs != nullptr && a.M > 0) ? (size_t)256 * (3 * a.M + 1) * sizeof(float) : 0;
     if (lds > 64 * 1024) { // above the default dynamic-LDS limit (M > 21: no SH degree the reference knows)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(preprocess_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     const int n_blocks = (f.P + 255) / 256;
@@ -383,7 +584,13 @@ hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState&
     }
     a.block0 = b0;
     if (b1 <= b0) return hipSuccess;
-    hipLaunchKernelGGL(preprocess_backward_kernel, dim3(b1 - b0), dim3(256), lds, st, a);
+    if (cam) {
+        hipLaunchKernelGGL(preprocess_backward_kernel<true>, dim3(b1 - b0), dim3(256), lds, st, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        return launch_camera_grad_finalize(f.P, bw.cam, st);
+    }
+    hipLaunchKernelGGL(preprocess_backward_kernel<false>, dim3(b1 - b0), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

@@ -159,7 +159,17 @@ struct FrameParams {
     int wild_cov; // forward, after the status read-back: some visible Gaussian has a Sigma^-1 entry >= 1e36 or not finite (depth keys then take the reciprocal with its domain check)
 };
 
+// stp_set_backward_camera_grads: the three outputs and the workspace (camera_grad_workspace_bytes) of one request
+struct CameraGradRequest {
+    float* dL_dview = nullptr; // nullptr: no request
+    float* dL_dproj = nullptr;
+    float* dL_dcam = nullptr;
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+};
+
 struct BackwardParams {
+    CameraGradRequest cam; // the per-Gaussian half also sums the camera gradients (stp_backward.hip)
     const float* pixel_colors;
     const float* dL_dpix;
     float* grad_rec;    // P x grad_stride: written by the render half, read by the per-Gaussian half
@@ -205,6 +215,9 @@ hipError_t launch_render_debug_finish(const FrameParams& f, const ImageState& im
 hipError_t launch_render_backward(const FrameParams& f, const GeometryState& g, const BinningState& b, const ImageState& img,
                                   const BackwardParams& bw, hipStream_t st, std::string* err);
 hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState& g, const int* radii, const BackwardParams& bw, hipStream_t st);
+size_t camera_grad_workspace_bytes(int P);
+// sums the per-workgroup rows the CAM kernel wrote (none for P == 0) into the three outputs; launch_preprocess_backward calls it itself
+hipError_t launch_camera_grad_finalize(int P, const CameraGradRequest& cam, hipStream_t st);
 hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t st);
 
 uint32_t higher_msb(uint32_t n);

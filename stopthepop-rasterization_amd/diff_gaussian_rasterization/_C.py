@@ -39,6 +39,25 @@ class StpSettings(ctypes.Structure):
 
 _lib_override = None
 
+# exports newer than ABI 7's first release: resolved when present (name -> (argtypes, restype))
+_OPTIONAL_SYMBOLS = {
+    "stp_camera_grad_workspace_bytes": ([ctypes.c_int], ctypes.c_size_t),
+    "stp_set_backward_camera_grads": ([ctypes.c_void_p] * 4 + [ctypes.c_size_t], None),
+}
+
+
+def _require(name: str):
+    """An optional export of the loaded library; RuntimeError naming it when the library predates it."""
+    L = _load()
+    if not hasattr(L, name):
+        raise RuntimeError(f"{library_path()} does not export {name} (a library built before camera gradients): rebuild it")
+    return getattr(L, name)
+
+
+def camera_grad_workspace_bytes(P: int) -> int:
+    """Bytes of the device workspace a backward with camera gradients needs for P Gaussians (include/stp_raster.h)."""
+    return int(_require("stp_camera_grad_workspace_bytes")(int(P)))
+
 
 def library_path() -> str:
     p = _lib_override or os.environ.get("STP_RASTER_LIB", os.path.join(_HERE, _LIB_NAME))
@@ -96,6 +115,10 @@ def _load():
     L.stp_binning_layout_count.restype = ci
     L.stp_forget_buffer.argtypes = [vp]
     L.stp_forget_buffer.restype = None
+    for name in _OPTIONAL_SYMBOLS:   # (an older library without them still loads: camera_grad_workspace_bytes / camera_grads=True raise)
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = _OPTIONAL_SYMBOLS[name]
     if L.stp_abi_version() != 7:
         raise ImportError("libstp_raster.so ABI version mismatch")
     _lib = L
@@ -320,9 +343,14 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, tan_fovx, tan_fovy,
                                  pixel_colors, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                                 imageBuffer, settings_dict, debug, phases=3, partial=None, chunk=None, outputs=None):
+                                 imageBuffer, settings_dict, debug, phases=3, partial=None, chunk=None, outputs=None,
+                                 camera_grads=False):
     """== RasterizeGaussiansBackwardCUDA (reference rasterize_points.cu:140-232).
     Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
+
+    camera_grads=True (extension, include/stp_raster.h: stp_set_backward_camera_grads): three more, dL_dviewmatrix, dL_dprojmatrix and
+    dL_dcampos, in the shapes of viewmatrix / projmatrix / campos, from the same per-Gaussian intermediates (per-Gaussian half only; a
+    chunked half refuses them).
 
     Extension for tile-row sharding (not in the reference): phases=1 runs only the render half and
     returns its per-Gaussian partial sums as the library's (P,16) gradient records (stp_raster.h);
@@ -335,10 +363,13 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
         if not (0 <= k < K <= 255) or (int(phases) & 1):
             raise ValueError("chunk = (k, K) with 0 <= k < K <= 255, per-Gaussian half only")
         phases = int(phases) | (K << 8) | (k << 16)
+    if camera_grads:
+        _require("stp_set_backward_camera_grads")
     out = (_host or _native()).rasterize_gaussians_backward(
         background, means3D, radii, opacities, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         inv_viewprojmatrix, tan_fovx, tan_fovy, pixel_colors, dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer,
-        imageBuffer, settings_dict, bool(debug), _records_log(settings_dict), int(phases), partial, None if outputs is None else list(outputs))
+        imageBuffer, settings_dict, bool(debug), _records_log(settings_dict), int(phases), partial, None if outputs is None else list(outputs),
+        bool(camera_grads))
     return out[0] if (int(phases) & 3) == 1 else tuple(out)
 
 

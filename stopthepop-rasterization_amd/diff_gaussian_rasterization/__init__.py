@@ -39,8 +39,99 @@ def cpu_deep_copy_tuple(input_tuple):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings):
+    rs = raster_settings
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (rs.viewmatrix, rs.projmatrix, rs.campos)):
+        # camera gradients (pose refinement): the camera tensors become explicit inputs of a second Function
+        return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                               rs.viewmatrix, rs.projmatrix, rs.campos, raster_settings)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings)
+
+
+def _forward_body(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos, rs,
+                  save_camera=False):
+    """The forward both autograd Functions share (the camera tensors are rs's own, or the camera Function's explicit inputs, which
+    save_camera=True saves for the backward behind the twelve tensors both Functions save)."""
+    sdict = rs.settings.to_dict()
+    ctx.log_lease = None
+    if any(ctx.needs_input_grad) and not rs.render_depth:
+        # a backward can follow: let the hierarchical / k-buffer forward record each pixel's blend order so that the
+        # backward replays it instead of re-sorting (extension of ours; ignored by the other sort modes) -- unless the
+        # backward-mode policy says otherwise (_C.set_backward_mode / STP_BACKWARD / settings._backward_mode: "resort",
+        # or "auto" with the device's blend-log budget used up by forwards that still wait for their backward).
+        # Not with render_depth: the depth-visualisation forward records no log, and a backward through it
+        # (meaningless in the reference too, but memory-safe there) must take the re-sorting path.
+        mode = sdict.get("_backward_mode")
+        uses_log = int(sdict["sort_settings"]["sort_mode"]) in (2, 3)
+        if uses_log and means3D.is_cuda and means3D.size(0) != 0 and _C.decide_recording(mode, means3D.device, rs.image_width, rs.image_height):
+            sdict["_record_blend_log"] = True
+            sdict["_backward_mode"] = "replay"
+            ctx.log_lease = _C.LogLease(_C._device_index(means3D.device), _C.blend_log_bytes(rs.image_width, rs.image_height))
+        else:
+            sdict["_backward_mode"] = "resort"
+    ctx.settings_dict = sdict
+    # positional layout of _C.rasterize_gaussians (22 arguments)
+    args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+            viewmatrix, projmatrix, rs.inv_viewprojmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
+            rs.image_width, sh, rs.sh_degree, campos, rs.prefiltered, sdict, rs.render_depth,
+            rs.debug)
+    if rs.debug:
+        cpu_args = cpu_deep_copy_tuple(args)  # snapshot before anything can corrupt them
+        try:
+            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args)
+        except Exception as ex:
+            torch.save(cpu_args, "snapshot_fw.dump")
+            print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+            raise ex
+    else:
+        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args)
+
+    if ctx.log_lease is not None:   # the library chose the log's depth for this frame: account what the buffer really holds
+        ctx.log_lease.resize(_C.blend_log_bytes(rs.image_width, rs.image_height, depth=_C.blend_log_depth(imgBuffer)))
+    ctx.raster_settings = rs
+    ctx.num_rendered = num_rendered
+    ctx.img_generation = _C.scratch_generation(imgBuffer)
+    ctx.bin_generation = _C.scratch_generation(binningBuffer)
+    ctx.save_for_backward(colors_precomp, means3D, opacities, scales, rotations, cov3Ds_precomp, radii, sh, color,
+                          geomBuffer, binningBuffer, imgBuffer, *((viewmatrix, projmatrix, campos) if save_camera else ()))
+    # radii is an integer output: without these two lines autograd materialises a (P,) zero "gradient" for it in
+    # every backward (a 4 MB fill kernel per step at 1 M Gaussians)
+    ctx.mark_non_differentiable(radii)
+    ctx.set_materialize_grads(False)
+    return color, radii
+
+
+def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_grads=False):
+    """The backward both autograd Functions share: the eight Gaussian gradients of _C.rasterize_gaussians_backward (+ the three camera
+    gradients with camera_grads=True)."""
+    num_rendered = ctx.num_rendered
+    rs = ctx.raster_settings
+    (colors_precomp, means3D, opacities, scales, rotations, cov3Ds_precomp, radii, sh, color, geomBuffer,
+     binningBuffer, imgBuffer) = ctx.saved_tensors[:12]
+    _C.check_scratch(imgBuffer, ctx.img_generation)
+    _C.check_scratch(binningBuffer, ctx.bin_generation)
+    if grad_out_color is None:  # (set_materialize_grads(False): cannot happen while the image is the only differentiable output)
+        grad_out_color = torch.zeros_like(color)
+    # positional layout of _C.rasterize_gaussians_backward (25 arguments)
+    args = (rs.bg, means3D, radii, opacities, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+            viewmatrix, projmatrix, rs.inv_viewprojmatrix, rs.tanfovx, rs.tanfovy, color, grad_out_color, sh,
+            rs.sh_degree, campos, geomBuffer, num_rendered, binningBuffer, imgBuffer, ctx.settings_dict,
+            rs.debug)
+    kw = {"camera_grads": True} if camera_grads else {}
+    if rs.debug:
+        cpu_args = cpu_deep_copy_tuple(args)
+        try:
+            out = _C.rasterize_gaussians_backward(*args, **kw)
+        except Exception as ex:
+            torch.save(cpu_args, "snapshot_bw.dump")
+            print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+            raise ex
+    else:
+        out = _C.rasterize_gaussians_backward(*args, **kw)
+    _C.release_scratch(imgBuffer); _C.release_scratch(binningBuffer)  # the blend log goes back to the library's free list
+    if ctx.log_lease is not None:
+        ctx.log_lease.release()
+    return out
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -48,87 +139,41 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings):
         rs = raster_settings
-        sdict = rs.settings.to_dict()
-        ctx.log_lease = None
-        if any(ctx.needs_input_grad) and not rs.render_depth:
-            # a backward can follow: let the hierarchical / k-buffer forward record each pixel's blend order so that the
-            # backward replays it instead of re-sorting (extension of ours; ignored by the other sort modes) -- unless the
-            # backward-mode policy says otherwise (_C.set_backward_mode / STP_BACKWARD / settings._backward_mode: "resort",
-            # or "auto" with the device's blend-log budget used up by forwards that still wait for their backward).
-            # Not with render_depth: the depth-visualisation forward records no log, and a backward through it
-            # (meaningless in the reference too, but memory-safe there) must take the re-sorting path.
-            mode = sdict.get("_backward_mode")
-            uses_log = int(sdict["sort_settings"]["sort_mode"]) in (2, 3)
-            if uses_log and means3D.is_cuda and means3D.size(0) != 0 and _C.decide_recording(mode, means3D.device, rs.image_width, rs.image_height):
-                sdict["_record_blend_log"] = True
-                sdict["_backward_mode"] = "replay"
-                ctx.log_lease = _C.LogLease(_C._device_index(means3D.device), _C.blend_log_bytes(rs.image_width, rs.image_height))
-            else:
-                sdict["_backward_mode"] = "resort"
-        ctx.settings_dict = sdict
-        # positional layout of _C.rasterize_gaussians (22 arguments)
-        args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-                rs.viewmatrix, rs.projmatrix, rs.inv_viewprojmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
-                rs.image_width, sh, rs.sh_degree, rs.campos, rs.prefiltered, sdict, rs.render_depth,
-                rs.debug)
-        if rs.debug:
-            cpu_args = cpu_deep_copy_tuple(args)  # snapshot before anything can corrupt them
-            try:
-                num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args)
-            except Exception as ex:
-                torch.save(cpu_args, "snapshot_fw.dump")
-                print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                raise ex
-        else:
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args)
-
-        if ctx.log_lease is not None:   # the library chose the log's depth for this frame: account what the buffer really holds
-            ctx.log_lease.resize(_C.blend_log_bytes(rs.image_width, rs.image_height, depth=_C.blend_log_depth(imgBuffer)))
-        ctx.raster_settings = rs
-        ctx.num_rendered = num_rendered
-        ctx.img_generation = _C.scratch_generation(imgBuffer)
-        ctx.bin_generation = _C.scratch_generation(binningBuffer)
-        ctx.save_for_backward(colors_precomp, means3D, opacities, scales, rotations, cov3Ds_precomp, radii, sh, color,
-                              geomBuffer, binningBuffer, imgBuffer)
-        # radii is an integer output: without these two lines autograd materialises a (P,) zero "gradient" for it in
-        # every backward (a 4 MB fill kernel per step at 1 M Gaussians)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii
+        return _forward_body(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.viewmatrix, rs.projmatrix,
+                             rs.campos, rs)
 
     @staticmethod
     def backward(ctx, grad_out_color, _):
-        num_rendered = ctx.num_rendered
         rs = ctx.raster_settings
-        (colors_precomp, means3D, opacities, scales, rotations, cov3Ds_precomp, radii, sh, color, geomBuffer,
-         binningBuffer, imgBuffer) = ctx.saved_tensors
-        _C.check_scratch(imgBuffer, ctx.img_generation)
-        _C.check_scratch(binningBuffer, ctx.bin_generation)
-        if grad_out_color is None:  # (set_materialize_grads(False): cannot happen while the image is the only differentiable output)
-            grad_out_color = torch.zeros_like(color)
-        # positional layout of _C.rasterize_gaussians_backward (25 arguments)
-        args = (rs.bg, means3D, radii, opacities, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-                rs.viewmatrix, rs.projmatrix, rs.inv_viewprojmatrix, rs.tanfovx, rs.tanfovy, color, grad_out_color, sh,
-                rs.sh_degree, rs.campos, geomBuffer, num_rendered, binningBuffer, imgBuffer, ctx.settings_dict,
-                rs.debug)
-        if rs.debug:
-            cpu_args = cpu_deep_copy_tuple(args)
-            try:
-                out = _C.rasterize_gaussians_backward(*args)
-            except Exception as ex:
-                torch.save(cpu_args, "snapshot_bw.dump")
-                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                raise ex
-        else:
-            out = _C.rasterize_gaussians_backward(*args)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = out
-        _C.release_scratch(imgBuffer); _C.release_scratch(binningBuffer)  # the blend log goes back to the library's free list
-        if ctx.log_lease is not None:
-            ctx.log_lease.release()
+         grad_rotations) = _backward_body(ctx, grad_out_color, rs.viewmatrix, rs.projmatrix, rs.campos)
         # one gradient per forward input, in forward's order
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                 grad_cov3Ds_precomp, None)
+
+
+class _RasterizeGaussiansCamera(torch.autograd.Function):
+    """_RasterizeGaussians with viewmatrix, projmatrix and campos as explicit inputs that get gradients (include/stp_raster.h:
+    stp_set_backward_camera_grads).  rasterize_gaussians() routes here only while grad mode is on and one of the three requires grad.
+    The three are independent inputs, as the forward reads them; inv_viewprojmatrix, the intrinsics and bg get none."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos,
+                raster_settings):
+        # (needs_input_grad counts the camera inputs: a frame where only the camera requires grad records the blend log too; the
+        # camera tensors are saved like the Gaussians: an in-place change before the backward raises instead of giving wrong gradients)
+        return _forward_body(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos,
+                             raster_settings, save_camera=True)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _):
+        viewmatrix, projmatrix, campos = ctx.saved_tensors[12:15]
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+         grad_rotations, grad_view, grad_proj, grad_campos) = _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, True)
+        grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
+                 grad_cov3Ds_precomp, grad_view, grad_proj, grad_campos)
+        # None for every input that does not require grad (frozen Gaussians: the camera's gradients only)
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad)) + (None,)
 
 
 class SortMode(IntEnum):
