@@ -190,18 +190,7 @@ __device__ __forceinline__ void init_bwd_pixel(BwdPixel& b, const RenderArgs& a,
     }
 }
 
-// Forward blend of the head entry; false = pixel saturated (nothing accumulated).
-__device__ __forceinline__ bool blend_forward(FwdPixel& p, const float* __restrict__ features, int id, float alpha)
-{
-    const float test_T = p.T * (1.0f - alpha);
-    if (test_T < T_THRESHOLD) return false;
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) p.C[ch] += features[3 * (size_t)id + ch] * alpha * p.T;
-    p.T = test_T;
-    return true;
-}
-
-// same, with the colour already in registers (prefetched when the entry became the queue front)
+// Forward blend of the head entry, its colour in registers; false = pixel saturated (nothing accumulated).
 __device__ __forceinline__ bool blend_forward_c(FwdPixel& p, const float (&c)[3], float alpha)
 {
     const float test_T = p.T * (1.0f - alpha);
@@ -313,39 +302,15 @@ template <int CAP> struct Window {
         }
         num++;
     }
-    // Branch-free form of insert() for the hot paths: inserts only where `pass` holds.  It reproduces the swap
-    // loop above exactly, ties included: the value carried through the loop is always max(candidate, depth[s-1]),
-    // so slot s swaps iff  d < depth[s]  and not (d < depth[s-1] and depth[s-1] == depth[s]); the payload follows
-    // the same chain, the depths themselves are one median-of-three per slot.
-    __device__ __forceinline__ void insert_if(bool pass, float d, int gid, float st)
-    {
-        const float c = pass ? d : FLT_MAX; // FLT_MAX is smaller than nothing: no slot changes
-        bool sw[CAP];
-        sw[0] = c < depth[0];
-#pragma unroll
-        for (int s = 1; s < CAP; s++) // (bitwise operators: no short-circuit control flow)
-            sw[s] = (bool)((int)(c < depth[s]) & ~((int)(c < depth[s - 1]) & (int)(depth[s - 1] == depth[s])) & 1);
-#pragma unroll
-        for (int s = 0; s < CAP; s++) {
-            const int oi = id[s];
-            const float os = store[s];
-            id[s] = sw[s] ? gid : oi;
-            store[s] = sw[s] ? st : os;
-            gid = sw[s] ? oi : gid;
-            st = sw[s] ? os : st;
-        }
-#pragma unroll
-        for (int s = CAP - 1; s > 0; s--) depth[s] = __builtin_amdgcn_fmed3f(depth[s - 1], depth[s], c);
-        depth[0] = fminf(depth[0], c);
-        num += (int)pass;
-    }
     // ---- the always-full form used by the forward head level -------------------------------------------------------
     // The queue always holds CAP slots: its k real entries in ascending order, preceded by CAP - k PADS of depth
     // -FLT_MAX (store 0).  One step = the reference's "pop the front if the queue is full, then insert the candidate if
     // it passes": the front slot is consumed by the caller -- a pad when the queue was not full, i.e. exactly when the
     // reference does not pop -- and replace_front() puts the candidate (or a new pad, when it did not pass) into the
     // remaining CAP - 1 slots.  No separate shift, no element count: slot s - 1 receives what the reference's swap loop
-    // leaves in slot s of the popped queue (same tie rule as insert_if), the last slot the element carried out.
+    // leaves in slot s of the popped queue, the last slot the element carried out.  Tie rule of that loop: the value it carries is always
+    // max(candidate, depth[s-1]), so slot s swaps iff  c < depth[s]  and not (c < depth[s-1] and depth[s-1] == depth[s]); the payload
+    // follows the same chain, the depths themselves are one median-of-three per slot.
     __device__ __forceinline__ void init_padded()
     {
         num = 0;
@@ -384,18 +349,6 @@ template <int CAP> struct Window {
         } else depth[0] = c;
         id[CAP - 1] = gid;
         store[CAP - 1] = st;
-    }
-    // pop() where `need` holds, as selects
-    __device__ __forceinline__ void pop_if(bool need)
-    {
-#pragma unroll
-        for (int i = 1; i < CAP; i++) {
-            depth[i - 1] = need ? depth[i] : depth[i - 1];
-            store[i - 1] = need ? store[i] : store[i - 1];
-            id[i - 1] = need ? id[i] : id[i - 1];
-        }
-        depth[CAP - 1] = need ? FLT_MAX : depth[CAP - 1];
-        num -= (int)need;
     }
     __device__ __forceinline__ void pop()
     {

@@ -21,7 +21,7 @@
 //     with the 4 new keys exchanged through DPP quad broadcasts (no LDS, no ds_bpermute).
 //   * a head feed fetches the four entries' records once per quad (lane q fetches entry q); the candidate
 //     evaluation takes them as DPP quad_perm OPERANDS of its multiplies (quad_mul / quad_fma), the head level
-//     is straight-line predicated code (Window::insert_if, pop_forward).
+//     is straight-line predicated code (head_candidate of stp_render_wave.h, Window::replace_front, pop_forward).
 //   * the head queue and the blend state are registers (compile-time indexed); the tail and mid rays sit in LDS.
 //
 // Template: HEAD = per-pixel queue, MID = 2x2 queue (8,12,20), CULL = hierarchical_4x4_culling, MODE = forward /
@@ -29,7 +29,7 @@
 // workgroup-shared LDS window; since the blend log only the fallback for tiles whose log overflowed) / recording
 // forward (writes the blend log that stp_render_replay.hip walks) / forward of the debug depth visualisation.
 #include "stp_internal.h"
-#include "stp_blend.h"
+#include "stp_render_wave.h"
 
 namespace stp {
 
@@ -103,13 +103,6 @@ struct HierLds { // dynamic-LDS carve, per workgroup (16 sub-tiles)
     static __host__ __device__ constexpr size_t total(int MID, int mode) { return mode == 1 ? wave_mask(MID) + 16 : hfifo(MID) + 64 * (size_t)HF_CAP * 4; }
 };
 
-__device__ __forceinline__ int hier_remap_tile(int wg, int n_wg)
-{
-    const int q = n_wg >> 3, r = n_wg & 7;
-    const int xcd = wg & 7, k = wg >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-
 // MODE: 0 = forward, 1 = backward by re-running the resort (the reference's scheme), 2 = forward that also records
 // every pixel's blend order (the training forward; its backward is the replay kernel of stp_render_replay.hip).
 // launch bounds: 4 waves per SIMD (<= 128 VGPRs) for the forward passes, 3 (<= 168) for the backward pass
@@ -125,42 +118,35 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     constexpr bool BACKWARD = MODE == MODE_BWD;
     constexpr bool RECORD = MODE == MODE_FWD_RECORD;
     constexpr bool DEPTHVIZ = MODE == MODE_FWD_DEPTH; // accumulate depth * alpha * T instead of colour (reference :1005-1008, stopthepop_common.cuh:264-282)
-    constexpr bool USE_POS = true; // queue payload: the entry's position in the tile list (relative to range.x) in every mode
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int OLDN = (MID - 4) / 4; // old mid entries owned per lane
 
+    // thread -> pixel: wave_pixel_map() of stp_render_wave.h, written out.  The one piece of the scaffold this kernel keeps local: taken from
+    // the function (same statements, same order) the default recording forwards -- 96 VGPRs for five waves per SIMD -- spill one more
+    // register (<4, 8, true, MODE_FWD_RECORD, true>: 0 -> 1, without culling 4 -> 5; profiles/EXPERIMENTS.md, "shared scaffold").
     const int lane = (int)(threadIdx.x & 63);
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // wave = sub-tile row inside the tile (wave-uniform: an SGPR)
     const int s = lane >> 4;               // sub-tile (DPP row) inside the wave
     const int x = lane & 15;               // lane inside the sub-tile
     const int m = x >> 2;                  // quad inside the sub-tile
     const int q = x & 3;                   // lane inside the quad
-
-    const int rows = a.ty1 - a.ty0;
-    const int t = a.tile_order ? (int)a.tile_order[blockIdx.x] : hier_remap_tile((int)blockIdx.x, a.gx * rows);
-    const int tile_x = t % a.gx, tile_y = a.ty0 + t / a.gx;
-    const uint2 range = a.ranges[tile_y * a.gx + tile_x];
-    if constexpr (BACKWARD) {
-        // fallback duty only: when the forward recorded blend logs, this kernel handles just the tiles whose log overflowed
-        if (a.flag_mode == 1 && a.tile_flags[tile_y * a.gx + tile_x] == 0u) return;
-    }
-
+    const int t = workgroup_tile(a);
+    const int tile_x = t % a.gx, tile_y = a.ty0 + t / a.gx, tile = tile_y * a.gx + tile_x;
+    const uint2 range = a.ranges[tile];
     const int cx = tile_x * TILE + 4 * s, cy = tile_y * TILE + 4 * w; // my sub-tile's corner pixel
     const int px = cx + 2 * (m & 1) + (q & 1), py = cy + 2 * (m >> 1) + (q >> 1);
     const bool inside = px < a.W && py < a.H;
+    if constexpr (BACKWARD) {
+        // fallback duty only: when the forward recorded blend logs, this kernel handles just the tiles whose log overflowed
+        if (a.flag_mode == 1 && a.tile_flags[tile] == 0u) return;
+    }
     bool active = inside;
     if constexpr (!BACKWARD) {
         // An empty tile is background.  Not only a shortcut: the forward's pads and stand-ins read "entry 0 of the tile's list" and multiply it
         // by a zero weight, which is harmless only while that entry exists -- in a frame WITHOUT ANY entry (num_rendered == 0 behind a
         // run-ahead launch) the record arrays are uninitialised memory, and 0 x NaN is NaN (found by tools/fuzz_parity.py, round 5).
         if (range.y <= range.x) {
-            if (inside) {
-                const size_t N = (size_t)a.W * a.H, pid = (size_t)a.W * py + px;
-                a.final_T[pid] = 1.0f;
-                if constexpr (RECORD) a.n_contrib[pid] = 0u;
-                if constexpr (DEPTHVIZ) { a.out_color[pid] = 0.0f; a.out_color[N + pid] = 1.0f; }
-                else { a.out_color[pid] = a.bg[0]; a.out_color[N + pid] = a.bg[1]; a.out_color[2 * N + pid] = a.bg[2]; }
-            }
+            if (inside) write_background_pixel<DEPTHVIZ, RECORD>(a, px, py);
             return;
         }
     }
@@ -171,7 +157,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         // holds yet; the hand-off to the render body below is the gather kernel's own between its passes.  Longer lists stay that kernel's.
         const int n = (int)(range.y - range.x); // (>= 1 here)
         if (a.fused_gather && n <= TS_SMALL) {
-            tile_sort_gather_lds(a.gather, reinterpret_cast<uint64_t*>(smem), tile_y * a.gx + tile_x, range, n, (int)threadIdx.x);
+            tile_sort_gather_lds(a.gather, reinterpret_cast<uint64_t*>(smem), tile, range, n, (int)threadIdx.x);
             __threadfence_block();
             __syncthreads();
         }
@@ -258,25 +244,17 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     const float4* const eD = a.entD + range.x;
     const float4* const eF = a.entF + range.x;
     const int list_last = max((int)(range.y - range.x) - 1, 0);
-    // entry record row `pos` of a list-ordered array: wave-uniform base (an SGPR pair) + one 32-bit byte offset, i.e.
-    // `global_load_dwordx4 v, v_off, s[base]` with no 64-bit address arithmetic (v_lshl_add_u64 issues at half rate)
-    auto ent_row = [&](const float4* base, int pos) __attribute__((always_inline)) -> float4 {
-        return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + ((uint32_t)pos << 4));
-    };
     int staged = 0; // list positions staged so far (workgroup-uniform); the ring covers [staged - BWD_RING, staged)
     int ccount = 0; // entries so far that survived culling for at least one of the tile's 16 sub-tiles (workgroup-uniform)
     auto to_id = [&](int v) __attribute__((always_inline)) -> int {
-        if constexpr (!USE_POS) return v;
-        else {
-            // the ring first (a plain LDS read: v = -1 reads slot BWD_RING-1, harmlessly); the few positions that have
-            // left the ring take the memory path together, in a wave-uniform branch that is almost never entered
-            int r = ring[v & (BWD_RING - 1)];
-            const bool old = v >= 0 && v < staged - BWD_RING;
-            if (__builtin_expect(__any(old), 0)) {
-                if (old) r = (int)a.point_list[range.x + min(v, list_last)];
-            }
-            return v < 0 ? -1 : r;
+        // the ring first (a plain LDS read: v = -1 reads slot BWD_RING-1, harmlessly); the few positions that have
+        // left the ring take the memory path together, in a wave-uniform branch that is almost never entered
+        int r = ring[v & (BWD_RING - 1)];
+        const bool old = v >= 0 && v < staged - BWD_RING;
+        if (__builtin_expect(__any(old), 0)) {
+            if (old) r = (int)a.point_list[range.x + min(v, list_last)];
         }
+        return v < 0 ? -1 : r;
     };
     if constexpr (BACKWARD) {
         for (int i = (int)threadIdx.x; i < BWD_WIN; i += 256) {
@@ -296,7 +274,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     // stores: 1.49 -> 1.79 ms.)
     // Addressing: the wave's slice is a wave-uniform base (SGPR pair) and the lane keeps ONE 32-bit cursor, so a store is
     // `global_store_short v_off, v_pos, s[base]` with no 64-bit address arithmetic in the blend step.
-    char* const log_wave = RECORD ? log_wave_slice(a.blend_log, tile_y * a.gx + tile_x, __builtin_amdgcn_readfirstlane(w), a.log_depth) : nullptr;
+    char* const log_wave = RECORD ? log_wave_slice(a.blend_log, tile, __builtin_amdgcn_readfirstlane(w), a.log_depth) : nullptr;
     // (rows [record][lane], stp_blend.h: the cursor is 2 * records so far -- also beyond the log's depth --, the address (cursor << 6) | 2 * lane)
     const uint32_t log_cap2 = 2u * (uint32_t)a.log_depth; // (wave-uniform) cursor of the first record that does not fit: it maps to the spare block
     const uint32_t log_lane16 = (uint32_t)lane << LOG_PIECE_SHIFT;
@@ -310,7 +288,6 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         log_j2 += upd ? 2u : 0u;
     };
     auto log_records = [&]() __attribute__((always_inline)) -> int { return (int)(log_j2 >> 1); };
-    auto log_finish = [&]() __attribute__((always_inline)) {};
 
     Window<HEAD> head;
     if constexpr (BACKWARD) head.init(); else head.init_padded(); // (forward passes: always-full queue, see Window::replace_front)
@@ -412,46 +389,30 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         for (int cs = (int)threadIdx.x; cs < BWD_WIN; cs += 256) flush_slot(cs, 0, 9);
     };
 
-    // The data a blend needs of its Gaussian (forward: colour; backward: conic, mean, colour) is fetched when
+    // Re-sorting backward: the data a blend needs of its Gaussian (conic, mean, colour) is fetched when
     // an entry BECOMES the front of the head queue -- one feed step (>100 instructions) before it is blended --
     // so the gather's latency is off the blend's critical path.
     int front_key = -1; // head.id[0] the registers below belong to
-    float front_col[3] = {0.0f, 0.0f, 0.0f};
     FrontData front_fd{};
     int front_gid = -1;
     auto refresh_front = [&]() __attribute__((always_inline)) {
         if (active && head.num > 0 && head.id[0] != front_key) {
             front_key = head.id[0];
-            if constexpr (BACKWARD) {
-                front_gid = to_id(front_key);
-                front_fd = load_front(a, front_gid);
-            } else {
-                front_gid = to_id(front_key);
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++) front_col[ch] = a.features[3 * (size_t)front_gid + ch];
-            }
+            front_gid = to_id(front_key);
+            front_fd = load_front(a, front_gid);
         }
     };
     auto blend_front = [&]() __attribute__((always_inline)) { // reference :386-417
         if (!active) { head.num--; return; }
-        bool ok;
-        if constexpr (BACKWARD) {
-            float g[9];
-            if (head.id[0] != front_key) refresh_front();
-            ok = blend_backward_terms(bp, a, px, py, front_fd, head.store[0], g);
-            if (ok) accumulate(head.id[0], front_gid, g);
-        } else {
-            if (head.id[0] != front_key) refresh_front(); // not prefetched (cannot happen after a refresh; kept for safety)
-            ok = blend_forward_c(fp, front_col, head.store[0]);
-            if constexpr (RECORD) {
-                log_append(ok, head.id[0]);
-            }
-        }
+        float g[9];
+        if (head.id[0] != front_key) refresh_front(); // not prefetched (cannot happen after a refresh; kept for safety)
+        const bool ok = blend_backward_terms(bp, a, px, py, front_fd, head.store[0], g);
+        if (ok) accumulate(head.id[0], front_gid, g);
         if (!ok) { active = false; head.num--; return; }
         head.pop();
     };
 
-    // Forward passes: branch-free version of blend_front() for every lane where `need` holds (reference :386-417).
+    // Forward passes: the branch-free blend of the always-full queue's front (reference :386-417).
     // The colour of the popped entry is only needed to accumulate C, which nothing else depends on: its gather is
     // issued here and consumed at the NEXT pop (one whole feed step later), when the previous pending product
     // pend_w * pend_c is added.  Lanes that do not blend issue a harmless load of Gaussian 0.
@@ -477,23 +438,17 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         active = active && (upd || !doing); // saturated pixels retire
     };
 
+    // (re-sorting backward only)
     auto feed_one = [&](int cid, float3 p0, float3 p1, float3 p2, float4 co, float2 xy) __attribute__((always_inline)) { // reference :479-522
         const float depth = depth_along_ray<FRCP>(p0, p1, p2, pix_dir);
         const float dx = xy.x - (float)px, dy = xy.y - (float)py;
         const float power = blend_power(dx, dy, co);
-        if constexpr (BACKWARD) {
-            if (!active || depth < 0.0f) return;
-            if (power > 0.0f) return;
-            const float G = exp_blend(power);
-            const float alpha = fminf(0.99f, co.w * G);
-            if (alpha < ALPHA_THRESHOLD) return;
-            head.insert(depth, cid, G);
-        } else { // same tests as one predicate: straight-line code, nothing to merge at a join
-            const float G = exp_blend(power);
-            const float alpha = fminf(0.99f, co.w * G);
-            const bool pass = active && cid != -1 && !(depth < 0.0f) && !(power > 0.0f) && !(alpha < ALPHA_THRESHOLD);
-            head.insert_if(pass, depth, cid, alpha);
-        }
+        if (!active || depth < 0.0f) return;
+        if (power > 0.0f) return;
+        const float G = exp_blend(power);
+        const float alpha = fminf(0.99f, co.w * G);
+        if (alpha < ALPHA_THRESHOLD) return;
+        head.insert(depth, cid, G);
     };
 
     // feed the four front mid entries mk/mi[0..3] to the quad's four head queues (reference :421-536).
@@ -514,7 +469,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
                 co = a.conic_opacity[gid_f];
                 xy = a.means2D[gid_f];
             }
-        } else { // entry record by position; a pad (-1, only while draining) reads entry 0; its opacity is zeroed below (STP_FEED(0)): alpha 0 fails the candidate tests
+        } else { // entry record by position; a pad (-1, only while draining) reads entry 0; its opacity is zeroed below (head_candidate<0>): alpha 0 fails the candidate tests
             pf = min(max(fid, 0), list_last); // (clamped from above too: depth keys that are NaN -- an overflowing Sigma^-1 -- break the counting ranks, and a stale slot must not become a wild address)
             eAq = ent_row(eA, pf); eBq = ent_row(eB, pf); eCq = ent_row(eC, pf); eDq = ent_row(eD, pf);
         }
@@ -527,16 +482,8 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         else pop_forward();                                                                                             \
         const int cid = quad_bcast_i<I>(BACKWARD ? fid : pf);                                                           \
         if constexpr (!BACKWARD) { /* straight-line evaluation, broadcast operands folded into the arithmetic */         \
-            if constexpr (I == 0) { /* (after the pop: the wait for the four loads stays behind it) */                  \
-                eDq.w = fid < 0 ? 0.0f : eDq.w;                                                                         \
-                dpp_hazard_guard_on(eDq.w); /* a VALU result that DPP operands read below */                            \
-            } else dpp_hazard_guard();                                                                                  \
-            const float depth = depth_along_ray_quad_ent<I, FRCP>(eAq, eBq, eCq, pix_dir);                              \
-            const float dx = quad_sub<I>(eCq.y, (float)px), dy = quad_sub<I>(eCq.z, (float)py);                         \
-            const float power = blend_power_quad<I>(dx, dy, eDq);                                                       \
-            const float alpha = min_099(quad_mul<I>(eDq.w, exp_blend(power)));                                          \
-            const bool pass = active && !(depth < 0.0f) && !(power > 0.0f) && !(alpha < ALPHA_THRESHOLD);               \
-            head.replace_front(pass, pass ? depth : -FLT_MAX, cid, alpha);                                              \
+            const HeadCandidate c = head_candidate<I, FRCP>(fid, eAq, eBq, eCq, eDq, pix_dir, px, py, active);          \
+            head.replace_front(c.pass, c.pass ? c.depth : -FLT_MAX, cid, c.alpha);                                      \
         } else if (cid != -1) {                                                                                         \
             const float3 b0 = make_float3(quad_bcast<I>(c0.x), quad_bcast<I>(c0.y), quad_bcast<I>(c0.z));               \
             const float3 b1 = make_float3(quad_bcast<I>(c1.x), quad_bcast<I>(c1.y), quad_bcast<I>(c1.z));               \
@@ -566,40 +513,14 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     // order, in the quad's FIFO.
     // Head steps then run on groups of four parked candidates with all 64 lanes of the wave taking part, as often as
     // the fullest quad of the wave needs; the exact per-pixel tests are unchanged.
-    constexpr bool HEAD_FILTER = !BACKWARD;
-    int hf_head = 0, hf_cnt = 0; // (quad-uniform)
-    constexpr int HF_REJECT = 0x40000000; // payload flag in the mid queue: no pixel of this quad can blend the entry (a pad, -1, carries it too)
-    // lane-local: can the entry with record rows C (mean in .yz) and D (conic, opacity) reach 1/255 at any of the four
-    // pixels of the quad whose corner pixel is (qx0, qy0)?  false = certainly not.
-    // (qxc, qyc): the quad's CENTRE.  With d = mean - centre, g = conic * d and e in {+-1/2}^2 the offsets of the four pixels,
-    // the negated exponent at a pixel is  Q(d) + g.e + Q(e)  with  Q(e) = (a + c) / 8 + b ex ey  -- exactly, for any conic --
-    // so its minimum over the four pixels is  Q(d) + (a + c) / 8 + min(b/4 - |gx + gy| / 2, -b/4 - |gx - gy| / 2):  sixteen
-    // instructions instead of the four evaluations' thirty.
-    auto quad_can_blend = [&](const float4 C, const float4 D, const float qxc, const float qyc) __attribute__((always_inline)) -> bool {
-        const float dx = C.y - qxc, dy = C.z - qyc;
-        const float gx = fmaf(D.y, dy, D.x * dx), gy = fmaf(D.z, dy, D.y * dx);
-        const float q2 = fmaf(gy, dy, gx * dx);                                  // 2 Q(d)
-        const float m2 = fminf(fmaf(D.y, 0.5f, -fabsf(gx + gy)), fmaf(D.y, -0.5f, -fabsf(gx - gy))); // 2 min(...)
-        const float qmin2 = fmaf(D.x + D.z, 0.25f, q2) + m2;                      // 2 x the smallest negated exponent, to a few ulp of its terms
-        // |this evaluation - blend_power_quad()| <= 10 * 2^-24 * (|a| + |b| + |c|) * far^2 = 6e-7 * S,  far = the largest |offset| of a pixel
-        const float far = fmaxf(fabsf(dx), fabsf(dy)) + 0.5f;
-        const float S = (fabsf(D.x) + fabsf(D.z) + fabsf(D.y)) * far * far;
-        const float pup = fmaf(qmin2, -0.5f, S * 2.0e-6f);
-        const float v = D.w * __builtin_amdgcn_exp2f(pup * 1.44269502162933349609375f); // (relative error < 2e-6 where it matters)
-        return !(v < ALPHA_THRESHOLD * 0.9999f);                                          // NaN: kept, the exact test decides
-    };
+    QuadFifo<HF_CAP> hf; // (head and count quad-uniform; the slots: HierLds::hfifo)
+    constexpr int HF_REJECT = 0x40000000; // payload flag in the mid queue: no pixel of this quad can blend the entry (quad_can_blend, stp_render_wave.h; a pad, -1, carries it too)
     // the four front entries of the quad's mid queue: those that can blend are parked, in order
     auto filter_push = [&](const QuadView& qv) __attribute__((always_inline)) {
-        const unsigned long long act = __ballot(active);
-        if (((act >> (lane & ~3)) & 0xFull) == 0ull) return; // whole quad saturated / outside
-        const int q = qv.q; int* const mi = qv.mi; int* const hfifo = qv.hfifo;
-        const int fid = mi[q];
+        if (!quad_live(__ballot(active), lane)) return; // whole quad saturated / outside
+        const int fid = qv.mi[qv.q];
         const bool keep = (fid & HF_REJECT) == 0;
-        int bits = keep ? (1 << q) : 0;
-        bits += __builtin_amdgcn_mov_dpp(bits, 0xB1, 0xF, 0xF, true); // quad_perm [1,0,3,2]
-        bits += __builtin_amdgcn_mov_dpp(bits, 0x4E, 0xF, 0xF, true); // quad_perm [2,3,0,1]: the quad's four verdicts in every lane
-        if (keep) hfifo[(hf_head + hf_cnt + __popc(bits & ((1 << q) - 1))) & (HF_CAP - 1)] = fid;
-        hf_cnt += __popc(bits);
+        hf.push(qv.hfifo, qv.q, keep, fid);
 #ifdef STP_HIER_STATS
         {   // candidates handed down / kept, one per quad and candidate
             const int shown = __popcll(__ballot(1)), kept = __popcll(__ballot(keep));
@@ -607,29 +528,19 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         }
 #endif
     };
-    // head steps on parked candidates.  force: until every FIFO is empty (end of the list); otherwise while some quad
-    // could not take another consumption round's 16 entries, or every quad with live pixels has a full group of four.
+    // head steps on parked candidates (when one is due: QuadFifo::round_due)
     auto head_round = [&](const bool force) __attribute__((always_inline)) -> bool { // false: nothing (more) to do now
-        const unsigned long long act = __ballot(active);
-        const bool qlive = ((act >> (lane & ~3)) & 0xFull) != 0ull;
-        if (!qlive) { hf_head = (hf_head + hf_cnt) & (HF_CAP - 1); hf_cnt = 0; } // nobody left to show them to
-        bool go;
-        if (force) go = __any(hf_cnt > 0);
-        else go = __any(hf_cnt > HF_CAP - 16) || (__all(hf_cnt >= 4 || !qlive) && __any(hf_cnt >= 4));
-        if (!go) return false;
-        const int n = min(hf_cnt, 4);
+        if (!hf.round_due(force, quad_live(__ballot(active), lane))) return false;
 #ifdef STP_HIER_STATS
         {   // head group steps, candidates in them (quad x candidate), forced ones
+            const int n = min(hf.cnt, 4);
             const int c = __popcll(__ballot(q < n));
             if (lane == 0) { atomicAdd(&g_hier_stats[12], 1ull); atomicAdd(&g_hier_stats[13], (unsigned long long)c); atomicAdd(&g_hier_stats[14], force ? 1ull : 0ull); }
         }
 #endif
         wave_sync();
         STP_QUAD_VIEW(FRESH_QUAD ? fresh_lane() : lane)
-        const int fid = q < n ? hfifo[(hf_head + q) & (HF_CAP - 1)] : -1;
-        hf_head = (hf_head + n) & (HF_CAP - 1);
-        hf_cnt -= n;
-        feed4_from(fid);
+        feed4_from(hf.take4(hfifo, q));
         return true;
     };
     auto head_rounds = [&](const bool force) __attribute__((always_inline)) {
@@ -641,10 +552,9 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     };
     // feed the four front mid entries mk/mi[0..3] to the quad's four head queues (reference :421-536).
     auto feed4 = [&](const QuadView& qv) __attribute__((always_inline)) {
-        if constexpr (HEAD_FILTER) filter_push(qv);
+        if constexpr (!BACKWARD) filter_push(qv);
         else {
-            const unsigned long long act = __ballot(active);
-            if (((act >> (lane & ~3)) & 0xFull) == 0ull) return; // whole quad saturated / outside
+            if (!quad_live(__ballot(active), lane)) return; // whole quad saturated / outside
             feed4_from(qv.mi[qv.q]); // payload: list position; lane q fetches entry q for the whole quad
         }
     };
@@ -751,7 +661,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
                     gid = min(max(gid, 0), list_last); // (see feed4_from)
                     const float4 enA = ent_row(eA, gid), enB = ent_row(eB, gid), enC = ent_row(eC, gid);
                     d = depth_along_ray_ent<FRCP>(enA, enB, enC, make_float3(mr.x, mr.y, mr.z));
-                    if constexpr (HEAD_FILTER) {
+                    if constexpr (!BACKWARD) {
                         if (!quad_can_blend(enC, ent_row(eD, gid), qxc, qyc)) gid |= HF_REJECT;
                     }
                 }
@@ -823,7 +733,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
                 if (!cullB) dB = depth_along_ray<FRCP>(p0, p1, p2, make_float3(rB.x, rB.y, rB.z));
             }
         }
-        const int payload = USE_POS ? (gi - (int)range.x) : id;
+        const int payload = gi - (int)range.x; // queue payload: the entry's position in the tile list in every mode
         // compact the survivors of each sub-tile to the front of its staging area, in list order
         // (ballots are wave-uniform: every row can read its own sub-tile's count from them)
         balA = __ballot(dA != FLT_MAX);
@@ -1051,7 +961,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
                 }
             } else go = __any(want != 0);
             // (head-level FIFOs: once the list is exhausted and nothing is left above them, one last pass empties them)
-            const bool last = HEAD_FILTER && draining && !go;
+            const bool last = !BACKWARD && draining && !go;
             if (!go && !last) break;
 #ifdef STP_HIER_STATS
             {   // consumption rounds by number of participating sub-tile rows, and live lanes in them
@@ -1075,7 +985,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
                 }
                 tail_drop16();
             }
-            if constexpr (HEAD_FILTER) head_rounds(last); // (all 64 lanes again; the one call site of the head steps)
+            if constexpr (!BACKWARD) head_rounds(last); // (all 64 lanes again; the one call site of the head steps)
             if (last) break;
         }
         if (draining) break;
@@ -1096,25 +1006,12 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
 
     if constexpr (RECORD) {
         // the reference leaves n_contrib unwritten in this mode; we keep the pixel's number of blended entries there
-        log_finish();
         const int nrec = log_records();
         if (inside) a.n_contrib[(size_t)a.W * py + px] = (uint32_t)nrec;
-        if (nrec > a.log_depth || (int)(range.y - range.x) > LOG_MAX_LIST) a.tile_flags[tile_y * a.gx + tile_x] = 1u; // log overflow: this tile's backward re-sorts
-        report_log_need(a.log_need, nrec, a.log_tag);
+        finish_blend_log(a, tile, nrec, (int)(range.y - range.x));
     }
     if constexpr (!BACKWARD) {
-        if (inside) { // n_contrib is deliberately not written by the plain forward (reference :1019)
-            const size_t N = (size_t)a.W * a.H, pid = (size_t)a.W * py + px;
-            a.final_T[pid] = fp.T;
-            if constexpr (DEPTHVIZ) { // reference outputDebugVis, stopthepop_common.cuh:297-301
-                a.out_color[pid] = depth_acc;
-                a.out_color[N + pid] = fp.T;
-            } else {
-                a.out_color[pid] = fp.C[0] + fp.T * a.bg[0];
-                a.out_color[N + pid] = fp.C[1] + fp.T * a.bg[1];
-                a.out_color[2 * N + pid] = fp.C[2] + fp.T * a.bg[2];
-            }
-        }
+        if (inside) write_forward_pixel<DEPTHVIZ, false>(a, px, py, fp, depth_acc, 0u); // (n_contrib: not by the plain forward, reference :1019; the recording forward's is above)
     }
 }
 

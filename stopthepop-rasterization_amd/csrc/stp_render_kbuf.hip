@@ -28,7 +28,7 @@
 // pop in front of the entry that follows the insertion which filled the window (count = that insertion's position + 1) or a
 // pop of the final drain (count = the whole list); both are known here without having looked at the entries in between.
 #include "stp_internal.h"
-#include "stp_blend.h"
+#include "stp_render_wave.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -51,265 +51,92 @@ extern "C" int stp_debug_kb_stats(unsigned long long* out40)
 
 namespace {
 
-constexpr int KB_CAP = 32; // list positions a quad's FIFO may hold (one round of 16 survivors adds up to 16)
-
-__device__ __forceinline__ int kb_remap_tile(int wg, int n_wg)
-{
-    const int q = n_wg >> 3, r = n_wg & 7;
-    const int xcd = wg & 7, k = wg >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-
-// can the entry with record rows C (mean in .yz) and D (conic, opacity) reach 1/255 at any of the four pixels of the 2x2 quad whose CENTRE is (qxc, qyc)?
-// (stp_render_hier.inc quad_can_blend: an upper bound of opacity * exp(power) over the four pixels that covers every rounding of the per-pixel
-// evaluation; NaN is kept, the exact test decides)
-__device__ __forceinline__ bool kb_quad_can_blend(const float4 C, const float4 D, const float qxc, const float qyc)
-{
-    const float dx = C.y - qxc, dy = C.z - qyc;
-    const float gx = fmaf(D.y, dy, D.x * dx), gy = fmaf(D.z, dy, D.y * dx);
-    const float q2 = fmaf(gy, dy, gx * dx);
-    const float m2 = fminf(fmaf(D.y, 0.5f, -fabsf(gx + gy)), fmaf(D.y, -0.5f, -fabsf(gx - gy)));
-    const float qmin2 = fmaf(D.x + D.z, 0.25f, q2) + m2; // 2 x the smallest negated exponent among the four pixels
-    const float far = fmaxf(fabsf(dx), fabsf(dy)) + 0.5f;
-    const float S = (fabsf(D.x) + fabsf(D.z) + fabsf(D.y)) * far * far;
-    const float pup = fmaf(qmin2, -0.5f, S * 2.0e-6f);
-    const float v = D.w * __builtin_amdgcn_exp2f(pup * 1.44269502162933349609375f);
-    return !(v < ALPHA_THRESHOLD * 0.9999f);
-}
-
 constexpr int KBW_FWD = 0, KBW_RECORD = 2, KBW_DEPTH = 3; // (the values of the hierarchical kernel's modes)
 
-template <int WIN> constexpr int kb_waves() { return WIN <= 4 ? 4 : WIN <= 16 ? 3 : 2; } // waves per SIMD the kernel is compiled for
-
-template <int WIN, int MODE, bool FRCP>
-__global__ void __launch_bounds__(256, kb_waves<WIN>()) render_kbuffer_wave_kernel(const RenderArgs a)
-{
-    constexpr bool RECORD = MODE == KBW_RECORD;
-    constexpr bool DEPTHVIZ = MODE == KBW_DEPTH;
-    __shared__ int s_stage[16 * 32];      // [sub-tile][survivor]: list positions of the staged batch, per sub-tile
-    __shared__ int s_fifo[64 * KB_CAP];   // [quad][slot]
-
-    const int lane = (int)(threadIdx.x & 63);
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int s = lane >> 4, x = lane & 15, m = x >> 2, q = x & 3;
-    const int rows = a.ty1 - a.ty0;
-    const int t = a.tile_order ? (int)a.tile_order[blockIdx.x] : kb_remap_tile((int)blockIdx.x, a.gx * rows);
-    const int tile_x = t % a.gx, tile_y = a.ty0 + t / a.gx, tile = tile_y * a.gx + tile_x;
-    const uint2 range = a.ranges[tile];
-    const int total = (int)(range.y - range.x);
-    const int cx = tile_x * TILE + 4 * s, cy = tile_y * TILE + 4 * w;
-    const int px = cx + 2 * (m & 1) + (q & 1), py = cy + 2 * (m >> 1) + (q >> 1);
-    const bool inside = px < a.W && py < a.H;
-    bool active = inside;
-    if (total <= 0) { // an empty tile is background (and its "entry 0" -- what pads and stand-ins read -- may not exist: stp_render_hier.inc)
-        if (inside) {
-            const size_t N = (size_t)a.W * a.H, pid = (size_t)a.W * py + px;
-            a.final_T[pid] = 1.0f;
-            a.n_contrib[pid] = 0u;
-            if constexpr (DEPTHVIZ) { a.out_color[pid] = 0.0f; a.out_color[N + pid] = 1.0f; }
-            else { a.out_color[pid] = a.bg[0]; a.out_color[N + pid] = a.bg[1]; a.out_color[2 * N + pid] = a.bg[2]; }
-        }
-        return;
-    }
-
-    const float3 cam = make_float3(a.cam[0], a.cam[1], a.cam[2]);
-    const float3 pix_dir = view_ray(a.inv_vp, cam, (float)px, (float)py, a.W, a.H);
-
-    const float4* const eA = a.entA + range.x;
-    const float4* const eB = a.entB + range.x;
-    const float4* const eC = a.entC + range.x;
-    const float4* const eD = a.entD + range.x;
-    const float4* const eF = a.entF + range.x;
-    const int list_last = max(total - 1, 0);
-    auto ent_row = [&](const float4* base, int pos) __attribute__((always_inline)) -> float4 { // SGPR base + 32-bit offset
-        return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + ((uint32_t)pos << 4));
-    };
-
-    // blend log (recording forward): blocked layout, whole pieces from blending lanes only (stp_blend.h: BlockedLogCursor)
-    BlockedLogCursor logc{RECORD ? log_wave_slice(a.blend_log, tile, w, a.log_depth) : nullptr, 2u * (uint32_t)a.log_depth, (uint32_t)lane << LOG_PIECE_SHIFT};
-    auto log_append = [&](bool upd, int pay) __attribute__((always_inline)) { logc.append(upd, pay); };
-    auto log_records = [&]() __attribute__((always_inline)) -> int { return logc.records(); };
-    auto log_finish = [&]() __attribute__((always_inline)) { logc.flush(); };
-
-    Window<WIN> head;
-    head.init_padded();
+// What the kernel body and a window policy share of a pixel: its blend state, its lists' record rows, and the record rows of the entry
+// at the FRONT of its window.  Neither window carries alpha: it is evaluated again at the pop, from the same record with the same
+// operations, hence to the same bits as when the entry passed its tests.  What the pop needs of the front entry -- mean, conic +
+// opacity, colour -- is fetched when the entry BECOMES the front, one step earlier.
+template <int MODE> struct KbPixel {
+    static constexpr bool RECORD = MODE == KBW_RECORD, DEPTHVIZ = MODE == KBW_DEPTH;
+    int lane, px, py;
+    bool active;
+    int total, list_last;
+    const float4 *eC, *eD, *eF;
+    float3 pix_dir;
     FwdPixel fp;
-    init_fwd_pixel(fp);
-    float depth_acc = 0.0f;
-    int contrib = total; // n_contrib of the plain / depth forward (see the header)
-    int cfull = total;   // what it becomes if the NEXT pop saturates the pixel
-
-    // The window does not carry alpha (W registers and W selects per step): it is evaluated again at the pop, from the same
-    // record with the same operations, hence to the same bits as when the entry passed its tests.  What the pop needs of
-    // the front entry -- mean, conic + opacity, colour -- is fetched when the entry BECOMES the front, one step earlier.
-    float4 frC = make_float4(0, 0, 0, 0), frD = frC, frF = frC;
-    auto fetch_front = [&]() __attribute__((always_inline)) {
-        const int nx = head.id[0]; // (a pad carries position 0: a harmless read)
-        frC = ent_row(eC, nx); frD = ent_row(eD, nx); frF = ent_row(eF, nx);
-    };
-    auto pop_forward = [&]() __attribute__((always_inline)) { // consumes slot 0 of the always-full window; replace_front() follows
+    float depth_acc;
+    int contrib; // n_contrib of the plain / depth forward (see the header)
+    int cfull;   // what it becomes if the NEXT pop saturates the pixel
+    BlockedLogCursor logc; // blend log (recording forward): blocked layout, whole pieces from blending lanes only (stp_blend.h)
+    float4 frC, frD, frF;
+    __device__ __forceinline__ void fetch_front(const int pos) { frC = ent_row(eC, pos); frD = ent_row(eD, pos); frF = ent_row(eF, pos); }
+    // blend the front entry (depth `depth0`, list position `pay`) where `doing` holds (reference blend_one, resorted_render.cuh:74-119)
+    __device__ __forceinline__ void blend_front(const bool doing, const float depth0, const int pay)
+    {
         const float alpha0 = fminf(0.99f, frD.w * exp_blend(blend_power(frC.y - (float)px, frC.z - (float)py, frD)));
         const float test_T = fp.T * (1.0f - alpha0);
-        const bool doing = active && !(head.depth[0] < 0.0f); // a pad in front = the reference's window is not full: nothing to blend
         const bool upd = doing && !(test_T < T_THRESHOLD);
-        const int pay = head.id[0];
         const float wgt = upd ? alpha0 * fp.T : 0.0f;
         fp.C[0] = fmaf(wgt, frF.x, fp.C[0]); fp.C[1] = fmaf(wgt, frF.y, fp.C[1]); fp.C[2] = fmaf(wgt, frF.z, fp.C[2]);
-        if constexpr (DEPTHVIZ) depth_acc += upd ? head.depth[0] * alpha0 * fp.T : 0.0f; // reference resorted_render.cuh:107
+        if constexpr (DEPTHVIZ) depth_acc += upd ? depth0 * alpha0 * fp.T : 0.0f; // reference resorted_render.cuh:107
         fp.T = upd ? test_T : fp.T;
-        if constexpr (RECORD) log_append(upd, pay);
+        if constexpr (RECORD) logc.append(upd, pay);
         else contrib = (doing && !upd) ? cfull : contrib;
-        active = active && (upd || !doing);
-    };
+        active = active && (upd || !doing); // a saturated pixel retires
+    }
+};
 
-    // four candidates per quad, lane q brings candidate q (list position, -1 = none): the hierarchical head level's step
-    auto feed4_from = [&](const int fid) __attribute__((always_inline)) {
-        const int pf = min(max(fid, 0), list_last);
-        float4 eAq = ent_row(eA, pf), eBq = ent_row(eB, pf), eCq = ent_row(eC, pf), eDq = ent_row(eD, pf);
+// ---- the window in REGISTERS: Window<WIN>'s always-full form, the hierarchical head level's step with HEAD = WIN ----------------------
+template <int WIN, int MODE, bool FRCP> struct KbRegWindow {
+    static constexpr int FIFO_CAP = 32; // list positions a quad's FIFO may hold (one round of 16 survivors adds up to 16)
+    static constexpr int WAVES = WIN <= 4 ? 4 : WIN <= 16 ? 3 : 2; // waves per SIMD the kernel is compiled for
+    static constexpr bool DOUBLE_ROUND = WIN <= 8; // (two copies of the group step: fewer register shuffles per step)
+    using Pixel = KbPixel<MODE>;
+    Window<WIN> head;
+    __device__ __forceinline__ void init(Pixel& k) { head.init_padded(); }
+    __device__ __forceinline__ void fetch_front(Pixel& k) { k.fetch_front(head.id[0]); } // (a pad carries position 0: a harmless read)
+    // consumes slot 0 of the always-full window; replace_front() follows.  A pad in front = the reference's window is not full: nothing to blend
+    __device__ __forceinline__ void pop_forward(Pixel& k) { k.blend_front(k.active && !(head.depth[0] < 0.0f), head.depth[0], head.id[0]); }
 #ifdef STP_KB_STATS
-#define STP_KB_STAT(PASS, D)                                                                                            \
-        {                                                                                                               \
-            int disp = 0;                                                                                               \
-            for (int s_ = 1; s_ < WIN; s_++) disp += (int)((D) < head.depth[s_]);                                       \
-            disp = (PASS) ? disp : -1;                                                                                  \
-            int mx = disp;                                                                                              \
-            for (int o_ = 1; o_ < 64; o_ <<= 1) mx = max(mx, __shfl_xor(mx, o_));                                       \
-            if (disp >= 0) atomicAdd(&g_kb_stats[min(disp, 15)], 1ull);                                                 \
-            const int np_ = __popcll(__ballot(PASS)), na_ = __popcll(__ballot(active));                                 \
-            if (lane == 0) { atomicAdd(&g_kb_stats[16 + min(max(mx, 0), 15)], 1ull); atomicAdd(&g_kb_stats[32], 1ull);  \
-                             atomicAdd(&g_kb_stats[33], (unsigned long long)np_); atomicAdd(&g_kb_stats[34], (unsigned long long)na_); } \
-        }
-#else
-#define STP_KB_STAT(PASS, D)
+    __device__ __forceinline__ void stat(const Pixel& k, const bool pass, const float depth)
+    {
+        int disp = 0;
+        for (int s_ = 1; s_ < WIN; s_++) disp += (int)(depth < head.depth[s_]);
+        disp = pass ? disp : -1;
+        int mx = disp;
+        for (int o_ = 1; o_ < 64; o_ <<= 1) mx = max(mx, __shfl_xor(mx, o_));
+        if (disp >= 0) atomicAdd(&g_kb_stats[min(disp, 15)], 1ull);
+        const int np_ = __popcll(__ballot(pass)), na_ = __popcll(__ballot(k.active));
+        if (k.lane == 0) { atomicAdd(&g_kb_stats[16 + min(max(mx, 0), 15)], 1ull); atomicAdd(&g_kb_stats[32], 1ull);
+                           atomicAdd(&g_kb_stats[33], (unsigned long long)np_); atomicAdd(&g_kb_stats[34], (unsigned long long)na_); }
+    }
 #endif
-#define STP_KB_FEED(I)                                                                                                  \
-    {                                                                                                                   \
-        pop_forward();                                                                                                  \
-        const int cid = quad_bcast_i<I>(pf);                                                                            \
-        if constexpr (I == 0) {                                                                                         \
-            eDq.w = fid < 0 ? 0.0f : eDq.w; /* no candidate: alpha 0 fails the tests */                                 \
-            dpp_hazard_guard_on(eDq.w);                                                                                 \
-        } else dpp_hazard_guard();                                                                                      \
-        const float depth = depth_along_ray_quad_ent<I, FRCP>(eAq, eBq, eCq, pix_dir);                                  \
-        const float dx = quad_sub<I>(eCq.y, (float)px), dy = quad_sub<I>(eCq.z, (float)py);                             \
-        const float power = blend_power_quad<I>(dx, dy, eDq);                                                           \
-        const float alpha = min_099(quad_mul<I>(eDq.w, exp_blend(power)));                                              \
-        const bool pass = active && !(depth < 0.0f) && !(power > 0.0f) && !(alpha < ALPHA_THRESHOLD);                   \
-        STP_KB_STAT(pass, depth)                                                                                        \
-        head.replace_front(pass, pass ? depth : -FLT_MAX, cid, 0.0f);                                                   \
-        fetch_front();                                                                                                  \
-        if constexpr (!RECORD) cfull = pass ? cid + 1 : cfull;                                                          \
+    // candidate I of a group of four (rows fetched by lane I of the quad from the clamped position pf): pop, look, fused pop + insert
+    template <int I> __device__ __forceinline__ void step(Pixel& k, const int fid, const int pf, const float4 eAq, const float4 eBq, const float4 eCq, float4& eDq)
+    {
+        pop_forward(k);
+        const int cid = quad_bcast_i<I>(pf);
+        const HeadCandidate c = head_candidate<I, FRCP>(fid, eAq, eBq, eCq, eDq, k.pix_dir, k.px, k.py, k.active);
+#ifdef STP_KB_STATS
+        stat(k, c.pass, c.depth);
+#endif
+        head.replace_front(c.pass, c.pass ? c.depth : -FLT_MAX, cid, 0.0f);
+        fetch_front(k);
+        if constexpr (!Pixel::RECORD) k.cfull = c.pass ? cid + 1 : k.cfull;
     }
-        STP_KB_FEED(0) STP_KB_FEED(1) STP_KB_FEED(2) STP_KB_FEED(3)
-#undef STP_KB_FEED
-    };
-
-    int* const hfifo = s_fifo + ((w * 4 + s) * 4 + m) * KB_CAP;
-    int hf_head = 0, hf_cnt = 0; // (quad-uniform)
-    auto head_round = [&](const bool force) __attribute__((always_inline)) -> bool { // false: nothing (more) to do now
-        const unsigned long long act = __ballot(active);
-        const bool qlive = ((act >> (lane & ~3)) & 0xFull) != 0ull;
-        if (!qlive) { hf_head = (hf_head + hf_cnt) & (KB_CAP - 1); hf_cnt = 0; } // nobody left to show them to
-        bool go;
-        if (force) go = __any(hf_cnt > 0);
-        else go = __any(hf_cnt > KB_CAP - 16) || (__all(hf_cnt >= 4 || !qlive) && __any(hf_cnt >= 4));
-        if (!go) return false;
-        const int n = min(hf_cnt, 4);
-        wave_sync();
-        const int fid = q < n ? hfifo[(hf_head + q) & (KB_CAP - 1)] : -1;
-        hf_head = (hf_head + n) & (KB_CAP - 1);
-        hf_cnt -= n;
-        feed4_from(fid);
-        return true;
-    };
-    auto head_rounds = [&](const bool force) __attribute__((always_inline)) {
-#pragma unroll 1
-        for (;;) {
-            if (!head_round(force)) break;
-            if constexpr (WIN <= 8) { if (!head_round(force)) break; } // (two copies of the group step: fewer register shuffles per step)
-        }
-    };
-
-    // ---- main loop: batches of 32 list entries -----------------------------------------------------------------------
-    const int half = lane >> 5, e = lane & 31;
-    const float sxA = (float)(tile_x * TILE + 8 * half), sxB = sxA + 4.0f, syf = (float)cy;
-    int* const stA = s_stage + (w * 4 + 2 * half) * 32; // my half's two sub-tiles: [0..32) and [32..64)
-    const int* const st_row = s_stage + (w * 4 + s) * 32;
-    const float qxc = (float)(px - (q & 1)) + 0.5f, qyc = (float)(py - (q >> 1)) + 0.5f; // centre of my 2x2 quad
-#pragma unroll 1
-    for (int base = 0; base < total; base += 32) {
-        if (!__any(active)) break;
-        // stage: lane = entry e of the batch x the sub-tile pair of my half
-        const int ep = base + e;
-        bool keepA = false, keepB = false;
-        if (ep < total) {
-            // (the sixteen sub-tile verdicts of this entry were computed by the entry gather, stp_tilesort.hip: subtile_keep_mask_kbuffer)
-            const uint32_t mask = __float_as_uint(*reinterpret_cast<const float*>(reinterpret_cast<const char*>(eF) + ((uint32_t)ep << 4) + 12));
-            const uint32_t mine = mask >> (4 * w + 2 * half);
-            keepA = (mine & 1u) != 0u;
-            keepB = (mine & 2u) != 0u;
-        }
-        const unsigned long long balA = __ballot(keepA), balB = __ballot(keepB);
-        const unsigned int mA = (unsigned int)(balA >> (32 * half)), mB = (unsigned int)(balB >> (32 * half));
-        const unsigned int below = (1u << e) - 1u;
-        wave_sync(); // (the previous batch's readers are done)
-        if (keepA) stA[__popc(mA & below)] = ep;
-        if (keepB) stA[32 + __popc(mB & below)] = ep;
-        wave_sync();
-        const int n_s = __popc((unsigned int)(((s & 1) ? balB : balA) >> (32 * (s >> 1)))); // my sub-tile's survivors
-        // feed: groups of four survivors per quad, head steps after every 16
-        int n_max = n_s;
-#pragma unroll
-        for (int o = 16; o < 64; o <<= 1) n_max = max(n_max, __shfl_xor(n_max, o));
-#pragma unroll 1
-        for (int g0 = 0; g0 < n_max; g0 += 16) {
-#pragma unroll 1
-            for (int g = g0; g < min(g0 + 16, n_max); g += 4) {
-                const int i = g + q;
-                int fid = -1;
-                if (i < n_s) fid = st_row[i];
-                bool keep = false;
-                const unsigned long long act = __ballot(active);
-                const bool qlive = ((act >> (lane & ~3)) & 0xFull) != 0ull;
-                if (fid >= 0 && qlive) keep = kb_quad_can_blend(ent_row(eC, fid), ent_row(eD, fid), qxc, qyc);
-                int bits = keep ? (1 << q) : 0;
-                bits += __builtin_amdgcn_mov_dpp(bits, 0xB1, 0xF, 0xF, true); // quad_perm [1,0,3,2]
-                bits += __builtin_amdgcn_mov_dpp(bits, 0x4E, 0xF, 0xF, true); // quad_perm [2,3,0,1]
-                if (keep) hfifo[(hf_head + hf_cnt + __popc(bits & ((1 << q) - 1))) & (KB_CAP - 1)] = fid;
-                hf_cnt += __popc(bits);
-            }
-            head_rounds(false);
-        }
-    }
-    head_rounds(true);
     // drain: fillers that sort LAST push the remaining real entries to the front, one per step
+    __device__ __forceinline__ void drain(Pixel& k)
+    {
 #pragma unroll 1
-    for (int it = 0; it < WIN; it++) {
-        pop_forward();
-        head.replace_front(false, FLT_MAX, 0, 0.0f);
-        fetch_front();
-        cfull = total; // (only the drain's first pop can be the one "in front of the next entry")
-    }
-
-    if constexpr (RECORD) log_finish();
-    if (inside) {
-        const size_t N = (size_t)a.W * a.H, pid = (size_t)a.W * py + px;
-        a.final_T[pid] = fp.T;
-        a.n_contrib[pid] = RECORD ? (uint32_t)log_records() : (uint32_t)contrib; // (recording forward: the pixel's number of log records)
-        if constexpr (DEPTHVIZ) {
-            a.out_color[pid] = depth_acc;
-            a.out_color[N + pid] = fp.T;
-        } else {
-            a.out_color[pid] = fp.C[0] + fp.T * a.bg[0];
-            a.out_color[N + pid] = fp.C[1] + fp.T * a.bg[1];
-            a.out_color[2 * N + pid] = fp.C[2] + fp.T * a.bg[2];
+        for (int it = 0; it < WIN; it++) {
+            pop_forward(k);
+            head.replace_front(false, FLT_MAX, 0, 0.0f);
+            fetch_front(k);
+            k.cfull = k.total; // (only the drain's first pop can be the one "in front of the next entry")
         }
     }
-    if constexpr (RECORD) {
-        if (log_records() > a.log_depth || total > LOG_MAX_LIST) a.tile_flags[tile] = 1u; // log overflow: this tile's backward re-sorts
-        report_log_need(a.log_need, log_records(), a.log_tag);
-    }
-}
+};
 
 
 // ---- the window as a per-lane RING in LDS ----------------------------------------------------------------------------------------------
@@ -328,119 +155,64 @@ __global__ void __launch_bounds__(256, kb_waves<WIN>()) render_kbuffer_wave_kern
 //     its equals: every run of equal depths among the displaced entries ends up rotated by one): such a step is detected while walking
 //     (two consecutive displaced entries of equal depth) and its payloads are rotated afterwards, in a branch that is almost never entered.
 // What the pop needs of the front entry is fetched when the entry becomes the front, as above; alpha is evaluated again at the pop.
-constexpr int KBR_CAP = 24; // list positions a quad's FIFO may hold in the ring kernel (a round of 16 survivors adds up to 16; not a power of two: 40 KB of LDS = four workgroups per CU)
-template <int WIN> constexpr int kb_ring_waves() { return WIN <= 16 ? 4 : 3; } // (LDS: 40 KB per workgroup at 16 entries, 48 / 56 KB at 20 / 24)
-template <int WIN> constexpr size_t kb_ring_lds() { return (size_t)WIN * 256 * 8 + 16 * 32 * 4 + 64 * KBR_CAP * 4; }
-
-template <int WIN, int MODE, bool FRCP>
-__global__ void __launch_bounds__(256, kb_ring_waves<WIN>()) render_kbuffer_ring_kernel(const RenderArgs a)
-{
-    constexpr bool RECORD = MODE == KBW_RECORD;
-    constexpr bool DEPTHVIZ = MODE == KBW_DEPTH;
-    constexpr bool POW2 = (WIN & (WIN - 1)) == 0;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* const ring = smem;                                                  // (depth, list position) [WIN][256]: slot-major, 8 bytes per thread
-    int* const s_stage = reinterpret_cast<int*>(smem + (size_t)WIN * 2048);   // [sub-tile][survivor]
-    int* const s_fifo = s_stage + 16 * 32;                                    // [quad][slot]
-
-    const int lane = (int)(threadIdx.x & 63);
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int s = lane >> 4, x = lane & 15, m = x >> 2, q = x & 3;
-    const int rows = a.ty1 - a.ty0;
-    const int t = a.tile_order ? (int)a.tile_order[blockIdx.x] : kb_remap_tile((int)blockIdx.x, a.gx * rows);
-    const int tile_x = t % a.gx, tile_y = a.ty0 + t / a.gx, tile = tile_y * a.gx + tile_x;
-    const uint2 range = a.ranges[tile];
-    const int total = (int)(range.y - range.x);
-    const int cx = tile_x * TILE + 4 * s, cy = tile_y * TILE + 4 * w;
-    const int px = cx + 2 * (m & 1) + (q & 1), py = cy + 2 * (m >> 1) + (q >> 1);
-    const bool inside = px < a.W && py < a.H;
-    bool active = inside;
-    if (total <= 0) { // an empty tile is background (and its "entry 0" -- what pads and stand-ins read -- may not exist: stp_render_hier.inc)
-        if (inside) {
-            const size_t N = (size_t)a.W * a.H, pid = (size_t)a.W * py + px;
-            a.final_T[pid] = 1.0f;
-            a.n_contrib[pid] = 0u;
-            if constexpr (DEPTHVIZ) { a.out_color[pid] = 0.0f; a.out_color[N + pid] = 1.0f; }
-            else { a.out_color[pid] = a.bg[0]; a.out_color[N + pid] = a.bg[1]; a.out_color[2 * N + pid] = a.bg[2]; }
-        }
-        return;
-    }
-
-    const float3 cam = make_float3(a.cam[0], a.cam[1], a.cam[2]);
-    const float3 pix_dir = view_ray(a.inv_vp, cam, (float)px, (float)py, a.W, a.H);
-
-    const float4* const eA = a.entA + range.x;
-    const float4* const eB = a.entB + range.x;
-    const float4* const eC = a.entC + range.x;
-    const float4* const eD = a.entD + range.x;
-    const float4* const eF = a.entF + range.x;
-    const int list_last = max(total - 1, 0);
-    auto ent_row = [&](const float4* base, int pos) __attribute__((always_inline)) -> float4 { // SGPR base + 32-bit offset
-        return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + ((uint32_t)pos << 4));
-    };
-
-    // blend log (recording forward): blocked layout, whole pieces from blending lanes only (stp_blend.h: BlockedLogCursor)
-    BlockedLogCursor logc{RECORD ? log_wave_slice(a.blend_log, tile, w, a.log_depth) : nullptr, 2u * (uint32_t)a.log_depth, (uint32_t)lane << LOG_PIECE_SHIFT};
-    auto log_append = [&](bool upd, int pay) __attribute__((always_inline)) {
-        logc.append(upd, pay);
-    };
-    auto log_records = [&]() __attribute__((always_inline)) -> int { return logc.records(); };
-    auto log_flush = [&]() __attribute__((always_inline)) { logc.flush(); };
-
+template <int WIN, int MODE, bool FRCP> struct KbRingWindow {
+    static constexpr int FIFO_CAP = 24; // (a round of 16 survivors adds up to 16; not a power of two: 40 KB of LDS = four workgroups per CU)
+    static constexpr int WAVES = WIN <= 16 ? 4 : 3; // (LDS: 40 KB per workgroup at 16 entries, 48 / 56 KB at 20 / 24)
+    static constexpr size_t RING_BYTES = (size_t)WIN * 256 * 8; // (depth, list position) [WIN][256]: slot-major, 8 bytes per thread
+    static constexpr size_t LDS_BYTES = RING_BYTES + 16 * 32 * 4 + 64 * FIFO_CAP * 4;
+    static constexpr bool DOUBLE_ROUND = false;
+    static constexpr bool POW2 = (WIN & (WIN - 1)) == 0;
+    using Pixel = KbPixel<MODE>;
     // the ring: logical entry k of my window lives in slot (rh + k) mod WIN of my column
-    const uint32_t col = (uint32_t)threadIdx.x * 8u;
-    int rn = 0, rh = 0;          // entries in my window, slot of its front
-    float back_d = -FLT_MAX;     // my window's LAST entry (-FLT_MAX: the window is empty) and the one in front of it (-FLT_MAX: none): nine candidates
-    int back_i = 0;              // in ten are placed against these two without an LDS access
-    float back2_d = -FLT_MAX;
-    int back2_i = 0;
-    auto wrap = [&](int p) __attribute__((always_inline)) -> int { // p in [0, 2 WIN) -> [0, WIN)
+    char* ring;
+    uint32_t col;
+    int rn, rh;          // entries in my window, slot of its front
+    float back_d;        // my window's LAST entry (-FLT_MAX: the window is empty) and the one in front of it (-FLT_MAX: none): nine candidates
+    int back_i;          // in ten are placed against these two without an LDS access
+    float back2_d;
+    int back2_i;
+    int fr_id;           // the front entry the pixel's front rows belong to
+    float fr_depth;
+    __device__ __forceinline__ void init(Pixel& k)
+    {
+        col = (uint32_t)threadIdx.x * 8u;
+        rn = 0; rh = 0;
+        back_d = -FLT_MAX; back_i = 0; back2_d = -FLT_MAX; back2_i = 0;
+        fr_id = 0; fr_depth = 0.0f;
+    }
+    static __device__ __forceinline__ int wrap(int p) // p in [0, 2 WIN) -> [0, WIN)
+    {
         if constexpr (POW2) return p & (WIN - 1);
         else return p - (p >= WIN ? WIN : 0);
-    };
-    auto prev_slot = [&](int p) __attribute__((always_inline)) -> int { // p in [0, WIN) -> the slot in front of it
+    }
+    static __device__ __forceinline__ int prev_slot(int p) // p in [0, WIN) -> the slot in front of it
+    {
         if constexpr (POW2) return (p - 1) & (WIN - 1);
         else return (p == 0 ? WIN : p) - 1;
-    };
-    auto slot_addr = [&](int p) __attribute__((always_inline)) -> char* { return ring + (((uint32_t)p << 11) + col); };
-    auto rd = [&](int p) __attribute__((always_inline)) -> float2 { return *reinterpret_cast<const float2*>(slot_addr(p)); }; // (.x depth, .y the position's bits)
-    auto wr = [&](int p, float d, int i) __attribute__((always_inline)) { *reinterpret_cast<float2*>(slot_addr(p)) = make_float2(d, __int_as_float(i)); };
+    }
+    __device__ __forceinline__ char* slot_addr(int p) const { return ring + (((uint32_t)p << 11) + col); }
+    __device__ __forceinline__ float2 rd(int p) const { return *reinterpret_cast<const float2*>(slot_addr(p)); } // (.x depth, .y the position's bits)
+    __device__ __forceinline__ void wr(int p, float d, int i) const { *reinterpret_cast<float2*>(slot_addr(p)) = make_float2(d, __int_as_float(i)); }
 
-    FwdPixel fp;
-    init_fwd_pixel(fp);
-    float depth_acc = 0.0f;
-    int contrib = total; // n_contrib of the plain / depth forward (see the header)
-    int cfull = total;   // what it becomes if the NEXT pop saturates the pixel
-
-    // the front entry's record rows (mean, conic + opacity, colour), fetched when an entry becomes the front
-    float4 frC = make_float4(0, 0, 0, 0), frD = frC, frF = frC;
-    int fr_id = 0;
-    float fr_depth = 0.0f;
-    auto fetch_front = [&]() __attribute__((always_inline)) { // (an empty window reads a stale slot: a harmless, clamped load)
+    __device__ __forceinline__ void fetch_front(Pixel& k) // (an empty window reads a stale slot: a harmless, clamped load)
+    {
         const float2 r = rd(rh);
-        fr_id = min(max(__float_as_int(r.y), 0), list_last);
-        if constexpr (DEPTHVIZ) fr_depth = r.x;
-        frC = ent_row(eC, fr_id); frD = ent_row(eD, fr_id); frF = ent_row(eF, fr_id);
-    };
-    // blend my window's front where `popping` holds (reference blend_one, resorted_render.cuh:74-119) and advance the ring's head
-    auto pop_front = [&](const bool popping) __attribute__((always_inline)) {
-        const float alpha0 = fminf(0.99f, frD.w * exp_blend(blend_power(frC.y - (float)px, frC.z - (float)py, frD)));
-        const float test_T = fp.T * (1.0f - alpha0);
-        const bool upd = popping && !(test_T < T_THRESHOLD);
-        const float wgt = upd ? alpha0 * fp.T : 0.0f;
-        fp.C[0] = fmaf(wgt, frF.x, fp.C[0]); fp.C[1] = fmaf(wgt, frF.y, fp.C[1]); fp.C[2] = fmaf(wgt, frF.z, fp.C[2]);
-        if constexpr (DEPTHVIZ) depth_acc += upd ? fr_depth * alpha0 * fp.T : 0.0f; // reference resorted_render.cuh:107
-        fp.T = upd ? test_T : fp.T;
-        if constexpr (RECORD) log_append(upd, fr_id);
-        else contrib = (popping && !upd) ? cfull : contrib;
-        active = active && (upd || !popping); // a saturated pixel retires
+        fr_id = min(max(__float_as_int(r.y), 0), k.list_last);
+        if constexpr (Pixel::DEPTHVIZ) fr_depth = r.x;
+        k.fetch_front(fr_id);
+    }
+    // blend my window's front where `popping` holds and advance the ring's head
+    __device__ __forceinline__ void pop_front(Pixel& k, const bool popping)
+    {
+        k.blend_front(popping, fr_depth, fr_id);
         rh = wrap(rh + (popping ? 1 : 0));
         rn -= popping ? 1 : 0;
         back_d = rn == 0 ? -FLT_MAX : back_d;
         back2_d = rn <= 1 ? -FLT_MAX : back2_d;
-    };
+    }
     // insert (depth, cid) into my window where `ins` holds; returns the logical index it took
-    auto ring_insert = [&](const bool ins, const float depth, const int cid) __attribute__((always_inline)) -> int {
+    __device__ __forceinline__ int ring_insert(const bool ins, const float depth, const int cid)
+    {
         int j = rn;                       // the logical index the candidate takes: behind everything, for a start
         int p = wrap(rh + rn);            // ... and its slot
         const bool mv1 = ins && depth < back_d;   // the last entry is deeper than the candidate (strictly: a new entry goes behind its equals): it moves up
@@ -498,79 +270,116 @@ __global__ void __launch_bounds__(256, kb_ring_waves<WIN>()) render_kbuffer_ring
             }
         }
         return j;
-    };
+    }
+    // candidate I of a group of four (rows fetched by lane I of the quad from the clamped position pf)
+    template <int I> __device__ __forceinline__ void step(Pixel& k, const int fid, const int pf, const float4 eAq, const float4 eBq, const float4 eCq, float4& eDq)
+    {
+        const int cid = quad_bcast_i<I>(pf);
+        const HeadCandidate c = head_candidate<I, FRCP>(fid, eAq, eBq, eCq, eDq, k.pix_dir, k.px, k.py, k.active);
+        pop_front(k, c.pass && rn == WIN); // a full window gives up its front before the candidate goes in
+        wave_sync();
+        fetch_front(k);                    // the front behind it: needed at the next pop, a candidate step from now
+        const bool ins = c.pass && k.active; // (a pixel that saturated at that pop is done)
+        const int at = ring_insert(ins, c.depth, cid);
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(ins && at == 0) != 0ull, 0)) { // the candidate IS the front now (a window that was empty, mostly)
+            wave_sync();
+            fetch_front(k);
+        }
+        if constexpr (!Pixel::RECORD) k.cfull = ins ? cid + 1 : k.cfull;
+    }
+    // drain: what is left in the window, front first.  Only a pop of a FULL window can be the reference's pop "in front of the next entry"
+    __device__ __forceinline__ void drain(Pixel& k)
+    {
+        if (rn != WIN) k.cfull = k.total;
+#pragma unroll 1
+        for (int it = 0; it < WIN; it++) {
+            if (!__any(k.active && rn > 0)) break;
+            pop_front(k, k.active && rn > 0);
+            wave_sync();
+            fetch_front(k);
+            k.cfull = k.total;
+        }
+    }
+};
+
+// ---- the kernel body: prologue, batch staging, quad pre-test and FIFO, head rounds, drain, epilogue -- whichever way the window is kept ----
+template <int MODE, class WINDOW>
+__device__ __forceinline__ void render_kbuffer_body(const RenderArgs& a, WINDOW& win, int* const s_stage /* [sub-tile][survivor] */, int* const s_fifo /* [quad][slot] */)
+{
+    constexpr bool RECORD = MODE == KBW_RECORD;
+    constexpr bool DEPTHVIZ = MODE == KBW_DEPTH;
+    constexpr int CAP = WINDOW::FIFO_CAP;
+
+    const WavePixel wp = wave_pixel_map(a);
+    const int lane = wp.lane, w = wp.w, s = wp.s, m = wp.m, q = wp.q, px = wp.px, py = wp.py;
+    const int total = (int)(wp.range.y - wp.range.x);
+    KbPixel<MODE> k;
+    k.lane = lane; k.px = px; k.py = py;
+    k.active = wp.inside;
+    if (total <= 0) { // an empty tile is background (and its "entry 0" -- what pads and stand-ins read -- may not exist: stp_render_hier.inc)
+        if (wp.inside) write_background_pixel<DEPTHVIZ, true>(a, px, py);
+        return;
+    }
+
+    const float3 cam = make_float3(a.cam[0], a.cam[1], a.cam[2]);
+    k.pix_dir = view_ray(a.inv_vp, cam, (float)px, (float)py, a.W, a.H);
+
+    const float4* const eA = a.entA + wp.range.x;
+    const float4* const eB = a.entB + wp.range.x;
+    const float4* const eC = a.entC + wp.range.x;
+    const float4* const eD = a.entD + wp.range.x;
+    const float4* const eF = a.entF + wp.range.x;
+    const int list_last = max(total - 1, 0);
+    k.eC = eC; k.eD = eD; k.eF = eF;
+    k.total = total; k.list_last = list_last;
+    k.logc = BlockedLogCursor{RECORD ? log_wave_slice(a.blend_log, wp.tile, w, a.log_depth) : nullptr, 2u * (uint32_t)a.log_depth, (uint32_t)lane << LOG_PIECE_SHIFT};
+
+    win.init(k);
+    init_fwd_pixel(k.fp);
+    k.depth_acc = 0.0f;
+    k.contrib = total;
+    k.cfull = total;
+    k.frC = make_float4(0, 0, 0, 0); k.frD = k.frC; k.frF = k.frC;
 
     // four candidates per quad, lane q brings candidate q (list position, -1 = none)
     auto feed4_from = [&](const int fid) __attribute__((always_inline)) {
         const int pf = min(max(fid, 0), list_last);
         float4 eAq = ent_row(eA, pf), eBq = ent_row(eB, pf), eCq = ent_row(eC, pf), eDq = ent_row(eD, pf);
-#define STP_KB_FEED(I)                                                                                                  \
-    {                                                                                                                   \
-        const int cid = quad_bcast_i<I>(pf);                                                                            \
-        if constexpr (I == 0) {                                                                                         \
-            eDq.w = fid < 0 ? 0.0f : eDq.w; /* no candidate: alpha 0 fails the tests */                                 \
-            dpp_hazard_guard_on(eDq.w);                                                                                 \
-        } else dpp_hazard_guard();                                                                                      \
-        const float depth = depth_along_ray_quad_ent<I, FRCP>(eAq, eBq, eCq, pix_dir);                                  \
-        const float dx = quad_sub<I>(eCq.y, (float)px), dy = quad_sub<I>(eCq.z, (float)py);                             \
-        const float power = blend_power_quad<I>(dx, dy, eDq);                                                           \
-        const float alpha = min_099(quad_mul<I>(eDq.w, exp_blend(power)));                                              \
-        const bool pass = active && !(depth < 0.0f) && !(power > 0.0f) && !(alpha < ALPHA_THRESHOLD);                   \
-        pop_front(pass && rn == WIN);   /* a full window gives up its front before the candidate goes in */             \
-        wave_sync();                                                                                                    \
-        fetch_front();                  /* the front behind it: needed at the next pop, a candidate step from now */    \
-        const bool ins = pass && active; /* (a pixel that saturated at that pop is done) */                             \
-        const int at = ring_insert(ins, depth, cid);                                                                    \
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(ins && at == 0) != 0ull, 0)) { /* the candidate IS the front now (a window that was empty, mostly) */ \
-            wave_sync();                                                                                                \
-            fetch_front();                                                                                              \
-        }                                                                                                               \
-        if constexpr (!RECORD) cfull = ins ? cid + 1 : cfull;                                                           \
-    }
-        STP_KB_FEED(0) STP_KB_FEED(1) STP_KB_FEED(2) STP_KB_FEED(3)
-#undef STP_KB_FEED
+        win.template step<0>(k, fid, pf, eAq, eBq, eCq, eDq);
+        win.template step<1>(k, fid, pf, eAq, eBq, eCq, eDq);
+        win.template step<2>(k, fid, pf, eAq, eBq, eCq, eDq);
+        win.template step<3>(k, fid, pf, eAq, eBq, eCq, eDq);
     };
 
-    int* const hfifo = s_fifo + ((w * 4 + s) * 4 + m) * KBR_CAP;
-    int hf_head = 0, hf_cnt = 0; // (quad-uniform)
-    auto fwrap = [&](int v) __attribute__((always_inline)) -> int { // v in [0, 3 KBR_CAP) -> [0, KBR_CAP)
-        v -= v >= 2 * KBR_CAP ? 2 * KBR_CAP : 0;
-        return v - (v >= KBR_CAP ? KBR_CAP : 0);
-    };
-    auto head_round = [&](const bool force) __attribute__((always_inline)) -> bool {
-        const unsigned long long act = __ballot(active);
-        const bool qlive = ((act >> (lane & ~3)) & 0xFull) != 0ull;
-        if (!qlive) { hf_head = fwrap(hf_head + hf_cnt); hf_cnt = 0; }
-        bool go;
-        if (force) go = __any(hf_cnt > 0);
-        else go = __any(hf_cnt > KBR_CAP - 16) || (__all(hf_cnt >= 4 || !qlive) && __any(hf_cnt >= 4));
-        if (!go) return false;
-        const int n = min(hf_cnt, 4);
+    int* const hfifo = s_fifo + ((w * 4 + s) * 4 + m) * CAP;
+    QuadFifo<CAP> hf;
+    auto head_round = [&](const bool force) __attribute__((always_inline)) -> bool { // false: nothing (more) to do now
+        if (!hf.round_due(force, quad_live(__ballot(k.active), lane))) return false;
         wave_sync();
-        const int fid = q < n ? hfifo[fwrap(hf_head + q)] : -1;
-        hf_head = fwrap(hf_head + n);
-        hf_cnt -= n;
-        feed4_from(fid);
+        feed4_from(hf.take4(hfifo, q));
         return true;
     };
     auto head_rounds = [&](const bool force) __attribute__((always_inline)) {
 #pragma unroll 1
         for (;;) {
             if (!head_round(force)) break;
+            if constexpr (WINDOW::DOUBLE_ROUND) { if (!head_round(force)) break; }
         }
     };
 
-    // ---- main loop: batches of 32 list entries (as in the kernel above) -----------------------------------------------
+    // ---- main loop: batches of 32 list entries -----------------------------------------------------------------------
     const int half = lane >> 5, e = lane & 31;
-    int* const stA = s_stage + (w * 4 + 2 * half) * 32;
+    int* const stA = s_stage + (w * 4 + 2 * half) * 32; // my half's two sub-tiles: [0..32) and [32..64)
     const int* const st_row = s_stage + (w * 4 + s) * 32;
-    const float qxc = (float)(px - (q & 1)) + 0.5f, qyc = (float)(py - (q >> 1)) + 0.5f;
+    const float qxc = (float)(px - (q & 1)) + 0.5f, qyc = (float)(py - (q >> 1)) + 0.5f; // centre of my 2x2 quad
 #pragma unroll 1
     for (int base = 0; base < total; base += 32) {
-        if (!__any(active)) break;
+        if (!__any(k.active)) break;
+        // stage: lane = entry e of the batch x the sub-tile pair of my half
         const int ep = base + e;
         bool keepA = false, keepB = false;
         if (ep < total) {
+            // (the sixteen sub-tile verdicts of this entry were computed by the entry gather, stp_tilesort.hip: subtile_keep_mask_kbuffer)
             const uint32_t mask = __float_as_uint(*reinterpret_cast<const float*>(reinterpret_cast<const char*>(eF) + ((uint32_t)ep << 4) + 12));
             const uint32_t mine = mask >> (4 * w + 2 * half);
             keepA = (mine & 1u) != 0u;
@@ -579,11 +388,12 @@ __global__ void __launch_bounds__(256, kb_ring_waves<WIN>()) render_kbuffer_ring
         const unsigned long long balA = __ballot(keepA), balB = __ballot(keepB);
         const unsigned int mA = (unsigned int)(balA >> (32 * half)), mB = (unsigned int)(balB >> (32 * half));
         const unsigned int below = (1u << e) - 1u;
-        wave_sync();
+        wave_sync(); // (the previous batch's readers are done)
         if (keepA) stA[__popc(mA & below)] = ep;
         if (keepB) stA[32 + __popc(mB & below)] = ep;
         wave_sync();
-        const int n_s = __popc((unsigned int)(((s & 1) ? balB : balA) >> (32 * (s >> 1))));
+        const int n_s = __popc((unsigned int)(((s & 1) ? balB : balA) >> (32 * (s >> 1)))); // my sub-tile's survivors
+        // feed: groups of four survivors per quad, head steps after every 16
         int n_max = n_s;
 #pragma unroll
         for (int o = 16; o < 64; o <<= 1) n_max = max(n_max, __shfl_xor(n_max, o));
@@ -595,54 +405,44 @@ __global__ void __launch_bounds__(256, kb_ring_waves<WIN>()) render_kbuffer_ring
                 int fid = -1;
                 if (i < n_s) fid = st_row[i];
                 bool keep = false;
-                const unsigned long long act = __ballot(active);
-                const bool qlive = ((act >> (lane & ~3)) & 0xFull) != 0ull;
-                if (fid >= 0 && qlive) keep = kb_quad_can_blend(ent_row(eC, fid), ent_row(eD, fid), qxc, qyc);
-                int bits = keep ? (1 << q) : 0;
-                bits += __builtin_amdgcn_mov_dpp(bits, 0xB1, 0xF, 0xF, true);
-                bits += __builtin_amdgcn_mov_dpp(bits, 0x4E, 0xF, 0xF, true);
-                if (keep) hfifo[fwrap(hf_head + hf_cnt + __popc(bits & ((1 << q) - 1)))] = fid;
-                hf_cnt += __popc(bits);
+                const bool qlive = quad_live(__ballot(k.active), lane); // (a ballot: every lane takes part, with or without an entry)
+                if (fid >= 0 && qlive) keep = quad_can_blend(ent_row(eC, fid), ent_row(eD, fid), qxc, qyc);
+                hf.push(hfifo, q, keep, fid);
             }
             head_rounds(false);
         }
     }
     head_rounds(true);
-    // drain: what is left in the window, front first.  Only a pop of a FULL window can be the reference's pop "in front of the next entry"
-    if (rn != WIN) cfull = total;
-#pragma unroll 1
-    for (int it = 0; it < WIN; it++) {
-        if (!__any(active && rn > 0)) break;
-        pop_front(active && rn > 0);
-        wave_sync();
-        fetch_front();
-        cfull = total;
-    }
+    win.drain(k);
 
-    if constexpr (RECORD) log_flush();
-    if (inside) {
-        const size_t N = (size_t)a.W * a.H, pid = (size_t)a.W * py + px;
-        a.final_T[pid] = fp.T;
-        a.n_contrib[pid] = RECORD ? (uint32_t)log_records() : (uint32_t)contrib;
-        if constexpr (DEPTHVIZ) {
-            a.out_color[pid] = depth_acc;
-            a.out_color[N + pid] = fp.T;
-        } else {
-            a.out_color[pid] = fp.C[0] + fp.T * a.bg[0];
-            a.out_color[N + pid] = fp.C[1] + fp.T * a.bg[1];
-            a.out_color[2 * N + pid] = fp.C[2] + fp.T * a.bg[2];
-        }
-    }
-    if constexpr (RECORD) {
-        if (log_records() > a.log_depth || total > LOG_MAX_LIST) a.tile_flags[tile] = 1u;
-        report_log_need(a.log_need, log_records(), a.log_tag);
-    }
+    if constexpr (RECORD) k.logc.flush();
+    if (wp.inside) write_forward_pixel<DEPTHVIZ, true>(a, px, py, k.fp, k.depth_acc, RECORD ? (uint32_t)k.logc.records() : (uint32_t)k.contrib); // (recording forward: the pixel's number of log records)
+    if constexpr (RECORD) finish_blend_log(a, wp.tile, k.logc.records(), total);
+}
+
+template <int WIN, int MODE, bool FRCP>
+__global__ void __launch_bounds__(256, (KbRegWindow<WIN, MODE, FRCP>::WAVES)) render_kbuffer_wave_kernel(const RenderArgs a)
+{
+    __shared__ int s_stage[16 * 32];
+    __shared__ int s_fifo[64 * KbRegWindow<WIN, MODE, FRCP>::FIFO_CAP];
+    KbRegWindow<WIN, MODE, FRCP> win;
+    render_kbuffer_body<MODE>(a, win, s_stage, s_fifo);
+}
+
+template <int WIN, int MODE, bool FRCP>
+__global__ void __launch_bounds__(256, (KbRingWindow<WIN, MODE, FRCP>::WAVES)) render_kbuffer_ring_kernel(const RenderArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    KbRingWindow<WIN, MODE, FRCP> win;
+    win.ring = smem;
+    int* const s_stage = reinterpret_cast<int*>(smem + win.RING_BYTES);
+    render_kbuffer_body<MODE>(a, win, s_stage, s_stage + 16 * 32);
 }
 
 template <int WIN, int MODE> hipError_t launch_kb_ring(const FrameParams& f, const RenderArgs& a, hipStream_t st)
 {
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(256);
-    constexpr size_t lds = kb_ring_lds<WIN>();
+    constexpr size_t lds = KbRingWindow<WIN, MODE, true>::LDS_BYTES;
     if (f.wild_cov) hipLaunchKernelGGL((render_kbuffer_ring_kernel<WIN, MODE, false>), grid, block, lds, st, a);
     else hipLaunchKernelGGL((render_kbuffer_ring_kernel<WIN, MODE, true>), grid, block, lds, st, a);
     return hipGetLastError();

@@ -24,7 +24,7 @@
 // few records that the re-sort moved behind the window fall back to global atomics.  Before the LDS adds,
 // lanes that hold the same position merge their terms pairwise with DPP (the adds serialise on equal addresses).
 #include "stp_internal.h"
-#include "stp_blend.h"
+#include "stp_render_wave.h"
 
 namespace stp {
 
@@ -47,13 +47,6 @@ namespace {
 constexpr int WINDOW = STP_REPLAY_WINDOW; // list positions per window (9 x 512 x 8 B = 36 KB of LDS: four workgroups per CU)
 constexpr int EXHAUSTED = 0x7fffffff; // "position" of a lane that has no record left
 
-__device__ __forceinline__ int replay_remap_tile(int wg, int n_wg)
-{
-    const int q = n_wg >> 3, r = n_wg & 7;
-    const int xcd = wg & 7, k = wg >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-
 // (One kernel for both kinds of tile: as two launches the mixed case -- C2-min -- loses more to the half-empty grids
 // than the lean loop gains.)
 // LOG_BLOCKED: the forward's log layout (stp_blend.h: rows in hierarchical mode, blocked in k-buffer mode)
@@ -63,15 +56,11 @@ __global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(cons
     __shared__ unsigned long long s_acc[9 * WINDOW]; // [term][position - window start]
     __shared__ float s_md[4];
 
-    const int lane = (int)(threadIdx.x & 63), w = (int)(threadIdx.x >> 6);
-    const int s = lane >> 4, x = lane & 15, m = x >> 2, q = x & 3;
-    const int rows = a.ty1 - a.ty0;
-    const int t = a.tile_order ? (int)a.tile_order[blockIdx.x] : replay_remap_tile((int)blockIdx.x, a.gx * rows);
-    const int tile_x = t % a.gx, tile_y = a.ty0 + t / a.gx, tile = tile_y * a.gx + tile_x;
+    const WavePixel wp = wave_pixel_map(a); // (the forward's thread -> pixel map, stp_render_wave.h)
+    const int lane = wp.lane, w = wp.w, x = wp.x, q = wp.q, tile = wp.tile, px = wp.px, py = wp.py;
     if (a.tile_flags[tile] != 0u) return; // log overflow: the re-sorting backward takes this tile
-    const uint2 range = a.ranges[tile];
-    const int px = tile_x * TILE + 4 * s + 2 * (m & 1) + (q & 1), py = tile_y * TILE + 4 * w + 2 * (m >> 1) + (q >> 1);
-    const bool inside = px < a.W && py < a.H;
+    const uint2 range = wp.range;
+    const bool inside = wp.inside;
     const int list_len = (int)(range.y - range.x);
     if (list_len <= 0) return;
 

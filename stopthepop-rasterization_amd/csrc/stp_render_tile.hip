@@ -16,22 +16,13 @@
 #include <cstdlib>
 #include <cstring>
 #include "stp_internal.h"
-#include "stp_blend.h"
+#include "stp_render_wave.h"
 
 namespace stp {
 
 namespace {
 
 constexpr int BLOCK = 256;
-
-// XCD-aware tile order: consecutive workgroup ids land on different XCDs (id % 8), so give every XCD
-// a contiguous run of tiles -- neighbouring tiles share Gaussians, which then hit in that XCD's L2.
-__device__ __forceinline__ int remap_tile(int wg, int n_wg)
-{
-    const int q = n_wg >> 3, r = n_wg & 7;
-    const int xcd = wg & 7, k = wg >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
 
 // Sum over the 64 lanes of a wave; result valid in every lane (uniform).
 __device__ __forceinline__ float wave_sum(float v)
@@ -57,8 +48,7 @@ struct TileCtx {
 __device__ __forceinline__ TileCtx tile_ctx(const RenderArgs& a)
 {
     TileCtx c;
-    const int rows = a.ty1 - a.ty0;
-    const int t = a.tile_order ? (int)a.tile_order[blockIdx.x] : remap_tile((int)blockIdx.x, a.gx * rows);
+    const int t = workgroup_tile(a); // (stp_render_wave.h)
     c.tx = t % a.gx;
     c.ty = a.ty0 + t / a.gx;
     c.tile = c.ty * a.gx + c.tx;
@@ -284,10 +274,8 @@ __global__ void __launch_bounds__(BLOCK) render_kbuffer_kernel(const RenderArgs 
     }
     const int lane = (int)(threadIdx.x & 63), w = (int)(threadIdx.x >> 6);
     if constexpr (RECORD) { // the replay kernel's pixel of (wave, lane): wave = row of four 4x4 sub-tiles, 2x2 quads inside
-        const int sb = lane >> 4, x = lane & 15, m = x >> 2, q = x & 3;
-        c.px = c.tx * TILE + 4 * sb + 2 * (m & 1) + (q & 1);
-        c.py = c.ty * TILE + 4 * w + 2 * (m >> 1) + (q >> 1);
-        c.inside = c.px < a.W && c.py < a.H;
+        const WavePixel wp = wave_pixel_map(a);
+        c.px = wp.px; c.py = wp.py; c.inside = wp.inside;
     }
     const float pxf = (float)c.px, pyf = (float)c.py;
     bool done = !c.inside;
@@ -381,23 +369,8 @@ __global__ void __launch_bounds__(BLOCK) render_kbuffer_kernel(const RenderArgs 
         while (win.num > 0 && !done) blend_one();
 
     if constexpr (!BACKWARD) {
-        if (c.inside) {
-            const size_t N = (size_t)a.W * a.H, pid = (size_t)a.W * c.py + c.px;
-            a.final_T[pid] = fp.T;
-            a.n_contrib[pid] = RECORD ? (uint32_t)nrec : contributor; // (recording forward: the pixel's number of log records)
-            if constexpr (DEPTHVIZ) {
-                a.out_color[pid] = depth_acc;
-                a.out_color[N + pid] = fp.T;
-            } else {
-                a.out_color[pid] = fp.C[0] + fp.T * a.bg[0];
-                a.out_color[N + pid] = fp.C[1] + fp.T * a.bg[1];
-                a.out_color[2 * N + pid] = fp.C[2] + fp.T * a.bg[2];
-            }
-        }
-        if constexpr (RECORD) {
-            if (nrec > a.log_depth || total > LOG_MAX_LIST) a.tile_flags[c.tile] = 1u; // log overflow: this tile's backward re-sorts
-            report_log_need(a.log_need, nrec, a.log_tag);
-        }
+        if (c.inside) write_forward_pixel<DEPTHVIZ, true>(a, c.px, c.py, fp, depth_acc, RECORD ? (uint32_t)nrec : contributor); // (recording forward: the pixel's number of log records)
+        if constexpr (RECORD) finish_blend_log(a, c.tile, nrec, total);
     }
 }
 
