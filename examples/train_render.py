@@ -3,7 +3,7 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
@@ -28,7 +28,8 @@ from diff_gaussian_rasterization import (CullingSettings, ExtendedSettings, Gaus
 def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, scaling_modifier: float = 1.0,
            override_color: torch.Tensor | None = None, render_depth: bool = False, debug: bool = False):
     """One frame.  Gradients flow to every model tensor; `viewspace_points.grad` is the screen-space positional
-    gradient densification uses."""
+    gradient densification uses -- and with `splat_args._absgrad = True`, `viewspace_points.absgrad` (after backward) the
+    sum of the ABSOLUTE per-pixel contributions to it (AbsGS / gsplat's absgrad)."""
     screenspace_points = torch.zeros_like(model.get_xyz, requires_grad=True)
     raster_settings = GaussianRasterizationSettings(
         image_height=int(camera.image_height), image_width=int(camera.image_width),
@@ -89,6 +90,7 @@ def main(argv=None):
     ap.add_argument("--config", default="full", choices=["full", "min", "kbuffer", "global"])
     ap.add_argument("--points", type=int, default=20000)
     ap.add_argument("--size", type=int, nargs=2, default=[320, 240], metavar=("W", "H"))
+    ap.add_argument("--absgrad", action="store_true", help="also accumulate the absolute screen-space gradient (densification statistic of AbsGS)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
@@ -106,13 +108,23 @@ def main(argv=None):
         model._opacity.sub_(1.0)
     opt = torch.optim.Adam([{"params": [model._features], "lr": 2e-2}, {"params": [model._opacity], "lr": 5e-2},
                             {"params": [model._xyz, model._scaling, model._rotation], "lr": 0.0}])
+    train_cfg = splat_config(args.config)
+    train_cfg._absgrad = args.absgrad   # (a request on the settings object; the depth rendering below keeps the plain settings: it refuses it)
+    # the densification statistic a trainer accumulates between two densify steps: the norm of the 2D positional gradient per visible
+    # Gaussian -- signed (3DGS: pulls from opposite sides cancel) and, with --absgrad, absolute (AbsGS: they add up)
+    stat_signed = torch.zeros(model.get_xyz.shape[0], device=dev)
+    stat_abs = torch.zeros_like(stat_signed)
     first = last = None
     for it in range(args.iters):
-        out = render(cam, model, bg, cfg)
+        out = render(cam, model, bg, train_cfg)
         loss = (out["render"] - target).abs().mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
         grad2d = out["viewspace_points"].grad  # what densification accumulates
+        vis = out["visibility_filter"]
+        stat_signed[vis] += grad2d[vis, :2].norm(dim=-1)
+        if args.absgrad:   # assigned by every backward, never accumulated: the running sum is the trainer's
+            stat_abs[vis] += out["viewspace_points"].absgrad[vis, :2].norm(dim=-1)
         opt.step()
         last = float(loss.detach())
         first = last if first is None else first
@@ -120,6 +132,9 @@ def main(argv=None):
             print(f"iter {it:3d}  L1 {last:.5f}  visible {int(out['visibility_filter'].sum())}  |grad2D| max {float(grad2d.norm(dim=1).max()):.3e}")
     with torch.no_grad():
         depth = render(cam, model, bg, cfg, render_depth=True)["render"]
+    if args.absgrad:
+        print(f"densification statistic, mean over Gaussians: signed {float(stat_signed.mean()):.3e}, absolute {float(stat_abs.mean()):.3e} "
+              f"(absolute >= signed for {float((stat_abs >= stat_signed * (1 - 1e-5)).float().mean()) * 100:.1f} % of them)")
     print(f"L1 {first:.5f} -> {last:.5f}; depth visualisation {tuple(depth.shape)} in [{float(depth.min()):.3f}, {float(depth.max()):.3f}]")
     return first, last
 

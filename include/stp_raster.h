@@ -31,6 +31,7 @@ extern "C" {
 #define STP_ABI_VERSION 7
 #define STP_GRAD_RECORD_FLOATS 16 /* floats per Gaussian in grad_records (see stp_backward) */
 #define STP_GRAD_RECORD_USED 9    /* of which these carry data; the record stride of stp_backward_phases' compact form (phases bit 2) */
+#define STP_GRAD_RECORD_ABS 9     /* first of the two slots that carry sum |dL/dmean2D| xy under stp_set_backward_absgrad (padded records only) */
 
 /* Replaces CudaRasterizer::SplattingSettings + SortSettings + SortQueueSizes + CullingSettings
    (rasterizer.h:27-135) and their json parser (rasterizer.h:160-182): the host binding fills this
@@ -126,7 +127,8 @@ void stp_set_forward_split(int tile_row, void* event);
    grad_records (P x STP_GRAD_RECORD_FLOATS floats) is the hand-over between the two halves of the backward.
    It takes the place of the reference's dL_dconic scratch tensor (rasterize_points.cu:181): the render half sums
    its nine per-Gaussian terms into ONE 64-byte record per Gaussian,
-       [0..2] dL/dcolour rgb   [3..4] dL/dmean2D xy   [5..7] dL/dconic xx, xy, yy   [8] dL/dopacity   [9..15] unused
+       [0..2] dL/dcolour rgb   [3..4] dL/dmean2D xy   [5..7] dL/dconic xx, xy, yy   [8] dL/dopacity
+       [9..10] sum |dL/dmean2D| xy (only with the absgrad request)   [11..15] unused
    (one atomic instruction / one L2 request per flush instead of nine into four arrays: 9x the flush rate on
    MI355X, tools/global_atomic_bench.hip); the per-Gaussian half reads the record and writes dL_dmean2D,
    dL_dopacity and dL_dcolor in the reference's layouts along with the remaining gradients. */
@@ -193,6 +195,24 @@ int stp_backward_phases(int phases, int P, int D, int M, int R,
    it pending. */
 size_t stp_camera_grad_workspace_bytes(int P);
 void stp_set_backward_camera_grads(float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* workspace, size_t workspace_bytes);
+
+/* Extension (not in the reference): absolute screen-space gradients ("absgrad", the densification statistic of AbsGS / gsplat).  The NEXT
+   stp_backward or stp_backward_phases of the calling thread also produces, for every Gaussian i,
+       dL_dmean2D_abs[3 i], [3 i + 1] = sum over pixels p of |g_x,p(i)|, |g_y,p(i)|      dL_dmean2D_abs[3 i + 2] = 0
+   where g_p(i) is what pixel p adds to dL_dmean2D[i] (the factors 0.5 W, 0.5 H included): dL_dmean2D is the signed sum of the same terms
+   over the same (pixel, Gaussian) pairs, so dL_dmean2D_abs >= |dL_dmean2D| elementwise up to rounding, with equality where a Gaussian
+   receives one contribution.  Every row is written (device pointer, P x 3 floats, no zero-fill by the caller): zeros for Gaussians with
+   radii <= 0.  The render half takes the absolute values per blended pair, before anything is summed, and adds them to slots
+   STP_GRAD_RECORD_ABS, + 1 of the Gaussian's padded record (the same atomic request as the nine sums); the per-Gaussian half moves them to
+   dL_dmean2D_abs before it reads -- and, with phases bit 3, clears -- the record (the cleared 48 bytes include both slots).  Every other
+   output of the call is what it is without the request, up to the run-to-run variation of the render half's float atomics.
+   A NULL pointer clears a pending request.  The request is consumed by the next stp_backward / stp_backward_phases of the thread, whatever
+   that call's outcome -- a call that fails, or that has nothing to do (P == 0), leaves no pointer behind -- with one exception: a render-only
+   call (phases = 1) that SUCCEEDS honours it -- the sums stay in slots 9, 10 of the records it fills -- and leaves it pending for the
+   per-Gaussian call, which must then get those records.  STP_ERR_INVALID_ARGUMENT: compact records (phases bit 2: 36 bytes per Gaussian have no room for the
+   two sums), or a chunked per-Gaussian half (phases bits 8-23: REFUSED, as camera gradients are -- one request is one whole per-Gaussian
+   half). */
+void stp_set_backward_absgrad(float* dL_dmean2D_abs /* P x 3 */);
 
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:188-193, rasterizer_impl.cu:161-173).
    `present` is P bytes (bool). */

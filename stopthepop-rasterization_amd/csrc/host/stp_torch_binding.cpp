@@ -67,6 +67,7 @@ struct Api {
     // optional (an older library without them still loads; asking it for camera gradients raises)
     decltype(&stp_camera_grad_workspace_bytes) camera_grad_workspace_bytes = nullptr;
     decltype(&stp_set_backward_camera_grads) set_backward_camera_grads = nullptr;
+    decltype(&stp_set_backward_absgrad) set_backward_absgrad = nullptr;
 } g_api;
 
 int load_library(const std::string& path)
@@ -86,6 +87,7 @@ int load_library(const std::string& path)
         throw std::runtime_error(path + " does not export the C ABI of include/stp_raster.h");
     a.camera_grad_workspace_bytes = reinterpret_cast<decltype(a.camera_grad_workspace_bytes)>(dlsym(h, "stp_camera_grad_workspace_bytes"));
     a.set_backward_camera_grads = reinterpret_cast<decltype(a.set_backward_camera_grads)>(dlsym(h, "stp_set_backward_camera_grads"));
+    a.set_backward_absgrad = reinterpret_cast<decltype(a.set_backward_absgrad)>(dlsym(h, "stp_set_backward_absgrad"));
     if (a.abi_version() != STP_ABI_VERSION) throw std::runtime_error(path + ": ABI version mismatch");
     g_api = a; // (a previously loaded library stays mapped: buffers of its forwards may still be in flight)
     return a.abi_version();
@@ -310,6 +312,8 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
 // runs the per-Gaussian half.
 // camera_grads (extension, include/stp_raster.h: stp_set_backward_camera_grads): the per-Gaussian half also returns dL/dviewmatrix,
 // dL/dprojmatrix and dL/dcampos, appended to the eight gradients in the shapes of the three inputs.
+// absgrad (extension, include/stp_raster.h: stp_set_backward_absgrad): one more (P,3) tensor, LAST in the result: the per-Gaussian sums over
+// pixels of |each pixel's contribution to dL/dmeans2D| (x, y; column 2 zero).  Whole backwards on padded records only.
 std::vector<torch::Tensor>
 rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& opacities,
                              const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
@@ -318,7 +322,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
                              const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                              const py::dict& settings, const bool debug, const bool record_log, const int phases, const c10::optional<torch::Tensor>& partial,
-                             const c10::optional<std::vector<torch::Tensor>>& outputs, const bool camera_grads)
+                             const c10::optional<std::vector<torch::Tensor>>& outputs, const bool camera_grads, const bool absgrad)
 {
     need_library();
     TORCH_CHECK(means3D.is_cuda(), "diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
@@ -327,6 +331,13 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
             throw std::runtime_error(std::string("camera gradients: the loaded libstp_raster.so does not export ") +
                                      (g_api.set_backward_camera_grads ? "stp_camera_grad_workspace_bytes" : "stp_set_backward_camera_grads") + "; rebuild it");
         TORCH_CHECK(phases & 2, "camera gradients come from the per-Gaussian half (phases bit 1)");
+    }
+    if (absgrad) {
+        if (!g_api.set_backward_absgrad)
+            throw std::runtime_error("absgrad: the loaded libstp_raster.so does not export stp_set_backward_absgrad (a library built before absgrad): rebuild it");
+        // (the render half leaves the two sums in the records it has just filled and the per-Gaussian half of the SAME call collects them: a
+        // half on its own would need the caller to carry request and records from one call to the other)
+        TORCH_CHECK((phases & 3) == 3, "absgrad needs both halves of the backward in one call (phases bits 0 and 1)");
     }
     const torch::Device dev = means3D.device();
     const int P = (int)means3D.size(0);
@@ -375,13 +386,16 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         TORCH_CHECK(dL_dview.numel() == 16 && dL_dproj.numel() == 16 && dL_dcam.numel() == 3, "camera gradients: viewmatrix and projmatrix must have 16 elements, campos 3");
         cam_ws = torch::empty({(int64_t)g_api.camera_grad_workspace_bytes(P)}, means3D.options().dtype(torch::kByte));
     }
-    auto request_camera_grads = [&] {
+    torch::Tensor dL_dmeans2D_abs;
+    if (absgrad) dL_dmeans2D_abs = torch::empty({P, 3}, fopt); // written in full by the library (zeros for invisible Gaussians)
+    auto make_requests = [&] { // (both are consumed by the library call that follows, on this thread)
+        if (absgrad && P != 0) g_api.set_backward_absgrad(dL_dmeans2D_abs.data_ptr<float>());
         if (camera_grads) g_api.set_backward_camera_grads(dL_dview.data_ptr<float>(), dL_dproj.data_ptr<float>(), dL_dcam.data_ptr<float>(), cam_ws.data_ptr(), (size_t)cam_ws.numel());
     };
     if (P == 0 && camera_grads) { // nothing to differentiate: the library writes the zeros
         const c10::hip::HIPGuard guard(dev.index());
         hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
-        request_camera_grads();
+        make_requests();
         const int rc = g_api.backward_phases(phases, 0, degree, M, R, nullptr, W, H, &s, nullptr, nullptr, nullptr, nullptr, nullptr, scale_modifier, nullptr,
                                            nullptr, nullptr, nullptr, nullptr, nullptr, tan_fovx, tan_fovy, nullptr, nullptr, nullptr, nullptr, nullptr,
                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, debug ? 1 : 0, (void*)stream);
@@ -399,7 +413,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
         forget_unless_same_storage(binningBuffer); // (a clone, a copy or a recycled address: the library then reads the buffer's own header)
         forget_unless_same_storage(imageBuffer);
-        request_camera_grads(); // (consumed by the call below, on this thread)
+        make_requests(); // (consumed by the call below, on this thread)
         const int rc = g_api.backward_phases(keep_records ? (phases | 8) : phases, P, degree, M, R, fptr(bg_), W, H, &s, fptr(m3_), fptr(sh_), fptr(op_), fptr(col_), fptr(sc_),
                                            scale_modifier, fptr(ro_), fptr(c3_), fptr(vm_), fptr(pm_), fptr(inv_), fptr(cam_), tan_fovx, tan_fovy,
                                            fptr(pix_), radii_.numel() ? radii_.data_ptr<int>() : nullptr, optb(geomBuffer), optb(binningBuffer),
@@ -413,8 +427,10 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         }
     }
     if ((phases & 3) == 1) return {records};
-    if (camera_grads) return {dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview, dL_dproj, dL_dcam};
-    return {dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations};
+    std::vector<torch::Tensor> result{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations};
+    if (camera_grads) result.insert(result.end(), {dL_dview, dL_dproj, dL_dcam});
+    if (absgrad) result.push_back(dL_dmeans2D_abs);
+    return result;
 }
 
 // == markVisible (reference rasterize_points.cu:234-253)

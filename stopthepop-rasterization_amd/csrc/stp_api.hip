@@ -1002,6 +1002,11 @@ void stp_set_backward_camera_grads(float* dL_dviewmatrix, float* dL_dprojmatrix,
     t_camera_grads = CameraGradRequest{dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, workspace, workspace_bytes};
 }
 
+// stp_set_backward_absgrad: the calling thread's request for its NEXT backward.  Every call takes it; only a render-only call that has run
+// puts it back for the per-Gaussian call (a call that fails, or has nothing to do, leaves no pointer behind)
+thread_local float* t_absgrad = nullptr;
+void stp_set_backward_absgrad(float* dL_dmean2D_abs) { t_absgrad = dL_dmean2D_abs; }
+
 int stp_backward_phases(int phases, int P, int D, int M, int R, const float* background, int width, int height, const StpSettings* settings,
                  const float* means3D, const float* shs, const float* opacities, const float* colors_precomp, const float* scales,
                  float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
@@ -1015,6 +1020,14 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     if (phases & 2) { // (one per-Gaussian half per request, whatever its outcome)
         cam = t_camera_grads;
         t_camera_grads = CameraGradRequest{};
+    }
+    float* const absgrad = t_absgrad;
+    t_absgrad = nullptr; // (put back at the end of a render-only call that ran)
+    if (absgrad) {
+        if (phases & 4)
+            return fail(STP_ERR_INVALID_ARGUMENT, "absgrad is not available with compact gradient records (phases bit 2): the 36-byte record has no room for the two extra sums");
+        if (((phases >> 8) & 0xFF) > 1)
+            return fail(STP_ERR_INVALID_ARGUMENT, "absgrad is not available from a chunked per-Gaussian half (phases bits 8-23)");
     }
     if (cam.dL_dview) {
         if (!cam.workspace || (reinterpret_cast<uintptr_t>(cam.workspace) & 15) != 0 || cam.workspace_bytes < camera_grad_workspace_bytes(P))
@@ -1049,6 +1062,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
 
     BackwardParams bw;
     bw.cam = cam;
+    bw.absgrad = absgrad;
     bw.pixel_colors = pixel_colors; bw.dL_dpix = dL_dpix; bw.dL_dmean2D = dL_dmean2D; bw.grad_rec = grad_records;
     bw.grad_stride = (phases & 4) ? STP_GRAD_RECORD_USED : STP_GRAD_RECORD_FLOATS;
     bw.clear_rec = (phases & 8) ? 1 : 0;
@@ -1075,6 +1089,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
         STP_DEBUG_SYNC("backward preprocess");
         g_timer.mark(7, st);
     }
+    if (!(phases & 2)) t_absgrad = absgrad; // render-only: the sums are in the records, the per-Gaussian call collects them
     return 0;
 }
 

@@ -534,6 +534,23 @@ __global__ void __launch_bounds__(1024) camera_grad_final_kernel(const double* _
     }
 }
 
+// absgrad request (stp_set_backward_absgrad): slots STP_GRAD_RECORD_ABS, + 1 of every visible Gaussian's record -> out[3 i], out[3 i + 1];
+// column 2 and the invisible Gaussians get zeros (every row is written: the caller does no zero-fill).  A kernel of its own, launched IN
+// FRONT of preprocess_backward_kernel -- which clears the records behind its read (clear_rec) and stays the kernel it was.  12 + 4 bytes
+// read and 12 written per Gaussian.
+__global__ void __launch_bounds__(256) absgrad_extract_kernel(int P, const int* __restrict__ radii, const float* __restrict__ rec, int stride,
+                                                              float* __restrict__ out)
+{
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= P) return;
+    float ax = 0.0f, ay = 0.0f;
+    if (radii[i] > 0) {
+        ax = rec[(size_t)stride * i + STP_GRAD_RECORD_ABS];
+        ay = rec[(size_t)stride * i + STP_GRAD_RECORD_ABS + 1];
+    }
+    out[3 * (size_t)i] = ax; out[3 * (size_t)i + 1] = ay; out[3 * (size_t)i + 2] = 0.0f;
+}
+
 constexpr int kCamMaxParts = 256;
 int camera_grad_parts(int n_rows) { return max(1, min(kCamMaxParts, (n_rows + 191) / 192)); }
 
@@ -584,6 +601,11 @@ hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState&
     }
     a.block0 = b0;
     if (b1 <= b0) return hipSuccess;
+    if (bw.absgrad != nullptr) { // (the caller has refused a chunked half and compact records with the request: all Gaussians, slots 9, 10 exist)
+        hipLaunchKernelGGL(absgrad_extract_kernel, dim3(n_blocks), dim3(256), 0, st, f.P, radii, (const float*)bw.grad_rec, bw.grad_stride, bw.absgrad);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     if (cam) {
         hipLaunchKernelGGL(preprocess_backward_kernel<true>, dim3(b1 - b0), dim3(256), lds, st, a);
         hipError_t e = hipGetLastError();

@@ -35,6 +35,9 @@ struct RenderArgs {
     const float* dL_dpix;
     float* grad_rec;   // P x grad_stride floats: the nine sums of a Gaussian in one record (stp_raster.h, stp_backward)
     int grad_stride;   // floats per record: STP_GRAD_RECORD_FLOATS (one 64-byte line), or 9 = compact (tile-row sharding: what crosses xGMI)
+    int absgrad;       // backward kernels (stp_set_backward_absgrad): non-zero = every blended pair also adds |g[3]|, |g[4]| -- the absolute values of its
+                       // two dL/dmean2D terms -- to slots STP_GRAD_RECORD_ABS, + 1 of its Gaussian's record.  (In the four bytes of padding behind
+                       // grad_stride: the kernarg layout of everything else is what it was.)
     // blend log (training forward -> replay backward): per (tile, wave, k, lane) the list position of the k-th
     // entry that lane's pixel blended; tile_flags[tile] != 0 marks a tile whose log overflowed
     uint32_t* blend_log;   // (storage; the records are log_t)
@@ -264,6 +267,14 @@ __device__ __forceinline__ float* grad_slot(const RenderArgs& a, int id, int k)
     return a.grad_rec + (size_t)a.grad_stride * id + k;
 }
 
+// the two extra sums of the absgrad request, straight to memory: |dL/dmean2D| of ONE blended pair (taken before any lanes are summed)
+constexpr int GRAD_ABS = STP_GRAD_RECORD_ABS;
+__device__ __forceinline__ void add_absgrad(const RenderArgs& a, int id, const float (&g)[9])
+{
+    atomicAdd(grad_slot(a, id, GRAD_ABS), fabsf(g[3]));
+    atomicAdd(grad_slot(a, id, GRAD_ABS + 1), fabsf(g[4]));
+}
+
 // Straightforward accumulation: nine hardware fp32 atomics (global_atomic_add_f32; build with
 // -munsafe-fp-atomics) per blended pair -- what the reference does (hierarchical_render.cuh:1131-1161).
 __device__ __forceinline__ bool blend_backward(BwdPixel& b, const RenderArgs& a, int px, int py, int id, float G)
@@ -273,6 +284,7 @@ __device__ __forceinline__ bool blend_backward(BwdPixel& b, const RenderArgs& a,
     if (!blend_backward_terms(b, a, px, py, fd, G, g)) return false;
 #pragma unroll
     for (int k = 0; k < 9; k++) atomicAdd(grad_slot(a, id, k), g[k]);
+    if (a.absgrad) add_absgrad(a, id, g);
     return true;
 }
 

@@ -340,6 +340,9 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         float g[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) g[k] = g_in[k];
+        // absgrad request (wave-uniform flag): this pixel's |dL/dmean2D| goes to memory as it is, in front of the quad pre-reduction -- the
+        // absolute value of a quad's sum is another quantity.  Two atomics per blend on the tiles this kernel takes; nothing in LDS.
+        if (a.absgrad) add_absgrad(a, id, g_in);
         const unsigned long long here = __ballot(1);
         bool mine = true; // do I write to LDS / memory?
         if (((here >> (lane & ~3)) & 0xFull) == 0xFull) {

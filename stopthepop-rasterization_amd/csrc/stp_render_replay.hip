@@ -45,15 +45,26 @@ namespace {
 #define STP_REPLAY_WINDOW 512
 #endif
 constexpr int WINDOW = STP_REPLAY_WINDOW; // list positions per window (9 x 512 x 8 B = 36 KB of LDS: four workgroups per CU)
+// The ABS instantiations (absgrad request: eleven sums per position) keep the 512 positions -- 11 x 512 x 8 B = 44 KB, THREE workgroups per
+// CU -- rather than a 256-position window at four (22 KB): see DESIGN section 3.2.  -DSTP_REPLAY_ABS_OCC=4 with a 256-position window
+// (-DSTP_REPLAY_WINDOW=256, which then also holds for the plain kernel) builds the other choice for a measurement.
+#ifndef STP_REPLAY_ABS_OCC
+#define STP_REPLAY_ABS_OCC 3
+#endif
 constexpr int EXHAUSTED = 0x7fffffff; // "position" of a lane that has no record left
 
 // (One kernel for both kinds of tile: as two launches the mixed case -- C2-min -- loses more to the half-empty grids
 // than the lean loop gains.)
 // LOG_BLOCKED: the forward's log layout (stp_blend.h: rows in hierarchical mode, blocked in k-buffer mode)
-template <bool LOG_BLOCKED>
-__global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(const RenderArgs a)
+// ABS: the absgrad request (stp_set_backward_absgrad).  Two more terms per blend, g[9] = |g[3]| and g[10] = |g[4]|, taken per lane BEFORE
+// the merge levels (those sum lanes on one list position: the absolute value of a merged sum is another quantity) and carried through the
+// merge, the fixed-point sums and the flush like the nine: eleven lanes of a 16-lane group hand a position over with the one atomic
+// instruction, into slots 9, 10 of the same 64-byte record.  ABS = false is the kernel as it was, instruction for instruction.
+template <bool LOG_BLOCKED, bool ABS>
+__global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC) render_replay_kernel(const RenderArgs a)
 {
-    __shared__ unsigned long long s_acc[9 * WINDOW]; // [term][position - window start]
+    constexpr int NT = ABS ? 11 : 9; // sums per list position
+    __shared__ unsigned long long s_acc[NT * WINDOW]; // [term][position - window start]
     __shared__ float s_md[4];
 
     const WavePixel wp = wave_pixel_map(a); // (the forward's thread -> pixel map, stp_render_wave.h)
@@ -64,7 +75,7 @@ __global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(cons
     const int list_len = (int)(range.y - range.x);
     if (list_len <= 0) return;
 
-    for (int i = (int)threadIdx.x; i < 9 * WINDOW; i += 256) s_acc[i] = 0ull;
+    for (int i = (int)threadIdx.x; i < NT * WINDOW; i += 256) s_acc[i] = 0ull;
 
     BwdPixel bp;
     init_bwd_pixel(bp, a, inside, px, py);
@@ -86,7 +97,9 @@ __global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(cons
     constexpr int FX_BITS = 31, FX_CAP_BITS = 20;
     const double fx_scale = ldexp(1.0, FX_BITS - md_exp), fx_inv = ldexp(1.0, md_exp - FX_BITS);
     // factor of term k that the blend step leaves out: applied once per sum
+    // (terms 9, 10 are sums of magnitudes: the magnitude of the factors of terms 3, 4)
     auto term_scale = [&](int k) __attribute__((always_inline)) -> float {
+        if constexpr (ABS) { if (k == 9) return 0.5f * (float)a.W; if (k == 10) return 0.5f * (float)a.H; }
         return k == 3 ? -0.5f * (float)a.W : k == 4 ? -0.5f * (float)a.H : (k >= 5 && k <= 7) ? -0.5f : 1.0f;
     };
     const double fx_inv_term = fx_inv * (double)term_scale(lane & 15); // (flush: lane & 15 is the term a lane writes back)
@@ -122,7 +135,7 @@ __global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(cons
     };
 
     // the gradient terms of one record (reference maths); false = nothing to add (no record, or the pixel saturates here)
-    auto blend_terms = [&](bool act, const Entry& cur, float (&g)[9]) __attribute__((always_inline)) -> bool {
+    auto blend_terms = [&](bool act, const Entry& cur, float (&g)[NT]) __attribute__((always_inline)) -> bool {
         // Straight-line form: every lane evaluates its (possibly stand-in) entry; a lane without a record, or whose pixel saturates
         // here, is switched off through its FACTORS -- all nine terms are linear in (T, T_final), so T := 0 and T_final := 0 make them
         // exact zeros (every other factor is finite: alpha <= 0.99, test_T >= 1e-6 where it is used, the stand-in is entry 0 of the
@@ -161,13 +174,14 @@ __global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(cons
         g[6] = u * dy;
         g[7] = v * dy;
         g[8] = G * dL_dalpha;
+        if constexpr (ABS) { g[9] = fabsf(g[3]); g[10] = fabsf(g[4]); } // (this lane's pair alone; exact zeros where the lane is switched off)
         bp.T = ok ? test_T : bp.T;
         return ok;
     };
     // merge lanes on the same position, then add to the window's sums (lo = first position of the window)
     // deep (wave-uniform): also the two mirror levels inside the 16-lane row
     // one_window (a literal at both call sites): the list fits the window -- no position lies in front of it, a position IS its slot
-    auto merge_and_add = [&](bool ok, int cur_pos, int cur_id, float (&g)[9], int lo, const bool deep, const bool one_window) __attribute__((always_inline)) {
+    auto merge_and_add = [&](bool ok, int cur_pos, int cur_id, float (&g)[NT], int lo, const bool deep, const bool one_window) __attribute__((always_inline)) {
         // Pairwise merge (DPP): a lane and its partner -- lane^1, lane^2, then the mirror lanes of its 8-lane half and
         // row -- that hold the same list position sum their terms in registers and only one of them goes to LDS.  Per
         // step 55 lanes blend on 17.5 distinct positions (C2); the LDS atomics serialise on equal addresses and were the
@@ -181,7 +195,7 @@ __global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(cons
                 const bool match = pk == key;                                                                       \
                 const float mf = (match && (LOWER)) ? 1.0f : 0.0f;                                                  \
                 dpp_hazard_guard(); /* g[] was written by ordinary VALU instructions a moment ago */                \
-                _Pragma("unroll") for (int kk = 0; kk < 9; kk++) g[kk] = partner_fma<CTRL>(g[kk], mf, g[kk]);       \
+                _Pragma("unroll") for (int kk = 0; kk < NT; kk++) g[kk] = partner_fma<CTRL>(g[kk], mf, g[kk]);      \
                 if (match && !(LOWER)) key = -2 - lane; /* the upper lane of a matching pair has handed its terms over */ \
             }
             STP_MERGE_LEVEL(0xB1, (q & 1) == 0) // partner lane ^ 1 (quad_perm [1,0,3,2])
@@ -212,14 +226,15 @@ __global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(cons
 #endif
         if (ok) {
             // (the three colour terms are alpha T dL/dpixel: below M each, below 16 M after the merge levels -- they cannot reach the
-            // fixed point's cap of 2^20 M and stay out of the range check)
+            // fixed point's cap of 2^20 M and stay out of the range check; the two absolute sums are IN it: after the merge levels a sum of
+            // magnitudes can exceed the magnitude of the merged signed term)
             float gmax = fabsf(g[3]);
 #pragma unroll
-            for (int kk = 4; kk < 9; kk++) gmax = fmaxf(gmax, fabsf(g[kk]));
+            for (int kk = 4; kk < NT; kk++) gmax = fmaxf(gmax, fabsf(g[kk]));
             const int slot = one_window ? cur_pos : (cur_pos & (WINDOW - 1));
-            if ((one_window || cur_pos >= lo) && gmax < fx_cap) { // nine adds, nothing else
+            if ((one_window || cur_pos >= lo) && gmax < fx_cap) { // nine (eleven) adds, nothing else
 #pragma unroll
-                for (int kk = 0; kk < 9; kk++) {
+                for (int kk = 0; kk < NT; kk++) {
                     // round-to-nearest integer of g*scale through the 1.5*2^52 trick (|g*scale| < 2^51 + margin)
                     const double tq = fma((double)g[kk], fx_scale, 6755399441055744.0);
                     const long long qv = __double_as_longlong(tq) - 0x4338000000000000ll;
@@ -227,7 +242,7 @@ __global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(cons
                 }
             } else { // a record the re-sort moved across a window boundary, or a term too large for the fixed point
 #pragma unroll
-                for (int kk = 0; kk < 9; kk++) atomicAdd(grad_slot(a, cur_id, kk), g[kk] * term_scale(kk));
+                for (int kk = 0; kk < NT; kk++) atomicAdd(grad_slot(a, cur_id, kk), g[kk] * term_scale(kk));
             }
         }
     };
@@ -239,7 +254,7 @@ __global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(cons
         const int term = lane & 15;
         for (int pp = f0 + (int)(threadIdx.x >> 4); pp < f1; pp += 16) {
             const int p = pp & (WINDOW - 1);
-            if (term < 9) {
+            if (term < NT) {
                 const long long v = (long long)s_acc[term * WINDOW + p];
                 if (v != 0) {
                     s_acc[term * WINDOW + p] = 0ull;
@@ -260,7 +275,7 @@ __global__ void __launch_bounds__(256, STP_REPLAY_OCC) render_replay_kernel(cons
         for (int o = 32; o > 0; o >>= 1) pmin = min(pmin, __shfl_xor(pmin, o));
         same_start = __popcll(__ballot(p0 == pmin && n > 0)) >= 40;
     }
-    float g[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float g[NT] = {};
     // Two dependent loads lead to a blend: log record (list position) -> the entry's record.  They are software
     // pipelined one step apart: `pos` / `en` hold the lane's next record and its entry, `pos1` the position of the one
     // after, each loaded an iteration before it is needed.
@@ -378,8 +393,12 @@ int blend_log_clamp_depth(int d) // (a multiple of the block: a lane's records c
 
 hipError_t launch_hier_replay(const FrameParams& f, const RenderArgs& a, hipStream_t st)
 {
-    if (log_blocked(f.s)) hipLaunchKernelGGL(render_replay_kernel<true>, dim3(f.gx * (f.ty1 - f.ty0)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(render_replay_kernel<false>, dim3(f.gx * (f.ty1 - f.ty0)), dim3(256), 0, st, a);
+    const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(256);
+    if (a.absgrad) { // (the absgrad request: eleven sums per position)
+        if (log_blocked(f.s)) hipLaunchKernelGGL((render_replay_kernel<true, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((render_replay_kernel<false, true>), grid, block, 0, st, a);
+    } else if (log_blocked(f.s)) hipLaunchKernelGGL((render_replay_kernel<true, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((render_replay_kernel<false, false>), grid, block, 0, st, a);
     return hipGetLastError();
 }
 

@@ -217,7 +217,10 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
             const float r0 = wave_sum(g_col[0]), r1 = wave_sum(g_col[1]), r2 = wave_sum(g_col[2]);
             const float r3 = wave_sum(g_mx), r4 = wave_sum(g_my), r5 = wave_sum(g_cxx), r6 = wave_sum(g_cxy), r7 = wave_sum(g_cyy);
             const float r8 = wave_sum(g_op);
-            if (lane < 9) { // lane k hands over term k: nine lanes, one atomic instruction, one 64-byte record
+            // absgrad request (wave-uniform): the wave's sums of |g_mx|, |g_my| -- absolute values per pixel, then the sum -- ride in lanes 9, 10
+            float r9 = 0.0f, r10 = 0.0f;
+            if (a.absgrad) { r9 = wave_sum(fabsf(g_mx)); r10 = wave_sum(fabsf(g_my)); }
+            if (lane < (a.absgrad ? 11 : 9)) { // lane k hands over term k: nine (eleven) lanes, one atomic instruction, one 64-byte record
                 float v = r0;
                 switch (lane) {
                 case 1: v = r1; break;
@@ -228,6 +231,8 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
                 case 6: v = r6; break;
                 case 7: v = r7; break;
                 case 8: v = r8; break;
+                case 9: v = r9; break;
+                case 10: v = r10; break;
                 default: break;
                 }
                 atomicAdd(grad_slot(a, s_id[j], lane), v);
@@ -471,6 +476,7 @@ hipError_t launch_render_backward(const FrameParams& f, const GeometryState& g, 
 {
     RenderArgs a = make_args(f, g, b, img);
     a.pixel_colors = bw.pixel_colors; a.dL_dpix = bw.dL_dpix; a.grad_rec = bw.grad_rec; a.grad_stride = bw.grad_stride;
+    a.absgrad = bw.absgrad != nullptr; // (the caller has refused compact records with the request: slots 9, 10 exist)
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(BLOCK);
     if (grid.x == 0) return hipSuccess;
     switch (f.s.sort_mode) {

@@ -48,12 +48,21 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      cov3Ds_precomp, raster_settings)
 
 
-def _forward_body(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos, rs,
+def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos, rs,
                   save_camera=False):
     """The forward both autograd Functions share (the camera tensors are rs's own, or the camera Function's explicit inputs, which
     save_camera=True saves for the backward behind the twelve tensors both Functions save)."""
     sdict = rs.settings.to_dict()
     ctx.log_lease = None
+    # absgrad (extension, settings._absgrad = True; include/stp_raster.h: stp_set_backward_absgrad): the backward also leaves the per-Gaussian
+    # sums of |each pixel's contribution to dL/dmean2D| in means2D.absgrad -- the densification statistic of AbsGS / gsplat.  The tensor
+    # the caller passed is kept (not saved: it takes no part in the maths) so that the backward can hang the attribute on it.
+    ctx.absgrad_target = None
+    if sdict.get("_absgrad"):
+        if rs.render_depth:
+            raise RuntimeError("absgrad (settings._absgrad) is not available with render_depth=True: the depth visualisation has no "
+                               "backward that could produce it")
+        ctx.absgrad_target = means2D
     if any(ctx.needs_input_grad) and not rs.render_depth:
         # a backward can follow: let the hierarchical / k-buffer forward record each pixel's blend order so that the
         # backward replays it instead of re-sorting (extension of ours; ignored by the other sort modes) -- unless the
@@ -118,6 +127,8 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
             rs.sh_degree, campos, geomBuffer, num_rendered, binningBuffer, imgBuffer, ctx.settings_dict,
             rs.debug)
     kw = {"camera_grads": True} if camera_grads else {}
+    if ctx.absgrad_target is not None:
+        kw["absgrad"] = True
     if rs.debug:
         cpu_args = cpu_deep_copy_tuple(args)
         try:
@@ -131,6 +142,9 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
     _C.release_scratch(imgBuffer); _C.release_scratch(binningBuffer)  # the blend log goes back to the library's free list
     if ctx.log_lease is not None:
         ctx.log_lease.release()
+    if ctx.absgrad_target is not None:   # (the extra tensor comes last; assigned, not accumulated: the trainer keeps its own statistic)
+        ctx.absgrad_target.absgrad = out[-1]
+        out = out[:-1]
     return out
 
 
@@ -139,8 +153,8 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings):
         rs = raster_settings
-        return _forward_body(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.viewmatrix, rs.projmatrix,
-                             rs.campos, rs)
+        return _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.viewmatrix,
+                             rs.projmatrix, rs.campos, rs)
 
     @staticmethod
     def backward(ctx, grad_out_color, _):
@@ -162,8 +176,8 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
                 raster_settings):
         # (needs_input_grad counts the camera inputs: a frame where only the camera requires grad records the blend log too; the
         # camera tensors are saved like the Gaussians: an in-place change before the backward raises instead of giving wrong gradients)
-        return _forward_body(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos,
-                             raster_settings, save_camera=True)
+        return _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix,
+                             campos, raster_settings, save_camera=True)
 
     @staticmethod
     def backward(ctx, grad_out_color, _):
@@ -251,7 +265,10 @@ class ExtendedSettings(_Settable):
                 "load_balancing": self.load_balancing, "proper_ewa_scaling": self.proper_ewa_scaling,
                 # (extension, not a dataclass field: `settings._backward_mode = "replay" | "resort" | "auto"` overrides the
                 # process-wide backward-mode policy of _C.set_backward_mode for the calls made with this settings object)
-                **({"_backward_mode": self._backward_mode} if getattr(self, "_backward_mode", None) else {})}
+                **({"_backward_mode": self._backward_mode} if getattr(self, "_backward_mode", None) else {}),
+                # (extension, not a dataclass field: `settings._absgrad = True` asks every backward of the calls made with this settings
+                # object for means2D.absgrad, the per-Gaussian sums of |each pixel's contribution to dL/dmean2D|)
+                **({"_absgrad": True} if getattr(self, "_absgrad", False) else {})}
 
     def to_json(self):
         return json.dumps(self.to_dict())

@@ -239,6 +239,11 @@ class _ShardedRasterize(torch.autograd.Function):
             raise RuntimeError("render_depth is not available with tile-row sharding (the depth colormap is normalised by the "
                                "whole frame's extrema); render it on one GPU")
         sdict = dict(rs.settings.to_dict())
+        if sdict.get("_absgrad"):
+            # the sums of |dL/dmean2D| live in slots 9, 10 of the padded 64-byte gradient record; what the ranks all-reduce is the compact
+            # (P, 9) record, which has no room for them (include/stp_raster.h: phases bit 2 refuses the request)
+            raise RuntimeError("absgrad (settings._absgrad) is not available with tile-row sharding: the compact (P, 9) gradient record "
+                               "that crosses the links between the two halves of the backward has no room for the two extra sums")
         y0, y1 = parts[rank]
         n_rows = tile_rows(rs.image_height)
         rows = (y0, y1) if y1 > y0 else (n_rows, n_rows)   # (an empty block; (0, 0) would mean "all rows" to the library)

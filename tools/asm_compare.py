@@ -5,7 +5,8 @@
     python tools/asm_compare.py DIR_A DIR_B
 
 Every *.s of the two directories (sub-directories included; one present on one side only is reported) is split per function symbol; comment lines,
-trailing comments and directives that carry no instruction are dropped, labels and instructions are kept.  Prints
+trailing comments and directives that carry no instruction are dropped, labels and instructions are kept (block labels without the
+function's index in its file, which shifts when a kernel is added in front of it).  Prints
 one line per kernel -- identical / differs (with the instruction counts) / only in one build -- and a total.
 Exit status 1 if anything differs.
 """
@@ -32,7 +33,7 @@ def functions(path):
             continue
         if s.startswith(".") and not s.endswith(":"):
             continue  # directive
-        body.append(s)
+        body.append(re.sub(r"\.LBB\d+_", ".LBB_", s))  # (block labels carry the function's index in its file: a kernel added in front shifts it)
     if name is not None:
         print(f"warning: {path}: function {name} has no .Lfunc_end label, skipped", file=sys.stderr)
     return out
