@@ -3,7 +3,7 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
@@ -91,6 +91,8 @@ def main(argv=None):
     ap.add_argument("--points", type=int, default=20000)
     ap.add_argument("--size", type=int, nargs=2, default=[320, 240], metavar=("W", "H"))
     ap.add_argument("--absgrad", action="store_true", help="also accumulate the absolute screen-space gradient (densification statistic of AbsGS)")
+    ap.add_argument("--prune-views", type=int, default=0, metavar="N",
+                    help="after training, a pruning pass over N views: the largest blend weight of every Gaussian over the views, then a threshold")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
@@ -135,6 +137,26 @@ def main(argv=None):
     if args.absgrad:
         print(f"densification statistic, mean over Gaussians: signed {float(stat_signed.mean()):.3e}, absolute {float(stat_abs.mean()):.3e} "
               f"(absolute >= signed for {float((stat_abs >= stat_signed * (1 - 1e-5)).float().mean()) * 100:.1f} % of them)")
+    if args.prune_views > 0:
+        # A pruning pass (RadSplat): a Gaussian whose blend weight alpha * T stays below a threshold on EVERY ray of every view contributes
+        # next to nothing to any pixel.  settings._blend_stats = True makes each backward leave means2D.blend_stats = (sum, max, count) of
+        # the blend weights per Gaussian; column 1 is accumulated as a maximum over the views.  The
+        # statistics do not depend on the loss: the sum of the image is as good as any.
+        prune_cfg = splat_config(args.config)
+        prune_cfg._blend_stats = True
+        views = [cam] + [camera_of(scenes.make_scene(P=8, W=W, H=H, sigma_min=1.0, sigma_max=9.0, seed=3 + v, camera="origin" if v % 2 else "orbit"), dev)
+                         for v in range(1, args.prune_views)]
+        score = torch.zeros(model.get_xyz.shape[0], device=dev)
+        hits = torch.zeros_like(score)
+        for view in views:
+            out = render(view, model, bg, prune_cfg)
+            out["render"].sum().backward()
+            stats = out["viewspace_points"].blend_stats   # assigned by every backward: the running maximum is the trainer's
+            score = torch.maximum(score, stats[:, 1])
+            hits += stats[:, 2]
+        keep = score >= 0.01
+        print(f"pruning pass over {len(views)} views: largest blend weight below 0.01 for {int((~keep).sum())} of {keep.numel()} Gaussians "
+              f"({int((hits == 0).sum())} of them never blended); a trainer would now keep model tensors[keep]")
     print(f"L1 {first:.5f} -> {last:.5f}; depth visualisation {tuple(depth.shape)} in [{float(depth.min()):.3f}, {float(depth.max()):.3f}]")
     return first, last
 

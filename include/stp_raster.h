@@ -32,6 +32,7 @@ extern "C" {
 #define STP_GRAD_RECORD_FLOATS 16 /* floats per Gaussian in grad_records (see stp_backward) */
 #define STP_GRAD_RECORD_USED 9    /* of which these carry data; the record stride of stp_backward_phases' compact form (phases bit 2) */
 #define STP_GRAD_RECORD_ABS 9     /* first of the two slots that carry sum |dL/dmean2D| xy under stp_set_backward_absgrad (padded records only) */
+#define STP_GRAD_RECORD_STATS 11  /* first of the three slots that carry sum, max and count of the blend weights under stp_set_backward_blend_stats (padded records only) */
 
 /* Replaces CudaRasterizer::SplattingSettings + SortSettings + SortQueueSizes + CullingSettings
    (rasterizer.h:27-135) and their json parser (rasterizer.h:160-182): the host binding fills this
@@ -128,7 +129,8 @@ void stp_set_forward_split(int tile_row, void* event);
    It takes the place of the reference's dL_dconic scratch tensor (rasterize_points.cu:181): the render half sums
    its nine per-Gaussian terms into ONE 64-byte record per Gaussian,
        [0..2] dL/dcolour rgb   [3..4] dL/dmean2D xy   [5..7] dL/dconic xx, xy, yy   [8] dL/dopacity
-       [9..10] sum |dL/dmean2D| xy (only with the absgrad request)   [11..15] unused
+       [9..10] sum |dL/dmean2D| xy (only with the absgrad request)
+       [11..13] sum, max, count of the blend weights (only with the blend-statistics request; the max as the float's bits)   [14..15] unused
    (one atomic instruction / one L2 request per flush instead of nine into four arrays: 9x the flush rate on
    MI355X, tools/global_atomic_bench.hip); the per-Gaussian half reads the record and writes dL_dmean2D,
    dL_dopacity and dL_dcolor in the reference's layouts along with the remaining gradients. */
@@ -213,6 +215,28 @@ void stp_set_backward_camera_grads(float* dL_dviewmatrix, float* dL_dprojmatrix,
    two sums), or a chunked per-Gaussian half (phases bits 8-23: REFUSED, as camera gradients are -- one request is one whole per-Gaussian
    half). */
 void stp_set_backward_absgrad(float* dL_dmean2D_abs /* P x 3 */);
+
+/* Extension (not in the reference): per-Gaussian blend statistics, what pruning and compaction methods rank Gaussians by.  The blend weight
+   of a (pixel, Gaussian) pair is w = alpha * T, T the transmittance in front of the blend: the share of the pixel's colour that comes from
+   that Gaussian.  The NEXT stp_backward or stp_backward_phases of the calling thread also produces, for every Gaussian i,
+       blend_stats[3 i]     = sum over pixels of w     (Mini-Splatting, Taming-3DGS)
+       blend_stats[3 i + 1] = max over pixels of w     (RadSplat)
+       blend_stats[3 i + 2] = number of pixels that blended it, as a float (LightGaussian; exact: a frame has fewer than 2^24 pixels)
+   over exactly the (pixel, Gaussian) pairs the forward blended, which are the pairs whose nine gradient terms the call adds: alpha >=
+   1/255, not the entry that saturates the pixel.  (The replay kernel's gradient terms may leave a pixel one pair early where its
+   transmittance sits on the saturation threshold to an ulp; the statistics follow the forward's blend log, so that both backward modes
+   count the same pairs.)  The values do not depend on dL_dpix (all-zero or non-finite pixel gradients give the same statistics).  Every row is written
+   (device pointer, P x 3 floats, no zero-fill by the caller): zeros for Gaussians with radii <= 0.  The render half adds the three terms
+   per blended pair to slots STP_GRAD_RECORD_STATS .. + 2 of the Gaussian's padded record -- sum and count with float adds, the maximum
+   with an unsigned integer maximum on the float's bits (w >= 0, the record starts zeroed) --; the per-Gaussian half moves them to
+   blend_stats before it reads the record and, with phases bit 3, zeroes the three slots behind its read (the 48 bytes that bit clears
+   end in front of slots 12, 13).  Every other output of the call is what it is without the request, up to the run-to-run variation of
+   the render half's float atomics.  Independent of stp_set_backward_absgrad; both requests may be pending for one call.
+   A NULL pointer clears a pending request.  Consumed like the absgrad request: by the next stp_backward / stp_backward_phases of the
+   thread whatever its outcome, except that a render-only call (phases = 1) that succeeds honours it and leaves it pending for the
+   per-Gaussian call, which must then get those records.  STP_ERR_INVALID_ARGUMENT: compact records (phases bit 2: the 36-byte record
+   has no room for the three terms), or a chunked per-Gaussian half (phases bits 8-23). */
+void stp_set_backward_blend_stats(float* blend_stats /* P x 3 */);
 
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:188-193, rasterizer_impl.cu:161-173).
    `present` is P bytes (bool). */

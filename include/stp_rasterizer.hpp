@@ -189,6 +189,8 @@ public:
     // `replayBlendLog` must equal the forward's recordBlendLog.
     // `dL_dmean2D_abs` (extension, optional: P x 3 floats, written in full): the per-Gaussian sums over pixels of |each pixel's contribution
     // to dL_dmean2D| -- the densification statistic of AbsGS (stp_raster.h: stp_set_backward_absgrad).
+    // `blend_stats` (extension, optional: P x 3 floats, written in full): per Gaussian the sum, the maximum and the count of its blend
+    // weights alpha * T over the pixels -- what pruning methods rank by (stp_raster.h: stp_set_backward_blend_stats).
     static void backward(const int P, int D, int M, int R, const float* background, const int width, int height,
                          const SortSettings sort_settings, const CullingSettings culling_settings,
                          const bool proper_ewa_scaling, const float* means3D, const float* shs, const float* opacities,
@@ -198,11 +200,13 @@ public:
                          const float* pixel_colors, const int* radii, char* geom_buffer, char* binning_buffer,
                          char* image_buffer, const float* dL_dpix, float* dL_dmean2D, float* grad_records, float* dL_dopacity,
                          float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                         float* dL_drot, bool debug, void* stream = nullptr, bool replayBlendLog = false, float* dL_dmean2D_abs = nullptr)
+                         float* dL_drot, bool debug, void* stream = nullptr, bool replayBlendLog = false, float* dL_dmean2D_abs = nullptr,
+                         float* blend_stats = nullptr)
     {
         StpSettings s = toPod(sort_settings, culling_settings, false, proper_ewa_scaling);
         s.record_blend_log = replayBlendLog ? 1 : 0;
         stp_set_backward_absgrad(dL_dmean2D_abs); // (consumed by the call below; nullptr clears a request left pending on this thread)
+        stp_set_backward_blend_stats(blend_stats);
         check(stp_backward(P, D, M, R, background, width, height, &s, means3D, shs, opacities, colors_precomp, scales,
                            scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, cam_pos,
                            tan_fovx, tan_fovy, pixel_colors, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,

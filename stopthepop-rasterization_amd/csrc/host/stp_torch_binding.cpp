@@ -68,6 +68,7 @@ struct Api {
     decltype(&stp_camera_grad_workspace_bytes) camera_grad_workspace_bytes = nullptr;
     decltype(&stp_set_backward_camera_grads) set_backward_camera_grads = nullptr;
     decltype(&stp_set_backward_absgrad) set_backward_absgrad = nullptr;
+    decltype(&stp_set_backward_blend_stats) set_backward_blend_stats = nullptr;
 } g_api;
 
 int load_library(const std::string& path)
@@ -88,6 +89,7 @@ int load_library(const std::string& path)
     a.camera_grad_workspace_bytes = reinterpret_cast<decltype(a.camera_grad_workspace_bytes)>(dlsym(h, "stp_camera_grad_workspace_bytes"));
     a.set_backward_camera_grads = reinterpret_cast<decltype(a.set_backward_camera_grads)>(dlsym(h, "stp_set_backward_camera_grads"));
     a.set_backward_absgrad = reinterpret_cast<decltype(a.set_backward_absgrad)>(dlsym(h, "stp_set_backward_absgrad"));
+    a.set_backward_blend_stats = reinterpret_cast<decltype(a.set_backward_blend_stats)>(dlsym(h, "stp_set_backward_blend_stats"));
     if (a.abi_version() != STP_ABI_VERSION) throw std::runtime_error(path + ": ABI version mismatch");
     g_api = a; // (a previously loaded library stays mapped: buffers of its forwards may still be in flight)
     return a.abi_version();
@@ -314,6 +316,8 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
 // dL/dprojmatrix and dL/dcampos, appended to the eight gradients in the shapes of the three inputs.
 // absgrad (extension, include/stp_raster.h: stp_set_backward_absgrad): one more (P,3) tensor, LAST in the result: the per-Gaussian sums over
 // pixels of |each pixel's contribution to dL/dmeans2D| (x, y; column 2 zero).  Whole backwards on padded records only.
+// blend_stats (extension, include/stp_raster.h: stp_set_backward_blend_stats): one more (P,3) tensor, behind absgrad's if both are asked
+// for: per Gaussian the sum, the maximum and the count of its blend weights alpha * T.  Whole backwards on padded records only.
 std::vector<torch::Tensor>
 rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& opacities,
                              const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
@@ -322,7 +326,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
                              const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                              const py::dict& settings, const bool debug, const bool record_log, const int phases, const c10::optional<torch::Tensor>& partial,
-                             const c10::optional<std::vector<torch::Tensor>>& outputs, const bool camera_grads, const bool absgrad)
+                             const c10::optional<std::vector<torch::Tensor>>& outputs, const bool camera_grads, const bool absgrad, const bool blend_stats)
 {
     need_library();
     TORCH_CHECK(means3D.is_cuda(), "diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
@@ -338,6 +342,11 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         // (the render half leaves the two sums in the records it has just filled and the per-Gaussian half of the SAME call collects them: a
         // half on its own would need the caller to carry request and records from one call to the other)
         TORCH_CHECK((phases & 3) == 3, "absgrad needs both halves of the backward in one call (phases bits 0 and 1)");
+    }
+    if (blend_stats) {
+        if (!g_api.set_backward_blend_stats)
+            throw std::runtime_error("blend_stats: the loaded libstp_raster.so does not export stp_set_backward_blend_stats (a library built before blend statistics): rebuild it");
+        TORCH_CHECK((phases & 3) == 3, "blend_stats needs both halves of the backward in one call (phases bits 0 and 1)");
     }
     const torch::Device dev = means3D.device();
     const int P = (int)means3D.size(0);
@@ -388,7 +397,10 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
     }
     torch::Tensor dL_dmeans2D_abs;
     if (absgrad) dL_dmeans2D_abs = torch::empty({P, 3}, fopt); // written in full by the library (zeros for invisible Gaussians)
-    auto make_requests = [&] { // (both are consumed by the library call that follows, on this thread)
+    torch::Tensor stats;
+    if (blend_stats) stats = torch::empty({P, 3}, fopt); // written in full by the library (zeros for invisible Gaussians)
+    auto make_requests = [&] { // (all are consumed by the library call that follows, on this thread)
+        if (blend_stats && P != 0) g_api.set_backward_blend_stats(stats.data_ptr<float>());
         if (absgrad && P != 0) g_api.set_backward_absgrad(dL_dmeans2D_abs.data_ptr<float>());
         if (camera_grads) g_api.set_backward_camera_grads(dL_dview.data_ptr<float>(), dL_dproj.data_ptr<float>(), dL_dcam.data_ptr<float>(), cam_ws.data_ptr(), (size_t)cam_ws.numel());
     };
@@ -430,6 +442,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
     std::vector<torch::Tensor> result{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations};
     if (camera_grads) result.insert(result.end(), {dL_dview, dL_dproj, dL_dcam});
     if (absgrad) result.push_back(dL_dmeans2D_abs);
+    if (blend_stats) result.push_back(stats);
     return result;
 }
 

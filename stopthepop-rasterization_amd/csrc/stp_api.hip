@@ -1006,6 +1006,9 @@ void stp_set_backward_camera_grads(float* dL_dviewmatrix, float* dL_dprojmatrix,
 // puts it back for the per-Gaussian call (a call that fails, or has nothing to do, leaves no pointer behind)
 thread_local float* t_absgrad = nullptr;
 void stp_set_backward_absgrad(float* dL_dmean2D_abs) { t_absgrad = dL_dmean2D_abs; }
+// stp_set_backward_blend_stats: the same rules, a request of its own (both may be pending for one call)
+thread_local float* t_blend_stats = nullptr;
+void stp_set_backward_blend_stats(float* blend_stats) { t_blend_stats = blend_stats; }
 
 int stp_backward_phases(int phases, int P, int D, int M, int R, const float* background, int width, int height, const StpSettings* settings,
                  const float* means3D, const float* shs, const float* opacities, const float* colors_precomp, const float* scales,
@@ -1021,13 +1024,21 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
         cam = t_camera_grads;
         t_camera_grads = CameraGradRequest{};
     }
+    // both per-thread requests are taken BEFORE either one's checks: a call that is refused for one leaves neither behind
     float* const absgrad = t_absgrad;
-    t_absgrad = nullptr; // (put back at the end of a render-only call that ran)
+    float* const blend_stats = t_blend_stats;
+    t_absgrad = nullptr; t_blend_stats = nullptr; // (put back at the end of a render-only call that ran)
     if (absgrad) {
         if (phases & 4)
             return fail(STP_ERR_INVALID_ARGUMENT, "absgrad is not available with compact gradient records (phases bit 2): the 36-byte record has no room for the two extra sums");
         if (((phases >> 8) & 0xFF) > 1)
             return fail(STP_ERR_INVALID_ARGUMENT, "absgrad is not available from a chunked per-Gaussian half (phases bits 8-23)");
+    }
+    if (blend_stats) {
+        if (phases & 4)
+            return fail(STP_ERR_INVALID_ARGUMENT, "blend statistics are not available with compact gradient records (phases bit 2): the 36-byte record has no room for the three extra terms");
+        if (((phases >> 8) & 0xFF) > 1)
+            return fail(STP_ERR_INVALID_ARGUMENT, "blend statistics are not available from a chunked per-Gaussian half (phases bits 8-23)");
     }
     if (cam.dL_dview) {
         if (!cam.workspace || (reinterpret_cast<uintptr_t>(cam.workspace) & 15) != 0 || cam.workspace_bytes < camera_grad_workspace_bytes(P))
@@ -1063,6 +1074,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     BackwardParams bw;
     bw.cam = cam;
     bw.absgrad = absgrad;
+    bw.blend_stats = blend_stats;
     bw.pixel_colors = pixel_colors; bw.dL_dpix = dL_dpix; bw.dL_dmean2D = dL_dmean2D; bw.grad_rec = grad_records;
     bw.grad_stride = (phases & 4) ? STP_GRAD_RECORD_USED : STP_GRAD_RECORD_FLOATS;
     bw.clear_rec = (phases & 8) ? 1 : 0;
@@ -1089,7 +1101,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
         STP_DEBUG_SYNC("backward preprocess");
         g_timer.mark(7, st);
     }
-    if (!(phases & 2)) t_absgrad = absgrad; // render-only: the sums are in the records, the per-Gaussian call collects them
+    if (!(phases & 2)) { t_absgrad = absgrad; t_blend_stats = blend_stats; } // render-only: the sums are in the records, the per-Gaussian call collects them
     return 0;
 }
 

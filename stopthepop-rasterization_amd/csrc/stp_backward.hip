@@ -551,6 +551,29 @@ __global__ void __launch_bounds__(256) absgrad_extract_kernel(int P, const int* 
     out[3 * (size_t)i] = ax; out[3 * (size_t)i + 1] = ay; out[3 * (size_t)i + 2] = 0.0f;
 }
 
+// blend-statistics request (stp_set_backward_blend_stats): slots STP_GRAD_RECORD_STATS .. + 2 of every visible Gaussian's record (sum and count
+// as floats, the maximum as a non-negative float's bits, which are the float) -> out[3 i .. 3 i + 2]; the invisible Gaussians get zeros
+// (every row is written).  Like the kernel above in front of preprocess_backward_kernel, whose clear_rec covers the first 48 bytes of a
+// record only -- slots 12, 13 lie behind them --: with `clear` this kernel zeroes the three slots behind its read.
+__global__ void __launch_bounds__(256) blend_stats_extract_kernel(int P, const int* __restrict__ radii, float* __restrict__ rec, int stride, int clear,
+                                                                  float* __restrict__ out)
+{
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= P) return;
+    float v[3] = {0.0f, 0.0f, 0.0f};
+    if (radii[i] > 0) {
+        float* const r = rec + (size_t)stride * i + STP_GRAD_RECORD_STATS;
+#pragma unroll
+        for (int k = 0; k < 3; k++) v[k] = r[k];
+        if (clear) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) r[k] = 0.0f;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) out[3 * (size_t)i + k] = v[k];
+}
+
 constexpr int kCamMaxParts = 256;
 int camera_grad_parts(int n_rows) { return max(1, min(kCamMaxParts, (n_rows + 191) / 192)); }
 
@@ -603,6 +626,11 @@ hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState&
     if (b1 <= b0) return hipSuccess;
     if (bw.absgrad != nullptr) { // (the caller has refused a chunked half and compact records with the request: all Gaussians, slots 9, 10 exist)
         hipLaunchKernelGGL(absgrad_extract_kernel, dim3(n_blocks), dim3(256), 0, st, f.P, radii, (const float*)bw.grad_rec, bw.grad_stride, bw.absgrad);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (bw.blend_stats != nullptr) { // (refused like the one above: all Gaussians, slots 11..13 exist)
+        hipLaunchKernelGGL(blend_stats_extract_kernel, dim3(n_blocks), dim3(256), 0, st, f.P, radii, bw.grad_rec, bw.grad_stride, bw.clear_rec, bw.blend_stats);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

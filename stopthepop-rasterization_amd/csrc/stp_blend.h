@@ -9,6 +9,8 @@
 
 namespace stp {
 
+constexpr int REQ_ABSGRAD = 1, REQ_BLEND_STATS = 2; // RenderArgs::requests
+
 // Pointers every render kernel needs (by value in the kernarg segment).
 struct RenderArgs {
     int W, H, gx, ty0, ty1;
@@ -35,9 +37,10 @@ struct RenderArgs {
     const float* dL_dpix;
     float* grad_rec;   // P x grad_stride floats: the nine sums of a Gaussian in one record (stp_raster.h, stp_backward)
     int grad_stride;   // floats per record: STP_GRAD_RECORD_FLOATS (one 64-byte line), or 9 = compact (tile-row sharding: what crosses xGMI)
-    int absgrad;       // backward kernels (stp_set_backward_absgrad): non-zero = every blended pair also adds |g[3]|, |g[4]| -- the absolute values of its
-                       // two dL/dmean2D terms -- to slots STP_GRAD_RECORD_ABS, + 1 of its Gaussian's record.  (In the four bytes of padding behind
-                       // grad_stride: the kernarg layout of everything else is what it was.)
+    int requests;      // backward kernels, bits REQ_*.  REQ_ABSGRAD (stp_set_backward_absgrad): every blended pair also adds |g[3]|, |g[4]| -- the absolute
+                       // values of its two dL/dmean2D terms -- to slots STP_GRAD_RECORD_ABS, + 1 of its Gaussian's record.  REQ_BLEND_STATS
+                       // (stp_set_backward_blend_stats): every blended pair also brings its blend weight alpha * T into slots STP_GRAD_RECORD_STATS .. + 2
+                       // (sum, max, count).  (In the four bytes of padding behind grad_stride: the kernarg layout of everything else is what it was.)
     // blend log (training forward -> replay backward): per (tile, wave, k, lane) the list position of the k-th
     // entry that lane's pixel blended; tile_flags[tile] != 0 marks a tile whose log overflowed
     uint32_t* blend_log;   // (storage; the records are log_t)
@@ -275,16 +278,36 @@ __device__ __forceinline__ void add_absgrad(const RenderArgs& a, int id, const f
     atomicAdd(grad_slot(a, id, GRAD_ABS + 1), fabsf(g[4]));
 }
 
+// the three terms of the blend-statistics request, straight to memory: the blend weight w = alpha * T of ONE blended pair joins the
+// Gaussian's sum, maximum and count.  The maximum is an unsigned integer maximum on the float's bits: w >= 0, and the order of
+// non-negative floats is the order of their bits; the slot starts as zero bits = 0.0f.
+constexpr int GRAD_STATS = STP_GRAD_RECORD_STATS;
+__device__ __forceinline__ void max_blend_weight(const RenderArgs& a, int id, float w)
+{
+    atomicMax(reinterpret_cast<unsigned int*>(grad_slot(a, id, GRAD_STATS + 1)), __float_as_uint(w));
+}
+__device__ __forceinline__ void add_blend_stats(const RenderArgs& a, int id, float w)
+{
+    atomicAdd(grad_slot(a, id, GRAD_STATS), w);
+    max_blend_weight(a, id, w);
+    atomicAdd(grad_slot(a, id, GRAD_STATS + 2), 1.0f);
+}
+// w of the pair blend_backward_terms() has just accepted (T_before = the pixel's transmittance in front of it): the expression of its
+// dchannel_dcolor, to the same bits
+__device__ __forceinline__ float blend_weight(float T_before, float opacity, float G) { return fminf(0.99f, opacity * G) * T_before; }
+
 // Straightforward accumulation: nine hardware fp32 atomics (global_atomic_add_f32; build with
 // -munsafe-fp-atomics) per blended pair -- what the reference does (hierarchical_render.cuh:1131-1161).
 __device__ __forceinline__ bool blend_backward(BwdPixel& b, const RenderArgs& a, int px, int py, int id, float G)
 {
     float g[9];
     const FrontData fd = load_front(a, id);
+    const float T_before = b.T;
     if (!blend_backward_terms(b, a, px, py, fd, G, g)) return false;
 #pragma unroll
     for (int k = 0; k < 9; k++) atomicAdd(grad_slot(a, id, k), g[k]);
-    if (a.absgrad) add_absgrad(a, id, g);
+    if (a.requests & REQ_ABSGRAD) add_absgrad(a, id, g);
+    if (a.requests & REQ_BLEND_STATS) add_blend_stats(a, id, blend_weight(T_before, fd.co.w, G));
     return true;
 }
 

@@ -172,6 +172,8 @@ struct BackwardParams {
     CameraGradRequest cam; // the per-Gaussian half also sums the camera gradients (stp_backward.hip)
     float* absgrad = nullptr; // stp_set_backward_absgrad (P x 3, or nullptr = no request): the render half also sums |dL/dmean2D| per pair into
                               // record slots 9, 10, the per-Gaussian half moves them here
+    float* blend_stats = nullptr; // stp_set_backward_blend_stats (P x 3, or nullptr = no request): the render half also collects sum, max and
+                                  // count of the blend weights per pair in record slots 11..13, the per-Gaussian half moves them here
     const float* pixel_colors;
     const float* dL_dpix;
     float* grad_rec;    // P x grad_stride: written by the render half, read by the per-Gaussian half

@@ -342,7 +342,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         for (int k = 0; k < 9; k++) g[k] = g_in[k];
         // absgrad request (wave-uniform flag): this pixel's |dL/dmean2D| goes to memory as it is, in front of the quad pre-reduction -- the
         // absolute value of a quad's sum is another quantity.  Two atomics per blend on the tiles this kernel takes; nothing in LDS.
-        if (a.absgrad) add_absgrad(a, id, g_in);
+        if (a.requests & REQ_ABSGRAD) add_absgrad(a, id, g_in);
         const unsigned long long here = __ballot(1);
         bool mine = true; // do I write to LDS / memory?
         if (((here >> (lane & ~3)) & 0xFull) == 0xFull) {
@@ -409,8 +409,11 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         if (!active) { head.num--; return; }
         float g[9];
         if (head.id[0] != front_key) refresh_front(); // not prefetched (cannot happen after a refresh; kept for safety)
+        const float T_before = bp.T;
         const bool ok = blend_backward_terms(bp, a, px, py, front_fd, head.store[0], g);
         if (ok) accumulate(head.id[0], front_gid, g);
+        // blend-statistics request (wave-uniform flag): this pair's blend weight goes to memory as it is, three atomics per blend
+        if (ok && (a.requests & REQ_BLEND_STATS)) add_blend_stats(a, front_gid, blend_weight(T_before, front_fd.co.w, head.store[0]));
         if (!ok) { active = false; head.num--; return; }
         head.pop();
     };

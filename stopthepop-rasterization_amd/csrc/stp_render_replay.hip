@@ -51,6 +51,15 @@ constexpr int WINDOW = STP_REPLAY_WINDOW; // list positions per window (9 x 512 
 #ifndef STP_REPLAY_ABS_OCC
 #define STP_REPLAY_ABS_OCC 3
 #endif
+// The STATS instantiations (blend-statistics request: three more terms per position) keep the 512 positions too: twelve terms are 48 KB and
+// three workgroups per CU, fourteen (both requests) 56 KB and two.  -DSTP_REPLAY_STATS_OCC / -DSTP_REPLAY_BOTH_OCC with a smaller
+// -DSTP_REPLAY_WINDOW build the other choices for a measurement.
+#ifndef STP_REPLAY_STATS_OCC
+#define STP_REPLAY_STATS_OCC 3
+#endif
+#ifndef STP_REPLAY_BOTH_OCC
+#define STP_REPLAY_BOTH_OCC 2
+#endif
 constexpr int EXHAUSTED = 0x7fffffff; // "position" of a lane that has no record left
 
 // (One kernel for both kinds of tile: as two launches the mixed case -- C2-min -- loses more to the half-empty grids
@@ -60,10 +69,20 @@ constexpr int EXHAUSTED = 0x7fffffff; // "position" of a lane that has no record
 // the merge levels (those sum lanes on one list position: the absolute value of a merged sum is another quantity) and carried through the
 // merge, the fixed-point sums and the flush like the nine: eleven lanes of a 16-lane group hand a position over with the one atomic
 // instruction, into slots 9, 10 of the same 64-byte record.  ABS = false is the kernel as it was, instruction for instruction.
-template <bool LOG_BLOCKED, bool ABS>
-__global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC) render_replay_kernel(const RenderArgs a)
+// STATS: the blend-statistics request (stp_set_backward_blend_stats).  Three more terms per blend behind the nine (eleven): the pair's blend
+// weight w = alpha T twice -- once to be summed, once to be maximised -- and a one to be counted.  They pass through the merge levels (the
+// maximum merges with a max), the window (a scale of their own: they do not depend on dL/dpixel; the maximum as the float's bits under a
+// 64-bit LDS max) and the flush into slots 11 .. 13 of the record (the maximum with an integer atomic max on the float's bits).  w comes
+// from the FORWARD's expressions (blend_power, exp_blend, a transmittance chain of its own), not from the lean G of the gradient terms: a
+// maximum has no summation order, so it is the re-sorting kernels' value bit for bit.  The pair SET is the forward's too -- every record of
+// the log --, not the gradient terms': their lean transmittance may call a pixel saturated one record earlier than the forward did, and a
+// count has no tolerance.  STATS = false is the kernel as it was.
+template <bool LOG_BLOCKED, bool ABS, bool STATS>
+__global__ void __launch_bounds__(256, STATS ? (ABS ? STP_REPLAY_BOTH_OCC : STP_REPLAY_STATS_OCC) : ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC)
+render_replay_kernel(const RenderArgs a)
 {
-    constexpr int NT = ABS ? 11 : 9; // sums per list position
+    constexpr int SI = ABS ? 11 : 9;          // the gradient terms; with STATS also the first statistics term in g[] and s_acc (record slots GRAD_STATS .. + 2)
+    constexpr int NT = SI + (STATS ? 3 : 0);  // terms per list position
     __shared__ unsigned long long s_acc[NT * WINDOW]; // [term][position - window start]
     __shared__ float s_md[4];
 
@@ -102,7 +121,16 @@ __global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC
         if constexpr (ABS) { if (k == 9) return 0.5f * (float)a.W; if (k == 10) return 0.5f * (float)a.H; }
         return k == 3 ? -0.5f * (float)a.W : k == 4 ? -0.5f * (float)a.H : (k >= 5 && k <= 7) ? -0.5f : 1.0f;
     };
-    const double fx_inv_term = fx_inv * (double)term_scale(lane & 15); // (flush: lane & 15 is the term a lane writes back)
+    double fx_inv_term_ = fx_inv * (double)term_scale(lane & 15); // (flush: lane & 15 is the term a lane writes back)
+    // the statistics' fixed point does not depend on dL/dpixel.  2^45: a blended pair has alpha >= 1/255 and T >= 1e-4, so w >= 2^-22 and every
+    // float w is a whole number of 2^-45 -- the on-chip sum is EXACT (a Gaussian blended once has sum == max, bit for bit); w <= 0.99, 16 lanes
+    // merge at most (2^49: inside the rounding trick's 2^51) and at most 256 pixels of a tile share a position (2^53).  The count is an integer.
+    constexpr double ST_SCALE = 35184372088832.0;
+    if constexpr (STATS) {
+        if ((lane & 15) == GRAD_STATS) fx_inv_term_ = 1.0 / ST_SCALE;
+        if ((lane & 15) == GRAD_STATS + 2) fx_inv_term_ = 1.0;
+    }
+    const double fx_inv_term = fx_inv_term_;
     const float fx_cap = (md_ok || md == 0.0f) ? ldexpf(1.0f, min(md_exp + FX_CAP_BITS, 126)) : 0.0f; // (a tile whose M is not finite: nothing fits, every term goes to memory)
 
     // Addressing: wave-uniform bases (SGPR pairs) + one 32-bit byte offset per load, so that the loop's loads are
@@ -134,7 +162,10 @@ __global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC
         return Entry{at(eC), at(eD), at(eF)};
     };
 
-    // the gradient terms of one record (reference maths); false = nothing to add (no record, or the pixel saturates here)
+    float Tx = 1.0f; // STATS: the pixel's transmittance as the forward chains it (bp.T follows the lean alpha)
+    bool g_done = false; // STATS: the lean transmittance has called the pixel saturated: no gradient terms from here on (without STATS the lane stops)
+    // the gradient terms of one record (reference maths); false = no gradient terms to add (no record, or the pixel saturates here).
+    // With STATS a record (`act`) always has its statistics to add, whatever this returns: see the callers.
     auto blend_terms = [&](bool act, const Entry& cur, float (&g)[NT]) __attribute__((always_inline)) -> bool {
         // Straight-line form: every lane evaluates its (possibly stand-in) entry; a lane without a record, or whose pixel saturates
         // here, is switched off through its FACTORS -- all nine terms are linear in (T, T_final), so T := 0 and T_final := 0 make them
@@ -149,7 +180,9 @@ __global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC
         const float G = __builtin_amdgcn_exp2f(fmaxf(e2, 0.0f) * -1.44269502162933349609375f);
         const float alpha = fminf(0.99f, co.w * G);
         const float test_T = bp.T * (1.0f - alpha);
-        const bool ok = act && !(test_T < T_THRESHOLD);
+        bool ok_ = act && !(test_T < T_THRESHOLD);
+        if constexpr (STATS) { ok_ = ok_ && !g_done; g_done = g_done || (act && !ok_); }
+        const bool ok = ok_;
         // dL/dalpha = sum_ch (c_ch - (final_ch - C_ch) / test_T) dL_ch  with the channel sums taken first: cd = c . dL, FD = final . dL (a
         // constant of the pixel), CD = C . dL (a running scalar, CD += alpha T cd) -- six instructions instead of fifteen, and one
         // accumulated scalar instead of three colours; 1 / (1 - alpha) = T / test_T costs a multiply instead of a second reciprocal
@@ -175,6 +208,15 @@ __global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC
         g[7] = v * dy;
         g[8] = G * dL_dalpha;
         if constexpr (ABS) { g[9] = fabsf(g[3]); g[10] = fabsf(g[4]); } // (this lane's pair alone; exact zeros where the lane is switched off)
+        if constexpr (STATS) {
+            // The pair set is the FORWARD's: every record of the log (`act`), which is what the re-sorting kernels blend.  `ok` may end a
+            // pixel one record early -- its lean transmittance is an ulp off the forward's, and the last record of a saturating pixel can
+            // sit on the threshold --: that pair's gradient terms are the exact zeros of a switched-off lane, its statistics are counted.
+            const float ax = fminf(0.99f, co.w * exp_blend(blend_power(dx, dy, co)));
+            const float wx = act ? ax * Tx : 0.0f;
+            g[SI] = wx; g[SI + 1] = wx; g[SI + 2] = act ? 1.0f : 0.0f;
+            Tx = act ? Tx * (1.0f - ax) : Tx;
+        }
         bp.T = ok ? test_T : bp.T;
         return ok;
     };
@@ -195,7 +237,10 @@ __global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC
                 const bool match = pk == key;                                                                       \
                 const float mf = (match && (LOWER)) ? 1.0f : 0.0f;                                                  \
                 dpp_hazard_guard(); /* g[] was written by ordinary VALU instructions a moment ago */                \
-                _Pragma("unroll") for (int kk = 0; kk < NT; kk++) g[kk] = partner_fma<CTRL>(g[kk], mf, g[kk]);      \
+                _Pragma("unroll") for (int kk = 0; kk < NT; kk++) {                                                 \
+                    if (STATS && kk == SI + 1) g[kk] = fmaxf(g[kk], partner_fma<CTRL>(g[kk], mf, 0.0f)); /* w >= 0, mf is 0 or 1 */ \
+                    else g[kk] = partner_fma<CTRL>(g[kk], mf, g[kk]);                                               \
+                }                                                                                                   \
                 if (match && !(LOWER)) key = -2 - lane; /* the upper lane of a matching pair has handed its terms over */ \
             }
             STP_MERGE_LEVEL(0xB1, (q & 1) == 0) // partner lane ^ 1 (quad_perm [1,0,3,2])
@@ -230,19 +275,30 @@ __global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC
             // magnitudes can exceed the magnitude of the merged signed term)
             float gmax = fabsf(g[3]);
 #pragma unroll
-            for (int kk = 4; kk < NT; kk++) gmax = fmaxf(gmax, fabsf(g[kk]));
+            for (int kk = 4; kk < SI; kk++) gmax = fmaxf(gmax, fabsf(g[kk])); // (the statistics have a scale of their own: not in the check)
             const int slot = one_window ? cur_pos : (cur_pos & (WINDOW - 1));
             if ((one_window || cur_pos >= lo) && gmax < fx_cap) { // nine (eleven) adds, nothing else
 #pragma unroll
-                for (int kk = 0; kk < NT; kk++) {
+                for (int kk = 0; kk < SI; kk++) {
                     // round-to-nearest integer of g*scale through the 1.5*2^52 trick (|g*scale| < 2^51 + margin)
                     const double tq = fma((double)g[kk], fx_scale, 6755399441055744.0);
                     const long long qv = __double_as_longlong(tq) - 0x4338000000000000ll;
                     atomicAdd(&s_acc[kk * WINDOW + slot], (unsigned long long)qv);
                 }
+                if constexpr (STATS) {
+                    const double tq = fma((double)g[SI], ST_SCALE, 6755399441055744.0);
+                    atomicAdd(&s_acc[SI * WINDOW + slot], (unsigned long long)(__double_as_longlong(tq) - 0x4338000000000000ll));
+                    atomicMax(&s_acc[(SI + 1) * WINDOW + slot], (unsigned long long)__float_as_uint(g[SI + 1]));
+                    atomicAdd(&s_acc[(SI + 2) * WINDOW + slot], (unsigned long long)(unsigned int)(int)g[SI + 2]); // (1 .. 16 after the merge levels)
+                }
             } else { // a record the re-sort moved across a window boundary, or a term too large for the fixed point
 #pragma unroll
-                for (int kk = 0; kk < NT; kk++) atomicAdd(grad_slot(a, cur_id, kk), g[kk] * term_scale(kk));
+                for (int kk = 0; kk < SI; kk++) atomicAdd(grad_slot(a, cur_id, kk), g[kk] * term_scale(kk));
+                if constexpr (STATS) {
+                    atomicAdd(grad_slot(a, cur_id, GRAD_STATS), g[SI]);
+                    max_blend_weight(a, cur_id, g[SI + 1]);
+                    atomicAdd(grad_slot(a, cur_id, GRAD_STATS + 2), g[SI + 2]);
+                }
             }
         }
     };
@@ -254,11 +310,14 @@ __global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC
         const int term = lane & 15;
         for (int pp = f0 + (int)(threadIdx.x >> 4); pp < f1; pp += 16) {
             const int p = pp & (WINDOW - 1);
-            if (term < NT) {
-                const long long v = (long long)s_acc[term * WINDOW + p];
+            // (term = the record slot a lane writes; row = where its sum lives in s_acc: the statistics follow the gradient terms directly)
+            const int row = (STATS && term >= GRAD_STATS) ? term - GRAD_STATS + SI : term;
+            if (term < SI || (STATS && term >= GRAD_STATS && term < GRAD_STATS + 3)) {
+                const long long v = (long long)s_acc[row * WINDOW + p];
                 if (v != 0) {
-                    s_acc[term * WINDOW + p] = 0ull;
-                    atomicAdd(grad_slot(a, __float_as_int(eC[pp].w), term), (float)((double)v * fx_inv_term));
+                    s_acc[row * WINDOW + p] = 0ull;
+                    if (STATS && term == GRAD_STATS + 1) max_blend_weight(a, __float_as_int(eC[pp].w), __uint_as_float((unsigned int)v));
+                    else atomicAdd(grad_slot(a, __float_as_int(eC[pp].w), term), (float)((double)v * fx_inv_term));
                 }
             }
         }
@@ -313,8 +372,12 @@ __global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC
             raw1 = log_at(min((uint32_t)(kr + 2), log_last_row));
             pos = pos1;
             const bool ok = blend_terms(have, cur, g);
-            if (have && !ok) n = kr; // (an ulp of difference against the forward's transmittance: stop where it says so)
-            merge_and_add(ok, cur_pos, cur_id, g, 0, dense, true);
+            if constexpr (STATS) { // every record goes to the merge and the adds with its statistics; the log is not cut short (g_done)
+                merge_and_add(have, cur_pos, cur_id, g, 0, dense, true);
+            } else {
+                if (have && !ok) n = kr; // (an ulp of difference against the forward's transmittance: stop where it says so)
+                merge_and_add(ok, cur_pos, cur_id, g, 0, dense, true);
+            }
         };
         // two copies of the step, the entry registers alternating between them (no copy of the ten entry words at the back edge)
         Entry en2 = en;
@@ -359,8 +422,12 @@ __global__ void __launch_bounds__(256, ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC
             pos1 = act ? (k + 1 < n ? rec : EXHAUSTED) : pos1;
             en = entry_at(pos);
             const bool ok = blend_terms(act, cur, g);
-            if (act && !ok) { n = k; pos = EXHAUSTED; pos1 = EXHAUSTED; } // (saturated one record earlier than the forward said)
-            merge_and_add(ok, cur_pos, cur_id, g, lo, same_start, false);
+            if constexpr (STATS) { // (as in the one-window loop)
+                merge_and_add(act, cur_pos, cur_id, g, lo, same_start, false);
+            } else {
+                if (act && !ok) { n = k; pos = EXHAUSTED; pos1 = EXHAUSTED; } // (saturated one record earlier than the forward said)
+                merge_and_add(ok, cur_pos, cur_id, g, lo, same_start, false);
+            }
         }
         flush_range(lo, last ? list_len : lo + STEP);
         if (last) break;
@@ -394,11 +461,24 @@ int blend_log_clamp_depth(int d) // (a multiple of the block: a lane's records c
 hipError_t launch_hier_replay(const FrameParams& f, const RenderArgs& a, hipStream_t st)
 {
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(256);
-    if (a.absgrad) { // (the absgrad request: eleven sums per position)
-        if (log_blocked(f.s)) hipLaunchKernelGGL((render_replay_kernel<true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((render_replay_kernel<false, true>), grid, block, 0, st, a);
-    } else if (log_blocked(f.s)) hipLaunchKernelGGL((render_replay_kernel<true, false>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((render_replay_kernel<false, false>), grid, block, 0, st, a);
+    const bool blocked = log_blocked(f.s);
+    switch (a.requests & (REQ_ABSGRAD | REQ_BLEND_STATS)) {
+    case REQ_ABSGRAD | REQ_BLEND_STATS: // (both requests: fourteen terms per position)
+        if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, true, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((render_replay_kernel<false, true, true>), grid, block, 0, st, a);
+        break;
+    case REQ_BLEND_STATS: // (the blend-statistics request: twelve)
+        if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, false, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((render_replay_kernel<false, false, true>), grid, block, 0, st, a);
+        break;
+    case REQ_ABSGRAD: // (the absgrad request: eleven)
+        if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, true, false>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((render_replay_kernel<false, true, false>), grid, block, 0, st, a);
+        break;
+    default:
+        if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, false, false>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((render_replay_kernel<false, false, false>), grid, block, 0, st, a);
+    }
     return hipGetLastError();
 }
 

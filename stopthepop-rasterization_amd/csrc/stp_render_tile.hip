@@ -38,6 +38,13 @@ __device__ __forceinline__ float wave_sum(float v)
     const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
     return (r0 + r1) + (r2 + r3);
 }
+// Maximum over the 64 lanes of a wave (finite values); result valid in every lane.
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    return v;
+}
 
 struct TileCtx {
     int tile, tx, ty, px, py;
@@ -188,9 +195,11 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
             if (!__any(use)) continue;
 
             float g_col[3] = {0, 0, 0}, g_mx = 0, g_my = 0, g_cxx = 0, g_cxy = 0, g_cyy = 0, g_op = 0;
+            float g_w = 0; // the pair's blend weight (blend-statistics request)
             if (use) {
                 T = T / (1.f - alpha);
                 const float dchannel_dcolor = alpha * T;
+                g_w = dchannel_dcolor;
                 float dL_dalpha = 0.0f;
 #pragma unroll
                 for (int ch = 0; ch < 3; ch++) {
@@ -219,8 +228,14 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
             const float r8 = wave_sum(g_op);
             // absgrad request (wave-uniform): the wave's sums of |g_mx|, |g_my| -- absolute values per pixel, then the sum -- ride in lanes 9, 10
             float r9 = 0.0f, r10 = 0.0f;
-            if (a.absgrad) { r9 = wave_sum(fabsf(g_mx)); r10 = wave_sum(fabsf(g_my)); }
-            if (lane < (a.absgrad ? 11 : 9)) { // lane k hands over term k: nine (eleven) lanes, one atomic instruction, one 64-byte record
+            if (a.requests & REQ_ABSGRAD) { r9 = wave_sum(fabsf(g_mx)); r10 = wave_sum(fabsf(g_my)); }
+            // blend-statistics request (wave-uniform): the wave's sum and maximum of the blend weights and its number of blending pixels ride
+            // in lanes 11 .. 13; lane 12 hands its term over with an integer maximum on the float's bits (stp_blend.h)
+            const bool stats = (a.requests & REQ_BLEND_STATS) != 0;
+            float r11 = 0.0f, r12 = 0.0f, r13 = 0.0f;
+            if (stats) { r11 = wave_sum(g_w); r12 = wave_max(g_w); r13 = wave_sum(use ? 1.0f : 0.0f); }
+            // lane k hands over term k: nine (eleven, twelve, fourteen) lanes, one 64-byte record
+            if (lane < 9 || ((a.requests & REQ_ABSGRAD) && lane < 11) || (stats && lane >= GRAD_STATS && lane < GRAD_STATS + 3)) {
                 float v = r0;
                 switch (lane) {
                 case 1: v = r1; break;
@@ -233,9 +248,13 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
                 case 8: v = r8; break;
                 case 9: v = r9; break;
                 case 10: v = r10; break;
+                case 11: v = r11; break;
+                case 12: v = r12; break;
+                case 13: v = r13; break;
                 default: break;
                 }
-                atomicAdd(grad_slot(a, s_id[j], lane), v);
+                if (lane == GRAD_STATS + 1) max_blend_weight(a, s_id[j], v);
+                else atomicAdd(grad_slot(a, s_id[j], lane), v);
             }
         }
     }
@@ -476,7 +495,8 @@ hipError_t launch_render_backward(const FrameParams& f, const GeometryState& g, 
 {
     RenderArgs a = make_args(f, g, b, img);
     a.pixel_colors = bw.pixel_colors; a.dL_dpix = bw.dL_dpix; a.grad_rec = bw.grad_rec; a.grad_stride = bw.grad_stride;
-    a.absgrad = bw.absgrad != nullptr; // (the caller has refused compact records with the request: slots 9, 10 exist)
+    // (the caller has refused compact records with either request: slots 9 .. 13 exist)
+    a.requests = (bw.absgrad != nullptr ? REQ_ABSGRAD : 0) | (bw.blend_stats != nullptr ? REQ_BLEND_STATS : 0);
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(BLOCK);
     if (grid.x == 0) return hipSuccess;
     switch (f.s.sort_mode) {

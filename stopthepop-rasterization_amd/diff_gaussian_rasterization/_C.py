@@ -44,9 +44,10 @@ _OPTIONAL_SYMBOLS = {
     "stp_camera_grad_workspace_bytes": ([ctypes.c_int], ctypes.c_size_t),
     "stp_set_backward_camera_grads": ([ctypes.c_void_p] * 4 + [ctypes.c_size_t], None),
     "stp_set_backward_absgrad": ([ctypes.c_void_p], None),
+    "stp_set_backward_blend_stats": ([ctypes.c_void_p], None),
 }
 # the feature an optional export came with (the rebuild message names it)
-_SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad"}
+_SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blend_stats": "blend statistics"}
 
 
 def _require(name: str):
@@ -347,7 +348,7 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
                                  cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, tan_fovx, tan_fovy,
                                  pixel_colors, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                                  imageBuffer, settings_dict, debug, phases=3, partial=None, chunk=None, outputs=None,
-                                 camera_grads=False, absgrad=False):
+                                 camera_grads=False, absgrad=False, blend_stats=False):
     """== RasterizeGaussiansBackwardCUDA (reference rasterize_points.cu:140-232).
     Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
 
@@ -358,6 +359,9 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
     absgrad=True (extension, include/stp_raster.h: stp_set_backward_absgrad): one more tensor, LAST in the tuple: (P, 3) float32, columns
     0, 1 = the per-Gaussian sums over pixels of |that pixel's contribution to dL_dmeans2D| (x, y), column 2 zero.  Needs the per-Gaussian
     half and the padded (P, 16) records: compact records and a chunked half refuse it.
+
+    blend_stats=True (extension, include/stp_raster.h: stp_set_backward_blend_stats): one more tensor, LAST in the tuple (behind absgrad's):
+    (P, 3) float32, per Gaussian the sum, the maximum and the count of its blend weights alpha * T over the pixels.  The same conditions.
 
     Extension for tile-row sharding (not in the reference): phases=1 runs only the render half and
     returns its per-Gaussian partial sums as the library's (P,16) gradient records (stp_raster.h);
@@ -374,11 +378,13 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
         _require("stp_set_backward_camera_grads")
     if absgrad:
         _require("stp_set_backward_absgrad")
+    if blend_stats:
+        _require("stp_set_backward_blend_stats")
     out = (_host or _native()).rasterize_gaussians_backward(
         background, means3D, radii, opacities, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         inv_viewprojmatrix, tan_fovx, tan_fovy, pixel_colors, dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer,
         imageBuffer, settings_dict, bool(debug), _records_log(settings_dict), int(phases), partial, None if outputs is None else list(outputs),
-        bool(camera_grads), bool(absgrad))
+        bool(camera_grads), bool(absgrad), bool(blend_stats))
     return out[0] if (int(phases) & 3) == 1 else tuple(out)
 
 

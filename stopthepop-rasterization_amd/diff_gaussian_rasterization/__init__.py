@@ -63,6 +63,15 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
             raise RuntimeError("absgrad (settings._absgrad) is not available with render_depth=True: the depth visualisation has no "
                                "backward that could produce it")
         ctx.absgrad_target = means2D
+    # blend statistics (extension, settings._blend_stats = True; include/stp_raster.h: stp_set_backward_blend_stats): the backward also leaves
+    # means2D.blend_stats, per Gaussian the sum, the maximum and the count of its blend weights alpha * T over the pixels -- what pruning
+    # methods rank by.  A request of its own: with or without _absgrad.
+    ctx.blend_stats_target = None
+    if sdict.get("_blend_stats"):
+        if rs.render_depth:
+            raise RuntimeError("blend statistics (settings._blend_stats) are not available with render_depth=True: the depth visualisation "
+                               "has no backward that could produce them")
+        ctx.blend_stats_target = means2D
     if any(ctx.needs_input_grad) and not rs.render_depth:
         # a backward can follow: let the hierarchical / k-buffer forward record each pixel's blend order so that the
         # backward replays it instead of re-sorting (extension of ours; ignored by the other sort modes) -- unless the
@@ -129,6 +138,8 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
     kw = {"camera_grads": True} if camera_grads else {}
     if ctx.absgrad_target is not None:
         kw["absgrad"] = True
+    if ctx.blend_stats_target is not None:
+        kw["blend_stats"] = True
     if rs.debug:
         cpu_args = cpu_deep_copy_tuple(args)
         try:
@@ -142,7 +153,11 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
     _C.release_scratch(imgBuffer); _C.release_scratch(binningBuffer)  # the blend log goes back to the library's free list
     if ctx.log_lease is not None:
         ctx.log_lease.release()
-    if ctx.absgrad_target is not None:   # (the extra tensor comes last; assigned, not accumulated: the trainer keeps its own statistic)
+    # (the extra tensors come last, the statistics behind absgrad's; assigned, not accumulated: the trainer keeps its own statistic)
+    if ctx.blend_stats_target is not None:
+        ctx.blend_stats_target.blend_stats = out[-1]
+        out = out[:-1]
+    if ctx.absgrad_target is not None:
         ctx.absgrad_target.absgrad = out[-1]
         out = out[:-1]
     return out
@@ -268,7 +283,9 @@ class ExtendedSettings(_Settable):
                 **({"_backward_mode": self._backward_mode} if getattr(self, "_backward_mode", None) else {}),
                 # (extension, not a dataclass field: `settings._absgrad = True` asks every backward of the calls made with this settings
                 # object for means2D.absgrad, the per-Gaussian sums of |each pixel's contribution to dL/dmean2D|)
-                **({"_absgrad": True} if getattr(self, "_absgrad", False) else {})}
+                **({"_absgrad": True} if getattr(self, "_absgrad", False) else {}),
+                # (the same for `settings._blend_stats = True`: means2D.blend_stats, per Gaussian the sum, max and count of its blend weights)
+                **({"_blend_stats": True} if getattr(self, "_blend_stats", False) else {})}
 
     def to_json(self):
         return json.dumps(self.to_dict())

@@ -244,6 +244,10 @@ class _ShardedRasterize(torch.autograd.Function):
             # (P, 9) record, which has no room for them (include/stp_raster.h: phases bit 2 refuses the request)
             raise RuntimeError("absgrad (settings._absgrad) is not available with tile-row sharding: the compact (P, 9) gradient record "
                                "that crosses the links between the two halves of the backward has no room for the two extra sums")
+        if sdict.get("_blend_stats"):   # (slots 11 .. 13 of the padded record: the same reason)
+            raise RuntimeError("blend statistics (settings._blend_stats) are not available with tile-row sharding: the compact (P, 9) "
+                               "gradient record that crosses the links between the two halves of the backward has no room for the three "
+                               "extra terms")
         y0, y1 = parts[rank]
         n_rows = tile_rows(rs.image_height)
         rows = (y0, y1) if y1 > y0 else (n_rows, n_rows)   # (an empty block; (0, 0) would mean "all rows" to the library)
