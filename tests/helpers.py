@@ -1,5 +1,6 @@
 """Shared helpers of the parity tests: settings dicts, running the product (GPU) and the oracle (CPU)
-on the same synthetic scene, and comparison metrics."""
+on the same synthetic scene, and comparison metrics; api_render(), the one forward + backward through the public
+API that the tests of the opt-in backward outputs (camera gradients, absgrad, blend statistics) share."""
 from __future__ import annotations
 
 import numpy as np
@@ -34,6 +35,127 @@ def ext_settings(d):
     if d.get("_backward_mode"):   # (our per-call extension rides on the settings object, see ExtendedSettings.to_dict)
         es._backward_mode = d["_backward_mode"]
     return es
+
+
+def _rel(a, b):
+    """largest difference relative to b's largest entry"""
+    return max_abs(a, b) / max(float(np.max(np.abs(b))), 1e-30)
+
+
+GAUSS = ("means3D", "means2D", "shs", "colors_precomp", "opacities", "scales", "rotations")
+CAMERA = ("viewmatrix", "projmatrix", "campos")
+
+
+def _scene_a():
+    from diff_gaussian_rasterization import scenes
+    return scenes.make_scene(P=300, W=48, H=32, sigma_min=1.0, sigma_max=9.0, seed=4)
+
+
+def _scene_b():
+    from diff_gaussian_rasterization import scenes
+    return scenes.make_scene(P=2500, W=48, H=32, sigma_min=2.0, sigma_max=12.0, seed=5, camera="orbit")   # lists of more than 1024 entries
+
+
+def _precomp(sc, seed=11):
+    """the scene with its colours given directly (colors_precomp as the leaf, no SH)"""
+    sc.colors_precomp = np.random.default_rng(seed).uniform(0.05, 1.0, (len(sc.means3D), 3)).astype(np.float32)
+    sc.shs = None
+    return sc
+
+
+def api_settings(sc, settings, device="cuda:0", render_depth=False, **camera):
+    """GaussianRasterizationSettings of scene sc on `device`.  settings: an ExtendedSettings; camera: tensors that stand in for the
+    scene's own viewmatrix, projmatrix, inv_viewprojmatrix or campos."""
+    import torch
+    import diff_gaussian_rasterization as dgr
+    t = lambda n: camera[n] if n in camera else torch.tensor(np.asarray(getattr(sc, n), np.float32), device=device)
+    return dgr.GaussianRasterizationSettings(
+        image_height=sc.H, image_width=sc.W, tanfovx=sc.tanfovx, tanfovy=sc.tanfovy, bg=t("bg"), scale_modifier=sc.scale_modifier,
+        viewmatrix=t("viewmatrix"), projmatrix=t("projmatrix"), inv_viewprojmatrix=t("inv_viewprojmatrix"), sh_degree=sc.sh_degree,
+        campos=t("campos"), prefiltered=False, settings=settings, render_depth=render_depth, debug=False)
+
+
+def api_render(sc, sdict, camera=(), gaussians=True, only=None, means2D_grad=True, cov3D=None, backward_mode=None, w=None,
+               lit_pixel=None, render_depth=False, backwards=1, forward_only=False, absgrad=False, stats=False):
+    """Forward + backward with dL_dout = w through the public API on cuda:0 (w: the scene's own dL_dout by default; the k-th of
+    `backwards` rounds on the same tensors uses k * w).
+    camera: the camera tensors that require grad (names; True: all three).  gaussians / only: do the Gaussian inputs require grad, and
+    which of them (None: all); means2D_grad: does means2D.  cov3D: a (P, 6) array passed instead of scales and rotations.
+    lit_pixel: flat index of the one pixel at which w is not zeroed.  forward_only: no backward.
+    absgrad, stats: the settings._absgrad and settings._blend_stats requests.
+    Returns a dict: "color", "radii", "grad_fn" (its type's name); "n_contrib" and "tile_flags" of the last forward that has a graph;
+    per request "absgrad" / "stats" (means2D's attribute after the last backward, None without one), "has_absgrad" / "has_stats" and the
+    list per backward, "absgrads" / "all_stats"; under its name every input's .grad (None where there is none)."""
+    import torch
+    import diff_gaussian_rasterization as dgr
+    from diff_gaussian_rasterization import _C
+    dev = torch.device("cuda:0")
+    camera = CAMERA if camera is True else (camera or ())
+    need = lambda n: gaussians and (only is None or n in only)
+    t = lambda a, rg=False: None if a is None else torch.tensor(np.asarray(a, np.float32), device=dev).requires_grad_(rg)
+    ten = {n: t(getattr(sc, n), need(n)) for n in ("means3D", "opacities", "shs", "colors_precomp", "scales", "rotations")}
+    ten["cov3D_precomp"] = t(cov3D, need("cov3D_precomp"))
+    if cov3D is not None:
+        ten["scales"] = ten["rotations"] = None
+    ten["means2D"] = torch.zeros_like(ten["means3D"], requires_grad=means2D_grad and need("means2D"))
+    cam = {n: t(getattr(sc, n), n in camera) for n in CAMERA}
+    d = dict(sdict)
+    if backward_mode:
+        d["_backward_mode"] = backward_mode
+    es = ext_settings(d)
+    if absgrad:
+        es._absgrad = True
+    if stats:
+        es._blend_stats = True
+    rs = api_settings(sc, es, dev, render_depth, **cam)
+    out = {"absgrads": [], "all_stats": []}
+    for k in range(backwards):
+        color, radii = dgr.GaussianRasterizer(rs)(ten["means3D"], ten["means2D"], ten["opacities"], shs=ten["shs"],
+                                                  colors_precomp=ten["colors_precomp"], scales=ten["scales"], rotations=ten["rotations"],
+                                                  cov3D_precomp=ten["cov3D_precomp"])
+        fn = color.grad_fn
+        out["grad_fn"] = type(fn).__name__ if fn is not None else None
+        if fn is not None and len(sc.means3D) > 0:
+            img_buf = fn.saved_tensors[11]
+            out["n_contrib"] = _C.image_array(img_buf, sc.W, sc.H, "n_contrib").reshape(-1)[:sc.W * sc.H].clone()
+            try:
+                out["tile_flags"] = _C.image_array(img_buf, sc.W, sc.H, "tile_flags").clone().cpu().numpy()
+            except KeyError:
+                out["tile_flags"] = None
+        weight = torch.tensor(np.asarray(sc.dL_dout if w is None else w, np.float32), device=dev) * float(k + 1)
+        if lit_pixel is not None:
+            mask = torch.zeros(sc.H * sc.W, device=dev)
+            mask[lit_pixel] = 1.0
+            weight = weight * mask.view(1, sc.H, sc.W)
+        if fn is not None and not forward_only:
+            color.backward(weight)   # (dL_dout as it is: a non-finite one must reach the kernels, not a product with the image)
+        for attr, every in (("absgrad", "absgrads"), ("blend_stats", "all_stats")):
+            if hasattr(ten["means2D"], attr):
+                out[every].append(getattr(ten["means2D"], attr))
+    out["color"], out["radii"] = color.detach(), radii
+    out["has_absgrad"], out["has_stats"] = hasattr(ten["means2D"], "absgrad"), hasattr(ten["means2D"], "blend_stats")
+    out["absgrad"], out["stats"] = getattr(ten["means2D"], "absgrad", None), getattr(ten["means2D"], "blend_stats", None)
+    for n, x in list(ten.items()) + list(cam.items()):
+        out[n] = None if x is None or x.grad is None else x.grad.detach().clone()
+    return out
+
+
+def _direct(sc, sd, cov3D=None):
+    """Forward through _C directly (the buffers a phase-split backward needs); returns the backward's positional arguments."""
+    import torch
+    from diff_gaussian_rasterization import _C
+    dev = torch.device("cuda:0")
+    empty = torch.Tensor([])
+    t = lambda a: empty if a is None else torch.tensor(np.asarray(a, np.float32), device=dev)
+    ten = dict(bg=t(sc.bg), means3D=t(sc.means3D), opac=t(sc.opacities), scales=t(None if cov3D is not None else sc.scales),
+               rots=t(None if cov3D is not None else sc.rotations), cov=t(cov3D), shs=t(sc.shs), colors=t(sc.colors_precomp),
+               view=t(sc.viewmatrix), proj=t(sc.projmatrix), inv=t(sc.inv_viewprojmatrix), cam=t(sc.campos), w=t(sc.dL_dout))
+    out = _C.rasterize_gaussians(ten["bg"], ten["means3D"], ten["colors"], ten["opac"], ten["scales"], ten["rots"], sc.scale_modifier,
+                                 ten["cov"], ten["view"], ten["proj"], ten["inv"], sc.tanfovx, sc.tanfovy, sc.H, sc.W, ten["shs"],
+                                 sc.sh_degree, ten["cam"], False, sd, False, False)
+    return (ten["bg"], ten["means3D"], out[2], ten["opac"], ten["colors"], ten["scales"], ten["rots"], sc.scale_modifier, ten["cov"],
+            ten["view"], ten["proj"], ten["inv"], sc.tanfovx, sc.tanfovy, out[1], ten["w"], ten["shs"], sc.sh_degree, ten["cam"], out[3],
+            out[0], out[4], out[5], sd, False)
 
 
 class GpuRun:

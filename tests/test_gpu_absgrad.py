@@ -9,76 +9,19 @@ pixels of |that pixel's contribution to dL/dmeans2D| (include/stp_raster.h: stp_
   * frames whose tiles are partly replayed and partly re-sorted;
   * the request moves nothing else; the surface (camera gradients, frozen means2D, empty frames, refusals, overwrite).
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
 
-from helpers import FULL_STP, ext_settings, max_abs, settings_dict
+from helpers import FULL_STP, GAUSS, _direct, _rel, _scene_a, _scene_b, api_render, api_settings, ext_settings, max_abs, settings_dict
 from diff_gaussian_rasterization import scenes
 import torch_ref_absgrad
 
 pytestmark = pytest.mark.gpu
 
-GAUSS = ("means3D", "means2D", "shs", "colors_precomp", "opacities", "scales", "rotations")
-
-
-def _rel(a, b):
-    return max_abs(a, b) / max(float(np.max(np.abs(b))), 1e-30)
-
-
-def render(sc, sdict, absgrad=True, backward_mode=None, w=None, lit_pixel=None, camera=False, only=None, means2D_grad=True,
-           render_depth=False, backwards=1, forward_only=False):
-    """One forward + backward of sum(w * image) through the public API on cuda:0.
-    lit_pixel: flat index of the one pixel at which w is not zeroed.  forward_only: no backward; "n_contrib" is returned.
-    only: names of the Gaussian inputs that require grad (None: all); means2D_grad: does means2D."""
-    import diff_gaussian_rasterization as dgr
-    from diff_gaussian_rasterization import _C
-    dev = torch.device("cuda:0")
-    need = lambda n: only is None or n in only
-    t = lambda a, rg=False: None if a is None else torch.tensor(np.asarray(a, np.float32), device=dev).requires_grad_(rg)
-    ten = dict(means3D=t(sc.means3D, need("means3D")), opacities=t(sc.opacities, need("opacities")), shs=t(sc.shs, need("shs")),
-               colors_precomp=t(sc.colors_precomp, need("colors_precomp")), scales=t(sc.scales, need("scales")),
-               rotations=t(sc.rotations, need("rotations")))
-    ten["means2D"] = torch.zeros_like(ten["means3D"], requires_grad=means2D_grad and need("means2D"))
-    cam = {n: t(a, camera) for n, a in (("viewmatrix", sc.viewmatrix), ("projmatrix", sc.projmatrix), ("campos", sc.campos))}
-    d = dict(sdict)
-    if backward_mode:
-        d["_backward_mode"] = backward_mode
-    es = ext_settings(d)
-    if absgrad:
-        es._absgrad = True
-    rs = dgr.GaussianRasterizationSettings(
-        image_height=sc.H, image_width=sc.W, tanfovx=sc.tanfovx, tanfovy=sc.tanfovy, bg=t(sc.bg), scale_modifier=sc.scale_modifier,
-        viewmatrix=cam["viewmatrix"], projmatrix=cam["projmatrix"], inv_viewprojmatrix=t(sc.inv_viewprojmatrix), sh_degree=sc.sh_degree,
-        campos=cam["campos"], prefiltered=False, settings=es, render_depth=render_depth, debug=False)
-    out = {"absgrads": []}
-    for k in range(backwards):
-        color, radii = dgr.GaussianRasterizer(rs)(ten["means3D"], ten["means2D"], ten["opacities"], shs=ten["shs"],
-                                                  colors_precomp=ten["colors_precomp"], scales=ten["scales"], rotations=ten["rotations"])
-        fn = color.grad_fn
-        out["grad_fn"] = type(fn).__name__ if fn is not None else None
-        if fn is not None and len(sc.means3D) > 0:
-            img_buf = fn.saved_tensors[11]
-            out["n_contrib"] = _C.image_array(img_buf, sc.W, sc.H, "n_contrib").reshape(-1)[:sc.W * sc.H].clone()
-            try:
-                out["tile_flags"] = _C.image_array(img_buf, sc.W, sc.H, "tile_flags").clone().cpu().numpy()
-            except KeyError:
-                out["tile_flags"] = None
-        weight = torch.tensor(np.asarray(sc.dL_dout if w is None else w, np.float32), device=dev) * float(k + 1)
-        if lit_pixel is not None:
-            mask = torch.zeros(sc.H * sc.W, device=dev)
-            mask[lit_pixel] = 1.0
-            weight = weight * mask.view(1, sc.H, sc.W)
-        if fn is not None and not forward_only:
-            (color * weight).sum().backward()
-        if hasattr(ten["means2D"], "absgrad"):
-            out["absgrads"].append(ten["means2D"].absgrad)
-    out["color"], out["radii"] = color.detach(), radii
-    out["has_attr"] = hasattr(ten["means2D"], "absgrad")
-    out["absgrad"] = ten["means2D"].absgrad if out["has_attr"] else None
-    for n, x in list(ten.items()) + list(cam.items()):
-        out[n] = None if x is None or x.grad is None else x.grad.detach().clone()
-    return out
+render = functools.partial(api_render, absgrad=True)
 
 
 def _check_shape(got, P):
@@ -118,14 +61,6 @@ def test_absgrad_matches_float64_yardstick(mode, backward_mode, camera):
 
 
 # ---- 2. a single contribution per Gaussian: absgrad == |grad| ----------------------------------------------------------------------
-def _scene_a():
-    return scenes.make_scene(P=300, W=48, H=32, sigma_min=1.0, sigma_max=9.0, seed=4)
-
-
-def _scene_b():
-    return scenes.make_scene(P=2500, W=48, H=32, sigma_min=2.0, sigma_max=12.0, seed=5, camera="orbit")   # lists of more than 1024 entries
-
-
 SINGLE = {
     "a-hier_full": (_scene_a, settings_dict(**FULL_STP)),
     "b-hier": (_scene_b, settings_dict(3)),
@@ -230,7 +165,7 @@ def test_request_changes_nothing_else(name, backward_mode):
     sc = scenes.make_scene(P=20000, W=256, H=256, sigma_min=1.0, sigma_max=10.0, seed=3, camera="orbit")
     a = render(sc, sd, backward_mode=backward_mode)
     b, b2 = render(sc, sd, absgrad=False, backward_mode=backward_mode), render(sc, sd, absgrad=False, backward_mode=backward_mode)
-    assert a["has_attr"] and not b["has_attr"] and not b2["has_attr"]
+    assert a["has_absgrad"] and not b["has_absgrad"] and not b2["has_absgrad"]
     assert torch.equal(a["color"], b["color"]) and torch.equal(a["radii"], b["radii"])
     for n in GAUSS:
         if b[n] is None:
@@ -244,23 +179,6 @@ def test_request_changes_nothing_else(name, backward_mode):
         else:
             assert (a[n] - b[n]).abs().max().item() <= 4 * spread, n
     _check_shape(a, sc.P)
-
-
-def _direct(sc, sd):
-    """Forward through _C directly; returns the backward's positional arguments."""
-    from diff_gaussian_rasterization import _C
-    dev = torch.device("cuda:0")
-    empty = torch.Tensor([])
-    t = lambda a: empty if a is None else torch.tensor(np.asarray(a, np.float32), device=dev)
-    ten = dict(bg=t(sc.bg), means3D=t(sc.means3D), opac=t(sc.opacities), scales=t(sc.scales), rots=t(sc.rotations), shs=t(sc.shs),
-               colors=t(sc.colors_precomp), view=t(sc.viewmatrix), proj=t(sc.projmatrix), inv=t(sc.inv_viewprojmatrix), cam=t(sc.campos),
-               w=t(sc.dL_dout))
-    out = _C.rasterize_gaussians(ten["bg"], ten["means3D"], ten["colors"], ten["opac"], ten["scales"], ten["rots"], sc.scale_modifier,
-                                 empty, ten["view"], ten["proj"], ten["inv"], sc.tanfovx, sc.tanfovy, sc.H, sc.W, ten["shs"],
-                                 sc.sh_degree, ten["cam"], False, sd, False, False)
-    return (ten["bg"], ten["means3D"], out[2], ten["opac"], ten["colors"], ten["scales"], ten["rots"], sc.scale_modifier, empty,
-            ten["view"], ten["proj"], ten["inv"], sc.tanfovx, sc.tanfovy, out[1], ten["w"], ten["shs"], sc.sh_degree, ten["cam"], out[3],
-            out[0], out[4], out[5], sd, False)
 
 
 @pytest.mark.parametrize("backward_mode", ["replay", "resort"])
@@ -301,7 +219,7 @@ def test_absgrad_with_camera_gradients():
     both, plain, cam = render(sc, sd, camera=True), render(sc, sd), render(sc, sd, camera=True, absgrad=False)
     assert both["grad_fn"] == "_RasterizeGaussiansCameraBackward" and plain["grad_fn"] == "_RasterizeGaussiansBackward"
     _check_shape(both, sc.P)
-    assert not cam["has_attr"]
+    assert not cam["has_absgrad"]
     assert _rel(both["absgrad"].cpu().numpy(), plain["absgrad"].cpu().numpy()) < 1e-5
     for n in ("viewmatrix", "projmatrix", "campos"):
         assert both[n] is not None and _rel(both[n].cpu().numpy(), cam[n].cpu().numpy()) < 1e-5, n
@@ -324,7 +242,7 @@ def test_absgrad_of_empty_and_culled_frames():
     for f in ("means3D", "scales", "rotations", "opacities", "shs"):
         setattr(empty, f, getattr(empty, f)[:0])
     got = render(empty, settings_dict(**FULL_STP), only=("opacities", "means2D"))
-    assert got["has_attr"] and got["absgrad"].shape == (0, 3) and got["absgrad"].dtype == torch.float32 and got["absgrad"].is_cuda
+    assert got["has_absgrad"] and got["absgrad"].shape == (0, 3) and got["absgrad"].dtype == torch.float32 and got["absgrad"].is_cuda
     behind = scenes.make_scene(P=200, W=48, H=40, sigma_min=1.0, sigma_max=8.0, seed=7)   # camera at the origin looking down +z
     behind.means3D = (behind.means3D * np.array([1, 1, -1], np.float32)).astype(np.float32)
     for sd in (settings_dict(**FULL_STP), settings_dict(2, per_pixel=16), settings_dict(0)):
@@ -334,7 +252,6 @@ def test_absgrad_of_empty_and_culled_frames():
 
 
 def test_absgrad_refusals():
-    import diff_gaussian_rasterization as dgr
     from diff_gaussian_rasterization import tile_shard
     sc = scenes.make_scene(P=100, W=48, H=40, sigma_min=1.0, sigma_max=6.0, seed=2, camera="orbit")
     with pytest.raises(RuntimeError, match="absgrad.*render_depth"):
@@ -343,10 +260,7 @@ def test_absgrad_refusals():
     t = lambda a: torch.tensor(np.asarray(a, np.float32), device=dev)
     es = ext_settings(settings_dict(3))
     es._absgrad = True
-    rs = dgr.GaussianRasterizationSettings(
-        image_height=sc.H, image_width=sc.W, tanfovx=sc.tanfovx, tanfovy=sc.tanfovy, bg=t(sc.bg), scale_modifier=1.0, viewmatrix=t(sc.viewmatrix),
-        projmatrix=t(sc.projmatrix), inv_viewprojmatrix=t(sc.inv_viewprojmatrix), sh_degree=sc.sh_degree, campos=t(sc.campos),
-        prefiltered=False, settings=es, render_depth=False, debug=False)
+    rs = api_settings(sc, es, dev)
     m = t(sc.means3D).requires_grad_(True)
     with pytest.raises(RuntimeError, match=r"absgrad.*tile-row sharding.*\(P, 9\)"):
         tile_shard.TileRowShardedRasterizer(rs, None, 0, 1)(m, torch.zeros_like(m), t(sc.opacities), shs=t(sc.shs), scales=t(sc.scales),

@@ -9,17 +9,17 @@ stp_set_backward_blend_stats).  Through the public API, except where the record 
   * the statistics do not depend on dL_dout; the request moves nothing else; with absgrad and camera gradients in one backward;
   * the record buffer is zero again behind a request; empty and culled frames, refusals, overwrite.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
 
-from helpers import FULL_STP, ext_settings, max_abs, settings_dict
+from helpers import FULL_STP, GAUSS, _direct, _precomp, _rel, _scene_a, _scene_b, api_render, api_settings, ext_settings, settings_dict
 from diff_gaussian_rasterization import scenes
 import torch_ref_blend_stats
 
 pytestmark = pytest.mark.gpu
-
-GAUSS = ("means3D", "means2D", "shs", "colors_precomp", "opacities", "scales", "rotations")
 
 MODES = {   # settings, the yardstick's order, the backward modes the settings have
     "global": (settings_dict(0), "global", (None,)),
@@ -30,64 +30,7 @@ CASES = [(m, bm) for m, (_, _, bms) in MODES.items() for bm in bms]
 CASE_IDS = [f"{m}-{bm or 'own'}" for m, bm in CASES]
 
 
-def _rel(a, b):
-    return max_abs(a, b) / max(float(np.max(np.abs(b))), 1e-30)
-
-
-def render(sc, sdict, stats=True, absgrad=False, backward_mode=None, w=None, lit_pixel=None, camera=False, render_depth=False,
-           backwards=1, forward_only=False, only=None):
-    """One forward + backward of sum(w * image) through the public API on cuda:0 (w: dL_dout, the scene's own by default).
-    lit_pixel: flat index of the one pixel at which w is not zeroed.  forward_only: no backward; "n_contrib" is returned.
-    only: names of the Gaussian inputs that require grad (None: all)."""
-    import diff_gaussian_rasterization as dgr
-    from diff_gaussian_rasterization import _C
-    dev = torch.device("cuda:0")
-    t = lambda a, rg=False: None if a is None else torch.tensor(np.asarray(a, np.float32), device=dev).requires_grad_(rg)
-    need = lambda n: only is None or n in only
-    ten = {n: t(getattr(sc, n), need(n)) for n in ("means3D", "opacities", "shs", "colors_precomp", "scales", "rotations")}
-    ten["means2D"] = torch.zeros_like(ten["means3D"], requires_grad=need("means2D"))
-    cam = {n: t(a, camera) for n, a in (("viewmatrix", sc.viewmatrix), ("projmatrix", sc.projmatrix), ("campos", sc.campos))}
-    d = dict(sdict)
-    if backward_mode:
-        d["_backward_mode"] = backward_mode
-    es = ext_settings(d)
-    if stats:
-        es._blend_stats = True
-    if absgrad:
-        es._absgrad = True
-    rs = dgr.GaussianRasterizationSettings(
-        image_height=sc.H, image_width=sc.W, tanfovx=sc.tanfovx, tanfovy=sc.tanfovy, bg=t(sc.bg), scale_modifier=sc.scale_modifier,
-        viewmatrix=cam["viewmatrix"], projmatrix=cam["projmatrix"], inv_viewprojmatrix=t(sc.inv_viewprojmatrix), sh_degree=sc.sh_degree,
-        campos=cam["campos"], prefiltered=False, settings=es, render_depth=render_depth, debug=False)
-    out = {"all_stats": []}
-    for k in range(backwards):
-        color, radii = dgr.GaussianRasterizer(rs)(ten["means3D"], ten["means2D"], ten["opacities"], shs=ten["shs"],
-                                                  colors_precomp=ten["colors_precomp"], scales=ten["scales"], rotations=ten["rotations"])
-        fn = color.grad_fn
-        out["grad_fn"] = type(fn).__name__ if fn is not None else None
-        if fn is not None and len(sc.means3D) > 0:
-            img_buf = fn.saved_tensors[11]
-            out["n_contrib"] = _C.image_array(img_buf, sc.W, sc.H, "n_contrib").reshape(-1)[:sc.W * sc.H].clone()
-            try:
-                out["tile_flags"] = _C.image_array(img_buf, sc.W, sc.H, "tile_flags").clone().cpu().numpy()
-            except KeyError:
-                out["tile_flags"] = None
-        weight = torch.tensor(np.asarray(sc.dL_dout if w is None else w, np.float32), device=dev) * float(k + 1)
-        if lit_pixel is not None:
-            mask = torch.zeros(sc.H * sc.W, device=dev)
-            mask[lit_pixel] = 1.0
-            weight = weight * mask.view(1, sc.H, sc.W)
-        if fn is not None and not forward_only:
-            color.backward(weight)   # (dL_dout as it is: a non-finite one must reach the kernels, not a product with the image)
-        if hasattr(ten["means2D"], "blend_stats"):
-            out["all_stats"].append(ten["means2D"].blend_stats)
-    out["color"], out["radii"] = color.detach(), radii
-    out["has_attr"] = hasattr(ten["means2D"], "blend_stats")
-    out["stats"] = ten["means2D"].blend_stats if out["has_attr"] else None
-    out["absgrad"] = getattr(ten["means2D"], "absgrad", None)
-    for n, x in list(ten.items()) + list(cam.items()):
-        out[n] = None if x is None or x.grad is None else x.grad.detach().clone()
-    return out
+render = functools.partial(api_render, stats=True)
 
 
 def _check_shape(got, P):
@@ -106,13 +49,6 @@ def _same_stats(a, b, what=""):
     assert torch.equal(a[:, 2], b[:, 2]), f"{what}: counts differ for {int((a[:, 2] != b[:, 2]).sum())} Gaussians"
     assert torch.equal(a[:, 1], b[:, 1]), f"{what}: maxima differ for {int((a[:, 1] != b[:, 1]).sum())} Gaussians"
     assert _rel(a[:, 0].cpu().numpy(), b[:, 0].cpu().numpy()) < 1e-5, what
-
-
-def _precomp(sc, seed=11):
-    """the scene with its colours given directly (colors_precomp as the leaf, no SH)"""
-    sc.colors_precomp = np.random.default_rng(seed).uniform(0.05, 1.0, (len(sc.means3D), 3)).astype(np.float32)
-    sc.shs = None
-    return sc
 
 
 # ---- 1. against the float64 yardstick --------------------------------------------------------------------------------------------
@@ -147,14 +83,6 @@ def test_blend_stats_match_float64_yardstick(mode, backward_mode, camera):
 
 
 # ---- 2. the sum is dL/dcolour under an all-ones dL_dout ----------------------------------------------------------------------------
-def _scene_a():
-    return scenes.make_scene(P=300, W=48, H=32, sigma_min=1.0, sigma_max=9.0, seed=4)
-
-
-def _scene_b():
-    return scenes.make_scene(P=2500, W=48, H=32, sigma_min=2.0, sigma_max=12.0, seed=5, camera="orbit")   # lists of more than 1024 entries
-
-
 @pytest.mark.parametrize("scene", ["a", "b"])
 @pytest.mark.parametrize("mode,backward_mode", CASES, ids=CASE_IDS)
 def test_sum_is_the_colour_gradient_under_all_ones(mode, backward_mode, scene):
@@ -255,7 +183,7 @@ def test_request_changes_nothing_else(mode, backward_mode):
     sc = scenes.make_scene(P=20000, W=256, H=256, sigma_min=1.0, sigma_max=10.0, seed=3, camera="orbit")
     a = render(sc, sd, backward_mode=backward_mode)
     b, b2 = render(sc, sd, stats=False, backward_mode=backward_mode), render(sc, sd, stats=False, backward_mode=backward_mode)
-    assert a["has_attr"] and not b["has_attr"] and not b2["has_attr"] and a["absgrad"] is None
+    assert a["has_stats"] and not b["has_stats"] and not b2["has_stats"] and a["absgrad"] is None
     assert torch.equal(a["color"], b["color"]) and torch.equal(a["radii"], b["radii"])
     for n in GAUSS:
         if b[n] is None:
@@ -280,7 +208,7 @@ def test_with_absgrad_and_camera_gradients(mode, backward_mode):
     all3 = render(sc, sd, absgrad=True, camera=True, **kw)
     only_stats, only_abs, only_cam = render(sc, sd, **kw), render(sc, sd, stats=False, absgrad=True, **kw), render(sc, sd, stats=False, camera=True, **kw)
     assert all3["grad_fn"] == "_RasterizeGaussiansCameraBackward" and only_stats["grad_fn"] == "_RasterizeGaussiansBackward"
-    assert not only_abs["has_attr"] and not only_cam["has_attr"] and only_stats["absgrad"] is None
+    assert not only_abs["has_stats"] and not only_cam["has_stats"] and only_stats["absgrad"] is None
     _check_shape(all3, sc.P)
     _same_stats(all3["stats"], only_stats["stats"], "all three")
     assert all3["absgrad"].shape == (sc.P, 3) and _rel(all3["absgrad"].cpu().numpy(), only_abs["absgrad"].cpu().numpy()) < 1e-5
@@ -292,23 +220,6 @@ def test_with_absgrad_and_camera_gradients(mode, backward_mode):
 
 
 # ---- 8. the record buffer behind a request -------------------------------------------------------------------------------------------
-def _direct(sc, sd):
-    """Forward through _C directly; returns the backward's positional arguments."""
-    from diff_gaussian_rasterization import _C
-    dev = torch.device("cuda:0")
-    empty = torch.Tensor([])
-    t = lambda a: empty if a is None else torch.tensor(np.asarray(a, np.float32), device=dev)
-    ten = dict(bg=t(sc.bg), means3D=t(sc.means3D), opac=t(sc.opacities), scales=t(sc.scales), rots=t(sc.rotations), shs=t(sc.shs),
-               colors=t(sc.colors_precomp), view=t(sc.viewmatrix), proj=t(sc.projmatrix), inv=t(sc.inv_viewprojmatrix), cam=t(sc.campos),
-               w=t(sc.dL_dout))
-    out = _C.rasterize_gaussians(ten["bg"], ten["means3D"], ten["colors"], ten["opac"], ten["scales"], ten["rots"], sc.scale_modifier,
-                                 empty, ten["view"], ten["proj"], ten["inv"], sc.tanfovx, sc.tanfovy, sc.H, sc.W, ten["shs"],
-                                 sc.sh_degree, ten["cam"], False, sd, False, False)
-    return (ten["bg"], ten["means3D"], out[2], ten["opac"], ten["colors"], ten["scales"], ten["rots"], sc.scale_modifier, empty,
-            ten["view"], ten["proj"], ten["inv"], sc.tanfovx, sc.tanfovy, out[1], ten["w"], ten["shs"], sc.sh_degree, ten["cam"], out[3],
-            out[0], out[4], out[5], sd, False)
-
-
 @pytest.mark.parametrize("mode,backward_mode", CASES, ids=CASE_IDS)
 def test_records_are_zero_again_behind_a_request(mode, backward_mode):
     """A caller who keeps the record buffer between steps (phases bit 3: the per-Gaussian half clears what it reads) finds it all zeros
@@ -360,7 +271,7 @@ def test_empty_culled_and_single_gaussian_frames():
     for f in ("means3D", "scales", "rotations", "opacities", "shs"):
         setattr(empty, f, getattr(empty, f)[:0])
     got = render(empty, settings_dict(**FULL_STP), only=("opacities", "means2D"))
-    assert got["has_attr"] and got["stats"].shape == (0, 3) and got["stats"].dtype == torch.float32 and got["stats"].is_cuda
+    assert got["has_stats"] and got["stats"].shape == (0, 3) and got["stats"].dtype == torch.float32 and got["stats"].is_cuda
     behind = scenes.make_scene(P=200, W=48, H=40, sigma_min=1.0, sigma_max=8.0, seed=7)   # camera at the origin looking down +z
     behind.means3D = (behind.means3D * np.array([1, 1, -1], np.float32)).astype(np.float32)
     for sd, _, _ in MODES.values():
@@ -378,7 +289,6 @@ def test_empty_culled_and_single_gaussian_frames():
 
 
 def test_blend_stats_refusals():
-    import diff_gaussian_rasterization as dgr
     from diff_gaussian_rasterization import tile_shard
     sc = scenes.make_scene(P=100, W=48, H=40, sigma_min=1.0, sigma_max=6.0, seed=2, camera="orbit")
     with pytest.raises(RuntimeError, match="blend statistics.*render_depth"):
@@ -387,10 +297,7 @@ def test_blend_stats_refusals():
     t = lambda a: torch.tensor(np.asarray(a, np.float32), device=dev)
     es = ext_settings(settings_dict(3))
     es._blend_stats = True
-    rs = dgr.GaussianRasterizationSettings(
-        image_height=sc.H, image_width=sc.W, tanfovx=sc.tanfovx, tanfovy=sc.tanfovy, bg=t(sc.bg), scale_modifier=1.0, viewmatrix=t(sc.viewmatrix),
-        projmatrix=t(sc.projmatrix), inv_viewprojmatrix=t(sc.inv_viewprojmatrix), sh_degree=sc.sh_degree, campos=t(sc.campos),
-        prefiltered=False, settings=es, render_depth=False, debug=False)
+    rs = api_settings(sc, es, dev)
     m = t(sc.means3D).requires_grad_(True)
     with pytest.raises(RuntimeError, match=r"blend statistics.*tile-row sharding.*\(P, 9\)"):
         tile_shard.TileRowShardedRasterizer(rs, None, 0, 1)(m, torch.zeros_like(m), t(sc.opacities), shs=t(sc.shs), scales=t(sc.scales),

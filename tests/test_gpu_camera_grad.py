@@ -9,55 +9,20 @@ stp_set_backward_camera_grads; routed by rasterize_gaussians() through _Rasteriz
   * frozen Gaussians, P = 0, a fully culled frame, a chunked per-Gaussian half;
   * pose refinement end to end: Adam on a 6-DoF pose recovers a perturbed camera.
 """
+import functools
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import FULL_STP, ext_settings, max_abs, settings_dict
+from helpers import CAMERA, FULL_STP, _direct, _rel, api_render, api_settings, ext_settings, max_abs, settings_dict
 from diff_gaussian_rasterization import scenes
 import torch_ref_camera
 
 pytestmark = pytest.mark.gpu
 
-CAMERA = ("viewmatrix", "projmatrix", "campos")
-
-
-def _rel(a, b):
-    return max_abs(a, b) / max(float(np.max(np.abs(b))), 1e-30)
-
-
-def render(sc, sdict, camera=CAMERA, gaussians=True, backward_mode=None, cov3D=None, w=None):
-    """One forward + backward of sum(dL_dout * image) through the public API on cuda:0.  camera: the camera tensors that require grad."""
-    import diff_gaussian_rasterization as dgr
-    dev = torch.device("cuda:0")
-    t = lambda a, rg=False: None if a is None else torch.tensor(np.asarray(a, np.float32), device=dev).requires_grad_(rg)
-    ten = dict(means3D=t(sc.means3D, gaussians), opacities=t(sc.opacities, gaussians), shs=t(sc.shs, gaussians),
-               colors_precomp=t(sc.colors_precomp, gaussians))
-    if cov3D is not None:
-        ten["cov3D_precomp"] = t(cov3D, gaussians)
-    else:
-        ten["scales"], ten["rotations"] = t(sc.scales, gaussians), t(sc.rotations, gaussians)
-    ten["means2D"] = torch.zeros_like(ten["means3D"], requires_grad=gaussians)
-    for n, a in (("viewmatrix", sc.viewmatrix), ("projmatrix", sc.projmatrix), ("campos", sc.campos)):
-        ten[n] = t(a, n in camera)
-    d = dict(sdict)
-    if backward_mode:
-        d["_backward_mode"] = backward_mode
-    rs = dgr.GaussianRasterizationSettings(
-        image_height=sc.H, image_width=sc.W, tanfovx=sc.tanfovx, tanfovy=sc.tanfovy, bg=t(sc.bg), scale_modifier=sc.scale_modifier,
-        viewmatrix=ten["viewmatrix"], projmatrix=ten["projmatrix"], inv_viewprojmatrix=t(sc.inv_viewprojmatrix), sh_degree=sc.sh_degree,
-        campos=ten["campos"], prefiltered=False, settings=ext_settings(d), render_depth=False, debug=False)
-    color, radii = dgr.GaussianRasterizer(rs)(ten["means3D"], ten["means2D"], ten["opacities"], shs=ten["shs"],
-                                              colors_precomp=ten["colors_precomp"], scales=ten.get("scales"),
-                                              rotations=ten.get("rotations"), cov3D_precomp=ten.get("cov3D_precomp"))
-    if color.requires_grad:
-        (color * torch.tensor(sc.dL_dout if w is None else w, device=dev)).sum().backward()
-    out = {"color": color.detach(), "radii": radii, "grad_fn": type(color.grad_fn).__name__ if color.grad_fn is not None else None}
-    for n, x in ten.items():
-        out[n] = None if x is None or x.grad is None else x.grad.detach().clone()
-    return out
+render = functools.partial(api_render, camera=CAMERA)   # camera: the camera tensors that require grad
 
 
 def tiny(seed=7, use_sh=True, degree=3, clamped=True, P=150, W=40, H=36):
@@ -167,23 +132,6 @@ def test_translation_gauge_full_size(name):
     cam_side = np.abs(f64(got["campos"])) + np.abs(V[:3, :] @ f64(got["viewmatrix"])[3, :]) + np.abs(P[:3, :] @ f64(got["projmatrix"])[3, :])
     print(f"{name}: residual / camera-side magnitude = {np.abs(res) / cam_side}")
     assert np.all(np.abs(res) <= 1e-5 * cam_side), (res, cam_side)
-
-
-def _direct(sc, sd, cov3D=None):
-    """Forward through _C directly (the buffers a phase-split backward needs); returns the backward's positional arguments."""
-    from diff_gaussian_rasterization import _C
-    dev = torch.device("cuda:0")
-    empty = torch.Tensor([])
-    t = lambda a: empty if a is None else torch.tensor(np.asarray(a, np.float32), device=dev)
-    ten = dict(bg=t(sc.bg), means3D=t(sc.means3D), opac=t(sc.opacities), scales=t(None if cov3D is not None else sc.scales),
-               rots=t(None if cov3D is not None else sc.rotations), cov=t(cov3D), shs=t(sc.shs), colors=t(sc.colors_precomp),
-               view=t(sc.viewmatrix), proj=t(sc.projmatrix), inv=t(sc.inv_viewprojmatrix), cam=t(sc.campos), w=t(sc.dL_dout))
-    out = _C.rasterize_gaussians(ten["bg"], ten["means3D"], ten["colors"], ten["opac"], ten["scales"], ten["rots"], sc.scale_modifier,
-                                 ten["cov"], ten["view"], ten["proj"], ten["inv"], sc.tanfovx, sc.tanfovy, sc.H, sc.W, ten["shs"],
-                                 sc.sh_degree, ten["cam"], False, sd, False, False)
-    return (ten["bg"], ten["means3D"], out[2], ten["opac"], ten["colors"], ten["scales"], ten["rots"], sc.scale_modifier, ten["cov"],
-            ten["view"], ten["proj"], ten["inv"], sc.tanfovx, sc.tanfovy, out[1], ten["w"], ten["shs"], sc.sh_degree, ten["cam"], out[3],
-            out[0], out[4], out[5], sd, False)
 
 
 @pytest.mark.parametrize("backward_mode", ["replay", "resort"])
@@ -327,10 +275,7 @@ def test_pose_refinement_end_to_end():
 
     def draw(pose):
         V, P, cam = _camera_from_pose(pose, V0, proj)
-        rs = dgr.GaussianRasterizationSettings(
-            image_height=sc.H, image_width=sc.W, tanfovx=sc.tanfovx, tanfovy=sc.tanfovy, bg=f(sc.bg), scale_modifier=1.0, viewmatrix=V,
-            projmatrix=P, inv_viewprojmatrix=torch.linalg.inv(P.detach().double()).float(), sh_degree=3, campos=cam, prefiltered=False,
-            settings=es, render_depth=False, debug=False)
+        rs = api_settings(sc, es, dev, viewmatrix=V, projmatrix=P, inv_viewprojmatrix=torch.linalg.inv(P.detach().double()).float(), campos=cam)
         return dgr.GaussianRasterizer(rs)(means, torch.zeros_like(means), opac, shs=shs, scales=scales, rotations=rots)[0]
 
     with torch.no_grad():
@@ -368,10 +313,7 @@ def test_camera_inputs_modified_in_place_raise():
     V = f(sc.viewmatrix) * 1.0
     V.requires_grad_(True)
     Vin = V.clone()   # a non-leaf the caller could modify in place
-    rs = dgr.GaussianRasterizationSettings(
-        image_height=sc.H, image_width=sc.W, tanfovx=sc.tanfovx, tanfovy=sc.tanfovy, bg=f(sc.bg), scale_modifier=1.0, viewmatrix=Vin,
-        projmatrix=f(sc.projmatrix), inv_viewprojmatrix=f(sc.inv_viewprojmatrix), sh_degree=3, campos=f(sc.campos), prefiltered=False,
-        settings=ext_settings(settings_dict(3)), render_depth=False, debug=False)
+    rs = api_settings(sc, ext_settings(settings_dict(3)), dev, viewmatrix=Vin)
     m = f(sc.means3D)
     color, _ = dgr.GaussianRasterizer(rs)(m, torch.zeros_like(m), f(sc.opacities), shs=f(sc.shs), scales=f(sc.scales), rotations=f(sc.rotations))
     with torch.no_grad():

@@ -6,6 +6,10 @@ compositing with a per-pixel order) and differentiated by torch.autograd.  It pi
 gradient maths* of oracle and kernels; discrete behaviour (tile binning, queue cadence) is pinned
 elsewhere.  Ordering modes: "global" (sort by the global depth key) and "exact" (sort by each
 pixel's own depth-along-ray, i.e. what the resorting modes converge to at low density).
+
+One dense renderer, render_core(), serves every float64 yardstick of the tests: render() / loss_and_grads() here, and through its hooks
+the camera gradients (torch_ref_camera.py), absgrad (torch_ref_absgrad.py) and the blend statistics (torch_ref_blend_stats.py).  A
+further yardstick is a further hook, not a copy; tests/test_yardstick_pin_cpu.py holds all four to recorded values.
 """
 from __future__ import annotations
 
@@ -47,14 +51,31 @@ def eval_sh(deg, sh, dirs):
     return res + 0.5
 
 
-def render(scene, order="global", proper_ewa_scaling=False, use_cov3D_precomp=False, depth_key="z"):
-    """Returns (image (3,H,W) float64 tensor, dict of leaf tensors with requires_grad)."""
+def render_core(scene, order="global", proper_ewa_scaling=False, use_cov3D_precomp=False, depth_key="z", camera_leaves=False,
+                offset_leaves=False):
+    """The one dense renderer.  Returns (image (3,H,W) float64 tensor, dict of leaf tensors with requires_grad, details).
+
+    camera_leaves: viewmatrix, projmatrix and campos are leaves too (torch_ref_camera.py), with two conventions where the camera enters:
+      * the three camera tensors are INDEPENDENT leaves, as the rasterizer reads them (it never checks that projmatrix = viewmatrix @ P
+        or that campos is the camera centre); culling, tile binning and every sort key see the detached camera;
+      * the 1.3 * tan_fov clamp of the view-space mean inside the EWA Jacobian is differentiated as the rasterizer differentiates it for
+        means3D (the reference's backward.cu): a clamped coordinate is a constant -- it carries no gradient to the view-space mean, and
+        its value enters J as a number.  Without the switch clamp(x / z) * z is differentiated, which also moves with z; the two agree
+        for every Gaussian inside the band, where the switch puts x itself into J and not (x / z) * z: an ulp or two on the image.
+    offset_leaves: two N x P zero leaves, "offsets_x" and "offsets_y", are added to the pixel offsets dx, dy (torch_ref_absgrad.py).
+    details: what torch_ref_blend_stats.py reads, without gradients.  Per (pixel, Gaussian) pair, N x P in the Gaussians' own order:
+    "w" the blend weight alpha * T (0 where the pair is not blended), "blended", "cand" (a candidate: in the tile rectangle, visible,
+    power <= 0 and, in the exact order, not behind the camera -- whatever its alpha) and "alpha"; in each pixel's sorted order, with the
+    sort index "idx": "test_T" = T * (1 - alpha) and "reached" (no entry in front of it saturated the pixel; the saturating entry
+    itself is reached); "T_final" (N,)."""
     dd = torch.float64
     t = lambda a: torch.tensor(np.asarray(a), dtype=dd)
     W, H = scene.W, scene.H
     V, PM, INV = t(scene.viewmatrix), t(scene.projmatrix), t(scene.inv_viewprojmatrix)
     cam, bg = t(scene.campos), t(scene.bg)
     leaves = {}
+    if camera_leaves:
+        leaves.update(viewmatrix=V.requires_grad_(True), projmatrix=PM.requires_grad_(True), campos=cam.requires_grad_(True))
     means = t(scene.means3D).requires_grad_(True); leaves["means3D"] = means
     opac = t(scene.opacities).requires_grad_(True); leaves["opacities"] = opac
     scales = t(scene.scales).requires_grad_(True); leaves["scales"] = scales
@@ -72,13 +93,21 @@ def render(scene, order="global", proper_ewa_scaling=False, use_cov3D_precomp=Fa
     else:
         Sigma_used = Sigma
 
-    pv = means @ V[:3, :3] + V[3, :3]
+    pv = means @ V[:3, :3] + V[3, :3]                  # view-space means (row-vector convention)
     tz = pv[:, 2]
     near_ok = (tz > 0.2).detach()
     fx, fy = W / (2 * scene.tanfovx), H / (2 * scene.tanfovy)
     limx, limy = 1.3 * scene.tanfovx, 1.3 * scene.tanfovy
-    txc = torch.clamp(pv[:, 0] / tz, -limx, limx) * tz
-    tyc = torch.clamp(pv[:, 1] / tz, -limy, limy) * tz
+    if camera_leaves:
+        with torch.no_grad():
+            rx, ry = pv[:, 0] / tz, pv[:, 1] / tz
+            in_x, in_y = (rx >= -limx) & (rx <= limx), (ry >= -limy) & (ry <= limy)
+            cx, cy = torch.clamp(rx, -limx, limx) * tz, torch.clamp(ry, -limy, limy) * tz
+        txc = torch.where(in_x, pv[:, 0], cx)
+        tyc = torch.where(in_y, pv[:, 1], cy)
+    else:
+        txc = torch.clamp(pv[:, 0] / tz, -limx, limx) * tz
+        tyc = torch.clamp(pv[:, 1] / tz, -limy, limy) * tz
     zero = torch.zeros_like(tz)
     J = torch.stack([fx / tz, zero, -fx * txc / (tz * tz), zero, fy / tz, -fy * tyc / (tz * tz)], 1).reshape(-1, 2, 3)
     Wm = V[:3, :3].T  # p_view = Wm p + t
@@ -121,13 +150,17 @@ def render(scene, order="global", proper_ewa_scaling=False, use_cov3D_precomp=Fa
     px, py = xs.reshape(-1), ys.reshape(-1)             # N
     dx = mx[None, :] - px[:, None]                      # N x P
     dy = my[None, :] - py[:, None]
+    if offset_leaves:   # one offset per (pixel, Gaussian) pair
+        leaves["offsets_x"] = torch.zeros(px.shape[0], P, dtype=dd, requires_grad=True)
+        leaves["offsets_y"] = torch.zeros(px.shape[0], P, dtype=dd, requires_grad=True)
+        dx, dy = dx + leaves["offsets_x"], dy + leaves["offsets_y"]
     power = -0.5 * (cA[None] * dx * dx + cC[None] * dy * dy) - cB[None] * dx * dy
     G = torch.exp(torch.clamp(power, max=0.0))
     alpha = torch.clamp(o[None] * G, max=0.99)
-    with torch.no_grad():
+    with torch.no_grad():   # per-pixel order: non-differentiable
         tx_, ty_ = torch.floor(px / 16), torch.floor(py / 16)
         in_rect = (tx_[:, None] >= x0[None]) & (tx_[:, None] < x1[None]) & (ty_[:, None] >= y0[None]) & (ty_[:, None] < y1[None])
-        keep = in_rect & visible[None] & (power <= 0) & (alpha >= 1.0 / 255.0)
+        cand = in_rect & visible[None] & (power <= 0)
         if order == "global":
             key = (tz if depth_key == "z" else (means - cam).norm(dim=1))[None].expand(px.shape[0], P)
         else:
@@ -143,28 +176,58 @@ def render(scene, order="global", proper_ewa_scaling=False, use_cov3D_precomp=Fa
             num = v @ u.T                                   # N x P
             den = torch.einsum("ni,pij,nj->np", v, Sinv, v)
             key = num / torch.clamp(den, min=1e-5)
-            keep &= key >= 0
+            cand &= key >= 0
+        keep = cand & (alpha >= 1.0 / 255.0)
         key = torch.where(keep, key, torch.full_like(key, float("inf")))
         idx = torch.argsort(key, dim=1, stable=True)
     a_s = torch.gather(torch.where(keep, alpha, torch.zeros_like(alpha)), 1, idx)
     one_m = 1 - a_s
     Tbefore = torch.cumprod(torch.cat([torch.ones(a_s.shape[0], 1, dtype=dd), one_m[:, :-1]], 1), 1)
     with torch.no_grad():
-        stop = (Tbefore * one_m) < 1e-4                   # first saturating entry ends the pixel
-        alive = torch.cumsum(stop.to(torch.int64), 1) == 0
+        test_T = Tbefore * one_m
+        stop = test_T < 1e-4                              # first saturating entry ends the pixel
+        stops = torch.cumsum(stop.to(torch.int64), 1)
+        alive = stops == 0
     wgt = torch.where(alive, a_s * Tbefore, torch.zeros_like(a_s))
     col_s = col[idx]                                      # N x P x 3
     C = (wgt[..., None] * col_s).sum(1)
     T_final = torch.where(alive, one_m, torch.ones_like(one_m)).prod(1)
     img = C + T_final[:, None] * bg[None]
-    return img.T.reshape(3, H, W), leaves
+    with torch.no_grad():
+        keep_s = torch.gather(keep, 1, idx)
+        unsort = lambda m: torch.zeros_like(m).scatter(1, idx, m)
+        details = {"w": unsort(wgt), "blended": unsort(alive & keep_s), "cand": cand, "alpha": alpha.detach(), "idx": idx,
+                   "test_T": test_T, "reached": keep_s & ((stops - stop.to(torch.int64)) == 0), "T_final": T_final.detach()}
+    return img.T.reshape(3, H, W), leaves, details
+
+
+def render(scene, order="global", proper_ewa_scaling=False, use_cov3D_precomp=False, depth_key="z"):
+    """Returns (image (3,H,W) float64 tensor, dict of leaf tensors with requires_grad)."""
+    return render_core(scene, order, proper_ewa_scaling, use_cov3D_precomp, depth_key)[:2]
 
 
 def loss_and_grads(scene, **kw):
-    img, leaves = render(scene, **kw)
+    """(image, {leaf name: gradient of sum(dL_dout * image)}) in float64 numpy; kw: render_core's."""
+    img, leaves, _ = render_core(scene, **kw)
     w = torch.tensor(scene.dL_dout, dtype=torch.float64)
     loss = (img * w).sum()
     names = list(leaves.keys())
     grads = torch.autograd.grad(loss, [leaves[n] for n in names], allow_unused=True)
     out = {n: (None if g is None else g.detach().numpy()) for n, g in zip(names, grads)}
     return img.detach().numpy(), out
+
+
+_cache = {}
+
+
+def cached(name, key, make):
+    """make()'s tuple of numpy arrays, made read-only.  key: a hashable name under which the result is kept, per yardstick `name`, for the
+    other tests of the session that need the same scene and order (None: not kept)."""
+    if key is not None and (name, key) in _cache:
+        return _cache[name, key]
+    out = make()
+    for arr in out:
+        arr.setflags(write=False)
+    if key is not None:
+        _cache[name, key] = out
+    return out
