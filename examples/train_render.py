@@ -3,12 +3,12 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
   model  : get_xyz, get_opacity, get_scaling, get_rotation, get_features, active_sh_degree
-and returns the trainer's usual dict (render, viewspace_points, visibility_filter, radii).
+and returns the trainer's usual dict (render, viewspace_points, visibility_filter, radii; "alpha" too when asked for).
 """
 from __future__ import annotations
 
@@ -29,7 +29,10 @@ def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, 
            override_color: torch.Tensor | None = None, render_depth: bool = False, debug: bool = False):
     """One frame.  Gradients flow to every model tensor; `viewspace_points.grad` is the screen-space positional
     gradient densification uses -- and with `splat_args._absgrad = True`, `viewspace_points.absgrad` (after backward) the
-    sum of the ABSOLUTE per-pixel contributions to it (AbsGS / gsplat's absgrad)."""
+    sum of the ABSOLUTE per-pixel contributions to it (AbsGS / gsplat's absgrad).
+    `bg_color` is three floats or a (3, H, W) image the frame is composed onto; where it requires grad it gets one.  With
+    `splat_args._alpha = True` the dict also carries "alpha", the pixel's opacity (1, H, W), differentiable like the image
+    (INTEGRATION.md section 3h)."""
     screenspace_points = torch.zeros_like(model.get_xyz, requires_grad=True)
     raster_settings = GaussianRasterizationSettings(
         image_height=int(camera.image_height), image_width=int(camera.image_width),
@@ -39,9 +42,12 @@ def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, 
         campos=camera.camera_center, prefiltered=False, settings=splat_args, render_depth=render_depth, debug=debug)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
     shs, colors = (None, override_color) if override_color is not None else (model.get_features, None)
-    image, radii = rasterizer(means3D=model.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors,
-                              opacities=model.get_opacity, scales=model.get_scaling, rotations=model.get_rotation)
-    return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+    image, radii, *alpha = rasterizer(means3D=model.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors,
+                                      opacities=model.get_opacity, scales=model.get_scaling, rotations=model.get_rotation)
+    out = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+    if alpha:   # (settings._alpha)
+        out["alpha"] = alpha[0]
+    return out
 
 
 def splat_config(name: str) -> ExtendedSettings:
@@ -93,6 +99,8 @@ def main(argv=None):
     ap.add_argument("--absgrad", action="store_true", help="also accumulate the absolute screen-space gradient (densification statistic of AbsGS)")
     ap.add_argument("--prune-views", type=int, default=0, metavar="N",
                     help="after training, a pruning pass over N views: the largest blend weight of every Gaussian over the views, then a threshold")
+    ap.add_argument("--mask-weight", type=float, default=0.0, metavar="W",
+                    help="add W * mean |alpha - target alpha| to the loss: mask supervision on the rasterizer's alpha output")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
@@ -100,8 +108,12 @@ def main(argv=None):
     W, H = args.size
     target_scene = scenes.make_scene(P=args.points, W=W, H=H, sigma_min=1.0, sigma_max=9.0, seed=3, camera="orbit")
     cam, bg, cfg = camera_of(target_scene, dev), torch.tensor(target_scene.bg, device=dev), splat_config(args.config)
+    masked = args.mask_weight > 0.0
+    target_cfg = splat_config(args.config)
+    target_cfg._alpha = masked   # (the target's own opacity is the mask the fit is supervised with)
     with torch.no_grad():
-        target = render(cam, ToyGaussians(target_scene, dev), bg, cfg)["render"]
+        target_out = render(cam, ToyGaussians(target_scene, dev), bg, target_cfg)
+        target, target_alpha = target_out["render"], target_out.get("alpha")
 
     # start from perturbed colours and opacities and fit them back
     model = ToyGaussians(target_scene, dev)
@@ -111,6 +123,7 @@ def main(argv=None):
     opt = torch.optim.Adam([{"params": [model._features], "lr": 2e-2}, {"params": [model._opacity], "lr": 5e-2},
                             {"params": [model._xyz, model._scaling, model._rotation], "lr": 0.0}])
     train_cfg = splat_config(args.config)
+    train_cfg._alpha = masked
     train_cfg._absgrad = args.absgrad   # (a request on the settings object; the depth rendering below keeps the plain settings: it refuses it)
     # the densification statistic a trainer accumulates between two densify steps: the norm of the 2D positional gradient per visible
     # Gaussian -- signed (3DGS: pulls from opposite sides cancel) and, with --absgrad, absolute (AbsGS: they add up)
@@ -120,6 +133,8 @@ def main(argv=None):
     for it in range(args.iters):
         out = render(cam, model, bg, train_cfg)
         loss = (out["render"] - target).abs().mean()
+        if masked:   # alpha is an output of the same autograd node: one backward serves both terms
+            loss = loss + args.mask_weight * (out["alpha"] - target_alpha).abs().mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
         grad2d = out["viewspace_points"].grad  # what densification accumulates

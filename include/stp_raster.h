@@ -238,6 +238,39 @@ void stp_set_backward_absgrad(float* dL_dmean2D_abs /* P x 3 */);
    has no room for the three terms), or a chunked per-Gaussian half (phases bits 8-23). */
 void stp_set_backward_blend_stats(float* blend_stats /* P x 3 */);
 
+/* Extension (not in the reference): alpha output, per-pixel background and background gradients.  Every forward keeps final_T, the
+   transmittance behind a pixel's last blend; the image is  out[ch, p] = C[ch, p] + final_T[p] * background[ch].
+   stp_set_forward_background -- the NEXT stp_forward of the calling thread
+       with bg_image  (3 x H x W floats): composes  out[ch, p] = C[ch, p] + final_T[p] * bg_image[ch, p]  instead; `background` is not read
+                      by the render kernels (it must still be a valid pointer).  The expression is the uniform one's: a bg_image filled with
+                      one colour gives the image of that `background` bit for bit;
+       with out_alpha (H x W floats): also writes  out_alpha[p] = 1 - final_T[p]  (0 for a pixel nothing blended into).
+   Every sort mode, PPX_FULL included; both launches of a split forward (stp_set_forward_split) and a redone run-ahead frame honour it.  The
+   request costs a wave-uniform branch per pixel in the kernels' epilogues; nothing else of the forward changes, and without a request the
+   forward is what it was.  P == 0 launches nothing: the caller's image and alpha stand.  STP_ERR_INVALID_ARGUMENT with
+   StpSettings::debug_visualization = STP_DEBUG_DEPTH (that image is not C + T * background).
+   stp_set_backward_background -- the NEXT stp_backward / stp_backward_phases of the calling thread that runs the render half (phases bit 0)
+       with bg_image       : the forward's per-pixel background (it MUST be given when the forward had one: final_T's weight in the loss and
+                             the colour behind each blend are formed from it), or NULL for a uniform `background`;
+       with dL_dalpha      (H x W floats): the gradient of the loss with respect to out_alpha.  The pixel prologues of the render half use
+                             dL/dfinal_T[p] = sum_ch B[ch, p] * dL_dpix[ch, p] - dL_dalpha[p]   (B = bg_image, or background[ch] for every p)
+                             where they used the first term; the nine per-Gaussian sums are otherwise formed as before.  A backward through
+                             alpha alone passes an all-zero dL_dpix;
+       with dL_dbackground : receives dL/dB[ch, p] = final_T[p] * dL_dpix[ch, p] -- 3 x H x W floats when bg_image is given, otherwise its
+                             sum over the pixels, 3 floats.  Written in full (no zero-fill by the caller; zeros for P == 0).  The sum
+                             runs in a fixed order without float atomics, like the camera gradients: equal inputs give bit-equal results.
+   All buffers are full-frame device buffers indexed by absolute pixel (W * y + x).  With a tile-row window (StpSettings::tile_y0 / tile_y1)
+   only the window's pixel rows are read or written, and the uniform sum covers the window's rows.  Nothing of the request lives in the
+   gradient records: compact records (phases bit 2) and a chunked per-Gaussian half are fine, and so are camera gradients, absgrad and blend
+   statistics in the same call.  No backward for PPX_FULL, as without the request.
+   Both requests are per thread and one-shot.  Any pointer may be NULL; all NULL clears a pending request.  The forward request is consumed
+   by the next stp_forward of the thread whatever that call's outcome (an invalid argument or P == 0 included).  The backward request is
+   consumed by the next stp_backward / stp_backward_phases of the thread WITH phases bit 0, whatever its outcome; a per-Gaussian-only call
+   (phases = 2) neither honours nor consumes it. */
+void stp_set_forward_background(const float* bg_image /* 3 x H x W */, float* out_alpha /* H x W */);
+void stp_set_backward_background(const float* bg_image /* the forward's, or NULL */, const float* dL_dalpha /* H x W, or NULL */,
+                                 float* dL_dbackground /* 3, or 3 x H x W when bg_image is given; or NULL */);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:188-193, rasterizer_impl.cu:161-173).
    `present` is P bytes (bool). */
 int stp_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

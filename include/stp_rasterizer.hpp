@@ -152,6 +152,8 @@ public:
     // Returns num_rendered.  `recordBlendLog`: set it when a backward with the same settings will follow (training) --
     // the forward then writes the per-pixel blend order into the image buffer and the backward replays it (DESIGN.md
     // section 3.1); the buffers returned by the three callbacks must stay valid until that backward has run.
+    // `bg_image` (extension, optional: 3 x H x W floats): a per-pixel background in the place of `background`; `out_alpha` (extension,
+    // optional: H x W floats): also receives alpha = 1 - final_T (stp_raster.h: stp_set_forward_background).
     static int forward(std::function<char*(size_t)> geometryBuffer, std::function<char*(size_t)> binningBuffer,
                        std::function<char*(size_t)> imageBuffer, const int P, int D, int M, const float* background,
                        const int width, int height, const SplattingSettings splatting_settings,
@@ -160,7 +162,7 @@ public:
                        const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
                        const float* inv_viewprojmatrix, const float* cam_pos, const float tan_fovx, float tan_fovy,
                        const bool prefiltered, float* out_color, int* radii = nullptr, bool debug = false,
-                       void* stream = nullptr, bool recordBlendLog = false)
+                       void* stream = nullptr, bool recordBlendLog = false, const float* bg_image = nullptr, float* out_alpha = nullptr)
     {
         StpSettings s = toPod(splatting_settings);
         s.record_blend_log = recordBlendLog ? 1 : 0;
@@ -169,6 +171,7 @@ public:
         case DebugVisualization::Depth: s.debug_visualization = STP_DEBUG_DEPTH; s.record_blend_log = 0; break;
         default: throw std::runtime_error("Debug visualization '" + toString(debugVisualization.type) + "' is not supported by libstp_raster");
         }
+        stp_set_forward_background(bg_image, out_alpha); // (consumed by the call below; two nullptr clear a request left pending on this thread)
         if (debugVisualization.timing_enabled) stp_timing_enable(1); // (restarts the running means: the text is per call, rasterizer_impl.cu:391-399)
         const int rendered = stp_forward(allocTrampoline, &geometryBuffer, allocTrampoline, &binningBuffer, allocTrampoline,
                                          &imageBuffer, P, D, M, background, width, height, &s, means3D, shs, colors_precomp,
@@ -203,10 +206,34 @@ public:
                          float* dL_drot, bool debug, void* stream = nullptr, bool replayBlendLog = false, float* dL_dmean2D_abs = nullptr,
                          float* blend_stats = nullptr)
     {
+        backwardWithBackground(P, D, M, R, background, width, height, sort_settings, culling_settings, proper_ewa_scaling, means3D, shs, opacities,
+                               colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix,
+                               cam_pos, tan_fovx, tan_fovy, pixel_colors, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D,
+                               grad_records, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream,
+                               replayBlendLog, dL_dmean2D_abs, blend_stats);
+    }
+
+    // backward() with the background extension (stp_raster.h: stp_set_backward_background) -- a function of its own: backward() keeps the
+    // reference's name for ONE function (its address can be taken) and the argument list it had.  `bg_image` the forward's per-pixel background (or nullptr), `dL_dalpha` the gradient of the forward's alpha output (H x W),
+    // `dL_dbackground` where dL/dbackground goes (3 floats, or 3 x H x W with bg_image).  All three may be nullptr.
+    static void backwardWithBackground(const int P, int D, int M, int R, const float* background, const int width, int height,
+                         const SortSettings sort_settings, const CullingSettings culling_settings,
+                         const bool proper_ewa_scaling, const float* means3D, const float* shs, const float* opacities,
+                         const float* colors_precomp, const float* scales, const float scale_modifier, const float* rotations,
+                         const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                         const float* inv_viewprojmatrix, const float* cam_pos, const float tan_fovx, float tan_fovy,
+                         const float* pixel_colors, const int* radii, char* geom_buffer, char* binning_buffer,
+                         char* image_buffer, const float* dL_dpix, float* dL_dmean2D, float* grad_records, float* dL_dopacity,
+                         float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                         float* dL_drot, bool debug, void* stream = nullptr, bool replayBlendLog = false, float* dL_dmean2D_abs = nullptr,
+                         float* blend_stats = nullptr, const float* bg_image = nullptr, const float* dL_dalpha = nullptr,
+                         float* dL_dbackground = nullptr)
+    {
         StpSettings s = toPod(sort_settings, culling_settings, false, proper_ewa_scaling);
         s.record_blend_log = replayBlendLog ? 1 : 0;
         stp_set_backward_absgrad(dL_dmean2D_abs); // (consumed by the call below; nullptr clears a request left pending on this thread)
         stp_set_backward_blend_stats(blend_stats);
+        stp_set_backward_background(bg_image, dL_dalpha, dL_dbackground);
         check(stp_backward(P, D, M, R, background, width, height, &s, means3D, shs, opacities, colors_precomp, scales,
                            scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, cam_pos,
                            tan_fovx, tan_fovy, pixel_colors, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,

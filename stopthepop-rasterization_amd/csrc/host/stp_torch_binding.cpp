@@ -69,6 +69,8 @@ struct Api {
     decltype(&stp_set_backward_camera_grads) set_backward_camera_grads = nullptr;
     decltype(&stp_set_backward_absgrad) set_backward_absgrad = nullptr;
     decltype(&stp_set_backward_blend_stats) set_backward_blend_stats = nullptr;
+    decltype(&stp_set_forward_background) set_forward_background = nullptr;
+    decltype(&stp_set_backward_background) set_backward_background = nullptr;
 } g_api;
 
 int load_library(const std::string& path)
@@ -90,6 +92,8 @@ int load_library(const std::string& path)
     a.set_backward_camera_grads = reinterpret_cast<decltype(a.set_backward_camera_grads)>(dlsym(h, "stp_set_backward_camera_grads"));
     a.set_backward_absgrad = reinterpret_cast<decltype(a.set_backward_absgrad)>(dlsym(h, "stp_set_backward_absgrad"));
     a.set_backward_blend_stats = reinterpret_cast<decltype(a.set_backward_blend_stats)>(dlsym(h, "stp_set_backward_blend_stats"));
+    a.set_forward_background = reinterpret_cast<decltype(a.set_forward_background)>(dlsym(h, "stp_set_forward_background"));
+    a.set_backward_background = reinterpret_cast<decltype(a.set_backward_background)>(dlsym(h, "stp_set_backward_background"));
     if (a.abi_version() != STP_ABI_VERSION) throw std::runtime_error(path + ": ABI version mismatch");
     g_api = a; // (a previously loaded library stays mapped: buffers of its forwards may still be in flight)
     return a.abi_version();
@@ -256,15 +260,28 @@ StpSettings settings_from_dict(const py::dict& d, bool record_log)
     return s;
 }
 
+// a background of shape exactly (3, H, W) is a per-pixel one (include/stp_raster.h: stp_set_forward_background); every other is three floats
+bool per_pixel_background(const torch::Tensor& bg, int H, int W)
+{
+    return bg.defined() && bg.dim() == 3 && bg.size(0) == 3 && bg.size(1) == H && bg.size(2) == W;
+}
+[[noreturn]] void raise_no_background_export(const char* name)
+{
+    throw std::runtime_error(std::string("alpha / background: the loaded libstp_raster.so does not export ") + name +
+                             " (a library built before the alpha output and per-pixel background): rebuild it");
+}
+
 // == RasterizeGaussiansCUDA (reference rasterize_points.cu:43-138).
-// Returns (num_rendered, out_color (3,H,W), radii (P,) int32, geomBuffer, binningBuffer, imgBuffer).
-std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+// Returns (num_rendered, out_color (3,H,W), radii (P,) int32, geomBuffer, binningBuffer, imgBuffer, alpha).
+// alpha (extension, include/stp_raster.h: stp_set_forward_background): with alpha = true the last element is 1 - final_T, (1,H,W); an
+// undefined tensor otherwise.  A background of shape exactly (3,H,W) is composed per pixel.
+std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors, const torch::Tensor& opacity,
                     const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier, const torch::Tensor& cov3D_precomp,
                     const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const torch::Tensor& inv_viewprojmatrix, const float tan_fovx,
                     const float tan_fovy, const int image_height, const int image_width, const torch::Tensor& sh, const int degree,
                     const torch::Tensor& campos, const bool prefiltered, const py::dict& settings, const bool render_depth, const bool debug,
-                    const bool record_log)
+                    const bool record_log, const bool alpha)
 {
     need_library();
     TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must have dimensions (num_points, 3)");
@@ -278,6 +295,10 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
     const bool zero = P == 0 || windowed;
     torch::Tensor out_color = zero ? torch::zeros({3, H, W}, fopt) : torch::empty({3, H, W}, fopt);
     torch::Tensor radii = zero ? torch::zeros({P}, iopt) : torch::empty({P}, iopt);
+    const bool bg_pixels = per_pixel_background(background, H, W);
+    if ((alpha || bg_pixels) && !g_api.set_forward_background) raise_no_background_export("stp_set_forward_background");
+    torch::Tensor out_alpha; // (like the image: every pixel of the rendered tile rows is written)
+    if (alpha) out_alpha = zero ? torch::zeros({1, H, W}, fopt) : torch::empty({1, H, W}, fopt);
     Resizer geom{torch::empty({0}, bopt), false, false, 0}, binning{torch::empty({0}, bopt), true, false, 1}, img{torch::empty({0}, bopt), true, false, 2};
     int rendered = 0;
     if (P != 0) {
@@ -295,6 +316,8 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
         int rc;
         {
             py::gil_scoped_release nogil; // (the call blocks once, on the num_rendered hand-over)
+            if (alpha || bg_pixels) // (consumed by the call below, on this thread)
+                g_api.set_forward_background(bg_pixels ? fptr(bg_) : nullptr, alpha ? out_alpha.data_ptr<float>() : nullptr);
             rc = g_api.forward(&Resizer::call, &geom, &Resizer::call, &binning, &Resizer::call, &img, P, degree, M, fptr(bg_), W, H, &s, fptr(m3_),
                              fptr(sh_), fptr(col_), fptr(op_), fptr(sc_), scale_modifier, fptr(ro_), fptr(c3_), fptr(vm_), fptr(pm_), fptr(inv_),
                              fptr(cam_), tan_fovx, tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(), radii.data_ptr<int>(), debug ? 1 : 0,
@@ -305,7 +328,7 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
         remember_storage(binning.t);
         remember_storage(img.t);
     }
-    return std::make_tuple(rendered, out_color, radii, geom.t, binning.t, img.t);
+    return std::make_tuple(rendered, out_color, radii, geom.t, binning.t, img.t, out_alpha);
 }
 
 // == RasterizeGaussiansBackwardCUDA (reference rasterize_points.cu:140-232).
@@ -318,6 +341,9 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
 // pixels of |each pixel's contribution to dL/dmeans2D| (x, y; column 2 zero).  Whole backwards on padded records only.
 // blend_stats (extension, include/stp_raster.h: stp_set_backward_blend_stats): one more (P,3) tensor, behind absgrad's if both are asked
 // for: per Gaussian the sum, the maximum and the count of its blend weights alpha * T.  Whole backwards on padded records only.
+// dL_dalpha / bg_grad (extension, include/stp_raster.h: stp_set_backward_background): the gradient of the forward's alpha output (1,H,W), and one
+// more tensor, LAST in the result: dL/dbackground in the background's shape, (3,) or (3,H,W).  A background of shape exactly (3,H,W) is
+// the forward's per-pixel one.  Calls with the render half (phases bit 0).
 std::vector<torch::Tensor>
 rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& opacities,
                              const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
@@ -326,7 +352,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
                              const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                              const py::dict& settings, const bool debug, const bool record_log, const int phases, const c10::optional<torch::Tensor>& partial,
-                             const c10::optional<std::vector<torch::Tensor>>& outputs, const bool camera_grads, const bool absgrad, const bool blend_stats)
+                             const c10::optional<std::vector<torch::Tensor>>& outputs, const bool camera_grads, const bool absgrad, const bool blend_stats,
+                             const c10::optional<torch::Tensor>& dL_dalpha, const bool bg_grad)
 {
     need_library();
     TORCH_CHECK(means3D.is_cuda(), "diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
@@ -351,6 +378,13 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
     const torch::Device dev = means3D.device();
     const int P = (int)means3D.size(0);
     const int H = (int)dL_dout_color.size(1), W = (int)dL_dout_color.size(2);
+    const bool bg_pixels = per_pixel_background(background, H, W);
+    const bool have_dalpha = dL_dalpha.has_value() && dL_dalpha->defined();
+    if (bg_pixels || have_dalpha || bg_grad) {
+        if (!g_api.set_backward_background) raise_no_background_export("stp_set_backward_background");
+        TORCH_CHECK(phases & 1, "alpha gradient / per-pixel background / background gradient belong to the render half (phases bit 0)");
+        TORCH_CHECK(!have_dalpha || dL_dalpha->numel() == (int64_t)H * W, "dL_dalpha must have H * W elements");
+    }
     const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
     const auto fopt = means3D.options().dtype(torch::kFloat32);
     const int rec_floats = (phases & 4) ? STP_GRAD_RECORD_USED : STP_GRAD_RECORD_FLOATS; // (bit 2: compact records, the tile-row shard's wire format)
@@ -399,7 +433,18 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
     if (absgrad) dL_dmeans2D_abs = torch::empty({P, 3}, fopt); // written in full by the library (zeros for invisible Gaussians)
     torch::Tensor stats;
     if (blend_stats) stats = torch::empty({P, 3}, fopt); // written in full by the library (zeros for invisible Gaussians)
+    torch::Tensor dL_dbg, dal_, bgpix_;
+    if (bg_grad) { // written in full by the library, except where nothing runs (P == 0) or a tile-row window leaves rows untouched
+        const std::vector<int64_t> shape = bg_pixels ? std::vector<int64_t>{3, H, W} : std::vector<int64_t>{3};
+        const bool windowed = settings.contains("_tile_rows") && !settings["_tile_rows"].is_none();
+        dL_dbg = (P == 0 || (bg_pixels && windowed)) ? torch::zeros(shape, fopt) : torch::empty(shape, fopt);
+    }
+    if (have_dalpha) dal_ = prep(*dL_dalpha, dev);
+    if (bg_pixels) bgpix_ = prep(background, dev);
     auto make_requests = [&] { // (all are consumed by the library call that follows, on this thread)
+        if ((bg_pixels || have_dalpha || bg_grad) && P != 0)
+            g_api.set_backward_background(bg_pixels ? bgpix_.data_ptr<float>() : nullptr, have_dalpha ? dal_.data_ptr<float>() : nullptr,
+                                          bg_grad ? dL_dbg.data_ptr<float>() : nullptr);
         if (blend_stats && P != 0) g_api.set_backward_blend_stats(stats.data_ptr<float>());
         if (absgrad && P != 0) g_api.set_backward_absgrad(dL_dmeans2D_abs.data_ptr<float>());
         if (camera_grads) g_api.set_backward_camera_grads(dL_dview.data_ptr<float>(), dL_dproj.data_ptr<float>(), dL_dcam.data_ptr<float>(), cam_ws.data_ptr(), (size_t)cam_ws.numel());
@@ -438,11 +483,12 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
             g_records[dev.index()] = KeptRecords{records, rec_stream};
         }
     }
-    if ((phases & 3) == 1) return {records};
+    if ((phases & 3) == 1) { if (bg_grad) return {records, dL_dbg}; return {records}; }
     std::vector<torch::Tensor> result{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations};
     if (camera_grads) result.insert(result.end(), {dL_dview, dL_dproj, dL_dcam});
     if (absgrad) result.push_back(dL_dmeans2D_abs);
     if (blend_stats) result.push_back(stats);
+    if (bg_grad) result.push_back(dL_dbg);
     return result;
 }
 

@@ -686,6 +686,11 @@ void stp_set_forward_split(int tile_row, void* event)
     t_forward_split.armed = event != nullptr;
 }
 
+// stp_set_forward_background: the request of the calling thread for its NEXT stp_forward (consumed there, whatever the call's outcome)
+struct ForwardBackground { const float* bg_image = nullptr; float* out_alpha = nullptr; };
+thread_local ForwardBackground t_forward_background;
+void stp_set_forward_background(const float* bg_image, float* out_alpha) { t_forward_background = ForwardBackground{bg_image, out_alpha}; }
+
 int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn binning_alloc, void* binning_user,
                 stp_alloc_fn image_alloc, void* image_user, int P, int D, int M, const float* background, int width, int height,
                 const StpSettings* settings, const float* means3D, const float* shs, const float* colors_precomp,
@@ -701,12 +706,16 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
         const ForwardSplit& s; hipStream_t st; bool done = false;
         ~SplitGuard() { if (s.armed && !done) (void)hipEventRecord(s.event, st); }
     } split_guard{split, st};
+    const ForwardBackground fbg = t_forward_background;
+    t_forward_background = ForwardBackground{};
     if (!settings || !geometry_alloc || !binning_alloc || !image_alloc) return fail(STP_ERR_INVALID_ARGUMENT, "null settings or allocator");
     if (P < 0 || width <= 0 || height <= 0) return fail(STP_ERR_INVALID_ARGUMENT, "bad sizes");
     if (P == 0) return 0; // reference rasterize_points.cu:93 -- nothing launched, caller's zero image stands
     if (!means3D || !opacities || !background || !viewmatrix || !projmatrix || !inv_viewprojmatrix || !cam_pos || !out_color)
         return fail(STP_ERR_INVALID_ARGUMENT, "null required input");
     if (int rc = check_settings(*settings, false)) return rc;
+    if ((fbg.bg_image || fbg.out_alpha) && settings->debug_visualization == STP_DEBUG_DEPTH)
+        return fail(STP_ERR_INVALID_ARGUMENT, "alpha output / per-pixel background (stp_set_forward_background) are not available with the debug depth visualisation: its image is not C + T * background");
     if (!colors_precomp && !shs) return fail(STP_ERR_INVALID_ARGUMENT, "neither SHs nor precomputed colours given");
     if (!cov3D_precomp && !(scales && rotations)) return fail(STP_ERR_INVALID_ARGUMENT, "neither scale/rotation nor precomputed covariance given");
     const bool with_inv = requires_depth_along_ray(*settings);
@@ -715,6 +724,7 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
     FrameParams f;
     fill_frame(f, P, D, M, background, width, height, *settings, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
                rotations, cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered);
+    f.bg_image = fbg.bg_image; f.out_alpha = fbg.out_alpha; // (every render launch of the call: both halves of a split forward, a redone run-ahead frame)
 
     size_t geom_bytes = 0;
     carve_geometry(nullptr, (size_t)P, with_inv, &geom_bytes);
@@ -1010,6 +1020,47 @@ void stp_set_backward_absgrad(float* dL_dmean2D_abs) { t_absgrad = dL_dmean2D_ab
 thread_local float* t_blend_stats = nullptr;
 void stp_set_backward_blend_stats(float* blend_stats) { t_blend_stats = blend_stats; }
 
+// stp_set_backward_background: the calling thread's request for its NEXT backward that runs the render half (phases bit 0), consumed there
+// whatever the call's outcome; a per-Gaussian-only call leaves it pending (nothing of it lives in the gradient records)
+struct BackwardBackground { const float* bg_image = nullptr; const float* dL_dalpha = nullptr; float* dL_dbackground = nullptr; };
+thread_local BackwardBackground t_backward_background;
+void stp_set_backward_background(const float* bg_image, const float* dL_dalpha, float* dL_dbackground)
+{
+    t_backward_background = BackwardBackground{bg_image, dL_dalpha, dL_dbackground};
+}
+namespace {
+// Scratch of the uniform background gradient's two-stage sum (stp_background.hip): a small ring of partial-row buffers per device, made at the
+// first request like the mailboxes, each with an event recorded behind the kernels that used it last.  A request takes the next slot and
+// orders its stream behind that event, so a slot is never written while an earlier user's sum kernel can still read it -- however many
+// threads and streams run backwards on the device.  The ring only keeps concurrent streams from waiting for each other in the common case.
+// g_background_mutex is held from taking a slot to recording its event (launches only: microseconds).
+constexpr int BG_RING = 8;
+struct BackgroundSlot { float* partials = nullptr; hipEvent_t done = nullptr; bool used = false; };
+struct BackgroundScratch { BackgroundSlot slot[BG_RING]; unsigned next = 0; bool ready = false; };
+BackgroundScratch g_background_scratch[MAX_DEVICES];
+std::mutex g_background_mutex;
+int acquire_background_scratch(BackgroundSlot** out, hipStream_t st) // caller holds g_background_mutex
+{
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= MAX_DEVICES) return fail(STP_ERR_HIP, "hipGetDevice failed");
+    BackgroundScratch& r = g_background_scratch[device];
+    if (!r.ready) {
+        const size_t bytes = background_grad_partials() * sizeof(float);
+        char* base = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&base), bytes * BG_RING) != hipSuccess) return fail(STP_ERR_HIP, "cannot create the background-gradient scratch");
+        for (int i = 0; i < BG_RING; i++) {
+            r.slot[i].partials = reinterpret_cast<float*>(base + bytes * i);
+            if (hipEventCreateWithFlags(&r.slot[i].done, hipEventDisableTiming) != hipSuccess) { (void)hipFree(base); return fail(STP_ERR_HIP, "cannot create the background-gradient scratch"); }
+        }
+        r.ready = true;
+    }
+    BackgroundSlot& s = r.slot[r.next++ % BG_RING];
+    if (s.used) STP_TRY(hipStreamWaitEvent(st, s.done, 0), "wait for the background-gradient scratch");
+    *out = &s;
+    return 0;
+}
+} // namespace
+
 int stp_backward_phases(int phases, int P, int D, int M, int R, const float* background, int width, int height, const StpSettings* settings,
                  const float* means3D, const float* shs, const float* opacities, const float* colors_precomp, const float* scales,
                  float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
@@ -1028,6 +1079,11 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     float* const absgrad = t_absgrad;
     float* const blend_stats = t_blend_stats;
     t_absgrad = nullptr; t_blend_stats = nullptr; // (put back at the end of a render-only call that ran)
+    BackwardBackground bbg;
+    if (phases & 1) { // (one render half per request, whatever its outcome)
+        bbg = t_backward_background;
+        t_backward_background = BackwardBackground{};
+    }
     if (absgrad) {
         if (phases & 4)
             return fail(STP_ERR_INVALID_ARGUMENT, "absgrad is not available with compact gradient records (phases bit 2): the 36-byte record has no room for the two extra sums");
@@ -1047,8 +1103,10 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
             return fail(STP_ERR_INVALID_ARGUMENT, "camera gradients are not available from a chunked per-Gaussian half (phases bits 8-23)");
     }
     if (!settings) return fail(STP_ERR_INVALID_ARGUMENT, "null settings");
-    if (P == 0) { // reference rasterize_points.cu:191 (a camera request still gets its outputs: zeros)
+    if (P == 0) { // reference rasterize_points.cu:191 (a camera request still gets its outputs: zeros; so does a background gradient -- the forward left the caller's image alone)
         if (cam.dL_dview) STP_TRY(launch_camera_grad_finalize(0, cam, st), "camera gradient launch");
+        if (bbg.dL_dbackground && (!bbg.bg_image || (width > 0 && height > 0)))
+            STP_TRY(hipMemsetAsync(bbg.dL_dbackground, 0, sizeof(float) * 3 * (bbg.bg_image ? (size_t)width * (size_t)height : (size_t)1), st), "background gradient fill");
         return 0;
     }
     if (int rc = check_settings(*settings, true)) return rc;
@@ -1075,6 +1133,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     bw.cam = cam;
     bw.absgrad = absgrad;
     bw.blend_stats = blend_stats;
+    bw.bg_image = bbg.bg_image; bw.dL_dalpha = bbg.dL_dalpha; bw.dL_dbackground = bbg.dL_dbackground;
     bw.pixel_colors = pixel_colors; bw.dL_dpix = dL_dpix; bw.dL_dmean2D = dL_dmean2D; bw.grad_rec = grad_records;
     bw.grad_stride = (phases & 4) ? STP_GRAD_RECORD_USED : STP_GRAD_RECORD_FLOATS;
     bw.clear_rec = (phases & 8) ? 1 : 0;
@@ -1083,6 +1142,13 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     bw.dL_dopacity = dL_dopacity; bw.dL_dcolor = dL_dcolor; bw.dL_dmean3D = dL_dmean3D; bw.dL_dcov3D = dL_dcov3D; bw.dL_dsh = dL_dsh;
     bw.dL_dscale = dL_dscale; bw.dL_drot = dL_drot;
 
+    // the uniform background gradient's scratch is taken BEFORE anything is launched: a call that cannot get it has done nothing
+    std::unique_lock<std::mutex> bg_lock;
+    BackgroundSlot* bg_slot = nullptr;
+    if ((phases & 1) && bw.dL_dbackground && !bw.bg_image) {
+        bg_lock = std::unique_lock<std::mutex>(g_background_mutex);
+        if (int rc = acquire_background_scratch(&bg_slot, st)) return rc;
+    }
     if (phases & 1) {
         g_timer.begin_backward();
         g_timer.mark(5, st);
@@ -1093,6 +1159,15 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
             return fail_hip(e, "backward render launch");
         }
         STP_DEBUG_SYNC("backward render");
+        if (bw.dL_dbackground) { // (reads final_T and dL_dpix only: nothing the render kernels write)
+            STP_TRY(launch_background_grad(f, img, bw, bg_slot ? bg_slot->partials : nullptr, st), "background gradient launch");
+            if (bg_slot) { // the slot's next user waits for these kernels (no event: wait for them here)
+                bg_slot->used = hipEventRecord(bg_slot->done, st) == hipSuccess;
+                if (!bg_slot->used) STP_TRY(hipStreamSynchronize(st), "synchronize behind the background gradient");
+                bg_lock.unlock();
+            }
+            STP_DEBUG_SYNC("background gradient");
+        }
         g_timer.mark(6, st);
     }
     if (phases & 2) {

@@ -58,6 +58,12 @@ struct RenderArgs {
     // rendering it, when the list holds 1 .. TS_SMALL entries (tile_sort_gather_lds, stp_tilesort.h); 0 = tile_sort_gather_kernel has done so
     int fused_gather;
     EntryGather gather;
+    // alpha output / per-pixel background (stp_set_forward_background, stp_set_backward_background): all three nullptr without a request.
+    // Read in the pixel prologues and epilogues only, behind a wave-uniform branch on the pointer.  (At the END: the kernarg layout of
+    // everything else is what it was.)
+    const float* bg_image;  // 3 x H x W, replaces bg[ch] for its pixel
+    float* out_alpha;       // H x W, forward: 1 - final_T
+    const float* dL_dalpha; // H x W, backward: subtracted from the pixel's weight of T_final
 };
 
 // A log record is a 16-bit list position (measured on C2: 2-byte records cost the forward 0.05 ms less than 4-byte
@@ -169,7 +175,7 @@ struct BwdPixel {
     float T_final;
     float dL_dpix[3];
     float final_color[3];
-    float bg_dot; // sum_ch bg[ch] * dL_dpix[ch]
+    float bg_dot; // dL/dT_final = sum_ch bg[ch] * dL_dpix[ch]  (- dL_dalpha with an alpha gradient)
     float T;
     float C[3];
 };
@@ -187,13 +193,35 @@ __device__ __forceinline__ void init_bwd_pixel(BwdPixel& b, const RenderArgs& a,
     b.T = 1.0f;
     b.T_final = inside ? a.final_T[pid] : 0.0f;
     b.bg_dot = 0.0f;
+    if (a.bg_image != nullptr) { // per-pixel background: B[ch, p] in the place of bg[ch]
 #pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        b.C[ch] = 0.0f;
-        b.dL_dpix[ch] = inside ? a.dL_dpix[ch * N + pid] : 0.0f;
-        b.final_color[ch] = inside ? (a.pixel_colors[ch * N + pid] - b.T_final * a.bg[ch]) : 0.0f;
-        b.bg_dot += a.bg[ch] * b.dL_dpix[ch];
+        for (int ch = 0; ch < 3; ch++) {
+            const float bgp = inside ? a.bg_image[ch * N + pid] : 0.0f;
+            b.C[ch] = 0.0f;
+            b.dL_dpix[ch] = inside ? a.dL_dpix[ch * N + pid] : 0.0f;
+            b.final_color[ch] = inside ? (a.pixel_colors[ch * N + pid] - b.T_final * bgp) : 0.0f;
+            b.bg_dot += bgp * b.dL_dpix[ch];
+        }
+    } else {
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            b.C[ch] = 0.0f;
+            b.dL_dpix[ch] = inside ? a.dL_dpix[ch * N + pid] : 0.0f;
+            b.final_color[ch] = inside ? (a.pixel_colors[ch * N + pid] - b.T_final * a.bg[ch]) : 0.0f;
+            b.bg_dot += a.bg[ch] * b.dL_dpix[ch];
+        }
     }
+    if (a.dL_dalpha != nullptr) b.bg_dot -= inside ? a.dL_dalpha[pid] : 0.0f; // alpha = 1 - T_final
+}
+
+// The largest factor the pixel's gradient terms are linear in: |dL_dpix| and, with an alpha gradient, |dL_dalpha| (which enters through
+// bg_dot) -- what the on-chip gradient windows of the replay and hierarchical backward size their fixed point by.  Without the alpha
+// gradient it is the colour gradients' maximum as before; a loss on alpha alone (dL_dpix all zero) would otherwise leave the scale at 0.
+__device__ __forceinline__ float bwd_pixel_scale(const BwdPixel& b, const RenderArgs& a, bool inside, int px, int py)
+{
+    float md = fmaxf(fmaxf(fabsf(b.dL_dpix[0]), fabsf(b.dL_dpix[1])), fabsf(b.dL_dpix[2]));
+    if (a.dL_dalpha != nullptr) md = fmaxf(md, inside ? fabsf(a.dL_dalpha[(size_t)a.W * py + px]) : 0.0f);
+    return md;
 }
 
 // Forward blend of the head entry, its colour in registers; false = pixel saturated (nothing accumulated).

@@ -156,6 +156,8 @@ struct FrameParams {
     uint32_t log_tag;    // ... tagged with 16 bits of the frame's kind
     int split_launch = 0; // this FrameParams describes ONE of the two render launches of a split forward (stp_set_forward_split): no tile order of the whole window
     int fused_gather = 0; // forward: the hierarchical render kernel sorts and gathers the tiles of up to TS_SMALL entries itself (RenderArgs::fused_gather), tile_sort_gather_kernel only the longer ones
+    const float* bg_image = nullptr; // forward, stp_set_forward_background: per-pixel background (3 x H x W) in the place of `background`
+    float* out_alpha = nullptr;      // ... and where the render kernels also write alpha = 1 - final_T (H x W)
     int wild_cov; // forward, after the status read-back: some visible Gaussian has a Sigma^-1 entry >= 1e36 or not finite (depth keys then take the reciprocal with its domain check)
 };
 
@@ -174,6 +176,11 @@ struct BackwardParams {
                               // record slots 9, 10, the per-Gaussian half moves them here
     float* blend_stats = nullptr; // stp_set_backward_blend_stats (P x 3, or nullptr = no request): the render half also collects sum, max and
                                   // count of the blend weights per pair in record slots 11..13, the per-Gaussian half moves them here
+    // stp_set_backward_background (all nullptr = no request): the render half reads the forward's per-pixel background and the alpha gradient in
+    // its pixel prologues; launch_background_grad forms dL/dbackground (3 floats, or 3 x H x W with bg_image) from final_T and dL_dpix
+    const float* bg_image = nullptr;
+    const float* dL_dalpha = nullptr;
+    float* dL_dbackground = nullptr;
     const float* pixel_colors;
     const float* dL_dpix;
     float* grad_rec;    // P x grad_stride: written by the render half, read by the per-Gaussian half
@@ -218,6 +225,10 @@ hipError_t launch_render_forward(const FrameParams& f, const GeometryState& g, c
 hipError_t launch_render_debug_finish(const FrameParams& f, const ImageState& img, float* out_color, hipStream_t st);
 hipError_t launch_render_backward(const FrameParams& f, const GeometryState& g, const BinningState& b, const ImageState& img,
                                   const BackwardParams& bw, hipStream_t st, std::string* err);
+// dL/dbackground over the window's pixel rows (stp_background.hip): T_final * dL_dpix per pixel, or its sum in a fixed order (uniform background);
+// `partials`: background_grad_partials() floats of device scratch for the uniform sum, free again when the launched kernels have run
+size_t background_grad_partials();
+hipError_t launch_background_grad(const FrameParams& f, const ImageState& img, const BackwardParams& bw, float* partials, hipStream_t st);
 hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState& g, const int* radii, const BackwardParams& bw, hipStream_t st);
 size_t camera_grad_workspace_bytes(int P);
 // sums the per-workgroup rows the CAM kernel wrote (none for P == 0) into the three outputs; launch_preprocess_backward calls it itself

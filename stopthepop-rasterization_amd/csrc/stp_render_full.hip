@@ -127,7 +127,11 @@ __global__ void __launch_bounds__(256) render_full_fwd_kernel(const RenderArgs a
                 a.final_T[pid] = T;
                 a.n_contrib[pid] = last_contributor;
                 if (a.debug_depth) { a.out_color[pid] = depth_acc; a.out_color[N + pid] = T; }
-                else for (int ch = 0; ch < 3; ch++) a.out_color[ch * N + pid] = C[ch] + T * a.bg[ch];
+                else {
+                    if (a.out_alpha != nullptr) a.out_alpha[pid] = 1.0f - T; // (stp_set_forward_background; see write_forward_pixel)
+                    if (a.bg_image != nullptr) for (int ch = 0; ch < 3; ch++) a.out_color[ch * N + pid] = C[ch] + T * a.bg_image[ch * N + pid];
+                    else for (int ch = 0; ch < 3; ch++) a.out_color[ch * N + pid] = C[ch] + T * a.bg[ch];
+                }
             }
         }
 }

@@ -318,7 +318,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     // the sums, and integer addition makes the on-chip part of the sum order-independent.
     float wave_md = 0.0f;
     if constexpr (BACKWARD) {
-        wave_md = fmaxf(fmaxf(fabsf(bp.dL_dpix[0]), fabsf(bp.dL_dpix[1])), fabsf(bp.dL_dpix[2]));
+        wave_md = bwd_pixel_scale(bp, a, inside, px, py);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) wave_md = fmaxf(wave_md, __shfl_xor(wave_md, off));
         // the window is shared by the four waves: one scale for the whole tile

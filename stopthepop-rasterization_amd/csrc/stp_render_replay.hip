@@ -103,7 +103,7 @@ render_replay_kernel(const RenderArgs a)
     float CD = 0.0f;
     const float tfbg = -bp.T_final * bp.bg_dot;
     int n = inside ? (int)a.n_contrib[(size_t)a.W * py + px] : 0;
-    float md = fmaxf(fmaxf(fabsf(bp.dL_dpix[0]), fabsf(bp.dL_dpix[1])), fabsf(bp.dL_dpix[2]));
+    float md = bwd_pixel_scale(bp, a, inside, px, py);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) md = fmaxf(md, __shfl_xor(md, off));
     // fixed-point scale of the sums (stp_render_hier.inc: "on-chip gradient window"): one for the workgroup

@@ -130,9 +130,16 @@ __global__ void __launch_bounds__(BLOCK) render_global_fwd_kernel(const RenderAr
             a.out_color[pid] = depth_acc;
             a.out_color[N + pid] = T;
         } else {
-            a.out_color[pid] = C0 + T * a.bg[0];
-            a.out_color[N + pid] = C1 + T * a.bg[1];
-            a.out_color[2 * N + pid] = C2 + T * a.bg[2];
+            if (a.out_alpha != nullptr) a.out_alpha[pid] = 1.0f - T; // (stp_set_forward_background; see write_forward_pixel)
+            if (a.bg_image != nullptr) {
+                a.out_color[pid] = C0 + T * a.bg_image[pid];
+                a.out_color[N + pid] = C1 + T * a.bg_image[N + pid];
+                a.out_color[2 * N + pid] = C2 + T * a.bg_image[2 * N + pid];
+            } else {
+                a.out_color[pid] = C0 + T * a.bg[0];
+                a.out_color[N + pid] = C1 + T * a.bg[1];
+                a.out_color[2 * N + pid] = C2 + T * a.bg[2];
+            }
         }
     }
 }
@@ -162,7 +169,11 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
     float last_alpha = 0.0f;
     if (c.inside)
         for (int ch = 0; ch < 3; ch++) dL_dpixel[ch] = a.dL_dpix[ch * N + pid];
-    const float bg_dot = a.bg[0] * dL_dpixel[0] + a.bg[1] * dL_dpixel[1] + a.bg[2] * dL_dpixel[2];
+    // dL/dT_final: the background's share (per pixel with stp_set_backward_background's bg_image) minus the alpha gradient (alpha = 1 - T_final)
+    float bg_dot;
+    if (a.bg_image != nullptr) bg_dot = c.inside ? a.bg_image[pid] * dL_dpixel[0] + a.bg_image[N + pid] * dL_dpixel[1] + a.bg_image[2 * N + pid] * dL_dpixel[2] : 0.0f;
+    else bg_dot = a.bg[0] * dL_dpixel[0] + a.bg[1] * dL_dpixel[1] + a.bg[2] * dL_dpixel[2];
+    if (a.dL_dalpha != nullptr) bg_dot -= c.inside ? a.dL_dalpha[pid] : 0.0f;
     const float ddelx_dx = 0.5f * (float)a.W, ddely_dy = 0.5f * (float)a.H;
     const int lane = lane_id();
 
@@ -418,6 +429,7 @@ static RenderArgs make_args(const FrameParams& f, const GeometryState& g, const 
     a.gather.keys = b.keys; a.gather.point_list = b.point_list; a.gather.gpack = g.gpack; a.gather.features = a.features;
     a.gather.gx = f.gx; a.gather.cull_mask = subtile_mask_kind(f.s);
     a.gather.entA = b.entA; a.gather.entB = b.entB; a.gather.entC = b.entC; a.gather.entD = b.entD; a.gather.entF = b.entF;
+    a.bg_image = f.bg_image; a.out_alpha = f.out_alpha; a.dL_dalpha = nullptr; // (forward: stp_set_forward_background; the backward sets its own)
     return a;
 }
 
@@ -497,6 +509,7 @@ hipError_t launch_render_backward(const FrameParams& f, const GeometryState& g, 
     a.pixel_colors = bw.pixel_colors; a.dL_dpix = bw.dL_dpix; a.grad_rec = bw.grad_rec; a.grad_stride = bw.grad_stride;
     // (the caller has refused compact records with either request: slots 9 .. 13 exist)
     a.requests = (bw.absgrad != nullptr ? REQ_ABSGRAD : 0) | (bw.blend_stats != nullptr ? REQ_BLEND_STATS : 0);
+    a.bg_image = bw.bg_image; a.out_alpha = nullptr; a.dL_dalpha = bw.dL_dalpha; // stp_set_backward_background
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(BLOCK);
     if (grid.x == 0) return hipSuccess;
     switch (f.s.sort_mode) {

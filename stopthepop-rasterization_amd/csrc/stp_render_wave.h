@@ -161,7 +161,11 @@ __device__ __forceinline__ void write_background_pixel(const RenderArgs& a, cons
     a.final_T[pid] = 1.0f;
     if constexpr (NCONTRIB) a.n_contrib[pid] = 0u;
     if constexpr (DEPTHVIZ) { a.out_color[pid] = 0.0f; a.out_color[N + pid] = 1.0f; }
-    else { a.out_color[pid] = a.bg[0]; a.out_color[N + pid] = a.bg[1]; a.out_color[2 * N + pid] = a.bg[2]; }
+    else {
+        if (a.out_alpha != nullptr) a.out_alpha[pid] = 0.0f;
+        if (a.bg_image != nullptr) { a.out_color[pid] = a.bg_image[pid]; a.out_color[N + pid] = a.bg_image[N + pid]; a.out_color[2 * N + pid] = a.bg_image[2 * N + pid]; }
+        else { a.out_color[pid] = a.bg[0]; a.out_color[N + pid] = a.bg[1]; a.out_color[2 * N + pid] = a.bg[2]; }
+    }
 }
 template <bool DEPTHVIZ, bool NCONTRIB>
 __device__ __forceinline__ void write_forward_pixel(const RenderArgs& a, const int px, const int py, const FwdPixel& fp, const float depth_acc, const uint32_t n_contrib)
@@ -173,9 +177,18 @@ __device__ __forceinline__ void write_forward_pixel(const RenderArgs& a, const i
         a.out_color[pid] = depth_acc;
         a.out_color[N + pid] = fp.T;
     } else {
-        a.out_color[pid] = fp.C[0] + fp.T * a.bg[0];
-        a.out_color[N + pid] = fp.C[1] + fp.T * a.bg[1];
-        a.out_color[2 * N + pid] = fp.C[2] + fp.T * a.bg[2];
+        // alpha output and per-pixel background (stp_set_forward_background): wave-uniform branches on the request's pointers; the
+        // per-pixel form is the uniform one's expression with B[ch, p] in the place of bg[ch]
+        if (a.bg_image != nullptr) {
+            a.out_color[pid] = fp.C[0] + fp.T * a.bg_image[pid];
+            a.out_color[N + pid] = fp.C[1] + fp.T * a.bg_image[N + pid];
+            a.out_color[2 * N + pid] = fp.C[2] + fp.T * a.bg_image[2 * N + pid];
+        } else {
+            a.out_color[pid] = fp.C[0] + fp.T * a.bg[0];
+            a.out_color[N + pid] = fp.C[1] + fp.T * a.bg[1];
+            a.out_color[2 * N + pid] = fp.C[2] + fp.T * a.bg[2];
+        }
+        if (a.out_alpha != nullptr) a.out_alpha[pid] = 1.0f - fp.T;
     }
 }
 // recording forwards, once per wave: a log that overflowed (a pixel with more records than the log's depth, a list too long for a

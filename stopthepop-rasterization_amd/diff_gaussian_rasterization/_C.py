@@ -45,9 +45,13 @@ _OPTIONAL_SYMBOLS = {
     "stp_set_backward_camera_grads": ([ctypes.c_void_p] * 4 + [ctypes.c_size_t], None),
     "stp_set_backward_absgrad": ([ctypes.c_void_p], None),
     "stp_set_backward_blend_stats": ([ctypes.c_void_p], None),
+    "stp_set_forward_background": ([ctypes.c_void_p] * 2, None),
+    "stp_set_backward_background": ([ctypes.c_void_p] * 3, None),
 }
 # the feature an optional export came with (the rebuild message names it)
-_SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blend_stats": "blend statistics"}
+_SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blend_stats": "blend statistics",
+                   "stp_set_forward_background": "the alpha output and per-pixel background",
+                   "stp_set_backward_background": "the alpha output and per-pixel background"}
 
 
 def _require(name: str):
@@ -332,23 +336,35 @@ def _records_log(d: dict) -> bool:
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, inv_viewprojmatrix, tan_fovx, tan_fovy, image_height, image_width,
-                        sh, degree, campos, prefiltered, settings_dict, render_depth, debug
+                        sh, degree, campos, prefiltered, settings_dict, render_depth, debug, alpha=False
                         ) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """== RasterizeGaussiansCUDA (reference rasterize_points.cu:43-138).
-    Returns (num_rendered, out_color (3,H,W), radii (P,) int32, geomBuffer, binningBuffer, imgBuffer)."""
+    Returns (num_rendered, out_color (3,H,W), radii (P,) int32, geomBuffer, binningBuffer, imgBuffer).
+
+    alpha=True (extension, include/stp_raster.h: stp_set_forward_background): one more tensor, LAST in the tuple: alpha = 1 - final_T,
+    (1,H,W) float32 (zeros for P == 0).  A `background` of shape exactly (3,H,W) is composed per pixel, out = C + final_T * background;
+    every other background is read as three floats.  Neither is available with render_depth."""
     if means3D.dim() != 2 or means3D.size(1) != 3:   # (the reference's first check, rasterize_points.cu:69-71)
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    return (_host or _native()).rasterize_gaussians(
+    if alpha or _per_pixel_background(background, image_height, image_width):
+        _require("stp_set_forward_background")
+    out = (_host or _native()).rasterize_gaussians(
         background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         inv_viewprojmatrix, tan_fovx, tan_fovy, int(image_height), int(image_width), sh, int(degree), campos, bool(prefiltered),
-        settings_dict, bool(render_depth), bool(debug), _records_log(settings_dict))
+        settings_dict, bool(render_depth), bool(debug), _records_log(settings_dict), bool(alpha))
+    return tuple(out) if alpha else tuple(out[:6])
+
+
+def _per_pixel_background(background, height, width) -> bool:
+    """A background of shape exactly (3, H, W) is a per-pixel one; every other is read as three floats."""
+    return isinstance(background, torch.Tensor) and tuple(background.shape) == (3, int(height), int(width))
 
 
 def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, tan_fovx, tan_fovy,
                                  pixel_colors, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                                  imageBuffer, settings_dict, debug, phases=3, partial=None, chunk=None, outputs=None,
-                                 camera_grads=False, absgrad=False, blend_stats=False):
+                                 camera_grads=False, absgrad=False, blend_stats=False, dL_dalpha=None, bg_grad=False):
     """== RasterizeGaussiansBackwardCUDA (reference rasterize_points.cu:140-232).
     Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
 
@@ -362,6 +378,12 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
 
     blend_stats=True (extension, include/stp_raster.h: stp_set_backward_blend_stats): one more tensor, LAST in the tuple (behind absgrad's):
     (P, 3) float32, per Gaussian the sum, the maximum and the count of its blend weights alpha * T over the pixels.  The same conditions.
+
+    dL_dalpha=(1,H,W) tensor (extension, include/stp_raster.h: stp_set_backward_background): the gradient of the forward's alpha output, which
+    joins the weight of final_T in every pixel's loss.  bg_grad=True: one more tensor, LAST in the tuple (behind the statistics):
+    dL/dbackground in the background's shape -- (3,) for a uniform background, (3,H,W) for a per-pixel one (a `background` of shape
+    exactly (3,H,W), which must be the forward's).  The (3,) sum runs in a fixed order: equal inputs give bit-equal results.  Both need the
+    render half (phases bit 0) and work with compact records; with phases=1 and bg_grad the result is (records, dL_dbackground).
 
     Extension for tile-row sharding (not in the reference): phases=1 runs only the render half and
     returns its per-Gaussian partial sums as the library's (P,16) gradient records (stp_raster.h);
@@ -380,12 +402,14 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
         _require("stp_set_backward_absgrad")
     if blend_stats:
         _require("stp_set_backward_blend_stats")
+    if dL_dalpha is not None or bg_grad or _per_pixel_background(background, dL_dout_color.shape[-2], dL_dout_color.shape[-1]):
+        _require("stp_set_backward_background")
     out = (_host or _native()).rasterize_gaussians_backward(
         background, means3D, radii, opacities, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         inv_viewprojmatrix, tan_fovx, tan_fovy, pixel_colors, dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer,
         imageBuffer, settings_dict, bool(debug), _records_log(settings_dict), int(phases), partial, None if outputs is None else list(outputs),
-        bool(camera_grads), bool(absgrad), bool(blend_stats))
-    return out[0] if (int(phases) & 3) == 1 else tuple(out)
+        bool(camera_grads), bool(absgrad), bool(blend_stats), dL_dalpha, bool(bg_grad))
+    return out[0] if (int(phases) & 3) == 1 and not bg_grad else tuple(out)
 
 
 def mark_visible(means3D, viewmatrix, projmatrix) -> torch.Tensor:

@@ -40,6 +40,11 @@ def cpu_deep_copy_tuple(input_tuple):
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings):
     rs = raster_settings
+    if torch.is_grad_enabled() and isinstance(rs.bg, torch.Tensor) and rs.bg.requires_grad:
+        # a learnable background: bg -- and the camera tensors, which get their gradients here too where they require them -- become explicit
+        # inputs of a third Function
+        return _RasterizeGaussiansBackground.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                                   rs.bg, rs.viewmatrix, rs.projmatrix, rs.campos, raster_settings)
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (rs.viewmatrix, rs.projmatrix, rs.campos)):
         # camera gradients (pose refinement): the camera tensors become explicit inputs of a second Function
         return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -49,10 +54,21 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
 
 
 def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos, rs,
-                  save_camera=False):
-    """The forward both autograd Functions share (the camera tensors are rs's own, or the camera Function's explicit inputs, which
-    save_camera=True saves for the backward behind the twelve tensors both Functions save)."""
+                  save_camera=False, bg=None):
+    """The forward the autograd Functions share (the camera tensors are rs's own, or the camera Function's explicit inputs, which
+    save_camera=True saves for the backward behind the twelve tensors every Function saves; bg: the background Function's explicit input,
+    saved behind them)."""
     sdict = rs.settings.to_dict()
+    save_bg = bg is not None
+    if bg is None:
+        bg = rs.bg
+    # alpha output and per-pixel background (extensions; include/stp_raster.h: stp_set_forward_background): settings._alpha = True adds
+    # alpha = 1 - final_T, (1, H, W), as a third, differentiable output; a bg of shape exactly (3, H, W) is composed per pixel
+    ctx.alpha = bool(sdict.get("_alpha"))
+    if rs.render_depth and (ctx.alpha or save_bg or _C._per_pixel_background(bg, rs.image_height, rs.image_width)):
+        # (save_bg: a bg that requires grad -- final_T * dL_dout is not the gradient of that image)
+        raise RuntimeError("the alpha output (settings._alpha), a per-pixel background and a background that requires grad are not available "
+                           "with render_depth=True: the depth visualisation's image is not C + T * background")
     ctx.log_lease = None
     # absgrad (extension, settings._absgrad = True; include/stp_raster.h: stp_set_backward_absgrad): the backward also leaves the per-Gaussian
     # sums of |each pixel's contribution to dL/dmean2D| in means2D.absgrad -- the densification statistic of AbsGS / gsplat.  The tensor
@@ -89,20 +105,21 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
             sdict["_backward_mode"] = "resort"
     ctx.settings_dict = sdict
     # positional layout of _C.rasterize_gaussians (22 arguments)
-    args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+    args = (bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             viewmatrix, projmatrix, rs.inv_viewprojmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
             rs.image_width, sh, rs.sh_degree, campos, rs.prefiltered, sdict, rs.render_depth,
             rs.debug)
+    kw = {"alpha": True} if ctx.alpha else {}   # (the alpha tensor comes last)
     if rs.debug:
         cpu_args = cpu_deep_copy_tuple(args)  # snapshot before anything can corrupt them
         try:
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args)
+            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, *extra = _C.rasterize_gaussians(*args, **kw)
         except Exception as ex:
             torch.save(cpu_args, "snapshot_fw.dump")
             print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
             raise ex
     else:
-        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args)
+        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, *extra = _C.rasterize_gaussians(*args, **kw)
 
     if ctx.log_lease is not None:   # the library chose the log's depth for this frame: account what the buffer really holds
         ctx.log_lease.resize(_C.blend_log_bytes(rs.image_width, rs.image_height, depth=_C.blend_log_depth(imgBuffer)))
@@ -111,27 +128,36 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
     ctx.img_generation = _C.scratch_generation(imgBuffer)
     ctx.bin_generation = _C.scratch_generation(binningBuffer)
     ctx.save_for_backward(colors_precomp, means3D, opacities, scales, rotations, cov3Ds_precomp, radii, sh, color,
-                          geomBuffer, binningBuffer, imgBuffer, *((viewmatrix, projmatrix, campos) if save_camera else ()))
+                          geomBuffer, binningBuffer, imgBuffer, *((viewmatrix, projmatrix, campos) if save_camera else ()),
+                          *((bg,) if save_bg else ()))
     # radii is an integer output: without these two lines autograd materialises a (P,) zero "gradient" for it in
     # every backward (a 4 MB fill kernel per step at 1 M Gaussians)
     ctx.mark_non_differentiable(radii)
     ctx.set_materialize_grads(False)
-    return color, radii
+    return (color, radii, extra[0]) if ctx.alpha else (color, radii)
 
 
-def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_grads=False):
-    """The backward both autograd Functions share: the eight Gaussian gradients of _C.rasterize_gaussians_backward (+ the three camera
-    gradients with camera_grads=True)."""
+def _grad_alpha(ctx, rest):
+    """The gradient of the alpha output among a backward's trailing arguments (None: alpha took no part in the loss, or there is none)."""
+    return rest[0] if ctx.alpha and rest else None
+
+
+def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_grads=False, grad_alpha=None, bg=None):
+    """The backward the autograd Functions share: the eight Gaussian gradients of _C.rasterize_gaussians_backward (+ the three camera
+    gradients with camera_grads=True, + dL/dbg last with bg, the background Function's saved input)."""
     num_rendered = ctx.num_rendered
     rs = ctx.raster_settings
     (colors_precomp, means3D, opacities, scales, rotations, cov3Ds_precomp, radii, sh, color, geomBuffer,
      binningBuffer, imgBuffer) = ctx.saved_tensors[:12]
     _C.check_scratch(imgBuffer, ctx.img_generation)
     _C.check_scratch(binningBuffer, ctx.bin_generation)
-    if grad_out_color is None:  # (set_materialize_grads(False): cannot happen while the image is the only differentiable output)
+    if grad_out_color is None:  # (set_materialize_grads(False): a loss on the alpha output alone)
         grad_out_color = torch.zeros_like(color)
+    bg_grad = bg is not None
+    if bg is None:
+        bg = rs.bg
     # positional layout of _C.rasterize_gaussians_backward (25 arguments)
-    args = (rs.bg, means3D, radii, opacities, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+    args = (bg, means3D, radii, opacities, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             viewmatrix, projmatrix, rs.inv_viewprojmatrix, rs.tanfovx, rs.tanfovy, color, grad_out_color, sh,
             rs.sh_degree, campos, geomBuffer, num_rendered, binningBuffer, imgBuffer, ctx.settings_dict,
             rs.debug)
@@ -140,6 +166,10 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
         kw["absgrad"] = True
     if ctx.blend_stats_target is not None:
         kw["blend_stats"] = True
+    if grad_alpha is not None:
+        kw["dL_dalpha"] = grad_alpha
+    if bg_grad:
+        kw["bg_grad"] = True
     if rs.debug:
         cpu_args = cpu_deep_copy_tuple(args)
         try:
@@ -153,14 +183,22 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
     _C.release_scratch(imgBuffer); _C.release_scratch(binningBuffer)  # the blend log goes back to the library's free list
     if ctx.log_lease is not None:
         ctx.log_lease.release()
-    # (the extra tensors come last, the statistics behind absgrad's; assigned, not accumulated: the trainer keeps its own statistic)
+    # (the extra tensors come last, the statistics behind absgrad's, dL/dbg behind both; assigned, not accumulated: the trainer keeps its own statistic)
+    grad_bg = None
+    if bg_grad:
+        grad_bg = out[-1]
+        out = out[:-1]
+        if grad_bg.shape != bg.shape:   # (a uniform background in another shape than (3,): its first three values are the colour)
+            full = torch.zeros(bg.numel(), dtype=grad_bg.dtype, device=grad_bg.device)
+            full[:3] = grad_bg
+            grad_bg = full.reshape(bg.shape)
     if ctx.blend_stats_target is not None:
         ctx.blend_stats_target.blend_stats = out[-1]
         out = out[:-1]
     if ctx.absgrad_target is not None:
         ctx.absgrad_target.absgrad = out[-1]
         out = out[:-1]
-    return out
+    return out + (grad_bg,) if bg_grad else out
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -172,10 +210,10 @@ class _RasterizeGaussians(torch.autograd.Function):
                              rs.projmatrix, rs.campos, rs)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _):
+    def backward(ctx, grad_out_color, _, *rest):   # (rest: the alpha output's gradient, with settings._alpha)
         rs = ctx.raster_settings
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _backward_body(ctx, grad_out_color, rs.viewmatrix, rs.projmatrix, rs.campos)
+         grad_rotations) = _backward_body(ctx, grad_out_color, rs.viewmatrix, rs.projmatrix, rs.campos, grad_alpha=_grad_alpha(ctx, rest))
         # one gradient per forward input, in forward's order
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                 grad_cov3Ds_precomp, None)
@@ -195,13 +233,37 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
                              campos, raster_settings, save_camera=True)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _):
+    def backward(ctx, grad_out_color, _, *rest):
         viewmatrix, projmatrix, campos = ctx.saved_tensors[12:15]
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations, grad_view, grad_proj, grad_campos) = _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, True)
+         grad_rotations, grad_view, grad_proj, grad_campos) = _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, True,
+                                                                             grad_alpha=_grad_alpha(ctx, rest))
         grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                  grad_cov3Ds_precomp, grad_view, grad_proj, grad_campos)
         # None for every input that does not require grad (frozen Gaussians: the camera's gradients only)
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad)) + (None,)
+
+
+class _RasterizeGaussiansBackground(torch.autograd.Function):
+    """_RasterizeGaussians with bg as an explicit input that gets a gradient (include/stp_raster.h: stp_set_backward_background): (3,) for a
+    uniform background, (3, H, W) for a per-pixel one.  rasterize_gaussians() routes here only while grad mode is on and rs.bg requires
+    grad.  viewmatrix, projmatrix and campos are explicit inputs too and get the camera gradients where they require grad."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, bg, viewmatrix, projmatrix, campos,
+                raster_settings):
+        return _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix,
+                             campos, raster_settings, save_camera=True, bg=bg)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _, *rest):
+        viewmatrix, projmatrix, campos, bg = ctx.saved_tensors[12:16]
+        camera_grads = any(ctx.needs_input_grad[9:12])
+        out = _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_grads, grad_alpha=_grad_alpha(ctx, rest), bg=bg)
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales, grad_rotations) = out[:8]
+        grad_view, grad_proj, grad_campos = out[8:11] if camera_grads else (None, None, None)
+        grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
+                 grad_cov3Ds_precomp, out[-1], grad_view, grad_proj, grad_campos)
         return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad)) + (None,)
 
 
@@ -285,7 +347,9 @@ class ExtendedSettings(_Settable):
                 # object for means2D.absgrad, the per-Gaussian sums of |each pixel's contribution to dL/dmean2D|)
                 **({"_absgrad": True} if getattr(self, "_absgrad", False) else {}),
                 # (the same for `settings._blend_stats = True`: means2D.blend_stats, per Gaussian the sum, max and count of its blend weights)
-                **({"_blend_stats": True} if getattr(self, "_blend_stats", False) else {})}
+                **({"_blend_stats": True} if getattr(self, "_blend_stats", False) else {}),
+                # (and for `settings._alpha = True`: the rasterizer returns (color, radii, alpha), alpha = 1 - final_T a differentiable output)
+                **({"_alpha": True} if getattr(self, "_alpha", False) else {})}
 
     def to_json(self):
         return json.dumps(self.to_dict())

@@ -248,6 +248,14 @@ class _ShardedRasterize(torch.autograd.Function):
             raise RuntimeError("blend statistics (settings._blend_stats) are not available with tile-row sharding: the compact (P, 9) "
                                "gradient record that crosses the links between the two halves of the backward has no room for the three "
                                "extra terms")
+        bg = rs.bg
+        if (sdict.get("_alpha") or _C._per_pixel_background(bg, rs.image_height, rs.image_width)
+                or (isinstance(bg, torch.Tensor) and bg.requires_grad)):
+            # the strips exchange colour rows only: a rank's alpha rows, its rows of a per-pixel background and its share of a background
+            # gradient would each need an exchange of their own, which is left out deliberately
+            raise RuntimeError("the alpha output (settings._alpha), a per-pixel background and a background that requires grad are not "
+                               "available with tile-row sharding: the strips' alpha and background rows are not exchanged between the ranks; "
+                               "render on one GPU")
         y0, y1 = parts[rank]
         n_rows = tile_rows(rs.image_height)
         rows = (y0, y1) if y1 > y0 else (n_rows, n_rows)   # (an empty block; (0, 0) would mean "all rows" to the library)
