@@ -3,7 +3,7 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--optimizer adam|sparse_adam]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
@@ -22,7 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "stopthepop-rasterization_amd"))
 from diff_gaussian_rasterization import (CullingSettings, ExtendedSettings, GaussianRasterizationSettings,  # noqa: E402
-                                         GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, scenes)
+                                         GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, SparseGaussianAdam, scenes)
 
 
 def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, scaling_modifier: float = 1.0,
@@ -101,6 +101,8 @@ def main(argv=None):
                     help="after training, a pruning pass over N views: the largest blend weight of every Gaussian over the views, then a threshold")
     ap.add_argument("--mask-weight", type=float, default=0.0, metavar="W",
                     help="add W * mean |alpha - target alpha| to the loss: mask supervision on the rasterizer's alpha output")
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "sparse_adam"],
+                    help="sparse_adam: SparseGaussianAdam, one fused launch that steps only the Gaussians visible in the frame (INTEGRATION.md section 3i)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
@@ -120,8 +122,13 @@ def main(argv=None):
     with torch.no_grad():
         model._features.mul_(0.3)
         model._opacity.sub_(1.0)
-    opt = torch.optim.Adam([{"params": [model._features], "lr": 2e-2}, {"params": [model._opacity], "lr": 5e-2},
-                            {"params": [model._xyz, model._scaling, model._rotation], "lr": 0.0}])
+    if args.optimizer == "sparse_adam":   # one group per tensor, as the trainers' training_setup() builds them
+        opt = SparseGaussianAdam([{"params": [model._features], "lr": 2e-2, "name": "f"}, {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
+                                  {"params": [model._xyz], "lr": 0.0, "name": "xyz"}, {"params": [model._scaling], "lr": 0.0, "name": "scaling"},
+                                  {"params": [model._rotation], "lr": 0.0, "name": "rotation"}], lr=0.0, eps=1e-15)
+    else:
+        opt = torch.optim.Adam([{"params": [model._features], "lr": 2e-2}, {"params": [model._opacity], "lr": 5e-2},
+                                {"params": [model._xyz, model._scaling, model._rotation], "lr": 0.0}])
     train_cfg = splat_config(args.config)
     train_cfg._alpha = masked
     train_cfg._absgrad = args.absgrad   # (a request on the settings object; the depth rendering below keeps the plain settings: it refuses it)
@@ -142,7 +149,10 @@ def main(argv=None):
         stat_signed[vis] += grad2d[vis, :2].norm(dim=-1)
         if args.absgrad:   # assigned by every backward, never accumulated: the running sum is the trainer's
             stat_abs[vis] += out["viewspace_points"].absgrad[vis, :2].norm(dim=-1)
-        opt.step()
+        if args.optimizer == "sparse_adam":   # the forward's radii are the visibility: no mask tensor on the way
+            opt.step(out["radii"], model.get_xyz.shape[0])
+        else:
+            opt.step()
         last = float(loss.detach())
         first = last if first is None else first
         if it % 10 == 0 or it == args.iters - 1:

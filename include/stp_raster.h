@@ -276,6 +276,25 @@ void stp_set_backward_background(const float* bg_image /* the forward's, or NULL
 int stp_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      uint8_t* present, void* stream);
 
+/* Extension (not in the reference): the fused sparse Adam step of 3DGS trainers (the SparseGaussianAdam of the accelerated rasterizer, a
+   trainer's --optimizer_type sparse_adam).  Tensor k holds numel_k = N * M_k floats, row i (M_k consecutive floats) belonging to Gaussian i.
+   For every tensor, every row i < N that is visible and every element of it, in float32:
+       m <- beta1 * m + (1 - beta1) * g      v <- beta2 * v + (1 - beta2) * g * g      p <- p - lr * m / (sqrt(v) + eps)
+   with 1 - beta formed in float32; no bias correction, no weight decay, no amsgrad.  Elements of invisible rows keep param, exp_avg and
+   exp_avg_sq bit for bit and their grad is never used (a NaN there changes nothing); non-finite gradients of visible rows propagate as the
+   expressions say.  `visible` is a device pointer read as it is: visible_kind 0 = N bytes (bool / uint8), non-zero = visible;
+   visible_kind 1 = N int32 (the radii a forward returned), > 0 = visible.  lr and eps are per tensor.  All pointers are device pointers to
+   contiguous float32 data; 16-byte aligned ones are streamed 16 bytes per lane, others one float at a time.  One kernel launch updates up
+   to eight tensors (more tensors: further launches), without atomics: equal inputs give equal bits.
+   Returns the number of kernel launches made (>= 0; 0 for N == 0, n_tensors == 0 or all numel == 0), or a negative StpStatus with the
+   reason in the last-error text.  Refused BEFORE anything is launched, so that nothing is half updated (STP_ERR_INVALID_ARGUMENT): a negative
+   count, a numel that N does not divide, numel >= 2^31, a null pointer of a tensor with elements or a null `visible`, an unknown
+   visible_kind.  A plain call: no host synchronisation, no allocation, no per-thread request state.  lr travels in the kernel arguments: a step
+   captured in a graph replays the lr it was captured with. */
+typedef struct { float* param; const float* grad; float* exp_avg; float* exp_avg_sq; long long numel; float lr, eps; } StpAdamTensor;
+int stp_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind /* 0: N bytes, non-zero = visible; 1: N int32, > 0 = visible */,
+                    float beta1, float beta2, void* stream);
+
 /* Sizes of the three scratch buffers (the reference's `required<State>()`, rasterizer_impl.h:68-75). */
 size_t stp_geometry_buffer_size(int P, const StpSettings* settings);
 size_t stp_binning_buffer_size(int R);

@@ -71,6 +71,7 @@ struct Api {
     decltype(&stp_set_backward_blend_stats) set_backward_blend_stats = nullptr;
     decltype(&stp_set_forward_background) set_forward_background = nullptr;
     decltype(&stp_set_backward_background) set_backward_background = nullptr;
+    decltype(&stp_sparse_adam) sparse_adam = nullptr;
 } g_api;
 
 int load_library(const std::string& path)
@@ -94,6 +95,7 @@ int load_library(const std::string& path)
     a.set_backward_blend_stats = reinterpret_cast<decltype(a.set_backward_blend_stats)>(dlsym(h, "stp_set_backward_blend_stats"));
     a.set_forward_background = reinterpret_cast<decltype(a.set_forward_background)>(dlsym(h, "stp_set_forward_background"));
     a.set_backward_background = reinterpret_cast<decltype(a.set_backward_background)>(dlsym(h, "stp_set_backward_background"));
+    a.sparse_adam = reinterpret_cast<decltype(a.sparse_adam)>(dlsym(h, "stp_sparse_adam"));
     if (a.abi_version() != STP_ABI_VERSION) throw std::runtime_error(path + ": ABI version mismatch");
     g_api = a; // (a previously loaded library stays mapped: buffers of its forwards may still be in flight)
     return a.abi_version();
@@ -510,6 +512,48 @@ torch::Tensor mark_visible(const torch::Tensor& means3D, const torch::Tensor& vi
     return present;
 }
 
+// == the fused sparse Adam step (extension, include/stp_raster.h: stp_sparse_adam; the step of SparseGaussianAdam in __init__.py): one library call
+// for all quadruples (param, grad, exp_avg, exp_avg_sq), on the caller's current stream.  visible: bool / uint8 (non-zero = visible) or the
+// int32 radii of the forward (> 0 = visible), N elements, read as it is.  Returns the kernel launches the library made.
+int sparse_adam(const std::vector<torch::Tensor>& params, const std::vector<torch::Tensor>& grads, const std::vector<torch::Tensor>& exp_avgs,
+                const std::vector<torch::Tensor>& exp_avg_sqs, const torch::Tensor& visible, const std::vector<double>& lrs, const std::vector<double>& epss,
+                const double beta1, const double beta2, const int64_t N)
+{
+    need_library();
+    if (!g_api.sparse_adam)
+        throw std::runtime_error("sparse_adam: the loaded libstp_raster.so does not export stp_sparse_adam (a library built before the sparse Adam step): rebuild it");
+    const size_t n = params.size();
+    TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n && lrs.size() == n && epss.size() == n,
+                "sparse_adam: params, grads, exp_avgs, exp_avg_sqs, lrs and epss must have one entry per tensor");
+    TORCH_CHECK(N >= 0 && N < (1ll << 31), "sparse_adam: N out of range");
+    TORCH_CHECK(visible.defined() && visible.is_cuda(), "diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
+    const torch::Device dev = visible.device();
+    const auto vt = visible.scalar_type();
+    TORCH_CHECK(vt == torch::kBool || vt == torch::kByte || vt == torch::kInt32, "sparse_adam: visible must be bool, uint8 or int32 (radii), got ", vt);
+    TORCH_CHECK(visible.numel() == N && visible.is_contiguous(), "sparse_adam: visible must be contiguous with N = ", N, " elements, got ", visible.numel());
+    std::vector<StpAdamTensor> table(n);
+    for (size_t k = 0; k < n; k++) {
+        const torch::Tensor* quad[4] = {&params[k], &grads[k], &exp_avgs[k], &exp_avg_sqs[k]};
+        static const char* const names[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
+        for (int j = 0; j < 4; j++) {
+            const torch::Tensor& t = *quad[j];
+            TORCH_CHECK(t.defined(), "sparse_adam: tensor ", k, ": ", names[j], " is undefined");
+            TORCH_CHECK(t.is_cuda(), "diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
+            TORCH_CHECK(t.device() == dev, "expected all tensors on ", dev, ", got one on ", t.device());
+            TORCH_CHECK(t.scalar_type() == torch::kFloat32, "expected float32 tensor, got ", t.scalar_type());
+            TORCH_CHECK(t.is_contiguous(), "sparse_adam: tensor ", k, ": ", names[j], " must be contiguous (it is updated in place)");
+            TORCH_CHECK(t.sizes() == params[k].sizes(), "sparse_adam: tensor ", k, ": ", names[j], " has shape ", t.sizes(), ", param has ", params[k].sizes());
+        }
+        table[k] = StpAdamTensor{params[k].data_ptr<float>(), grads[k].data_ptr<float>(), exp_avgs[k].data_ptr<float>(), exp_avg_sqs[k].data_ptr<float>(),
+                                 (long long)params[k].numel(), (float)lrs[k], (float)epss[k]};
+    }
+    const c10::hip::HIPGuard guard(dev.index());
+    const int rc = g_api.sparse_adam((int)n, table.data(), (int)N, visible.data_ptr(), vt == torch::kInt32 ? 1 : 0, (float)beta1, (float)beta2,
+                                     (void*)c10::hip::getCurrentHIPStream(dev.index()).stream());
+    if (rc < 0) raise_last(rc);
+    return rc;
+}
+
 // ---- scratch pool surface -------------------------------------------------------------------------------------------
 int64_t scratch_generation(const torch::Tensor& buf) // token the autograd function keeps with a pooled buffer (0 for ordinary ones)
 {
@@ -575,6 +619,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("rasterize_gaussians", &rasterize_gaussians);
     m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward);
     m.def("mark_visible", &mark_visible);
+    m.def("sparse_adam", &sparse_adam);
     m.def("scratch_generation", &scratch_generation);
     m.def("check_scratch", &check_scratch);
     m.def("release_scratch", &release_scratch);

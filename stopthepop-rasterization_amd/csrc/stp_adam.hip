@@ -1,0 +1,191 @@
+// stp_adam.hip -- the fused sparse Adam step of stp_sparse_adam (no counterpart in the reference; the semantics are those of the
+// SparseGaussianAdam of the accelerated 3DGS rasterizer): for every element of every Gaussian (row) that is visible in the frame
+//     m <- b1 * m + (1 - b1) * g      v <- b2 * v + (1 - b2) * g * g      p <- p - lr * m / (sqrt(v) + eps)
+// in float32, without bias correction; the elements of invisible rows are neither read nor written.
+//
+// One launch serves up to ADAM_MAX_TENSORS tensors.  The kernel arguments carry a table of descriptors by value; a tensor of numel
+// elements owns ceil(numel / ADAM_UNIT) consecutive work units, a workgroup is one unit and finds its tensor by a wave-uniform search
+// for the last descriptor whose first unit is not behind its own (blockIdx.x is in SGPRs: the search is scalar code).
+//
+// Streaming shape.  p, g, m and v of a unit are read and p, m, v written with 16 bytes per lane where all four pointers are 16-byte
+// aligned (every tensor torch allocates); a thread owns the 16-byte pieces t, t + 256, t + 512 and t + 768 of its unit, so that a wave's
+// access is 1 KiB contiguous per stream, and the last numel % 4 elements of a tensor belong to the first threads of its last unit.
+// Tensors with an unaligned pointer take the same units one float per lane and access.  Every piece has exactly one owner; a piece that
+// is only partly visible is written back whole, the lanes of its invisible rows carrying the bits that were loaded.  A piece without a
+// visible element is skipped before its loads are issued (exec-masked: a wave whose pieces are all invisible branches over loads, maths
+// and stores, and has read nothing but visibility).  No atomics, no LDS, no scratch; equal inputs give equal bits.
+//
+// Row index.  The row of element e is e / M (M = numel / N floats per Gaussian).  It is formed with a HOST-COMPUTED MULTIPLIER
+// (stp_adam_div.h: mulhi(e, ceil(2^(32+s) / M)) >> s with 2^s < M <= 2^(s+1), exact for every e < 2^31 -- the proof is in that header,
+// and tests/cpp/adam_div_check.cpp holds it against e / M), once per 16-byte piece; the three following elements advance (row, e % M)
+// by increment and compare.  No integer division sequence on the device.  Chosen over instantiations per M because one kernel then
+// serves every row width -- a trainer's feature tensors are (P, 15, 3) today and anything tomorrow -- at the cost of one v_mul_hi_u32
+// per 16 bytes of each of seven streams.
+//
+// Visibility is read where the trainer has it: N bytes (bool / uint8, non-zero = visible) or the N int32 radii of the forward (> 0 =
+// visible).  A lane reads the entry of its piece's first row and again only where the row changes inside the piece.
+//
+// sqrt and the division are the correctly rounded ones (the kernel has about 180 VALU slots per element at the HBM rate and uses a
+// fraction): a denormal v or denominator is handled like any other value.
+#include "stp_internal.h"
+#include "stp_adam_div.h"
+
+namespace stp {
+
+namespace {
+
+constexpr int ADAM_BLOCK = 256;
+constexpr int ADAM_PIECES = 4;                              // 16-byte pieces a thread owns in its unit
+constexpr uint32_t ADAM_UNIT = ADAM_BLOCK * ADAM_PIECES * 4; // elements of a work unit (4096: 16 KiB of each stream)
+constexpr int ADAM_MAX_TENSORS = 8;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct AdamDesc {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    uint32_t M, numel;
+    float lr, eps;
+    uint32_t first_unit; // of this tensor among the launch's units
+    uint32_t wide;       // 16-byte accesses (all four pointers aligned)
+    AdamDivisor div;     // e / M
+};
+struct AdamTable {
+    AdamDesc t[ADAM_MAX_TENSORS];
+};
+
+template <int KIND> __device__ __forceinline__ bool row_visible(const void* __restrict__ visible, uint32_t row)
+{
+    if constexpr (KIND == 0) return static_cast<const uint8_t*>(visible)[row] != 0;
+    else return static_cast<const int32_t*>(visible)[row] > 0;
+}
+
+struct AdamCoef { float b1, omb1, b2, omb2, lr, eps; };
+
+// one element's step (fused multiply-adds written out, so that the result does not hang on the compiler's contraction choices)
+__device__ __forceinline__ void adam_element(float& p, const float g, float& m, float& v, const AdamCoef& c)
+{
+    m = __fmaf_rn(c.b1, m, c.omb1 * g);
+    v = __fmaf_rn(c.omb2 * g, g, c.b2 * v);
+    p = p - (c.lr * m) / (__fsqrt_rn(v) + c.eps);
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(ADAM_BLOCK) sparse_adam_kernel(const AdamTable table, const int n_tensors, const void* __restrict__ visible,
+                                                                 const float b1, const float b2)
+{
+    // wave-uniform search: the last tensor whose first unit is <= this workgroup's
+    const uint32_t unit = blockIdx.x;
+    int ti = 0;
+#pragma unroll
+    for (int i = 1; i < ADAM_MAX_TENSORS; i++)
+        if (i < n_tensors && unit >= table.t[i].first_unit) ti = i;
+    const AdamDesc& d = table.t[ti];
+    const uint32_t M = d.M, numel = d.numel;
+    const AdamDivisor div = d.div;
+    const AdamCoef c = {b1, 1.0f - b1, b2, 1.0f - b2, d.lr, d.eps};
+    float* __restrict__ const P = d.p;
+    const float* __restrict__ const G = d.g;
+    float* __restrict__ const Mo = d.m;
+    float* __restrict__ const V = d.v;
+    const uint32_t base = (unit - d.first_unit) * ADAM_UNIT; // < numel < 2^31
+    const uint32_t tid = threadIdx.x;
+
+    if (d.wide) {
+        const uint32_t numel4 = numel & ~3u;
+#pragma unroll
+        for (int k = 0; k < ADAM_PIECES; k++) {
+            const uint32_t e0 = base + 4u * (tid + (uint32_t)k * ADAM_BLOCK);
+            if (e0 >= numel4) break; // (e0 + 3 < numel4 <= numel: whole pieces only)
+            uint32_t row = adam_div(e0, div), rem = e0 - row * M;
+            bool vis[4];
+            vis[0] = row_visible<KIND>(visible, row);
+#pragma unroll
+            for (int j = 1; j < 4; j++) {
+                vis[j] = vis[j - 1];
+                if (++rem == M) { // the next row begins inside the piece
+                    rem = 0;
+                    row++;
+                    vis[j] = row_visible<KIND>(visible, row);
+                }
+            }
+            if (!(vis[0] | vis[1] | vis[2] | vis[3])) continue; // nothing visible: no load, no store
+            const uint32_t q = e0 >> 2;
+            f32x4 p = reinterpret_cast<f32x4*>(P)[q], m = reinterpret_cast<f32x4*>(Mo)[q], v = reinterpret_cast<f32x4*>(V)[q];
+            const f32x4 g = reinterpret_cast<const f32x4*>(G)[q];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                float pj = p[j], mj = m[j], vj = v[j];
+                adam_element(pj, g[j], mj, vj, c);
+                p[j] = vis[j] ? pj : p[j]; // (an invisible lane keeps the bits that were loaded, whatever its g holds)
+                m[j] = vis[j] ? mj : m[j];
+                v[j] = vis[j] ? vj : v[j];
+            }
+            reinterpret_cast<f32x4*>(P)[q] = p;
+            reinterpret_cast<f32x4*>(Mo)[q] = m;
+            reinterpret_cast<f32x4*>(V)[q] = v;
+        }
+        // the tensor's last numel % 4 elements: threads 0 .. 2 of its last unit
+        const uint32_t e = numel4 + tid;
+        if (e < numel && numel - base <= ADAM_UNIT) {
+            if (row_visible<KIND>(visible, adam_div(e, div))) {
+                float pj = P[e], mj = Mo[e], vj = V[e];
+                adam_element(pj, G[e], mj, vj, c);
+                P[e] = pj;
+                Mo[e] = mj;
+                V[e] = vj;
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int k = 0; k < ADAM_PIECES * 4; k++) {
+            const uint32_t e = base + tid + (uint32_t)k * ADAM_BLOCK;
+            if (e >= numel) break;
+            if (!row_visible<KIND>(visible, adam_div(e, div))) continue;
+            float pj = P[e], mj = Mo[e], vj = V[e];
+            adam_element(pj, G[e], mj, vj, c);
+            P[e] = pj;
+            Mo[e] = mj;
+            V[e] = vj;
+        }
+    }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+} // namespace
+
+int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind, float beta1, float beta2,
+                       hipStream_t st, hipError_t* err)
+{
+    *err = hipSuccess;
+    int launches = 0;
+    for (int next = 0; next < n_tensors;) {
+        AdamTable table{};
+        int n = 0;
+        uint32_t units = 0;
+        for (; next < n_tensors && n < ADAM_MAX_TENSORS; next++) {
+            const StpAdamTensor& t = tensors[next];
+            if (t.numel == 0) continue;
+            AdamDesc& d = table.t[n++];
+            d.p = t.param; d.g = t.grad; d.m = t.exp_avg; d.v = t.exp_avg_sq;
+            d.numel = (uint32_t)t.numel;
+            d.M = (uint32_t)(t.numel / N);
+            d.lr = t.lr; d.eps = t.eps;
+            d.first_unit = units;
+            d.wide = aligned16(t.param) && aligned16(t.grad) && aligned16(t.exp_avg) && aligned16(t.exp_avg_sq);
+            d.div = adam_divisor(d.M);
+            units += (d.numel + ADAM_UNIT - 1) / ADAM_UNIT; // <= 2^19 per tensor
+        }
+        if (n == 0) break;
+        if (visible_kind == 0) hipLaunchKernelGGL(sparse_adam_kernel<0>, dim3(units), dim3(ADAM_BLOCK), 0, st, table, n, visible, beta1, beta2);
+        else hipLaunchKernelGGL(sparse_adam_kernel<1>, dim3(units), dim3(ADAM_BLOCK), 0, st, table, n, visible, beta1, beta2);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return launches; }
+        launches++;
+    }
+    return launches;
+}
+
+} // namespace stp

@@ -1203,4 +1203,31 @@ int stp_mark_visible(int P, const float* means3D, const float* viewmatrix, const
     return 0;
 }
 
+int stp_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind, float beta1, float beta2, void* stream)
+{
+    // everything is checked before the first launch: a refused call has updated nothing
+    if (n_tensors < 0 || N < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_sparse_adam: negative count");
+    if (visible_kind != 0 && visible_kind != 1)
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_sparse_adam: unknown visible_kind " + std::to_string(visible_kind) + " (0: N bytes, 1: N int32 radii)");
+    if (n_tensors > 0 && !tensors) return fail(STP_ERR_INVALID_ARGUMENT, "stp_sparse_adam: null tensor table");
+    bool any = false;
+    for (int k = 0; k < n_tensors; k++) {
+        const StpAdamTensor& t = tensors[k];
+        const std::string which = "stp_sparse_adam: tensor " + std::to_string(k);
+        if (t.numel < 0) return fail(STP_ERR_INVALID_ARGUMENT, which + ": negative numel");
+        if (t.numel >= (1ll << 31)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": numel " + std::to_string(t.numel) + " >= 2^31");
+        if (t.numel == 0) continue;
+        if (N == 0 || t.numel % N != 0)
+            return fail(STP_ERR_INVALID_ARGUMENT, which + ": numel " + std::to_string(t.numel) + " is not a multiple of N = " + std::to_string(N));
+        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer");
+        any = true;
+    }
+    if (!any) return 0;
+    if (!visible) return fail(STP_ERR_INVALID_ARGUMENT, "stp_sparse_adam: null visible");
+    hipError_t e;
+    const int launches = launch_sparse_adam(n_tensors, tensors, N, visible, visible_kind, beta1, beta2, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "sparse_adam launch");
+    return launches;
+}
+
 } // extern "C"

@@ -234,6 +234,10 @@ size_t camera_grad_workspace_bytes(int P);
 // sums the per-workgroup rows the CAM kernel wrote (none for P == 0) into the three outputs; launch_preprocess_backward calls it itself
 hipError_t launch_camera_grad_finalize(int P, const CameraGradRequest& cam, hipStream_t st);
 hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t st);
+// the fused sparse Adam step (stp_adam.hip) over tensors stp_sparse_adam has validated: one launch per eight tensors with elements; returns
+// the launches made, *err = the launch error that ended them early (or hipSuccess)
+int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind, float beta1, float beta2,
+                       hipStream_t st, hipError_t* err);
 
 uint32_t higher_msb(uint32_t n);
 

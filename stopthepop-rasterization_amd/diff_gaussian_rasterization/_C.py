@@ -47,11 +47,14 @@ _OPTIONAL_SYMBOLS = {
     "stp_set_backward_blend_stats": ([ctypes.c_void_p], None),
     "stp_set_forward_background": ([ctypes.c_void_p] * 2, None),
     "stp_set_backward_background": ([ctypes.c_void_p] * 3, None),
+    "stp_sparse_adam": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
+                        ctypes.c_int),
 }
 # the feature an optional export came with (the rebuild message names it)
 _SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blend_stats": "blend statistics",
                    "stp_set_forward_background": "the alpha output and per-pixel background",
-                   "stp_set_backward_background": "the alpha output and per-pixel background"}
+                   "stp_set_backward_background": "the alpha output and per-pixel background",
+                   "stp_sparse_adam": "the sparse Adam step"}
 
 
 def _require(name: str):
@@ -415,6 +418,24 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
 def mark_visible(means3D, viewmatrix, projmatrix) -> torch.Tensor:
     """== markVisible (reference rasterize_points.cu:234-253)."""
     return (_host or _native()).mark_visible(means3D, viewmatrix, projmatrix)
+
+
+def sparse_adam(params, grads, exp_avgs, exp_avg_sqs, visible, lrs, epss, beta1, beta2, N) -> int:
+    """The fused sparse Adam step (extension, include/stp_raster.h: stp_sparse_adam) of all the quadruples (param, grad, exp_avg, exp_avg_sq)
+    in ONE library call on the current stream: rows i < N with visible[i] take  m <- b1 m + (1 - b1) g,  v <- b2 v + (1 - b2) g g,
+    p <- p - lr m / (sqrt(v) + eps)  in place, every other row keeps its bits.  visible: bool / uint8 (non-zero = visible) or the int32 radii
+    of the forward (> 0 = visible), N elements; lrs / epss: one value per tensor.  Returns the kernel launches made (one per eight tensors)."""
+    _require("stp_sparse_adam")
+    return int((_host or _native()).sparse_adam(list(params), list(grads), list(exp_avgs), list(exp_avg_sqs), visible, [float(x) for x in lrs],
+                                                [float(x) for x in epss], float(beta1), float(beta2), int(N)))
+
+
+def adamUpdate(param, grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps, N, M) -> None:
+    """The single-tensor step under the name and argument order of the accelerated rasterizer's `_C.adamUpdate`: a one-tensor sparse_adam
+    (M, the floats per Gaussian, must be numel / N)."""
+    if int(N) * int(M) != param.numel():
+        raise RuntimeError(f"adamUpdate: param has {param.numel()} elements, N * M = {int(N) * int(M)}")
+    sparse_adam([param], [grad], [exp_avg], [exp_avg_sq], visible, [lr], [eps], b1, b2, N)
 
 
 # ---- introspection helpers (tests / bench; not part of the reference surface) -----------------------

@@ -25,7 +25,7 @@ import torch.nn as nn
 from . import _C
 
 __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes", "SortSettings", "CullingSettings",
-           "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer"]
+           "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam"]
 
 
 def enum_dict_factory(data):
@@ -412,3 +412,73 @@ class GaussianRasterizer(nn.Module):
         empty = lambda t: torch.Tensor([]) if t is None else t  # absent optional input == empty CPU tensor
         return rasterize_gaussians(means3D, means2D, empty(shs), empty(colors_precomp), opacities, empty(scales),
                                    empty(rotations), empty(cov3D_precomp), rs)
+
+
+class SparseGaussianAdam(torch.optim.Adam):
+    """Adam whose step updates only the Gaussians visible in the frame, all tensors in one fused kernel launch (extension; the class of the
+    same name in the accelerated 3DGS rasterizer, a trainer's `--optimizer_type sparse_adam`; include/stp_raster.h: stp_sparse_adam).
+
+        opt = SparseGaussianAdam([{"params": [xyz], "lr": ..., "name": "xyz"}, ...], lr=0.0, eps=1e-15)
+        ...
+        opt.step(radii > 0, N)        # or opt.step(radii, N): the forward's int32 radii are read as they are (> 0 = visible)
+
+    For every group's tensor with a gradient, every row i < N with visibility[i] and each of its numel / N elements, in float32:
+        m <- b1 m + (1 - b1) g      v <- b2 v + (1 - b2) g g      p <- p - lr m / (sqrt(v) + eps)
+    There is NO bias correction (as upstream), no weight decay and no amsgrad; rows that are not visible keep param and state bit for bit and
+    their gradient is not read.  Every group holds exactly one tensor; lr and eps are the group's, read at every step (a trainer's schedule
+    writes group["lr"]), betas must agree across the groups.  The state is torch.optim.Adam's -- state[p]["step"], ["exp_avg"], ["exp_avg_sq"]
+    -- so that densification code that concatenates, prunes or replaces those tensors and swaps group["params"][0] keeps working, and
+    state_dict() / load_state_dict() are Adam's.  state["step"] counts the steps that found a gradient on the tensor.
+    `last_launches` holds the kernel launches of the latest step (one per eight tensors)."""
+
+    _REFUSED = ("weight_decay", "amsgrad", "maximize", "capturable", "fused", "foreach")
+
+    def __init__(self, params, lr, eps, betas=(0.9, 0.999), **options):
+        for name, value in options.items():
+            if name not in self._REFUSED:
+                raise TypeError(f"SparseGaussianAdam got an unexpected option {name!r}")
+            self._refuse(name, value)
+        super().__init__(params=params, lr=lr, eps=eps, betas=betas)
+        for group in self.param_groups:   # (options can also ride in a group's dict)
+            for name in self._REFUSED:
+                self._refuse(name, group.get(name))
+            self._one_tensor(group)
+        self.last_launches = 0
+
+    @staticmethod
+    def _refuse(name, value):
+        if value is not None and value is not False and value != 0:
+            raise ValueError(f"SparseGaussianAdam does not support {name} (got {name}={value!r}): the fused step is plain Adam without bias "
+                             "correction on the visible rows")
+
+    @staticmethod
+    def _one_tensor(group):
+        if len(group["params"]) != 1:
+            raise AssertionError("more than one tensor in group")
+
+    @torch.no_grad()
+    def step(self, visibility, N):
+        params, grads, exp_avgs, exp_avg_sqs, lrs, epss = [], [], [], [], [], []
+        betas = None
+        for group in self.param_groups:
+            self._one_tensor(group)
+            param = group["params"][0]
+            if param.grad is None:
+                continue
+            if betas is None:
+                betas = tuple(group["betas"])
+            elif tuple(group["betas"]) != betas:
+                raise ValueError(f"SparseGaussianAdam steps all groups in one kernel launch: betas must agree, got {betas} and {tuple(group['betas'])}")
+            state = self.state[param]
+            if len(state) == 0:   # created as torch.optim.Adam creates it
+                state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                state["exp_avg"] = torch.zeros_like(param, memory_format=torch.preserve_format)
+                state["exp_avg_sq"] = torch.zeros_like(param, memory_format=torch.preserve_format)
+            state["step"] += 1
+            params.append(param)
+            grads.append(param.grad)
+            exp_avgs.append(state["exp_avg"])
+            exp_avg_sqs.append(state["exp_avg_sq"])
+            lrs.append(float(group["lr"]))
+            epss.append(float(group["eps"]))
+        self.last_launches = _C.sparse_adam(params, grads, exp_avgs, exp_avg_sqs, visibility, lrs, epss, betas[0], betas[1], N) if params else 0
