@@ -143,9 +143,8 @@ __global__ void __launch_bounds__(OS.sort.block_size) os_iteration_kernel(const 
 constexpr uint32_t OWN_MIN = 1u << 16, OWN_MAX = 1u << 30;
 bool own_onesweep_driver(size_t R)
 {
-    static const char* const env = std::getenv("STP_TILE_SORT");
-    static const bool lib = env && std::strcmp(env, "rocprim") == 0;
-    static const bool always = env && std::strcmp(env, "own") == 0; // (tests: also below OWN_MIN)
+    const bool lib = switches().tile_sort == Switches::TILE_SORT_ROCPRIM;  // STP_TILE_SORT=rocprim
+    const bool always = switches().tile_sort == Switches::TILE_SORT_OWN;   // STP_TILE_SORT=own (tests: also below OWN_MIN)
     return !lib && (R >= OWN_MIN || (always && R > 0)) && R < OWN_MAX;
 }
 #else  // another rocPRIM: the library's host function only
@@ -226,7 +225,7 @@ hipError_t launch_sort(const FrameParams& f, const BinningState& b, int R, bool 
     return hipGetLastError();
 }
 
-// ---- binning by tile counters (STP_SORT=counters; not the default, see stp_api.hip) ----------------------------------
+// ---- binning by tile counters (STP_SORT=counters; not the default, see stp_forward.hip) ----------------------------------
 // The reference (and the default path) brings the duplicates into tile order with a device-wide radix sort of all R
 // (key, id) pairs.  The tile of every duplicate is known when it is emitted, and a tile's segment length is known once
 // every Gaussian has been preprocessed: preprocess_kernel counts entries per tile (one fire-and-forget atomic per

@@ -72,7 +72,7 @@ typedef uint16_t log_t;
 constexpr int LOG_MAX_LIST = 65535;
 // Depth of the log = records per pixel it can hold (2 B each; + spare rows, see below): a RUN-TIME value since round 4
 // (RenderArgs::log_depth), chosen per frame by the host from the blends per pixel the previous recording forwards of the same kind
-// needed (stp_api.hip: log_depth_for) -- C2 blends at most 114 entries per pixel, C3 155, C5 195 (profiles/r03_log_depth_stats.txt), so
+// needed (stp_forward.hip: log_depth_for) -- C2 blends at most 114 entries per pixel, C3 155, C5 195 (profiles/r03_log_depth_stats.txt), so
 // one fixed depth either wastes memory or sends tiles to the re-sorting fallback, and ONE such tile costs 1.25 ms (profiles/r04_log_depth_ab.txt).
 // BLEND_LOG_DEPTH is the depth of a frame nothing is known about yet; a pixel that blends more flags its tile as before.
 #ifndef STP_LOG_DEPTH

@@ -1,5 +1,6 @@
-// stp_internal.h -- host-side internals of libstp_raster.so: scratch-buffer carving and the
-// launcher interface between the C ABI (stp_api.hip) and the kernel translation units.
+// stp_internal.h -- host-side internals of libstp_raster.so: scratch-buffer carving, what the host files of the C ABI (stp_api.hip,
+// stp_forward.hip, stp_buffers.hip, stp_timer.hip) need from each other, and the launcher interface between them and the kernel
+// translation units.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,11 +10,14 @@
 #include <string>
 
 #include "../../include/stp_raster.h"
+#include "stp_switches.h"
 
 namespace stp {
 
 constexpr int TILE = 16;
 constexpr size_t ALIGN = 256; // sub-array alignment inside the scratch buffers
+static_assert(ALIGN == 256, "Switches::carve_skew (stp_switches.h) is masked to a multiple of 256");
+constexpr int MAX_DEVICES = 32; // per-device helpers (timers, mailbox rings, side streams, size guesses, background scratch) are arrays of this size
 
 enum SortMode { MODE_GLOBAL = 0, MODE_FULL = 1, MODE_KBUFFER = 2, MODE_HIER = 3 };
 enum SortOrder { ORDER_Z = 0, ORDER_DISTANCE = 1, ORDER_PTD_CENTER = 2, ORDER_PTD_MAX = 3 };
@@ -44,11 +48,7 @@ struct Carver {
     explicit Carver(char* b) : base(b) {}
     // STP_CARVE_SKEW=n (experiment, profiles/EXPERIMENTS.md round 6: HBM channel aliasing between the SoA arrays a kernel streams side by side):
     // n extra bytes (a multiple of ALIGN) in front of every sub-array but the first
-    static size_t skew()
-    {
-        static const size_t v = [] { const char* e = std::getenv("STP_CARVE_SKEW"); return e ? ((size_t)std::strtoull(e, nullptr, 0) & ~(ALIGN - 1)) : (size_t)0; }();
-        return v;
-    }
+    static size_t skew() { return switches().carve_skew; }
     template <typename T> T* take(size_t count, size_t* off_out = nullptr)
     {
         off = (off + ALIGN - 1) & ~(ALIGN - 1);
@@ -94,14 +94,14 @@ struct ImageState { // reference ImageState, rasterizer_impl.cu:195-202 (ranges 
     uint32_t* tile_counts; // T
     uint32_t* tile_cursor; // T
     uint32_t* bin_total;   // 2
-    uint32_t* header;      // 4: {STP_HEADER_MAGIC_IMAGE, log_depth, ~log_depth, 0} -- the blend log's depth travels WITH the buffer (stp_api.hip: buffer headers)
+    uint32_t* header;      // 4: {STP_HEADER_MAGIC_IMAGE, log_depth, ~log_depth, 0} -- the blend log's depth travels WITH the buffer (stp_buffers.hip: buffer headers)
     uint32_t* tile_flags; // T   0 = this tile's log is valid, 1 = its log overflowed, 0xFFFFFFFF = the forward recorded no log
     uint32_t* blend_log;  // T * 4 waves * (log_depth + spare) rows * 64 lanes of u16 (only with the blend log)
     int log_depth;        // records per pixel the log holds (0: none)
 };
 
 struct BinningState { // reference BinningState, rasterizer_impl.cu:204-217
-    uint32_t* header;      // first 256 bytes of the buffer: {STP_HEADER_MAGIC_BINNING, entries the buffer was carved for, ~that, 0} (stp_api.hip: buffer headers)
+    uint32_t* header;      // first 256 bytes of the buffer: {STP_HEADER_MAGIC_BINNING, entries the buffer was carved for, ~that, 0} (stp_buffers.hip: buffer headers)
     uint32_t* point_list;
     uint32_t* point_list_unsorted;
     uint64_t* keys;
@@ -125,6 +125,24 @@ struct NamedOffset { const char* name; size_t offset; size_t count; };
 GeometryState carve_geometry(char* base, size_t P, bool with_inv, size_t* total, NamedOffset* names = nullptr, int* n_names = nullptr);
 ImageState carve_image(char* base, int W, int H, int ty0, int ty1, int log_depth /* 0: no blend log */, size_t* total, NamedOffset* names = nullptr, int* n_names = nullptr); // the tile-row window's share, frame-coordinate indexing
 BinningState carve_binning(char* base, size_t R, size_t* total, NamedOffset* names = nullptr, int* n_names = nullptr);
+void clamp_tile_rows(int height, int& y0, int& y1); // StpSettings::tile_y0 / tile_y1 -> the frame's tile-row window (y1 <= 0: the whole frame)
+
+// ---- the error state (stp_api.hip): ONE message per thread, set by whichever file refuses the call ----
+int fail(int code, const std::string& msg);
+int fail_hip(hipError_t e, const char* what);
+#define STP_TRY(expr, what) do { hipError_t _e = (expr); if (_e != hipSuccess) return fail_hip(_e, what); } while (0)
+#define STP_DEBUG_SYNC(what) /* (wherever a stream `st` and a flag `debug` are in scope) */ STP_TRY(debug ? hipStreamSynchronize(st) : hipSuccess, what)
+
+// ---- the stage timer (stp_timer.hip): no-ops unless stp_timing_enable(1); the calling thread's current device ----
+void timer_begin_forward();
+void timer_begin_backward();
+void timer_mark(int i, hipStream_t st); // events 0..4: forward stage boundaries, 5..7: backward
+
+// ---- what a buffer was carved with (stp_buffers.hip: buffer headers): cache of this process, else the buffer's own header ----
+void remember_layout(const void* binning, uint32_t count, int64_t R);
+void remember_log_depth(const void* image, uint32_t depth, int64_t R);
+int layout_of(const char* binning, uint32_t R, uint32_t* cap, hipStream_t st = nullptr, bool have_stream = false);
+int log_depth_of(const char* image, int64_t R, uint32_t* depth, hipStream_t st = nullptr, bool have_stream = false);
 
 int blend_log_rows(int depth); // rows of 64 records per wave in a blend log of that depth (stp_render_replay.hip / stp_blend.h)
 int blend_log_default_depth(); // depth of a frame nothing is known about
@@ -196,6 +214,19 @@ struct BackwardParams {
     float* dL_dscale;
     float* dL_drot;
 };
+
+// ---- argument checks and frame description shared by the forward and the backward (stp_api.hip) ----
+int check_settings(const StpSettings& s, bool backward);
+void fill_frame(FrameParams& f, int P, int D, int M, const float* background, int width, int height, const StpSettings& s, const float* means3D,
+                const float* shs, const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+                const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* inv_viewprojmatrix, const float* cam_pos,
+                float tan_fovx, float tan_fovy, int prefiltered);
+
+// ---- the one-shot per-thread requests (stp_api.hip: the stp_set_* setters, and the rules by which a call takes them) ----
+struct ForwardSplit { int row = 0; hipEvent_t event = nullptr; bool armed = false; };      // stp_set_forward_split
+struct ForwardBackground { const float* bg_image = nullptr; float* out_alpha = nullptr; }; // stp_set_forward_background
+struct ForwardRequests { ForwardSplit split; ForwardBackground background; };
+ForwardRequests take_forward_requests();
 
 // ---- launchers (one per stage; each returns hipSuccess or the launch error) ----
 hipError_t launch_preprocess(const FrameParams& f, const GeometryState& g, int* radii, uint32_t* tile_counts, hipStream_t st); // tile_counts: nullptr = do not count per tile

@@ -436,10 +436,10 @@ struct DupArgs {
     uint64_t* keys;
     uint32_t* values;
     uint32_t* tile_cursor; // binning by tile counters: next free slot of every tile's segment (nullptr: slots by point_offsets)
-    uint32_t cap;          // slots the arrays hold: a run-ahead forward (stp_api.hip) launches on a capacity, not on num_rendered; 0xFFFFFFFF = exact
+    uint32_t cap;          // slots the arrays hold: a run-ahead forward (stp_forward.hip) launches on a capacity, not on num_rendered; 0xFFFFFFFF = exact
     int n_gauss_blocks;    // workgroups that own Gaussians; the DUP_PAD_BLOCKS behind them fill [num_rendered, cap) with padding entries
     int n_pad_blocks;      // DUP_PAD_BLOCKS for a capacity launch, else 0
-    uint32_t* header;      // the binning buffer's header (stp_api.hip: buffer headers), written by the first thread
+    uint32_t* header;      // the binning buffer's header (stp_buffers.hip: buffer headers), written by the first thread
     uint32_t header_cap;   // entries the buffer was carved for
     uint32_t* zero_ptr;    // cleared by the DUP_ZERO_BLOCKS workgroups behind those: the tile-bit sort's histograms, look-back states and block
     uint32_t zero_words;   // counters (stp_binning.hip: sort_zero_region), which the library's own driver clears with five separate fill launches
@@ -775,7 +775,7 @@ __global__ void __launch_bounds__(256) frame_init_kernel(uint32_t* __restrict__ 
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < 64) status[i] = 0u;
-    if (i == 0) { header[0] = STP_HEADER_MAGIC_IMAGE; header[1] = log_depth; header[2] = ~log_depth; header[3] = 0u; } // the image buffer describes itself (stp_api.hip: buffer headers)
+    if (i == 0) { header[0] = STP_HEADER_MAGIC_IMAGE; header[1] = log_depth; header[2] = ~log_depth; header[3] = 0u; } // the image buffer describes itself (stp_buffers.hip: buffer headers)
     if (i < T) { // the tiles of the frame's tile-row window (the arrays hold no others: carve_image)
         ranges[tile0 + i] = make_uint2(0u, 0u);
         tile_flags[tile0 + i] = flag_value;
@@ -802,26 +802,15 @@ hipError_t launch_ranges(const FrameParams& f, const BinningState& b, const Imag
     return e;
 }
 
-bool tile_order_enabled()
-{
-    // MEASURED (round 6, one box, alternating, profiles/r06_experiments/tile_order_ab.txt; forward / replay ms): C2-full 0.855 / 0.855 -> 0.822 / 0.824 (432 -> 443
-    // frames/s: even the homogeneous frame ends on a tail), C2L (40 % of the Gaussians in 12 clusters) 1.03 / 0.98 -> 0.75 / 0.72 (373 -> 465 frames/s), C2H
-    // 0.96 / 0.855 -> 0.61 / 0.51, C3 +1.3 %, C5 unchanged; the order kernel itself 9 us.  STP_TILE_ORDER=0: the XCD-contiguous order of rounds 1-5.
-    static const bool on = [] { const char* e = std::getenv("STP_TILE_ORDER"); return !(e && e[0] == '0'); }();
-    return on;
-}
+bool tile_order_enabled() { return switches().tile_order; }
+// MEASURED (round 6, one box, alternating, profiles/r06_experiments/tile_order_ab.txt; forward / replay ms): C2-full 0.855 / 0.855 -> 0.822 / 0.824 (432 -> 443
+// frames/s: even the homogeneous frame ends on a tail), C2L (40 % of the Gaussians in 12 clusters) 1.03 / 0.98 -> 0.75 / 0.72 (373 -> 465 frames/s), C2H
+// 0.96 / 0.855 -> 0.61 / 0.51, C3 +1.3 %, C5 unchanged; the order kernel itself 9 us.  STP_TILE_ORDER=0: the XCD-contiguous order of rounds 1-5.
 // STP_GATHER_ORDER (experiments, round 6; default 0): 0 = the entry gather in the XCD-contiguous spatial order, 1 = longest first inside every XCD's run, 2 = longest first over
 // the frame.  MEASURED (sort stage ms, one box, alternating): 1: C2-full 0.320 -> 0.324, C5 1.110 -> 1.172, C3 0.970 -> 0.955, C2L 0.381 -> 0.372; 2: C2-full 0.311 -> 0.320,
 // C5 1.14 -> 1.21, C3 0.944 -> 0.900, C2L 0.378 -> 0.328 -- what the gather gains at the tail it loses in the L2 (neighbouring tiles share their Gaussians' lines).
-bool gather_order_enabled()
-{
-    return gather_order_mode() != 0;
-}
-int gather_order_mode()
-{
-    static const int m = [] { const char* e = std::getenv("STP_GATHER_ORDER"); return e ? std::atoi(e) : 0; }();
-    return m;
-}
+bool gather_order_enabled() { return gather_order_mode() != 0; }
+int gather_order_mode() { return switches().gather_order; }
 hipError_t launch_tile_order(const FrameParams& f, const ImageState& img, hipStream_t st)
 {
     const int T = f.gx * (f.ty1 - f.ty0);

@@ -465,8 +465,7 @@ hipError_t launch_kbuffer_wave(int mode, const FrameParams& f, const RenderArgs&
     const int w = f.s.queue_per_pixel; // reference forward.cu:409-425: the next supported window
     *handled = true;
     // windows of 8 .. 16 entries: the ring-in-LDS kernel (STP_KBUFFER=wave keeps the register window for them too)
-    static const char* const kb_env = std::getenv("STP_KBUFFER");
-    static const bool ring = !(kb_env && std::strcmp(kb_env, "wave") == 0);
+    const bool ring = switches().kbuffer != Switches::KBUFFER_WAVE;
 #define STP_KBW(WIN) return mode == KBW_RECORD ? launch_kb_win<WIN, KBW_RECORD>(f, a, st) : mode == KBW_DEPTH ? launch_kb_win<WIN, KBW_DEPTH>(f, a, st) : launch_kb_win<WIN, KBW_FWD>(f, a, st)
 #define STP_KBR(WIN) return mode == KBW_RECORD ? launch_kb_ring<WIN, KBW_RECORD>(f, a, st) : mode == KBW_DEPTH ? launch_kb_ring<WIN, KBW_DEPTH>(f, a, st) : launch_kb_ring<WIN, KBW_FWD>(f, a, st)
     if (w <= 1) STP_KBW(1);

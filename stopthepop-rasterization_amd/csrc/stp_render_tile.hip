@@ -421,7 +421,7 @@ static RenderArgs make_args(const FrameParams& f, const GeometryState& g, const 
     a.entA = b.entA; a.entB = b.entB; a.entC = b.entC; a.entD = b.entD; a.entF = b.entF;
     a.final_T = img.final_T; a.n_contrib = img.n_contrib;
     a.blend_log = img.blend_log; a.tile_flags = img.tile_flags; a.flag_mode = 0;
-    static const bool counters = [] { const char* e = std::getenv("STP_SORT"); return e && std::strcmp(e, "counters") == 0; }(); // (that path uses tile_cursor itself)
+    const bool counters = switches().atomic_bin; // (STP_SORT=counters: that path uses tile_cursor itself)
     a.tile_order = (tile_order_used(f) && !counters && !f.split_launch) ? img.tile_cursor + f.gx * f.ty0 : nullptr;
     a.log_depth = img.log_depth; a.log_need = f.log_need; a.log_tag = f.log_tag;
     a.debug_depth = f.s.debug_visualization == STP_DEBUG_DEPTH ? 1 : 0; a.means3D = f.means3D;
@@ -474,8 +474,7 @@ hipError_t launch_render_forward(const FrameParams& f, const GeometryState& g, c
     case MODE_KBUFFER: {
         // the wave64 kernel of stp_render_kbuf.hip (STP_KBUFFER=tile keeps the one-entry-per-wave kernel of this file for
         // comparison; the results are the same)
-        static const char* const kb_env = std::getenv("STP_KBUFFER");
-        static const bool kb_tile = kb_env && std::strcmp(kb_env, "tile") == 0;
+        const bool kb_tile = switches().kbuffer == Switches::KBUFFER_TILE;
         if (!kb_tile) {
             bool handled = false;
             const hipError_t e = launch_kbuffer_wave(a.debug_depth ? KB_FWD_DEPTH : uses_blend_log(f.s) ? KB_FWD_RECORD : KB_FWD, f, a, st, &handled);

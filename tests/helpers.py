@@ -166,7 +166,7 @@ class GpuRun:
         """cov3D_precomp: (P,6) array -> passed INSTEAD of scales/rotations (ref: __init__.py:286-289 allows exactly one).
         warm: the frame is rendered TWICE.  The library's default forward takes the reference's path -- hand-over of num_rendered in the
         middle of the frame, exact binning size; with run-ahead switched on (_C.set_run_ahead) every forward but the first of its kind is
-        launched as a whole on a capacity guessed from the frames before (stp_api.hip).  The untracked first pass runs the default path,
+        launched as a whole on a capacity guessed from the frames before (stp_forward.hip).  The untracked first pass runs the default path,
         the second -- the one the tests inspect -- the run-ahead path; both must return the same image, radii and count, bit for bit.
         run_ahead (with warm=False): run this one frame with the switch set like this."""
         import torch

@@ -473,7 +473,7 @@ def test_tile_row_windows_paste_to_the_full_frame():
 
 def test_tile_row_window_holds_only_its_rows_of_the_image_state():
     """A forward restricted to a tile-row window (a rank of a tile-row shard) allocates the per-pixel arrays, the tile ranges and the blend
-    log for ITS rows only (stp_api.hip: carve_image) -- a third of the rows, a third of the log -- and its arrays are the full frame's rows."""
+    log for ITS rows only (stp_buffers.hip: carve_image) -- a third of the rows, a third of the log -- and its arrays are the full frame's rows."""
     from diff_gaussian_rasterization import _C
     sc = scenes.make_scene(P=20000, W=320, H=240, sigma_min=1.0, sigma_max=10.0, seed=8, camera="orbit")
     sd = settings_dict(**FULL_STP)
@@ -790,7 +790,7 @@ def test_c2_whole_frame_is_the_oracle_with_its_threshold_decisions_forced(c2_sce
             assert _rel(a, b) < 1e-4, k
 
 
-# ---------------------------------------------------------------- the run-ahead forward (stp_api.hip, round 4)
+# ---------------------------------------------------------------- the run-ahead forward (stp_forward.hip, round 4)
 def _layout_count(g):
     import ctypes
     from diff_gaussian_rasterization import _C
@@ -870,7 +870,7 @@ def test_gradient_record_buffer_is_kept_clean_between_backwards():
 
 
 def test_blend_log_depth_follows_the_scene():
-    """The blend log's depth is chosen per frame (stp_api.hip: log_depth_for): a frame nothing is known about gets 192 records per pixel,
+    """The blend log's depth is chosen per frame (stp_forward.hip: log_depth_for): a frame nothing is known about gets 192 records per pixel,
     every recording forward reports the largest blend count of its pixels, and the frames of the same kind after it size their log by it
     -- smaller for a scene that blends a few dozen entries per pixel, deeper (up to 512) for one that overflowed."""
     from diff_gaussian_rasterization import _C
