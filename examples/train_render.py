@@ -3,7 +3,7 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--optimizer adam|sparse_adam]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
@@ -22,7 +22,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "stopthepop-rasterization_amd"))
 from diff_gaussian_rasterization import (CullingSettings, ExtendedSettings, GaussianRasterizationSettings,  # noqa: E402
-                                         GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, SparseGaussianAdam, scenes)
+                                         GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, SparseGaussianAdam, photometric_loss,
+                                         scenes)
 
 
 def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, scaling_modifier: float = 1.0,
@@ -103,6 +104,8 @@ def main(argv=None):
                     help="add W * mean |alpha - target alpha| to the loss: mask supervision on the rasterizer's alpha output")
     ap.add_argument("--optimizer", default="adam", choices=["adam", "sparse_adam"],
                     help="sparse_adam: SparseGaussianAdam, one fused launch that steps only the Gaussians visible in the frame (INTEGRATION.md section 3i)")
+    ap.add_argument("--loss", default="l1", choices=["l1", "l1_ssim"],
+                    help="l1_ssim: the trainers' 0.8 * L1 + 0.2 * (1 - SSIM) from the fused photometric_loss (INTEGRATION.md section 3j)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
@@ -137,9 +140,13 @@ def main(argv=None):
     stat_signed = torch.zeros(model.get_xyz.shape[0], device=dev)
     stat_abs = torch.zeros_like(stat_signed)
     first = last = None
+    label = "L1" if args.loss == "l1" else "0.8 L1 + 0.2 (1 - SSIM)"
     for it in range(args.iters):
         out = render(cam, model, bg, train_cfg)
-        loss = (out["render"] - target).abs().mean()
+        if args.loss == "l1_ssim":   # both terms from one fused kernel pair; the printed figure is this loss then
+            loss = photometric_loss(out["render"], target, lambda_dssim=0.2)
+        else:
+            loss = (out["render"] - target).abs().mean()
         if masked:   # alpha is an output of the same autograd node: one backward serves both terms
             loss = loss + args.mask_weight * (out["alpha"] - target_alpha).abs().mean()
         opt.zero_grad(set_to_none=True)
@@ -156,7 +163,7 @@ def main(argv=None):
         last = float(loss.detach())
         first = last if first is None else first
         if it % 10 == 0 or it == args.iters - 1:
-            print(f"iter {it:3d}  L1 {last:.5f}  visible {int(out['visibility_filter'].sum())}  |grad2D| max {float(grad2d.norm(dim=1).max()):.3e}")
+            print(f"iter {it:3d}  {label} {last:.5f}  visible {int(out['visibility_filter'].sum())}  |grad2D| max {float(grad2d.norm(dim=1).max()):.3e}")
     with torch.no_grad():
         depth = render(cam, model, bg, cfg, render_depth=True)["render"]
     if args.absgrad:
@@ -182,7 +189,7 @@ def main(argv=None):
         keep = score >= 0.01
         print(f"pruning pass over {len(views)} views: largest blend weight below 0.01 for {int((~keep).sum())} of {keep.numel()} Gaussians "
               f"({int((hits == 0).sum())} of them never blended); a trainer would now keep model tensors[keep]")
-    print(f"L1 {first:.5f} -> {last:.5f}; depth visualisation {tuple(depth.shape)} in [{float(depth.min()):.3f}, {float(depth.max()):.3f}]")
+    print(f"{label} {first:.5f} -> {last:.5f}; depth visualisation {tuple(depth.shape)} in [{float(depth.min()):.3f}, {float(depth.max()):.3f}]")
     return first, last
 
 

@@ -295,6 +295,31 @@ typedef struct { float* param; const float* grad; float* exp_avg; float* exp_avg
 int stp_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind /* 0: N bytes, non-zero = visible; 1: N int32, > 0 = visible */,
                     float beta1, float beta2, void* stream);
 
+/* Extension (not in the reference): the fused photometric loss of 3DGS trainers, (1 - lambda) * L1 + lambda * (1 - SSIM) -- upstream's
+   l1_loss and ssim() with window_size = 11 and size_average = True, the pair the `fused-ssim` extension replaces.  `image` (x) and `target`
+   (y) are `planes` contiguous float32 planes of H x W (a (C, H, W) or (B, C, H, W) tensor: planes = B * C), n = planes * H * W.  With
+   blur = the 2-D correlation with the outer product of w_k = exp(-(k - 5)^2 / 4.5) / sum (k = 0 .. 10) and ZERO padding of 5, per plane:
+       mu1 = blur(x), mu2 = blur(y), s1 = blur(x^2) - mu1^2, s2 = blur(y^2) - mu2^2, s12 = blur(x y) - mu1 mu2, C1 = 0.01^2, C2 = 0.03^2
+       A = 2 mu1 mu2 + C1, B = 2 s12 + C2, Cc = mu1^2 + mu2^2 + C1, D = s1 + s2 + C2,  m = A B / (Cc D)
+   stp_photometric_forward writes out2[0] = mean |x - y| and out2[1] = mean m (device memory) and, when `maps` is not NULL, the three
+   derivative maps dm/dmu1, dm/ds1, dm/ds12 (map k of element e at maps[k * n + e]) that stp_photometric_backward reads:
+       dL/dx = blur(s d1) + 2 x blur(s d2) + y blur(s d3) + (g0 / n) sign(x - y),  s = g1 / n,  sign(0) = 0,  (g0, g1) = dL_dout2
+   (dL_dout2 is read from DEVICE memory; there is no gradient for `target`).  `workspace`: stp_photometric_workspace_floats floats of
+   device memory, free again when the forward's kernels have run.  A kernel's workgroup owns a tile of STP_PHOTOMETRIC_TILE_W x
+   STP_PHOTOMETRIC_TILE_H pixels of one plane; all sums run in a fixed order without atomics: equal inputs give equal bits.
+   Each call returns the number of kernel launches made (forward 2, backward 1; 0 when planes, H or W is 0: nothing is touched), or a
+   negative StpStatus with the reason in the last-error text.  Refused BEFORE anything is launched (STP_ERR_INVALID_ARGUMENT): a negative
+   size, planes * H * W >= 2^31, a null image, target, out2, workspace, dL_dout2 or dL_dimage, null maps in the backward.  Plain calls: no
+   host synchronisation, no allocation, no per-thread request state. */
+#define STP_PHOTOMETRIC_TILE_W 64
+#define STP_PHOTOMETRIC_TILE_H 16
+size_t stp_photometric_workspace_floats(int planes, int H, int W);   /* floats of `workspace` (the forward's partial sums) */
+int stp_photometric_forward(int planes, int H, int W, const float* image, const float* target,
+                            float* out2 /* device: mean |x-y|, mean SSIM */, float* maps /* 3*planes*H*W floats, or NULL */,
+                            float* workspace, void* stream);
+int stp_photometric_backward(int planes, int H, int W, const float* image, const float* target, const float* maps,
+                             const float* dL_dout2 /* device, 2 floats */, float* dL_dimage, void* stream);
+
 /* Sizes of the three scratch buffers (the reference's `required<State>()`, rasterizer_impl.h:68-75). */
 size_t stp_geometry_buffer_size(int P, const StpSettings* settings);
 size_t stp_binning_buffer_size(int R);

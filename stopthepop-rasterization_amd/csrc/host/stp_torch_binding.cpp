@@ -29,6 +29,7 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <string>
@@ -72,6 +73,9 @@ struct Api {
     decltype(&stp_set_forward_background) set_forward_background = nullptr;
     decltype(&stp_set_backward_background) set_backward_background = nullptr;
     decltype(&stp_sparse_adam) sparse_adam = nullptr;
+    decltype(&stp_photometric_workspace_floats) photometric_workspace_floats = nullptr;
+    decltype(&stp_photometric_forward) photometric_forward = nullptr;
+    decltype(&stp_photometric_backward) photometric_backward = nullptr;
 } g_api;
 
 int load_library(const std::string& path)
@@ -96,6 +100,9 @@ int load_library(const std::string& path)
     a.set_forward_background = reinterpret_cast<decltype(a.set_forward_background)>(dlsym(h, "stp_set_forward_background"));
     a.set_backward_background = reinterpret_cast<decltype(a.set_backward_background)>(dlsym(h, "stp_set_backward_background"));
     a.sparse_adam = reinterpret_cast<decltype(a.sparse_adam)>(dlsym(h, "stp_sparse_adam"));
+    a.photometric_workspace_floats = reinterpret_cast<decltype(a.photometric_workspace_floats)>(dlsym(h, "stp_photometric_workspace_floats"));
+    a.photometric_forward = reinterpret_cast<decltype(a.photometric_forward)>(dlsym(h, "stp_photometric_forward"));
+    a.photometric_backward = reinterpret_cast<decltype(a.photometric_backward)>(dlsym(h, "stp_photometric_backward"));
     if (a.abi_version() != STP_ABI_VERSION) throw std::runtime_error(path + ": ABI version mismatch");
     g_api = a; // (a previously loaded library stays mapped: buffers of its forwards may still be in flight)
     return a.abi_version();
@@ -554,6 +561,75 @@ int sparse_adam(const std::vector<torch::Tensor>& params, const std::vector<torc
     return rc;
 }
 
+// == the fused photometric loss (extension, include/stp_raster.h: stp_photometric_forward / _backward; photometric_loss and fused_ssim in
+// __init__.py), on the caller's current stream.  image, target: float32 (C, H, W) or (B, C, H, W) on one GPU, made contiguous here.
+struct PhotometricShape { int planes, H, W; };
+static PhotometricShape photometric_check(const char* who, const torch::Tensor& image, const torch::Tensor& target)
+{
+    if (!g_api.photometric_forward || !g_api.photometric_backward || !g_api.photometric_workspace_floats)
+        throw std::runtime_error(std::string(who) + ": the loaded libstp_raster.so does not export stp_photometric_forward (a library built before the photometric loss): rebuild it");
+    TORCH_CHECK(image.defined() && target.defined(), who, ": image and target must be tensors");
+    // (what is wrong with the tensors themselves first, where they live last: every refusal can be met without a GPU)
+    TORCH_CHECK(image.scalar_type() == torch::kFloat32, "expected float32 tensor, got ", image.scalar_type());
+    TORCH_CHECK(target.scalar_type() == torch::kFloat32, "expected float32 tensor, got ", target.scalar_type());
+    TORCH_CHECK(image.dim() == 3 || image.dim() == 4, who, ": image must be (C, H, W) or (B, C, H, W), got ", image.dim(), " dimensions");
+    TORCH_CHECK(image.sizes() == target.sizes(), who, ": image has shape ", image.sizes(), ", target has ", target.sizes());
+    TORCH_CHECK(target.device() == image.device(), "expected all tensors on ", image.device(), ", got one on ", target.device());
+    TORCH_CHECK(image.is_cuda(), "diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
+    const int64_t H = image.size(-2), W = image.size(-1), planes = H * W > 0 ? image.numel() / (H * W) : 0;
+    TORCH_CHECK(image.numel() < (1ll << 31), who, ": ", image.numel(), " elements >= 2^31");
+    return PhotometricShape{(int)planes, (int)H, (int)W};
+}
+
+// -> (out2 = [mean |image - target|, mean SSIM], the three derivative maps (3, *image.shape) or an undefined tensor)
+std::tuple<torch::Tensor, torch::Tensor> photometric_forward(const torch::Tensor& image_in, const torch::Tensor& target_in, const bool want_maps)
+{
+    need_library();
+    const PhotometricShape s = photometric_check("photometric_forward", image_in, target_in);
+    const torch::Tensor image = image_in.contiguous(), target = target_in.contiguous();
+    const auto opt = image.options();
+    const c10::hip::HIPGuard guard(image.device().index());
+    torch::Tensor out2 = torch::empty({2}, opt), maps;
+    if (image.numel() == 0) { // the mean of nothing, as torch's
+        out2.fill_(std::numeric_limits<float>::quiet_NaN());
+        if (want_maps) maps = torch::empty({3, 0}, opt);
+        return {out2, maps};
+    }
+    if (want_maps) {
+        std::vector<int64_t> shape{3};
+        for (const int64_t d : image.sizes()) shape.push_back(d);
+        maps = torch::empty(shape, opt);
+    }
+    torch::Tensor workspace = torch::empty({(int64_t)g_api.photometric_workspace_floats(s.planes, s.H, s.W)}, opt);
+    const int rc = g_api.photometric_forward(s.planes, s.H, s.W, image.data_ptr<float>(), target.data_ptr<float>(), out2.data_ptr<float>(),
+                                             want_maps ? maps.data_ptr<float>() : nullptr, workspace.data_ptr<float>(),
+                                             (void*)c10::hip::getCurrentHIPStream(image.device().index()).stream());
+    if (rc < 0) raise_last(rc);
+    return {out2, maps};
+}
+
+// -> dL/dimage (image's shape); grad_out2 = dL/dout2, two floats on the device (read there: no host synchronisation)
+torch::Tensor photometric_backward(const torch::Tensor& image_in, const torch::Tensor& target_in, const torch::Tensor& maps, const torch::Tensor& grad_out2_in)
+{
+    need_library();
+    const PhotometricShape s = photometric_check("photometric_backward", image_in, target_in);
+    const torch::Tensor image = image_in.contiguous(), target = target_in.contiguous();
+    TORCH_CHECK(maps.defined() && maps.is_cuda() && maps.device() == image.device() && maps.scalar_type() == torch::kFloat32 && maps.is_contiguous() &&
+                    maps.numel() == 3 * image.numel(),
+                "photometric_backward: maps must be the contiguous float32 tensor of 3 * image.numel() elements a forward with want_maps returned");
+    TORCH_CHECK(grad_out2_in.defined() && grad_out2_in.is_cuda() && grad_out2_in.device() == image.device() && grad_out2_in.numel() == 2,
+                "photometric_backward: grad_out2 must hold two elements on the device of image");
+    const torch::Tensor grad_out2 = grad_out2_in.to(torch::kFloat32).contiguous();
+    const c10::hip::HIPGuard guard(image.device().index());
+    torch::Tensor dL_dimage = torch::empty(image.sizes(), image.options());
+    if (image.numel() == 0) return dL_dimage;
+    const int rc = g_api.photometric_backward(s.planes, s.H, s.W, image.data_ptr<float>(), target.data_ptr<float>(), maps.data_ptr<float>(),
+                                              grad_out2.data_ptr<float>(), dL_dimage.data_ptr<float>(),
+                                              (void*)c10::hip::getCurrentHIPStream(image.device().index()).stream());
+    if (rc < 0) raise_last(rc);
+    return dL_dimage;
+}
+
 // ---- scratch pool surface -------------------------------------------------------------------------------------------
 int64_t scratch_generation(const torch::Tensor& buf) // token the autograd function keeps with a pooled buffer (0 for ordinary ones)
 {
@@ -620,6 +696,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward);
     m.def("mark_visible", &mark_visible);
     m.def("sparse_adam", &sparse_adam);
+    m.def("photometric_forward", &photometric_forward);
+    m.def("photometric_backward", &photometric_backward);
     m.def("scratch_generation", &scratch_generation);
     m.def("check_scratch", &check_scratch);
     m.def("release_scratch", &release_scratch);

@@ -1,6 +1,6 @@
 // stp_api.hip -- the C ABI of libstp_raster.so (declared in include/stp_raster.h): the per-thread error state, the argument checks
-// and frame description that forward and backward share, the one-shot per-thread requests, and the backward, mark-visible and sparse
-// Adam calls.  Replaces CudaRasterizer::Rasterizer::{backward,markVisible} (reference cuda_rasterizer/rasterizer_impl.cu:417-526,
+// and frame description that forward and backward share, the one-shot per-thread requests, and the backward, mark-visible, sparse
+// Adam and photometric-loss calls.  Replaces CudaRasterizer::Rasterizer::{backward,markVisible} (reference cuda_rasterizer/rasterizer_impl.cu:417-526,
 // 161-173).  The forward is stp_forward.hip, the scratch buffers and their queries stp_buffers.hip, the stage timer stp_timer.hip.
 //
 // The calls are re-entrant: the scratch buffers belong to the caller, stp_last_error and the requests are per thread, and the
@@ -295,6 +295,50 @@ int stp_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const vo
     hipError_t e;
     const int launches = launch_sparse_adam(n_tensors, tensors, N, visible, visible_kind, beta1, beta2, (hipStream_t)stream, &e);
     if (e != hipSuccess) return fail_hip(e, "sparse_adam launch");
+    return launches;
+}
+
+// the sizes of a photometric call: 0 = empty work, 1 = work, negative = refused (with the last error set)
+static int check_photometric_sizes(const char* who, int planes, int H, int W)
+{
+    if (planes < 0 || H < 0 || W < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative size");
+    if (planes == 0 || H == 0 || W == 0) return 0;
+    const long long rows = (long long)planes * H; // < 2^62
+    if (rows >= (1ll << 31) || rows * W >= (1ll << 31))
+        return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": planes * H * W = " + std::to_string(planes) + " * " + std::to_string(H) + " * " + std::to_string(W) + " >= 2^31");
+    return 1;
+}
+
+size_t stp_photometric_workspace_floats(int planes, int H, int W)
+{
+    if (planes <= 0 || H <= 0 || W <= 0) return 0;
+    const long long rows = (long long)planes * H;
+    if (rows >= (1ll << 31) || rows * W >= (1ll << 31)) return 0; // (a size the calls refuse)
+    return 2 * (size_t)photometric_groups(planes, H, W);
+}
+
+int stp_photometric_forward(int planes, int H, int W, const float* image, const float* target, float* out2, float* maps, float* workspace, void* stream)
+{
+    // everything is checked before the first launch
+    const int work = check_photometric_sizes("stp_photometric_forward", planes, H, W);
+    if (work <= 0) return work;
+    if (!image || !target || !out2 || !workspace) return fail(STP_ERR_INVALID_ARGUMENT, "stp_photometric_forward: null pointer");
+    hipError_t e;
+    const int launches = launch_photometric_forward(planes, H, W, image, target, out2, maps, workspace, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "photometric forward launch");
+    return launches;
+}
+
+int stp_photometric_backward(int planes, int H, int W, const float* image, const float* target, const float* maps, const float* dL_dout2,
+                             float* dL_dimage, void* stream)
+{
+    const int work = check_photometric_sizes("stp_photometric_backward", planes, H, W);
+    if (work <= 0) return work;
+    if (!maps) return fail(STP_ERR_INVALID_ARGUMENT, "stp_photometric_backward: null maps (a forward without maps cannot be differentiated)");
+    if (!image || !target || !dL_dout2 || !dL_dimage) return fail(STP_ERR_INVALID_ARGUMENT, "stp_photometric_backward: null pointer");
+    hipError_t e;
+    const int launches = launch_photometric_backward(planes, H, W, image, target, maps, dL_dout2, dL_dimage, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "photometric backward launch");
     return launches;
 }
 

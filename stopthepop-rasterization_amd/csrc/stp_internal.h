@@ -269,6 +269,14 @@ hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmat
 // the launches made, *err = the launch error that ended them early (or hipSuccess)
 int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind, float beta1, float beta2,
                        hipStream_t st, hipError_t* err);
+// the fused photometric loss (stp_loss.hip) over arguments stp_photometric_* have validated (planes * H * W in [1, 2^31)): workgroups of the
+// tiled kernels (= rows of two partial sums in the workspace); the forward = tile kernel (with the three derivative maps when `maps`) + the
+// one-workgroup sum, the backward = one tile kernel.  Both return the launches made, *err = the launch error that ended them early
+uint32_t photometric_groups(int planes, int H, int W);
+int launch_photometric_forward(int planes, int H, int W, const float* image, const float* target, float* out2, float* maps, float* workspace,
+                               hipStream_t st, hipError_t* err);
+int launch_photometric_backward(int planes, int H, int W, const float* image, const float* target, const float* maps, const float* dL_dout2,
+                                float* dL_dimage, hipStream_t st, hipError_t* err);
 
 uint32_t higher_msb(uint32_t n);
 

@@ -49,12 +49,17 @@ _OPTIONAL_SYMBOLS = {
     "stp_set_backward_background": ([ctypes.c_void_p] * 3, None),
     "stp_sparse_adam": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
                         ctypes.c_int),
+    "stp_photometric_workspace_floats": ([ctypes.c_int] * 3, ctypes.c_size_t),
+    "stp_photometric_forward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int),
+    "stp_photometric_backward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int),
 }
 # the feature an optional export came with (the rebuild message names it)
 _SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blend_stats": "blend statistics",
                    "stp_set_forward_background": "the alpha output and per-pixel background",
                    "stp_set_backward_background": "the alpha output and per-pixel background",
-                   "stp_sparse_adam": "the sparse Adam step"}
+                   "stp_sparse_adam": "the sparse Adam step",
+                   "stp_photometric_workspace_floats": "the photometric loss", "stp_photometric_forward": "the photometric loss",
+                   "stp_photometric_backward": "the photometric loss"}
 
 
 def _require(name: str):
@@ -436,6 +441,24 @@ def adamUpdate(param, grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps, N, M)
     if int(N) * int(M) != param.numel():
         raise RuntimeError(f"adamUpdate: param has {param.numel()} elements, N * M = {int(N) * int(M)}")
     sparse_adam([param], [grad], [exp_avg], [exp_avg_sq], visible, [lr], [eps], b1, b2, N)
+
+
+def photometric_forward(image, target, want_maps):
+    """The forward of the fused photometric loss (extension, include/stp_raster.h: stp_photometric_forward) on the current stream:
+    (out2, maps) with out2 = [mean |image - target|, mean SSIM(image, target)] (float32, on the device) and maps = the three derivative
+    maps (3, *image.shape) the backward reads, or None when want_maps is false.  image, target: float32 (C, H, W) or (B, C, H, W) of equal
+    shape on one GPU; non-contiguous ones are made contiguous.  Two kernel launches, no host synchronisation."""
+    for name in ("stp_photometric_workspace_floats", "stp_photometric_forward", "stp_photometric_backward"):
+        _require(name)
+    out2, maps = (_host or _native()).photometric_forward(image, target, bool(want_maps))
+    return out2, (maps if want_maps else None)
+
+
+def photometric_backward(image, target, maps, grad_out2):
+    """dL/dimage of the fused photometric loss (stp_photometric_backward) from the maps of a forward with want_maps and grad_out2 = dL/dout2,
+    two floats ON THE DEVICE (the kernel reads them there).  One kernel launch, no host synchronisation.  There is no gradient for target."""
+    _require("stp_photometric_backward")
+    return (_host or _native()).photometric_backward(image, target, maps, grad_out2)
 
 
 # ---- introspection helpers (tests / bench; not part of the reference surface) -----------------------

@@ -25,7 +25,8 @@ import torch.nn as nn
 from . import _C
 
 __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes", "SortSettings", "CullingSettings",
-           "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam"]
+           "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam",
+           "photometric_terms", "fused_ssim", "photometric_loss"]
 
 
 def enum_dict_factory(data):
@@ -482,3 +483,56 @@ class SparseGaussianAdam(torch.optim.Adam):
             lrs.append(float(group["lr"]))
             epss.append(float(group["eps"]))
         self.last_launches = _C.sparse_adam(params, grads, exp_avgs, exp_avg_sqs, visibility, lrs, epss, betas[0], betas[1], N) if params else 0
+
+
+class _PhotometricTerms(torch.autograd.Function):
+    """(image, target) -> the (2,) tensor [mean |image - target|, mean SSIM(image, target)] of the fused photometric kernels.  The three
+    derivative maps are stored only when a gradient can be asked for (grad mode on and image.requires_grad); target gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, image, target, want_maps):
+        out2, maps = _C.photometric_forward(image, target, want_maps)
+        ctx.has_maps = maps is not None
+        if ctx.has_maps:
+            ctx.save_for_backward(image, target, maps)
+        return out2
+
+    @staticmethod
+    def backward(ctx, grad_out2):
+        if not ctx.has_maps:
+            raise RuntimeError("photometric_terms: this forward stored no derivative maps (fused_ssim(train=False)): it cannot be differentiated")
+        image, target, maps = ctx.saved_tensors
+        return _C.photometric_backward(image, target, maps, grad_out2), None, None
+
+
+def _photometric(image, target, store_maps=True) -> torch.Tensor:
+    want_maps = bool(store_maps) and torch.is_grad_enabled() and isinstance(image, torch.Tensor) and image.requires_grad
+    return _PhotometricTerms.apply(image, target, want_maps)
+
+
+def photometric_terms(image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """Both terms of a 3DGS trainer's loss from one fused kernel pair (extension; include/stp_raster.h: stp_photometric_forward): the (2,)
+    float32 tensor  [mean |image - target|, mean SSIM(image, target)]  on the device -- upstream's l1_loss(image, target) and
+    ssim(image, target) with window_size = 11 and size_average = True (Gaussian window of sigma 1.5, zero padding of 5, C1 = 0.01^2,
+    C2 = 0.03^2).  image, target: float32 (C, H, W) or (B, C, H, W) of equal shape on one GPU, every (H, W) plane on its own, H and W of
+    any size; non-contiguous tensors are made contiguous.  Differentiable in image; a target that requires grad is accepted and gets NO
+    gradient (None), as upstream's fused kernel gives none.  Deterministic: equal inputs give equal bits, forward and backward.  Refused
+    with a RuntimeError: CPU tensors, other dtypes than float32, shapes that differ, fewer than 3 or more than 4 dimensions, tensors on
+    different devices.  No host synchronisation anywhere: the backward reads the upstream gradient from device memory."""
+    return _photometric(image, target)
+
+
+def fused_ssim(img1: torch.Tensor, img2: torch.Tensor, padding: str = "same", train: bool = True) -> torch.Tensor:
+    """The mean SSIM of img1 against img2 under the name and argument order of the `fused-ssim` package: a scalar tensor, differentiable
+    in img1 (img2 gets no gradient).  padding must be "same" (zero padding of 5; "valid" is not built); train=False stores no derivative
+    maps (evaluation: the result is bit-equal to train=True and cannot be differentiated)."""
+    if padding != "same":
+        raise ValueError(f"fused_ssim: padding={padding!r} is not supported, only \"same\" (zero padding of 5; \"valid\" is not built)")
+    return _photometric(img1, img2, store_maps=train)[1]
+
+
+def photometric_loss(image: torch.Tensor, target: torch.Tensor, lambda_dssim: float = 0.2) -> torch.Tensor:
+    """The 3DGS trainers' loss  (1 - lambda_dssim) * L1(image, target) + lambda_dssim * (1 - SSIM(image, target))  as a scalar tensor,
+    composed on the two device scalars of photometric_terms (which see for shapes, refusals and the gradient rules)."""
+    terms = _photometric(image, target)
+    return (1.0 - lambda_dssim) * terms[0] + lambda_dssim * (1.0 - terms[1])
