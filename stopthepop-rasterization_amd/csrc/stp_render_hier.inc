@@ -314,8 +314,12 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     // ds_add_u64 ~7 (tools/lds_atomic_bench.hip).  The sums are therefore 64-bit FIXED POINT: every term of a
     // tile is linear in dL/dpixel of one of its 256 pixels, so with M = max |dL/dpixel| over the tile (rounded
     // up to a power of two) a term t is stored as round(t * 2^31 / M); |t| < 2^20 M fits 51 bits (anything
-    // larger -- never seen -- goes to memory directly), resolution is M * 4.7e-10, well below fp32 round-off of
-    // the sums, and integer addition makes the on-chip part of the sum order-independent.
+    // larger -- never seen -- goes to memory directly), and integer addition makes the on-chip part of the sum
+    // order-independent.  Resolution is M * 4.7e-10 per add, whatever the pixel: below fp32 round-off of the sums
+    // only where the Gaussian's pixels have |dL/dpixel| near M.  Dynamic range of dL/dpixel INSIDE a tile costs
+    // resolution: against u * sum |term| (u = 2^-24) the half-quantum per add sums to 0.6 (median) .. 8.5 under a
+    // dense N(0,1) image, and to 6e5 for a faint Gaussian of a tile with one pixel 2^20 above the others
+    // (tests/torch_ref_colour_bound.py: Q; DESIGN.md section 4).
     float wave_md = 0.0f;
     if constexpr (BACKWARD) {
         wave_md = bwd_pixel_scale(bp, a, inside, px, py);
@@ -359,10 +363,14 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         if (!mine) return;
         int cs = -1;
         if (pos >= staged - BWD_RING) cs = ring_cs[pos & (BWD_RING - 1)];
-        float gmax = fabsf(g[0]);
+        // The range check takes the SUM of the magnitudes, not their maximum: fmaxf drops a NaN operand, so with dL/dpixel non-finite in
+        // one channel only -- that channel's colour term and the six geometric terms NaN, the other two colour terms finite -- a maximum
+        // came out finite, and the NaN terms went through the integer conversion below as large finite garbage.  A sum keeps a NaN or an
+        // inf of any term, the comparison is then false and the terms go to memory as they are.  (sum < cap implies every term < cap.)
+        float gsum = fabsf(g[0]);
 #pragma unroll
-        for (int k = 1; k < 9; k++) gmax = fmaxf(gmax, fabsf(g[k]));
-        if (cs >= 0 && tag[cs] == pos && gmax < fx_cap) {
+        for (int k = 1; k < 9; k++) gsum += fabsf(g[k]);
+        if (cs >= 0 && tag[cs] == pos && gsum < fx_cap) {
 #pragma unroll
             for (int k = 0; k < 9; k++) {
                 // round-to-nearest integer of g*scale through the 1.5*2^52 trick (|g*scale| < 2^51 + margin)

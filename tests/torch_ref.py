@@ -8,8 +8,9 @@ elsewhere.  Ordering modes: "global" (sort by the global depth key) and "exact" 
 pixel's own depth-along-ray, i.e. what the resorting modes converge to at low density).
 
 One dense renderer, render_core(), serves every float64 yardstick of the tests: render() / loss_and_grads() here, and through its hooks
-the camera gradients (torch_ref_camera.py), absgrad (torch_ref_absgrad.py) and the blend statistics (torch_ref_blend_stats.py).  A
-further yardstick is a further hook, not a copy; tests/test_yardstick_pin_cpu.py holds all four to recorded values.
+the camera gradients (torch_ref_camera.py), absgrad (torch_ref_absgrad.py), the blend statistics (torch_ref_blend_stats.py) and the
+per-Gaussian bound on the colour gradient (torch_ref_colour_bound.py).  A further yardstick is a further hook, not a copy;
+tests/test_yardstick_pin_cpu.py holds the first four to recorded values, tests/test_upstream_grad_cpu.py the fifth.
 """
 from __future__ import annotations
 
