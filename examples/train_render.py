@@ -3,12 +3,12 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
   model  : get_xyz, get_opacity, get_scaling, get_rotation, get_features, active_sh_degree
-and returns the trainer's usual dict (render, viewspace_points, visibility_filter, radii; "alpha" too when asked for).
+and returns the trainer's usual dict (render, viewspace_points, visibility_filter, radii; "alpha" and "invdepth" too when asked for).
 """
 from __future__ import annotations
 
@@ -33,7 +33,8 @@ def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, 
     sum of the ABSOLUTE per-pixel contributions to it (AbsGS / gsplat's absgrad).
     `bg_color` is three floats or a (3, H, W) image the frame is composed onto; where it requires grad it gets one.  With
     `splat_args._alpha = True` the dict also carries "alpha", the pixel's opacity (1, H, W), differentiable like the image
-    (INTEGRATION.md section 3h)."""
+    (INTEGRATION.md section 3h); with `splat_args._invdepth = True` "invdepth", the blended inverse depth sum alpha T / z (1, H, W) that
+    upstream's rasterizer returns as `invdepths`, differentiable too."""
     screenspace_points = torch.zeros_like(model.get_xyz, requires_grad=True)
     raster_settings = GaussianRasterizationSettings(
         image_height=int(camera.image_height), image_width=int(camera.image_width),
@@ -43,11 +44,13 @@ def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, 
         campos=camera.camera_center, prefiltered=False, settings=splat_args, render_depth=render_depth, debug=debug)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
     shs, colors = (None, override_color) if override_color is not None else (model.get_features, None)
-    image, radii, *alpha = rasterizer(means3D=model.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors,
+    image, radii, *extra = rasterizer(means3D=model.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors,
                                       opacities=model.get_opacity, scales=model.get_scaling, rotations=model.get_rotation)
     out = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
-    if alpha:   # (settings._alpha)
-        out["alpha"] = alpha[0]
+    if getattr(splat_args, "_alpha", False):      # (the extra outputs in their order: alpha, then the inverse depth)
+        out["alpha"] = extra.pop(0)
+    if getattr(splat_args, "_invdepth", False):
+        out["invdepth"] = extra.pop(0)
     return out
 
 
@@ -102,6 +105,9 @@ def main(argv=None):
                     help="after training, a pruning pass over N views: the largest blend weight of every Gaussian over the views, then a threshold")
     ap.add_argument("--mask-weight", type=float, default=0.0, metavar="W",
                     help="add W * mean |alpha - target alpha| to the loss: mask supervision on the rasterizer's alpha output")
+    ap.add_argument("--depth-weight", type=float, default=0.0, metavar="W",
+                    help="add W * mean |invdepth - target invdepth| to the loss: depth regularisation on the rasterizer's inverse-depth output "
+                         "(upstream's `-d` monocular depth priors; INTEGRATION.md section 3k)")
     ap.add_argument("--optimizer", default="adam", choices=["adam", "sparse_adam"],
                     help="sparse_adam: SparseGaussianAdam, one fused launch that steps only the Gaussians visible in the frame (INTEGRATION.md section 3i)")
     ap.add_argument("--loss", default="l1", choices=["l1", "l1_ssim"],
@@ -116,9 +122,11 @@ def main(argv=None):
     masked = args.mask_weight > 0.0
     target_cfg = splat_config(args.config)
     target_cfg._alpha = masked   # (the target's own opacity is the mask the fit is supervised with)
+    with_depth = args.depth_weight > 0.0
+    target_cfg._invdepth = with_depth   # (... and its own inverse depth the depth prior)
     with torch.no_grad():
         target_out = render(cam, ToyGaussians(target_scene, dev), bg, target_cfg)
-        target, target_alpha = target_out["render"], target_out.get("alpha")
+        target, target_alpha, target_invdepth = target_out["render"], target_out.get("alpha"), target_out.get("invdepth")
 
     # start from perturbed colours and opacities and fit them back
     model = ToyGaussians(target_scene, dev)
@@ -134,6 +142,7 @@ def main(argv=None):
                                 {"params": [model._xyz, model._scaling, model._rotation], "lr": 0.0}])
     train_cfg = splat_config(args.config)
     train_cfg._alpha = masked
+    train_cfg._invdepth = with_depth
     train_cfg._absgrad = args.absgrad   # (a request on the settings object; the depth rendering below keeps the plain settings: it refuses it)
     # the densification statistic a trainer accumulates between two densify steps: the norm of the 2D positional gradient per visible
     # Gaussian -- signed (3DGS: pulls from opposite sides cancel) and, with --absgrad, absolute (AbsGS: they add up)
@@ -149,6 +158,8 @@ def main(argv=None):
             loss = (out["render"] - target).abs().mean()
         if masked:   # alpha is an output of the same autograd node: one backward serves both terms
             loss = loss + args.mask_weight * (out["alpha"] - target_alpha).abs().mean()
+        if with_depth:   # (and so is the inverse depth: no second render)
+            loss = loss + args.depth_weight * (out["invdepth"] - target_invdepth).abs().mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
         grad2d = out["viewspace_points"].grad  # what densification accumulates

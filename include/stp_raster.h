@@ -33,6 +33,7 @@ extern "C" {
 #define STP_GRAD_RECORD_USED 9    /* of which these carry data; the record stride of stp_backward_phases' compact form (phases bit 2) */
 #define STP_GRAD_RECORD_ABS 9     /* first of the two slots that carry sum |dL/dmean2D| xy under stp_set_backward_absgrad (padded records only) */
 #define STP_GRAD_RECORD_STATS 11  /* first of the three slots that carry sum, max and count of the blend weights under stp_set_backward_blend_stats (padded records only) */
+#define STP_GRAD_RECORD_INVDEPTH 14 /* the slot that carries dL/d(1/z) of the Gaussian under stp_set_backward_invdepth (padded records only) */
 
 /* Replaces CudaRasterizer::SplattingSettings + SortSettings + SortQueueSizes + CullingSettings
    (rasterizer.h:27-135) and their json parser (rasterizer.h:160-182): the host binding fills this
@@ -130,7 +131,8 @@ void stp_set_forward_split(int tile_row, void* event);
    its nine per-Gaussian terms into ONE 64-byte record per Gaussian,
        [0..2] dL/dcolour rgb   [3..4] dL/dmean2D xy   [5..7] dL/dconic xx, xy, yy   [8] dL/dopacity
        [9..10] sum |dL/dmean2D| xy (only with the absgrad request)
-       [11..13] sum, max, count of the blend weights (only with the blend-statistics request; the max as the float's bits)   [14..15] unused
+       [11..13] sum, max, count of the blend weights (only with the blend-statistics request; the max as the float's bits)
+       [14] dL/d(1/z) (only with the inverse-depth request)   [15] unused
    (one atomic instruction / one L2 request per flush instead of nine into four arrays: 9x the flush rate on
    MI355X, tools/global_atomic_bench.hip); the per-Gaussian half reads the record and writes dL_dmean2D,
    dL_dopacity and dL_dcolor in the reference's layouts along with the remaining gradients. */
@@ -271,6 +273,34 @@ void stp_set_forward_background(const float* bg_image /* 3 x H x W */, float* ou
 void stp_set_backward_background(const float* bg_image /* the forward's, or NULL */, const float* dL_dalpha /* H x W, or NULL */,
                                  float* dL_dbackground /* 3, or 3 x H x W when bg_image is given; or NULL */);
 
+/* Extension (the `invdepths` output of the official 3DGS rasterizer, gsplat's RGB+ED): a differentiable inverse-depth image.
+       invdepth[p] = sum_i w_i(p) / z_i,   w_i(p) = alpha_i(p) * T_i(p)
+   over exactly the (pixel, Gaussian) pairs the forward blends for the colour, in the same order with the same weights.  z_i is the
+   view-space z of Gaussian i's centre -- the value the near test compares with 0.2; not the sort key `depths`, not the depth along the
+   pixel's ray --, 1 / z_i one IEEE division per Gaussian in the preprocess kernel (kept in the geometry buffer, sub-array "invz", for
+   the backward).  No background term, no division by alpha: 0 where nothing blended.  Mathematically a fourth colour channel with a zero
+   background.
+   stp_set_forward_invdepth -- the NEXT stp_forward of the calling thread also writes out_invdepth (H x W floats).  Every sort mode
+       (PPX_FULL forward only, as always); the render kernels are compile-time variants of their own (four accumulators), the kernels
+       of a forward without the request are what they were.  Both launches of a split forward and a redone run-ahead frame honour it.
+       P == 0 launches nothing: the caller's buffer stands.  STP_ERR_INVALID_ARGUMENT with StpSettings::debug_visualization =
+       STP_DEBUG_DEPTH.  Consumed by the next stp_forward of the thread whatever its outcome; NULL clears a pending request.
+   stp_set_backward_invdepth -- the NEXT stp_backward / stp_backward_phases of the calling thread treats (1 / z_i, invdepth, dL_dinvdepth)
+       as a fourth channel of the render half's dL/dalpha sums -- the gradient reaches means2D, conics and opacities like a colour
+       gradient's -- and sums alpha * T * dL_dinvdepth per Gaussian into slot STP_GRAD_RECORD_INVDEPTH of its padded record; the
+       per-Gaussian half adds -slot / z_i^2 to dL/dt_z in front of dL_dmean3D and the camera gradients' partial sums (every visible
+       Gaussian, whatever its covariance path), and with phases bit 3 clears the slot behind its read.  dL_dcolor / dL_dsh get nothing
+       from it.  `invdepth` is the forward's output, `dL_dinvdepth` the loss gradient with respect to it (both H x W).  A backward
+       through invdepth alone passes an all-zero dL_dpix.
+   All three buffers are full-frame device buffers indexed by absolute pixel (W * y + x); with a tile-row window only the window's rows
+   are read or written.  The backward request is taken by the next stp_backward / stp_backward_phases of the thread whatever its
+   outcome, with the absgrad request's one exception: a render-only call (phases = 1) that succeeds leaves it pending for the
+   per-Gaussian call, which must then get those records.  Both pointers NULL clears a pending request.  STP_ERR_INVALID_ARGUMENT: only
+   one of the two pointers, compact records (phases bit 2: the 36-byte record has no slot 14), or a chunked per-Gaussian half (phases
+   bits 8-23: REFUSED, as absgrad is).  Independent of the camera, absgrad, blend-statistics and background requests. */
+void stp_set_forward_invdepth(float* out_invdepth /* H x W */);
+void stp_set_backward_invdepth(const float* invdepth /* the forward's, H x W */, const float* dL_dinvdepth /* H x W */);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:188-193, rasterizer_impl.cu:161-173).
    `present` is P bytes (bool). */
 int stp_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
@@ -349,7 +379,7 @@ size_t stp_blend_log_bytes_depth(int width, int height, int tile_y0, int tile_y1
 
 /* Introspection of the (otherwise opaque) scratch buffers, for parity tests and debugging.
    Fills byte offset and element count of a named sub-array; returns 0 or STP_ERR_INVALID_ARGUMENT.
-   geometry names: depths clamped radii rects2D means2D cov3D cov3D_inv conic_opacity rgb tiles_touched point_offsets
+   geometry names: depths clamped radii rects2D means2D cov3D cov3D_inv conic_opacity rgb tiles_touched point_offsets invz
    binning names : point_list point_list_unsorted keys keys_unsorted
    image names   : final_T n_contrib ranges */
 int stp_geometry_layout(int P, const StpSettings* settings, const char* name, size_t* offset, size_t* count);

@@ -72,6 +72,8 @@ struct Api {
     decltype(&stp_set_backward_blend_stats) set_backward_blend_stats = nullptr;
     decltype(&stp_set_forward_background) set_forward_background = nullptr;
     decltype(&stp_set_backward_background) set_backward_background = nullptr;
+    decltype(&stp_set_forward_invdepth) set_forward_invdepth = nullptr;
+    decltype(&stp_set_backward_invdepth) set_backward_invdepth = nullptr;
     decltype(&stp_sparse_adam) sparse_adam = nullptr;
     decltype(&stp_photometric_workspace_floats) photometric_workspace_floats = nullptr;
     decltype(&stp_photometric_forward) photometric_forward = nullptr;
@@ -99,6 +101,8 @@ int load_library(const std::string& path)
     a.set_backward_blend_stats = reinterpret_cast<decltype(a.set_backward_blend_stats)>(dlsym(h, "stp_set_backward_blend_stats"));
     a.set_forward_background = reinterpret_cast<decltype(a.set_forward_background)>(dlsym(h, "stp_set_forward_background"));
     a.set_backward_background = reinterpret_cast<decltype(a.set_backward_background)>(dlsym(h, "stp_set_backward_background"));
+    a.set_forward_invdepth = reinterpret_cast<decltype(a.set_forward_invdepth)>(dlsym(h, "stp_set_forward_invdepth"));
+    a.set_backward_invdepth = reinterpret_cast<decltype(a.set_backward_invdepth)>(dlsym(h, "stp_set_backward_invdepth"));
     a.sparse_adam = reinterpret_cast<decltype(a.sparse_adam)>(dlsym(h, "stp_sparse_adam"));
     a.photometric_workspace_floats = reinterpret_cast<decltype(a.photometric_workspace_floats)>(dlsym(h, "stp_photometric_workspace_floats"));
     a.photometric_forward = reinterpret_cast<decltype(a.photometric_forward)>(dlsym(h, "stp_photometric_forward"));
@@ -284,13 +288,15 @@ bool per_pixel_background(const torch::Tensor& bg, int H, int W)
 // Returns (num_rendered, out_color (3,H,W), radii (P,) int32, geomBuffer, binningBuffer, imgBuffer, alpha).
 // alpha (extension, include/stp_raster.h: stp_set_forward_background): with alpha = true the last element is 1 - final_T, (1,H,W); an
 // undefined tensor otherwise.  A background of shape exactly (3,H,W) is composed per pixel.
-std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+// invdepth (extension, include/stp_raster.h: stp_set_forward_invdepth): with invdepth = true one more element behind alpha's: sum alpha T / z,
+// (1,H,W); an undefined tensor otherwise.
+std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors, const torch::Tensor& opacity,
                     const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier, const torch::Tensor& cov3D_precomp,
                     const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const torch::Tensor& inv_viewprojmatrix, const float tan_fovx,
                     const float tan_fovy, const int image_height, const int image_width, const torch::Tensor& sh, const int degree,
                     const torch::Tensor& campos, const bool prefiltered, const py::dict& settings, const bool render_depth, const bool debug,
-                    const bool record_log, const bool alpha)
+                    const bool record_log, const bool alpha, const bool invdepth)
 {
     need_library();
     TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must have dimensions (num_points, 3)");
@@ -308,6 +314,13 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
     if ((alpha || bg_pixels) && !g_api.set_forward_background) raise_no_background_export("stp_set_forward_background");
     torch::Tensor out_alpha; // (like the image: every pixel of the rendered tile rows is written)
     if (alpha) out_alpha = zero ? torch::zeros({1, H, W}, fopt) : torch::empty({1, H, W}, fopt);
+    if (invdepth) {
+        if (!g_api.set_forward_invdepth)
+            throw std::runtime_error("invdepth: the loaded libstp_raster.so does not export stp_set_forward_invdepth (a library built before the inverse-depth output): rebuild it");
+        if (render_depth) throw std::runtime_error("the inverse-depth output is not available with render_depth (the debug depth visualisation)");
+    }
+    torch::Tensor out_invdepth; // (like the image: every pixel of the rendered tile rows is written)
+    if (invdepth) out_invdepth = zero ? torch::zeros({1, H, W}, fopt) : torch::empty({1, H, W}, fopt);
     Resizer geom{torch::empty({0}, bopt), false, false, 0}, binning{torch::empty({0}, bopt), true, false, 1}, img{torch::empty({0}, bopt), true, false, 2};
     int rendered = 0;
     if (P != 0) {
@@ -327,6 +340,7 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
             py::gil_scoped_release nogil; // (the call blocks once, on the num_rendered hand-over)
             if (alpha || bg_pixels) // (consumed by the call below, on this thread)
                 g_api.set_forward_background(bg_pixels ? fptr(bg_) : nullptr, alpha ? out_alpha.data_ptr<float>() : nullptr);
+            if (invdepth) g_api.set_forward_invdepth(out_invdepth.data_ptr<float>());
             rc = g_api.forward(&Resizer::call, &geom, &Resizer::call, &binning, &Resizer::call, &img, P, degree, M, fptr(bg_), W, H, &s, fptr(m3_),
                              fptr(sh_), fptr(col_), fptr(op_), fptr(sc_), scale_modifier, fptr(ro_), fptr(c3_), fptr(vm_), fptr(pm_), fptr(inv_),
                              fptr(cam_), tan_fovx, tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(), radii.data_ptr<int>(), debug ? 1 : 0,
@@ -337,7 +351,7 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
         remember_storage(binning.t);
         remember_storage(img.t);
     }
-    return std::make_tuple(rendered, out_color, radii, geom.t, binning.t, img.t, out_alpha);
+    return std::make_tuple(rendered, out_color, radii, geom.t, binning.t, img.t, out_alpha, out_invdepth);
 }
 
 // == RasterizeGaussiansBackwardCUDA (reference rasterize_points.cu:140-232).
@@ -353,6 +367,9 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
 // dL_dalpha / bg_grad (extension, include/stp_raster.h: stp_set_backward_background): the gradient of the forward's alpha output (1,H,W), and one
 // more tensor, LAST in the result: dL/dbackground in the background's shape, (3,) or (3,H,W).  A background of shape exactly (3,H,W) is
 // the forward's per-pixel one.  Calls with the render half (phases bit 0).
+// dL_dinvdepth / invdepth (extension, include/stp_raster.h: stp_set_backward_invdepth): the gradient of the forward's inverse-depth output and
+// that output itself, both (1,H,W).  No extra result: the gradient arrives in the eight (and the camera's three).  Whole backwards on padded
+// records only.
 std::vector<torch::Tensor>
 rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& opacities,
                              const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
@@ -362,7 +379,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                              const py::dict& settings, const bool debug, const bool record_log, const int phases, const c10::optional<torch::Tensor>& partial,
                              const c10::optional<std::vector<torch::Tensor>>& outputs, const bool camera_grads, const bool absgrad, const bool blend_stats,
-                             const c10::optional<torch::Tensor>& dL_dalpha, const bool bg_grad)
+                             const c10::optional<torch::Tensor>& dL_dalpha, const bool bg_grad,
+                             const c10::optional<torch::Tensor>& dL_dinvdepth, const c10::optional<torch::Tensor>& invdepth)
 {
     need_library();
     TORCH_CHECK(means3D.is_cuda(), "diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
@@ -393,6 +411,14 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         if (!g_api.set_backward_background) raise_no_background_export("stp_set_backward_background");
         TORCH_CHECK(phases & 1, "alpha gradient / per-pixel background / background gradient belong to the render half (phases bit 0)");
         TORCH_CHECK(!have_dalpha || dL_dalpha->numel() == (int64_t)H * W, "dL_dalpha must have H * W elements");
+    }
+    const bool have_dinv = dL_dinvdepth.has_value() && dL_dinvdepth->defined();
+    if (have_dinv) {
+        if (!g_api.set_backward_invdepth)
+            throw std::runtime_error("invdepth: the loaded libstp_raster.so does not export stp_set_backward_invdepth (a library built before the inverse-depth output): rebuild it");
+        TORCH_CHECK((phases & 3) == 3, "the inverse-depth gradient needs both halves of the backward in one call (phases bits 0 and 1)");
+        TORCH_CHECK(invdepth.has_value() && invdepth->defined(), "dL_dinvdepth needs the forward's invdepth");
+        TORCH_CHECK(dL_dinvdepth->numel() == (int64_t)H * W && invdepth->numel() == (int64_t)H * W, "dL_dinvdepth and invdepth must have H * W elements");
     }
     const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
     const auto fopt = means3D.options().dtype(torch::kFloat32);
@@ -450,10 +476,13 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
     }
     if (have_dalpha) dal_ = prep(*dL_dalpha, dev);
     if (bg_pixels) bgpix_ = prep(background, dev);
+    torch::Tensor dinv_, inv_out_;
+    if (have_dinv) { dinv_ = prep(*dL_dinvdepth, dev); inv_out_ = prep(*invdepth, dev); }
     auto make_requests = [&] { // (all are consumed by the library call that follows, on this thread)
         if ((bg_pixels || have_dalpha || bg_grad) && P != 0)
             g_api.set_backward_background(bg_pixels ? bgpix_.data_ptr<float>() : nullptr, have_dalpha ? dal_.data_ptr<float>() : nullptr,
                                           bg_grad ? dL_dbg.data_ptr<float>() : nullptr);
+        if (have_dinv && P != 0) g_api.set_backward_invdepth(inv_out_.data_ptr<float>(), dinv_.data_ptr<float>());
         if (blend_stats && P != 0) g_api.set_backward_blend_stats(stats.data_ptr<float>());
         if (absgrad && P != 0) g_api.set_backward_absgrad(dL_dmeans2D_abs.data_ptr<float>());
         if (camera_grads) g_api.set_backward_camera_grads(dL_dview.data_ptr<float>(), dL_dproj.data_ptr<float>(), dL_dcam.data_ptr<float>(), cam_ws.data_ptr(), (size_t)cam_ws.numel());

@@ -55,7 +55,8 @@ void fill_frame(FrameParams& f, int P, int D, int M, const float* background, in
 // ---- the one-shot requests of the calling thread: set by the stp_set_* calls below, each taken by the next call it is meant for.  ALL of
 // ---- them live in this one struct, and the two functions below are the only ones that take them.
 struct BackwardBackground { const float* bg_image = nullptr; const float* dL_dalpha = nullptr; float* dL_dbackground = nullptr; }; // stp_set_backward_background
-struct BackwardRequests { CameraGradRequest cam; float* absgrad = nullptr; float* blend_stats = nullptr; BackwardBackground background; };
+struct BackwardInvdepth { const float* invdepth = nullptr; const float* dL_dinvdepth = nullptr; }; // stp_set_backward_invdepth
+struct BackwardRequests { CameraGradRequest cam; float* absgrad = nullptr; float* blend_stats = nullptr; BackwardBackground background; BackwardInvdepth invdepth; };
 struct PendingRequests { ForwardRequests forward; BackwardRequests backward; };
 static thread_local PendingRequests t_pending;
 
@@ -67,7 +68,7 @@ ForwardRequests take_forward_requests() { return std::exchange(t_pending.forward
 //       bit 1 leaves them pending.
 //   backward background: consumed by the next backward that runs the render half (phases bit 0), whatever its outcome.  A call without
 //       bit 0 leaves it pending (nothing of it lives in the gradient records).
-//   absgrad and blend statistics: taken by EVERY backward, and BOTH before either one's checks, so a call that is refused for one leaves
+//   absgrad, blend statistics and inverse depth: taken by EVERY backward, and BOTH before either one's checks, so a call that is refused for one leaves
 //       neither behind.  stp_backward_phases puts them back (keep_for_per_gaussian_call) only at the end of a render-only call
 //       (!(phases & 2)) that ran to its end: the sums are in the records then, and the per-Gaussian call collects them.  A call that
 //       fails, or has nothing to do, leaves no pointer behind.
@@ -77,10 +78,14 @@ static BackwardRequests take_backward_requests(int phases)
     BackwardRequests r;
     if (phases & 2) r.cam = std::exchange(p.cam, CameraGradRequest{});
     r.absgrad = std::exchange(p.absgrad, nullptr); r.blend_stats = std::exchange(p.blend_stats, nullptr);
+    r.invdepth = std::exchange(p.invdepth, BackwardInvdepth{});
     if (phases & 1) r.background = std::exchange(p.background, BackwardBackground{});
     return r;
 }
-static void keep_for_per_gaussian_call(const BackwardRequests& r) { t_pending.backward.absgrad = r.absgrad; t_pending.backward.blend_stats = r.blend_stats; }
+static void keep_for_per_gaussian_call(const BackwardRequests& r)
+{
+    t_pending.backward.absgrad = r.absgrad; t_pending.backward.blend_stats = r.blend_stats; t_pending.backward.invdepth = r.invdepth;
+}
 
 } // namespace stp
 
@@ -104,6 +109,8 @@ void stp_set_backward_camera_grads(float* dL_dviewmatrix, float* dL_dprojmatrix,
 void stp_set_backward_absgrad(float* dL_dmean2D_abs) { t_pending.backward.absgrad = dL_dmean2D_abs; }
 void stp_set_backward_blend_stats(float* blend_stats) { t_pending.backward.blend_stats = blend_stats; }
 void stp_set_backward_background(const float* bg_image, const float* dL_dalpha, float* dL_dbackground) { t_pending.backward.background = BackwardBackground{bg_image, dL_dalpha, dL_dbackground}; }
+void stp_set_forward_invdepth(float* out_invdepth) { t_pending.forward.out_invdepth = out_invdepth; }
+void stp_set_backward_invdepth(const float* invdepth, const float* dL_dinvdepth) { t_pending.backward.invdepth = BackwardInvdepth{invdepth, dL_dinvdepth}; }
 
 namespace {
 // Scratch of the uniform background gradient's two-stage sum (stp_background.hip): a small ring of partial-row buffers per device, made at the
@@ -164,6 +171,15 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
         if (((phases >> 8) & 0xFF) > 1)
             return fail(STP_ERR_INVALID_ARGUMENT, "blend statistics are not available from a chunked per-Gaussian half (phases bits 8-23)");
     }
+    const BackwardInvdepth& binv = req.invdepth;
+    if (binv.invdepth || binv.dL_dinvdepth) {
+        if (!binv.invdepth || !binv.dL_dinvdepth)
+            return fail(STP_ERR_INVALID_ARGUMENT, "inverse depth: the forward's invdepth and dL_dinvdepth must both be given");
+        if (phases & 4)
+            return fail(STP_ERR_INVALID_ARGUMENT, "the inverse-depth gradient is not available with compact gradient records (phases bit 2): the 36-byte record has no room for the extra sum");
+        if (((phases >> 8) & 0xFF) > 1)
+            return fail(STP_ERR_INVALID_ARGUMENT, "the inverse-depth gradient is not available from a chunked per-Gaussian half (phases bits 8-23)");
+    }
     if (cam.dL_dview) {
         if (!cam.workspace || (reinterpret_cast<uintptr_t>(cam.workspace) & 15) != 0 || cam.workspace_bytes < camera_grad_workspace_bytes(P))
             return fail(STP_ERR_INVALID_ARGUMENT, "camera gradients: the workspace is null, not 16-byte aligned or smaller than stp_camera_grad_workspace_bytes(P)");
@@ -202,6 +218,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     bw.absgrad = absgrad;
     bw.blend_stats = blend_stats;
     bw.bg_image = bbg.bg_image; bw.dL_dalpha = bbg.dL_dalpha; bw.dL_dbackground = bbg.dL_dbackground;
+    bw.invdepth = binv.invdepth; bw.dL_dinvdepth = binv.dL_dinvdepth;
     bw.pixel_colors = pixel_colors; bw.dL_dpix = dL_dpix; bw.dL_dmean2D = dL_dmean2D; bw.grad_rec = grad_records;
     bw.grad_stride = (phases & 4) ? STP_GRAD_RECORD_USED : STP_GRAD_RECORD_FLOATS;
     bw.clear_rec = (phases & 8) ? 1 : 0;

@@ -65,7 +65,10 @@ __device__ __forceinline__ float opaque(float v)
 // TERMS = true: the same chain rule evaluated for this Gaussian's camera terms only (cg[kCamTerms]): nothing is stored, and every input is
 // read through opaque(), so none of its arithmetic is shared with -- or changes the instruction selection of -- the TERMS = false pass that
 // writes the Gaussian's gradients (bit-identical with and without a camera request).
-template <bool TERMS>
+// INVD: the inverse-depth request (stp_set_backward_invdepth): slot STP_GRAD_RECORD_INVDEPTH of the record holds dL/d(1/z) of the Gaussian,
+// z = t.z the view-space depth of its centre; -slot / z^2 joins dL/dt_z in front of dL/dmean and the camera terms.  INVD = false is the
+// function as it was.
+template <bool TERMS, bool INVD>
 __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, float* sh_row, float* cg)
 {
     const float* __restrict__ view = a.view;
@@ -96,6 +99,12 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         rec0 = make_float4(opaque(rec0.x), opaque(rec0.y), opaque(rec0.z), opaque(rec0.w));
         rec1 = make_float4(opaque(rec1.x), opaque(rec1.y), opaque(rec1.z), opaque(rec1.w));
         rec_op = opaque(rec_op);
+    }
+    float rec_invz = 0.0f;
+    if constexpr (INVD) { // (padded records only: the caller has refused compact ones with the request)
+        rec_invz = a.grad_rec[16 * (size_t)idx + STP_GRAD_RECORD_INVDEPTH];
+        if constexpr (TERMS) rec_invz = opaque(rec_invz);
+        else if (a.clear_rec) const_cast<float*>(a.grad_rec)[16 * (size_t)idx + STP_GRAD_RECORD_INVDEPTH] = 0.0f;
     }
     if (!TERMS && a.clear_rec) { // only records of visible Gaussians are ever written by the render half, and all of those pass through here
         float* const r = const_cast<float*>(a.grad_rec) + (size_t)a.grad_stride * idx;
@@ -208,7 +217,9 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         const float tz = 1.f / t.z, tz2 = tz * tz, tz3 = tz2 * tz;
         const float dL_dtx = x_grad_mul * -a.h_x * tz2 * dL_dJ02;
         const float dL_dty = y_grad_mul * -a.h_y * tz2 * dL_dJ12;
-        const float dL_dtz = -a.h_x * tz2 * dL_dJ00 - a.h_y * tz2 * dL_dJ11 + (2 * a.h_x * t.x) * tz3 * dL_dJ02 + (2 * a.h_y * t.y) * tz3 * dL_dJ12;
+        float dL_dtz_ = -a.h_x * tz2 * dL_dJ00 - a.h_y * tz2 * dL_dJ11 + (2 * a.h_x * t.x) * tz3 * dL_dJ02 + (2 * a.h_y * t.y) * tz3 * dL_dJ12;
+        if constexpr (INVD) dL_dtz_ -= rec_invz * tz2; // d(1/z)/dz = -1 / z^2 (every visible Gaussian: no clamp mask on this path)
+        const float dL_dtz = dL_dtz_;
         dmean.x = view[0] * dL_dtx + view[1] * dL_dty + view[2] * dL_dtz;
         dmean.y = view[4] * dL_dtx + view[5] * dL_dty + view[6] * dL_dtz;
         dmean.z = view[8] * dL_dtx + view[9] * dL_dty + view[10] * dL_dtz;
@@ -386,7 +397,7 @@ __device__ __forceinline__ float wave_sum(float v) // every lane ends with the s
     return v;
 }
 
-template <bool CAM>
+template <bool CAM, bool INVD>
 __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreArgs a)
 {
     extern __shared__ float s_rows[]; // [256][3M + 1]
@@ -428,9 +439,9 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreAr
                 // opaque branch: the gradient pass below is the CAM = false kernel's, arithmetic for arithmetic
                 int go = 1;
                 asm volatile("" : "+s"(go));
-                if (go) gaussian_backward<true>(a, idx, s_rows + tid * row_stride, cg);
+                if (go) gaussian_backward<true, INVD>(a, idx, s_rows + tid * row_stride, cg);
             }
-            gaussian_backward<false>(a, idx, s_rows + tid * row_stride, cg);
+            gaussian_backward<false, INVD>(a, idx, s_rows + tid * row_stride, cg);
         } else { // invisible: all gradients are zero
             a.dL_dcolor[3 * (size_t)idx] = 0.0f; a.dL_dcolor[3 * (size_t)idx + 1] = 0.0f; a.dL_dcolor[3 * (size_t)idx + 2] = 0.0f;
             a.dL_dmean2D[3 * (size_t)idx] = 0.0f; a.dL_dmean2D[3 * (size_t)idx + 1] = 0.0f;
@@ -610,7 +621,9 @@ hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState&
     a.dL_dmean2D = bw.dL_dmean2D; a.grad_rec = bw.grad_rec; a.grad_stride = bw.grad_stride; a.clear_rec = bw.clear_rec; a.dL_dopacity = bw.dL_dopacity; a.dL_dcolor = bw.dL_dcolor;
     a.dL_dmean3D = bw.dL_dmean3D; a.dL_dcov3D = bw.dL_dcov3D; a.dL_dsh = bw.dL_dsh; a.dL_dscale = bw.dL_dscale; a.dL_drot = bw.dL_drot;
     a.cam_rows = cam ? reinterpret_cast<float*>(bw.cam.workspace) : nullptr;
-    const void* kernel = cam ? reinterpret_cast<const void*>(preprocess_backward_kernel<true>) : reinterpret_cast<const void*>(preprocess_backward_kernel<false>);
+    const bool invd = bw.dL_dinvdepth != nullptr; // (stp_set_backward_invdepth; the caller has refused a chunked half and compact records with it: slot 14 exists)
+    const void* kernel = cam ? (invd ? reinterpret_cast<const void*>(preprocess_backward_kernel<true, true>) : reinterpret_cast<const void*>(preprocess_backward_kernel<true, false>))
+                             : (invd ? reinterpret_cast<const void*>(preprocess_backward_kernel<false, true>) : reinterpret_cast<const void*>(preprocess_backward_kernel<false, false>));
     const size_t lds = (a.shs != nullptr && a.M > 0) ? (size_t)256 * (3 * a.M + 1) * sizeof(float) : 0;
     if (lds > 64 * 1024) { // above the default dynamic-LDS limit (M > 21: no SH degree the reference knows)
         hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -635,12 +648,14 @@ hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState&
         if (e != hipSuccess) return e;
     }
     if (cam) {
-        hipLaunchKernelGGL(preprocess_backward_kernel<true>, dim3(b1 - b0), dim3(256), lds, st, a);
+        if (invd) hipLaunchKernelGGL((preprocess_backward_kernel<true, true>), dim3(b1 - b0), dim3(256), lds, st, a);
+        else hipLaunchKernelGGL((preprocess_backward_kernel<true, false>), dim3(b1 - b0), dim3(256), lds, st, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         return launch_camera_grad_finalize(f.P, bw.cam, st);
     }
-    hipLaunchKernelGGL(preprocess_backward_kernel<false>, dim3(b1 - b0), dim3(256), lds, st, a);
+    if (invd) hipLaunchKernelGGL((preprocess_backward_kernel<false, true>), dim3(b1 - b0), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((preprocess_backward_kernel<false, false>), dim3(b1 - b0), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

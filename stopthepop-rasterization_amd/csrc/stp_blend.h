@@ -9,7 +9,7 @@
 
 namespace stp {
 
-constexpr int REQ_ABSGRAD = 1, REQ_BLEND_STATS = 2; // RenderArgs::requests
+constexpr int REQ_ABSGRAD = 1, REQ_BLEND_STATS = 2, REQ_INVDEPTH = 4; // RenderArgs::requests
 
 // Pointers every render kernel needs (by value in the kernarg segment).
 struct RenderArgs {
@@ -64,6 +64,12 @@ struct RenderArgs {
     const float* bg_image;  // 3 x H x W, replaces bg[ch] for its pixel
     float* out_alpha;       // H x W, forward: 1 - final_T
     const float* dL_dalpha; // H x W, backward: subtracted from the pixel's weight of T_final
+    // inverse-depth output (stp_set_forward_invdepth, stp_set_backward_invdepth): all nullptr without a request.  The forward's INVD variants
+    // blend D += alpha T invz[id] and write out_invdepth; the backward kernels (REQ_INVDEPTH) read the pixel's D_final and dL/dD.
+    const float* invz;         // P: 1 / view-space z per Gaussian (GeometryState::invz)
+    float* out_invdepth;       // H x W, forward
+    const float* invdepth;     // H x W, backward: the forward's output
+    const float* dL_dinvdepth; // H x W, backward
 };
 
 // A log record is a 16-bit list position (measured on C2: 2-byte records cost the forward 0.05 ms less than 4-byte
@@ -170,6 +176,8 @@ struct FwdPixel {
     float T;
     float C[3];
 };
+// the accumulator the INVD forward variants carry beside the colour: D = sum alpha T / z (no background term)
+struct FwdDepth { float D = 0.0f; };
 
 struct BwdPixel {
     float T_final;
@@ -178,6 +186,8 @@ struct BwdPixel {
     float bg_dot; // dL/dT_final = sum_ch bg[ch] * dL_dpix[ch]  (- dL_dalpha with an alpha gradient)
     float T;
     float C[3];
+    // INVD instantiations only (the inverse-depth request): the fourth channel's final value, its gradient and running sum
+    float D_final, dL_dD, D;
 };
 
 __device__ __forceinline__ void init_fwd_pixel(FwdPixel& p)
@@ -186,6 +196,10 @@ __device__ __forceinline__ void init_fwd_pixel(FwdPixel& p)
     p.C[0] = p.C[1] = p.C[2] = 0.0f;
 }
 
+// INVD (here and below): the kernel is an instantiation for the inverse-depth request (stp_set_backward_invdepth, REQ_INVDEPTH) -- a compile-time
+// flag, so that the kernels of a backward without the request are what they were, register for register.  INVD = false never touches the
+// three extra members of BwdPixel or FrontData::z.
+template <bool INVD = false>
 __device__ __forceinline__ void init_bwd_pixel(BwdPixel& b, const RenderArgs& a, bool inside, int px, int py)
 {
     const size_t N = (size_t)a.W * a.H;
@@ -212,15 +226,22 @@ __device__ __forceinline__ void init_bwd_pixel(BwdPixel& b, const RenderArgs& a,
         }
     }
     if (a.dL_dalpha != nullptr) b.bg_dot -= inside ? a.dL_dalpha[pid] : 0.0f; // alpha = 1 - T_final
+    if constexpr (INVD) { // a fourth channel without a background: D_final is the forward's output as it is
+        b.D = 0.0f;
+        b.D_final = inside ? a.invdepth[pid] : 0.0f;
+        b.dL_dD = inside ? a.dL_dinvdepth[pid] : 0.0f;
+    }
 }
 
 // The largest factor the pixel's gradient terms are linear in: |dL_dpix| and, with an alpha gradient, |dL_dalpha| (which enters through
 // bg_dot) -- what the on-chip gradient windows of the replay and hierarchical backward size their fixed point by.  Without the alpha
 // gradient it is the colour gradients' maximum as before; a loss on alpha alone (dL_dpix all zero) would otherwise leave the scale at 0.
+template <bool INVD = false>
 __device__ __forceinline__ float bwd_pixel_scale(const BwdPixel& b, const RenderArgs& a, bool inside, int px, int py)
 {
     float md = fmaxf(fmaxf(fabsf(b.dL_dpix[0]), fabsf(b.dL_dpix[1])), fabsf(b.dL_dpix[2]));
     if (a.dL_dalpha != nullptr) md = fmaxf(md, inside ? fabsf(a.dL_dalpha[(size_t)a.W * py + px]) : 0.0f);
+    if constexpr (INVD) md = fmaxf(md, fabsf(b.dL_dD)); // (a loss on the inverse depth alone would leave the scale at 0 as well)
     return md;
 }
 
@@ -240,17 +261,20 @@ __device__ __forceinline__ bool blend_forward_c(FwdPixel& p, const float (&c)[3]
 // Produces the nine per-Gaussian terms g[0..2] = dL/dcolour, g[3..4] = dL/dmean2D (x,y),
 // g[5..7] = dL/dconic (xx, xy, yy), g[8] = dL/dopacity; the caller decides how they are accumulated.
 // Returns false (and leaves g untouched) when the pixel saturates.
-struct FrontData { float4 co; float2 xy; float c[3]; }; // what a backward blend reads of its Gaussian
+struct FrontData { float4 co; float2 xy; float c[3]; float z; }; // what a backward blend reads of its Gaussian (z = 1 / view-space z: INVD only)
 
+template <bool INVD = false>
 __device__ __forceinline__ FrontData load_front(const RenderArgs& a, int id)
 {
     FrontData f;
     f.co = a.conic_opacity[id];
     f.xy = a.means2D[id];
     f.c[0] = a.features[3 * (size_t)id + 0]; f.c[1] = a.features[3 * (size_t)id + 1]; f.c[2] = a.features[3 * (size_t)id + 2];
+    if constexpr (INVD) f.z = a.invz[id];
     return f;
 }
 
+template <bool INVD = false>
 __device__ __forceinline__ bool blend_backward_terms(BwdPixel& b, const RenderArgs& a, int px, int py, const FrontData& fd, float G, float (&g)[9])
 {
     const float4 co = fd.co;
@@ -272,6 +296,11 @@ __device__ __forceinline__ bool blend_backward_terms(BwdPixel& b, const RenderAr
         const float accum_rec = (b.final_color[ch] - b.C[ch]) * rcp_test_T;
         dL_dalpha += (c - accum_rec) * b.dL_dpix[ch];
         g[ch] = dchannel_dcolor * b.dL_dpix[ch];
+    }
+    if constexpr (INVD) { // the fourth channel (1 / z, D_final, dL/dD): the same expressions, no background share
+        b.D += fd.z * alpha * b.T;
+        const float accum_rec = (b.D_final - b.D) * rcp_test_T;
+        dL_dalpha += (fd.z - accum_rec) * b.dL_dD;
     }
     dL_dalpha *= b.T;
     dL_dalpha += (-b.T_final * rcp_1ma) * b.bg_dot;
@@ -320,22 +349,27 @@ __device__ __forceinline__ void add_blend_stats(const RenderArgs& a, int id, flo
     max_blend_weight(a, id, w);
     atomicAdd(grad_slot(a, id, GRAD_STATS + 2), 1.0f);
 }
+// the one sum of the inverse-depth request, straight to memory: dL/d(1/z) of ONE blended pair = its blend weight times the pixel's dL/dD
+constexpr int GRAD_INVDEPTH = STP_GRAD_RECORD_INVDEPTH;
+__device__ __forceinline__ void add_invdepth(const RenderArgs& a, int id, float w_dL) { atomicAdd(grad_slot(a, id, GRAD_INVDEPTH), w_dL); }
 // w of the pair blend_backward_terms() has just accepted (T_before = the pixel's transmittance in front of it): the expression of its
 // dchannel_dcolor, to the same bits
 __device__ __forceinline__ float blend_weight(float T_before, float opacity, float G) { return fminf(0.99f, opacity * G) * T_before; }
 
 // Straightforward accumulation: nine hardware fp32 atomics (global_atomic_add_f32; build with
 // -munsafe-fp-atomics) per blended pair -- what the reference does (hierarchical_render.cuh:1131-1161).
+template <bool INVD = false>
 __device__ __forceinline__ bool blend_backward(BwdPixel& b, const RenderArgs& a, int px, int py, int id, float G)
 {
     float g[9];
-    const FrontData fd = load_front(a, id);
+    const FrontData fd = load_front<INVD>(a, id);
     const float T_before = b.T;
-    if (!blend_backward_terms(b, a, px, py, fd, G, g)) return false;
+    if (!blend_backward_terms<INVD>(b, a, px, py, fd, G, g)) return false;
 #pragma unroll
     for (int k = 0; k < 9; k++) atomicAdd(grad_slot(a, id, k), g[k]);
     if (a.requests & REQ_ABSGRAD) add_absgrad(a, id, g);
     if (a.requests & REQ_BLEND_STATS) add_blend_stats(a, id, blend_weight(T_before, fd.co.w, G));
+    if constexpr (INVD) add_invdepth(a, id, blend_weight(T_before, fd.co.w, G) * b.dL_dD);
     return true;
 }
 

@@ -34,6 +34,7 @@ GeometryState carve_geometry(char* base, size_t P, bool with_inv, size_t* total,
     g.block_prefix = c.take<uint32_t>((P + 255) / 256, &off);
     g.scan_temp_bytes = scan_temp_bytes(P);
     g.scan_temp = c.take<char>(g.scan_temp_bytes);
+    g.invz = c.take<float>(P, &off); note("invz", off, P); // (behind everything else: the other sub-arrays are where they were)
     if (total) *total = c.total();
     if (n_names) *n_names = n;
     return g;

@@ -421,6 +421,8 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
     if (int rc = check_settings(*settings, false)) return rc;
     if ((fbg.bg_image || fbg.out_alpha) && settings->debug_visualization == STP_DEBUG_DEPTH)
         return fail(STP_ERR_INVALID_ARGUMENT, "alpha output / per-pixel background (stp_set_forward_background) are not available with the debug depth visualisation: its image is not C + T * background");
+    if (req.out_invdepth && settings->debug_visualization == STP_DEBUG_DEPTH)
+        return fail(STP_ERR_INVALID_ARGUMENT, "the inverse-depth output (stp_set_forward_invdepth) is not available with the debug depth visualisation");
     if (!colors_precomp && !shs) return fail(STP_ERR_INVALID_ARGUMENT, "neither SHs nor precomputed colours given");
     if (!cov3D_precomp && !(scales && rotations)) return fail(STP_ERR_INVALID_ARGUMENT, "neither scale/rotation nor precomputed covariance given");
     const bool with_inv = requires_depth_along_ray(*settings);
@@ -429,6 +431,7 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
     FrameParams& f = c.f;
     fill_frame(f, P, D, M, background, width, height, *settings, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
                rotations, cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered);
+    f.out_invdepth = req.out_invdepth;
     f.bg_image = fbg.bg_image; f.out_alpha = fbg.out_alpha; // (every render launch of the call: both halves of a split forward, a redone run-ahead frame)
     if (int rc = c.carve_geometry_and_image(geometry_alloc, geometry_user, image_alloc, image_user, with_inv)) return rc;
 

@@ -82,6 +82,7 @@ struct GeometryState {
     uint32_t* block_prefix;  // ceil(P / 256)
     char* scan_temp;
     size_t scan_temp_bytes;
+    float* invz;             // P: 1 / view-space z of the visible Gaussians; written only by a forward with the inverse-depth request (LAST in the carve)
 };
 
 struct ImageState { // reference ImageState, rasterizer_impl.cu:195-202 (ranges sized per tile, not per pixel)
@@ -176,6 +177,7 @@ struct FrameParams {
     int fused_gather = 0; // forward: the hierarchical render kernel sorts and gathers the tiles of up to TS_SMALL entries itself (RenderArgs::fused_gather), tile_sort_gather_kernel only the longer ones
     const float* bg_image = nullptr; // forward, stp_set_forward_background: per-pixel background (3 x H x W) in the place of `background`
     float* out_alpha = nullptr;      // ... and where the render kernels also write alpha = 1 - final_T (H x W)
+    float* out_invdepth = nullptr;   // forward, stp_set_forward_invdepth: the render kernels' INVD variants also write sum(alpha T / z) (H x W); preprocess keeps 1 / z
     int wild_cov; // forward, after the status read-back: some visible Gaussian has a Sigma^-1 entry >= 1e36 or not finite (depth keys then take the reciprocal with its domain check)
 };
 
@@ -199,6 +201,10 @@ struct BackwardParams {
     const float* bg_image = nullptr;
     const float* dL_dalpha = nullptr;
     float* dL_dbackground = nullptr;
+    // stp_set_backward_invdepth (both nullptr = no request): the forward's inverse-depth image and the loss gradient with respect to it.  The
+    // render half takes them as a fourth channel and sums alpha T dL per Gaussian into record slot 14, the per-Gaussian half chains it to t_z
+    const float* invdepth = nullptr;
+    const float* dL_dinvdepth = nullptr;
     const float* pixel_colors;
     const float* dL_dpix;
     float* grad_rec;    // P x grad_stride: written by the render half, read by the per-Gaussian half
@@ -225,7 +231,7 @@ void fill_frame(FrameParams& f, int P, int D, int M, const float* background, in
 // ---- the one-shot per-thread requests (stp_api.hip: the stp_set_* setters, and the rules by which a call takes them) ----
 struct ForwardSplit { int row = 0; hipEvent_t event = nullptr; bool armed = false; };      // stp_set_forward_split
 struct ForwardBackground { const float* bg_image = nullptr; float* out_alpha = nullptr; }; // stp_set_forward_background
-struct ForwardRequests { ForwardSplit split; ForwardBackground background; };
+struct ForwardRequests { ForwardSplit split; ForwardBackground background; float* out_invdepth = nullptr; /* stp_set_forward_invdepth */ };
 ForwardRequests take_forward_requests();
 
 // ---- launchers (one per stage; each returns hipSuccess or the launch error) ----

@@ -332,6 +332,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(const PreArgs a)
     a.g.means2D[idx] = mean2D;
     a.g.conic_opacity[idx] = co;
     a.g.tiles_touched[idx] = (uint32_t)tile_count;
+    if (a.g.invz != nullptr) a.g.invz[idx] = 1.0f / pv.z; // inverse-depth request only (stp_set_forward_invdepth): one IEEE division, pv.z > 0.2
     if (a.g.gpack != nullptr) { // the same values once more, as one 64-byte line per Gaussian (see gather_entries_kernel)
         const float4 s0 = a.g.cov3D_inv[3 * (size_t)idx + 0], s1 = a.g.cov3D_inv[3 * (size_t)idx + 1], s2 = a.g.cov3D_inv[3 * (size_t)idx + 2];
         float4* const gp = a.g.gpack + 4 * (size_t)idx;
@@ -673,6 +674,7 @@ hipError_t launch_preprocess(const FrameParams& f, const GeometryState& g, int* 
     a.means3D = f.means3D; a.scales = f.scales; a.rotations = f.rotations; a.opacities = f.opacities; a.shs = f.shs;
     a.cov3D_precomp = f.cov3D_precomp; a.colors_precomp = f.colors_precomp; a.view = f.viewmatrix; a.proj = f.projmatrix; a.cam = f.cam_pos;
     a.radii = radii; a.g = g; a.tile_counts = tile_counts;
+    if (f.out_invdepth == nullptr) a.g.invz = nullptr; // (written only under the request)
     hipLaunchKernelGGL(preprocess_kernel, dim3((f.P + 255) / 256), dim3(256), 0, st, a);
     return hipGetLastError();
 }

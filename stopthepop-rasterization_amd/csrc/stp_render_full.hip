@@ -29,8 +29,11 @@ __device__ __forceinline__ float ordered_to_float(uint32_t o)
     return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
 
+// INVD: the inverse-depth request (stp_set_forward_invdepth): D += alpha T / z beside the colour; INVD = false is the kernel as it was
+template <bool INVD>
 __global__ void __launch_bounds__(256) render_full_fwd_kernel(const RenderArgs a)
 {
+    __shared__ float s_invz[INVD ? 256 : 1];
     __shared__ uint64_t s_key[1024];
     __shared__ float s_alpha[256];  // < 0: skipped entry, otherwise alpha
     __shared__ float s_col[3][256];
@@ -64,6 +67,7 @@ __global__ void __launch_bounds__(256) render_full_fwd_kernel(const RenderArgs a
             __syncthreads();
             for (int i = 0; i < 3; i++) s_key[256 * (i + 1) + tid] = make_key(i * 256 + tid); // slots 256..1023
             float T = 1.0f, C[3] = {0, 0, 0}, depth_acc = 0.0f;
+            float Dz = 0.0f; // (INVD)
             uint32_t contributor = 0, last_contributor = 0;
             bool done = false;
             int todo = total;
@@ -99,6 +103,7 @@ __global__ void __launch_bounds__(256) render_full_fwd_kernel(const RenderArgs a
                         s_col[0][tid] = a.features[3 * (size_t)id];
                         s_col[1][tid] = a.features[3 * (size_t)id + 1];
                         s_col[2][tid] = a.features[3 * (size_t)id + 2];
+                        if constexpr (INVD) s_invz[tid] = a.invz[id];
                     }
                     s_alpha[tid] = alpha;
                     if (tid == 0) s_stop = 256;
@@ -116,6 +121,7 @@ __global__ void __launch_bounds__(256) render_full_fwd_kernel(const RenderArgs a
                         if (test_T < T_THRESHOLD) { done = true; continue; }
                         for (int ch = 0; ch < 3; ch++) C[ch] += s_col[ch][idx] * alpha * T;
                         if (a.debug_depth) depth_acc += ordered_to_float((uint32_t)(s_key[idx] >> 32)) * alpha * T; // reference resorted_render.cuh:647
+                        if constexpr (INVD) Dz += s_invz[idx] * alpha * T;
                         T = test_T;
                         last_contributor = contributor;
                     }
@@ -126,6 +132,7 @@ __global__ void __launch_bounds__(256) render_full_fwd_kernel(const RenderArgs a
                 const size_t pid = (size_t)a.W * py + px;
                 a.final_T[pid] = T;
                 a.n_contrib[pid] = last_contributor;
+                if constexpr (INVD) a.out_invdepth[pid] = Dz;
                 if (a.debug_depth) { a.out_color[pid] = depth_acc; a.out_color[N + pid] = T; }
                 else {
                     if (a.out_alpha != nullptr) a.out_alpha[pid] = 1.0f - T; // (stp_set_forward_background; see write_forward_pixel)
@@ -141,7 +148,8 @@ __global__ void __launch_bounds__(256) render_full_fwd_kernel(const RenderArgs a
 struct RenderArgs;
 hipError_t launch_full_fwd(const FrameParams& f, const RenderArgs& a, hipStream_t st)
 {
-    hipLaunchKernelGGL(render_full_fwd_kernel, dim3(f.gx * (f.ty1 - f.ty0)), dim3(256), 0, st, a);
+    if (a.out_invdepth != nullptr) hipLaunchKernelGGL(render_full_fwd_kernel<true>, dim3(f.gx * (f.ty1 - f.ty0)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(render_full_fwd_kernel<false>, dim3(f.gx * (f.ty1 - f.ty0)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

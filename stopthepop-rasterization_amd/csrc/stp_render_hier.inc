@@ -100,23 +100,42 @@ struct HierLds { // dynamic-LDS carve, per workgroup (16 sub-tiles)
     static __host__ __device__ constexpr size_t ring(int MID) { return dirty(MID) + (size_t)BWD_WIN * 4; }
     static __host__ __device__ constexpr size_t ring_cs(int MID) { return ring(MID) + (size_t)BWD_RING * 4; }
     static __host__ __device__ constexpr size_t wave_mask(int MID) { return ring_cs(MID) + (size_t)BWD_RING * 4; }
-    static __host__ __device__ constexpr size_t total(int MID, int mode) { return mode == 1 ? wave_mask(MID) + 16 : hfifo(MID) + 64 * (size_t)HF_CAP * 4; }
+    static __host__ __device__ constexpr size_t total(int MID, int mode) { return (mode == 1 || mode == 6) ? wave_mask(MID) + 16 : hfifo(MID) + 64 * (size_t)HF_CAP * 4; }
 };
 
 // MODE: 0 = forward, 1 = backward by re-running the resort (the reference's scheme), 2 = forward that also records
 // every pixel's blend order (the training forward; its backward is the replay kernel of stp_render_replay.hip).
 // launch bounds: 4 waves per SIMD (<= 128 VGPRs) for the forward passes, 3 (<= 168) for the backward pass
 constexpr int MODE_FWD = 0, MODE_BWD = 1, MODE_FWD_RECORD = 2, MODE_FWD_DEPTH = 3; // 3: forward of the debug depth visualisation
+// 4 / 5: the forward / recording forward with the inverse-depth output (stp_set_forward_invdepth): a fourth accumulator D += alpha T / z.
+// Instantiations of their own, the default queue sizes' at four waves per SIMD (128 VGPRs): their five-wave build has no register to spare.
+// 6: the re-sorting backward with the fourth channel (stp_set_backward_invdepth).
+constexpr int MODE_FWD_INVD = 4, MODE_FWD_RECORD_INVD = 5, MODE_BWD_INVD = 6;
+constexpr bool mode_invd(int mode) { return mode == MODE_FWD_INVD || mode == MODE_FWD_RECORD_INVD || mode == MODE_BWD_INVD; }
+constexpr bool mode_bwd(int mode) { return mode == MODE_BWD || mode == MODE_BWD_INVD; }
+// waves per SIMD of the forwards with the inverse-depth output: sized so that none of them spills (the four extra registers do not fit
+// the budgets the plain forwards of the larger queues already overrun)
+constexpr int invd_fwd_waves(int head, bool frcp) { return (head == 4 && frcp) ? 4 : head <= 8 ? 3 : 2; }
+// waves per SIMD an instantiation is compiled for.  Backward: STP_BWD_WAVES; with the fourth channel two at heads 12 and 16, whose plain kernels
+// spill at three already (the variants do not).  Forward: five for the default queue sizes (STP_FWD_WAVES), otherwise four.
+constexpr int hier_waves(int head, int mid, int mode, bool frcp)
+{
+    if (mode == MODE_BWD_INVD) return head >= 12 ? 2 : STP_BWD_WAVES;
+    if (mode == MODE_BWD) return STP_BWD_WAVES;
+    if (mode_invd(mode)) return invd_fwd_waves(head, frcp);
+    return (head == 4 && mid == 8 && frcp) ? STP_FWD_WAVES : 4;
+}
 
 // FRCP: the frame's Sigma^-1 entries are all tame (stp_forward knows from preprocess_kernel's status word), the depth
 // keys' reciprocal needs no domain check (rcp_ieee<true>)
 template <int HEAD, int MID, bool CULL, int MODE, bool FRCP>
-__global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD == 4 && MID == 8 && FRCP) ? STP_FWD_WAVES : 4) render_hier_kernel(const RenderArgs a)
+__global__ void __launch_bounds__(256, hier_waves(HEAD, MID, MODE, FRCP)) render_hier_kernel(const RenderArgs a)
 {
+    constexpr bool INVD = mode_invd(MODE);
     // (the mid level's lane views from a fresh lane id: only where the register budget needs it -- five waves per SIMD WITH 4x4 culling, see STP_FWD_WAVES)
-    constexpr bool FRESH_QUAD = MODE != MODE_BWD && HEAD == 4 && MID == 8 && FRCP && STP_FWD_WAVES >= 5 && CULL;
-    constexpr bool BACKWARD = MODE == MODE_BWD;
-    constexpr bool RECORD = MODE == MODE_FWD_RECORD;
+    constexpr bool FRESH_QUAD = !mode_bwd(MODE) && !INVD && HEAD == 4 && MID == 8 && FRCP && STP_FWD_WAVES >= 5 && CULL;
+    constexpr bool BACKWARD = mode_bwd(MODE);
+    constexpr bool RECORD = MODE == MODE_FWD_RECORD || MODE == MODE_FWD_RECORD_INVD;
     constexpr bool DEPTHVIZ = MODE == MODE_FWD_DEPTH; // accumulate depth * alpha * T instead of colour (reference :1005-1008, stopthepop_common.cuh:264-282)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int OLDN = (MID - 4) / 4; // old mid entries owned per lane
@@ -147,10 +166,11 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         // run-ahead launch) the record arrays are uninitialised memory, and 0 x NaN is NaN (found by tools/fuzz_parity.py, round 5).
         if (range.y <= range.x) {
             if (inside) write_background_pixel<DEPTHVIZ, RECORD>(a, px, py);
+            if constexpr (INVD) { if (inside) a.out_invdepth[(size_t)a.W * py + px] = 0.0f; }
             return;
         }
     }
-    if constexpr (MODE == MODE_FWD || MODE == MODE_FWD_RECORD) {
+    if constexpr (MODE == MODE_FWD || MODE == MODE_FWD_RECORD || MODE == MODE_FWD_INVD || MODE == MODE_FWD_RECORD_INVD) {
         // Fused entry gather (RenderArgs::fused_gather): the workgroup sorts its tile's list and writes keys, list and entry records itself --
         // what tile_sort_gather_kernel<TS_SMALL> did in a launch of its own in front of this one, whose memory latency lay on the critical
         // path.  Here the other workgroups on the CU, busy blending, hide it.  The keys take the first 8 KB of the LDS carve, which nothing
@@ -293,7 +313,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     if constexpr (BACKWARD) head.init(); else head.init_padded(); // (forward passes: always-full queue, see Window::replace_front)
     FwdPixel fp;
     BwdPixel bp;
-    if constexpr (BACKWARD) init_bwd_pixel(bp, a, inside, px, py);
+    if constexpr (BACKWARD) init_bwd_pixel<INVD>(bp, a, inside, px, py);
     else init_fwd_pixel(fp);
 
     int n_tail = 0; // valid entries in my sub-tile's tail (uniform per 16-lane row)
@@ -322,7 +342,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     // (tests/torch_ref_colour_bound.py: Q; DESIGN.md section 4).
     float wave_md = 0.0f;
     if constexpr (BACKWARD) {
-        wave_md = bwd_pixel_scale(bp, a, inside, px, py);
+        wave_md = bwd_pixel_scale<INVD>(bp, a, inside, px, py);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) wave_md = fmaxf(wave_md, __shfl_xor(wave_md, off));
         // the window is shared by the four waves: one scale for the whole tile
@@ -410,7 +430,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         if (active && head.num > 0 && head.id[0] != front_key) {
             front_key = head.id[0];
             front_gid = to_id(front_key);
-            front_fd = load_front(a, front_gid);
+            front_fd = load_front<INVD>(a, front_gid);
         }
     };
     auto blend_front = [&]() __attribute__((always_inline)) { // reference :386-417
@@ -418,10 +438,12 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         float g[9];
         if (head.id[0] != front_key) refresh_front(); // not prefetched (cannot happen after a refresh; kept for safety)
         const float T_before = bp.T;
-        const bool ok = blend_backward_terms(bp, a, px, py, front_fd, head.store[0], g);
+        const bool ok = blend_backward_terms<INVD>(bp, a, px, py, front_fd, head.store[0], g);
         if (ok) accumulate(head.id[0], front_gid, g);
         // blend-statistics request (wave-uniform flag): this pair's blend weight goes to memory as it is, three atomics per blend
         if (ok && (a.requests & REQ_BLEND_STATS)) add_blend_stats(a, front_gid, blend_weight(T_before, front_fd.co.w, head.store[0]));
+        // inverse-depth request (MODE_BWD_INVD): alpha T dL/dD of this pair goes to memory as it is, one atomic per blend
+        if constexpr (INVD) if (ok) add_invdepth(a, front_gid, blend_weight(T_before, front_fd.co.w, head.store[0]) * bp.dL_dD);
         if (!ok) { active = false; head.num--; return; }
         head.pop();
     };
@@ -433,7 +455,17 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     float pend_w = 0.0f;
     float pend_c[3] = {0.0f, 0.0f, 0.0f};
     float depth_acc = 0.0f;
+    // INVD: 1 / z of the popped entry rides the same one-step-late product.  It comes by Gaussian id from the geometry buffer, and the id from
+    // the entry's record row C: two dependent loads, so the id is requested at the pop, 1 / z at the NEXT pop (the id has arrived by then)
+    // and its product is added at the pop after that -- two weights in flight (pend_w2: the entry pend_z belongs to).
+    float inv_D = 0.0f, pend_w2 = 0.0f, pend_z = 0.0f, pend_idf = 0.0f;
     auto pop_forward = [&]() __attribute__((always_inline)) { // consumes slot 0 of the always-full queue; replace_front() follows
+        if constexpr (INVD) {
+            inv_D = fmaf(pend_w2, pend_z, inv_D);
+            const float zl = a.invz[__float_as_int(pend_idf)]; // (a lane that did not blend holds a stand-in's id: a harmless load, weight and value zeroed)
+            pend_z = pend_w != 0.0f ? zl : 0.0f;
+            pend_w2 = pend_w;
+        }
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) fp.C[ch] = fmaf(pend_w, pend_c[ch], fp.C[ch]);
         const float alpha0 = head.store[0];
@@ -443,6 +475,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         const int pay = head.id[0]; // (never negative: pads carry position 0)
         const float4 colr = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(eF) + ((uint32_t)pay << 4)); // (uniform base + 32-bit offset; a pad reads entry 0: harmless, see pend_w)
         pend_c[0] = colr.x; pend_c[1] = colr.y; pend_c[2] = colr.z;
+        if constexpr (INVD) pend_idf = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(eC) + ((uint32_t)pay << 4) + 12); // (the entry's Gaussian id: the last word of row C)
         pend_w = upd ? alpha0 * fp.T : 0.0f;
         if constexpr (DEPTHVIZ) depth_acc += upd ? head.depth[0] * alpha0 * fp.T : 0.0f;
         fp.T = upd ? test_T : fp.T;
@@ -1016,6 +1049,11 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
         }
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) fp.C[ch] = fmaf(pend_w, pend_c[ch], fp.C[ch]); // the last popped entry
+        if constexpr (INVD) { // the last two popped entries
+            inv_D = fmaf(pend_w2, pend_z, inv_D);
+            const float zl = a.invz[__float_as_int(pend_idf)];
+            inv_D = fmaf(pend_w, pend_w != 0.0f ? zl : 0.0f, inv_D);
+        }
     }
 
     if constexpr (RECORD) {
@@ -1026,6 +1064,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_BWD ? STP_BWD_WAVES : (HEAD 
     }
     if constexpr (!BACKWARD) {
         if (inside) write_forward_pixel<DEPTHVIZ, false>(a, px, py, fp, depth_acc, 0u); // (n_contrib: not by the plain forward, reference :1019; the recording forward's is above)
+        if constexpr (INVD) { if (inside) a.out_invdepth[(size_t)a.W * py + px] = inv_D; }
     }
 }
 

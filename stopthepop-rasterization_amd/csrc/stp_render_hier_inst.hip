@@ -1,6 +1,7 @@
 // stp_render_hier_inst.hip -- one slice of the hierarchical kernel's instantiation ladder.
 // Compiled several times by the Makefile with -DSTP_INST_MID={8,12,20} -DSTP_INST_MODE={0,1,2}
-// (0 forward, 1 resorting backward, 2 recording forward, 3 depth-visualisation forward), so the
+// (0 forward, 1 resorting backward, 2 recording forward, 3 depth-visualisation forward, 4 / 5 forward / recording forward with the
+// inverse-depth output, 6 resorting backward with the inverse-depth gradient), so the
 // template instantiations (HEAD x CULL per slice) build in parallel.  Queue-size ladders follow the
 // reference: forward HEAD in {4,8,16} (forward.cu:465-472), backward HEAD in {4,8,12,16}
 // (backward.cu:745-752), MID in {8,12,20}.  -DSTP_FASTBUILD keeps only HEAD 4 (with MID 8), the
@@ -22,6 +23,12 @@
 #define STP_FN STP_CAT(launch_hier_rec_mid, STP_INST_MID)
 #elif STP_INST_MODE == 3
 #define STP_FN STP_CAT(launch_hier_dbg_mid, STP_INST_MID)
+#elif STP_INST_MODE == 4
+#define STP_FN STP_CAT(launch_hier_fwdz_mid, STP_INST_MID)
+#elif STP_INST_MODE == 5
+#define STP_FN STP_CAT(launch_hier_recz_mid, STP_INST_MID)
+#elif STP_INST_MODE == 6
+#define STP_FN STP_CAT(launch_hier_bwdz_mid, STP_INST_MID)
 #else
 #define STP_FN STP_CAT(launch_hier_fwd_mid, STP_INST_MID)
 #endif
@@ -33,7 +40,7 @@ hipError_t STP_FN(const FrameParams& f, const RenderArgs& a, hipStream_t st, boo
 {
     constexpr int MID = STP_INST_MID;
     constexpr int MODE = STP_INST_MODE;
-    constexpr bool BWD = MODE == 1;
+    constexpr bool BWD = MODE == 1 || MODE == 6;
     const int head = f.s.queue_per_pixel;
     const bool cull = f.s.hierarchical_4x4_culling != 0;
     *handled = true;

@@ -52,13 +52,20 @@ extern "C" int stp_debug_kb_stats(unsigned long long* out40)
 namespace {
 
 constexpr int KBW_FWD = 0, KBW_RECORD = 2, KBW_DEPTH = 3; // (the values of the hierarchical kernel's modes)
+constexpr int KBW_FWD_INVD = 4, KBW_RECORD_INVD = 5;      // the forward and the recording forward with the inverse-depth output (stp_set_forward_invdepth)
 
 // What the kernel body and a window policy share of a pixel: its blend state, its lists' record rows, and the record rows of the entry
 // at the FRONT of its window.  Neither window carries alpha: it is evaluated again at the pop, from the same record with the same
 // operations, hence to the same bits as when the entry passed its tests.  What the pop needs of the front entry -- mean, conic +
 // opacity, colour -- is fetched when the entry BECOMES the front, one step earlier.
 template <int MODE> struct KbPixel {
-    static constexpr bool RECORD = MODE == KBW_RECORD, DEPTHVIZ = MODE == KBW_DEPTH;
+    static constexpr bool RECORD = MODE == KBW_RECORD || MODE == KBW_RECORD_INVD, DEPTHVIZ = MODE == KBW_DEPTH;
+    // INVD: a fourth accumulator D += alpha T / z.  1 / z comes by Gaussian id (the front entry's record row C carries it) from the geometry
+    // buffer: the load is issued at the entry's blend and its product is added one blend later (or in the epilogue), like the hierarchical
+    // kernel's colour.  A lane that does not blend keeps (0, 0): the row it read may be a stand-in's.
+    static constexpr bool INVD = MODE == KBW_FWD_INVD || MODE == KBW_RECORD_INVD;
+    const float* invz;
+    float D, pend_w, pend_z;
     int lane, px, py;
     bool active;
     int total, list_last;
@@ -80,6 +87,12 @@ template <int MODE> struct KbPixel {
         const float wgt = upd ? alpha0 * fp.T : 0.0f;
         fp.C[0] = fmaf(wgt, frF.x, fp.C[0]); fp.C[1] = fmaf(wgt, frF.y, fp.C[1]); fp.C[2] = fmaf(wgt, frF.z, fp.C[2]);
         if constexpr (DEPTHVIZ) depth_acc += upd ? depth0 * alpha0 * fp.T : 0.0f; // reference resorted_render.cuh:107
+        if constexpr (INVD) {
+            D = fmaf(pend_w, pend_z, D);
+            const float zl = invz[__float_as_int(frC.w)];
+            pend_z = upd ? zl : 0.0f;
+            pend_w = wgt;
+        }
         fp.T = upd ? test_T : fp.T;
         if constexpr (RECORD) logc.append(upd, pay);
         else contrib = (doing && !upd) ? cfull : contrib;
@@ -90,7 +103,8 @@ template <int MODE> struct KbPixel {
 // ---- the window in REGISTERS: Window<WIN>'s always-full form, the hierarchical head level's step with HEAD = WIN ----------------------
 template <int WIN, int MODE, bool FRCP> struct KbRegWindow {
     static constexpr int FIFO_CAP = 32; // list positions a quad's FIFO may hold (one round of 16 survivors adds up to 16)
-    static constexpr int WAVES = WIN <= 4 ? 4 : WIN <= 16 ? 3 : 2; // waves per SIMD the kernel is compiled for
+    // waves per SIMD the kernel is compiled for; the inverse-depth variants (four more registers per lane) one fewer, so that none spills
+    static constexpr int WAVES = KbPixel<MODE>::INVD ? (WIN <= 4 ? 3 : 2) : WIN <= 4 ? 4 : WIN <= 16 ? 3 : 2;
     static constexpr bool DOUBLE_ROUND = WIN <= 8; // (two copies of the group step: fewer register shuffles per step)
     using Pixel = KbPixel<MODE>;
     Window<WIN> head;
@@ -157,7 +171,7 @@ template <int WIN, int MODE, bool FRCP> struct KbRegWindow {
 // What the pop needs of the front entry is fetched when the entry becomes the front, as above; alpha is evaluated again at the pop.
 template <int WIN, int MODE, bool FRCP> struct KbRingWindow {
     static constexpr int FIFO_CAP = 24; // (a round of 16 survivors adds up to 16; not a power of two: 40 KB of LDS = four workgroups per CU)
-    static constexpr int WAVES = WIN <= 16 ? 4 : 3; // (LDS: 40 KB per workgroup at 16 entries, 48 / 56 KB at 20 / 24)
+    static constexpr int WAVES = KbPixel<MODE>::INVD ? 3 : WIN <= 16 ? 4 : 3; // (LDS: 40 KB per workgroup at 16 entries, 48 / 56 KB at 20 / 24; the inverse-depth variants: three, none spills)
     static constexpr size_t RING_BYTES = (size_t)WIN * 256 * 8; // (depth, list position) [WIN][256]: slot-major, 8 bytes per thread
     static constexpr size_t LDS_BYTES = RING_BYTES + 16 * 32 * 4 + 64 * FIFO_CAP * 4;
     static constexpr bool DOUBLE_ROUND = false;
@@ -306,8 +320,9 @@ template <int WIN, int MODE, bool FRCP> struct KbRingWindow {
 template <int MODE, class WINDOW>
 __device__ __forceinline__ void render_kbuffer_body(const RenderArgs& a, WINDOW& win, int* const s_stage /* [sub-tile][survivor] */, int* const s_fifo /* [quad][slot] */)
 {
-    constexpr bool RECORD = MODE == KBW_RECORD;
+    constexpr bool RECORD = KbPixel<MODE>::RECORD;
     constexpr bool DEPTHVIZ = MODE == KBW_DEPTH;
+    constexpr bool INVD = KbPixel<MODE>::INVD;
     constexpr int CAP = WINDOW::FIFO_CAP;
 
     const WavePixel wp = wave_pixel_map(a);
@@ -318,6 +333,7 @@ __device__ __forceinline__ void render_kbuffer_body(const RenderArgs& a, WINDOW&
     k.active = wp.inside;
     if (total <= 0) { // an empty tile is background (and its "entry 0" -- what pads and stand-ins read -- may not exist: stp_render_hier.inc)
         if (wp.inside) write_background_pixel<DEPTHVIZ, true>(a, px, py);
+        if constexpr (INVD) { if (wp.inside) a.out_invdepth[(size_t)a.W * py + px] = 0.0f; }
         return;
     }
 
@@ -337,6 +353,7 @@ __device__ __forceinline__ void render_kbuffer_body(const RenderArgs& a, WINDOW&
     win.init(k);
     init_fwd_pixel(k.fp);
     k.depth_acc = 0.0f;
+    if constexpr (INVD) { k.invz = a.invz; k.D = 0.0f; k.pend_w = 0.0f; k.pend_z = 0.0f; }
     k.contrib = total;
     k.cfull = total;
     k.frC = make_float4(0, 0, 0, 0); k.frD = k.frC; k.frF = k.frC;
@@ -417,6 +434,7 @@ __device__ __forceinline__ void render_kbuffer_body(const RenderArgs& a, WINDOW&
 
     if constexpr (RECORD) k.logc.flush();
     if (wp.inside) write_forward_pixel<DEPTHVIZ, true>(a, px, py, k.fp, k.depth_acc, RECORD ? (uint32_t)k.logc.records() : (uint32_t)k.contrib); // (recording forward: the pixel's number of log records)
+    if constexpr (INVD) { if (wp.inside) a.out_invdepth[(size_t)a.W * py + px] = fmaf(k.pend_w, k.pend_z, k.D); } // (+ the last blended entry)
     if constexpr (RECORD) finish_blend_log(a, wp.tile, k.logc.records(), total);
 }
 
@@ -458,7 +476,7 @@ template <int WIN, int MODE> hipError_t launch_kb_win(const FrameParams& f, cons
 
 } // namespace
 
-// mode: 0 forward, 2 recording forward, 3 depth visualisation.  Every window size of the reference's ladder (forward.cu:409-425)
+// mode: 0 forward, 2 recording forward, 3 depth visualisation, 4 / 5 forward / recording forward with the inverse-depth output.  Every window size of the reference's ladder (forward.cu:409-425)
 // has a kernel here: four waves per SIMD up to 4 entries, three up to 16, two for 20 and 24 (164-187 VGPRs, no scratch)
 hipError_t launch_kbuffer_wave(int mode, const FrameParams& f, const RenderArgs& a, hipStream_t st, bool* handled)
 {
@@ -466,8 +484,10 @@ hipError_t launch_kbuffer_wave(int mode, const FrameParams& f, const RenderArgs&
     *handled = true;
     // windows of 8 .. 16 entries: the ring-in-LDS kernel (STP_KBUFFER=wave keeps the register window for them too)
     const bool ring = switches().kbuffer != Switches::KBUFFER_WAVE;
-#define STP_KBW(WIN) return mode == KBW_RECORD ? launch_kb_win<WIN, KBW_RECORD>(f, a, st) : mode == KBW_DEPTH ? launch_kb_win<WIN, KBW_DEPTH>(f, a, st) : launch_kb_win<WIN, KBW_FWD>(f, a, st)
-#define STP_KBR(WIN) return mode == KBW_RECORD ? launch_kb_ring<WIN, KBW_RECORD>(f, a, st) : mode == KBW_DEPTH ? launch_kb_ring<WIN, KBW_DEPTH>(f, a, st) : launch_kb_ring<WIN, KBW_FWD>(f, a, st)
+#define STP_KBW(WIN) return mode == KBW_RECORD ? launch_kb_win<WIN, KBW_RECORD>(f, a, st) : mode == KBW_DEPTH ? launch_kb_win<WIN, KBW_DEPTH>(f, a, st) : \
+                            mode == KBW_FWD_INVD ? launch_kb_win<WIN, KBW_FWD_INVD>(f, a, st) : mode == KBW_RECORD_INVD ? launch_kb_win<WIN, KBW_RECORD_INVD>(f, a, st) : launch_kb_win<WIN, KBW_FWD>(f, a, st)
+#define STP_KBR(WIN) return mode == KBW_RECORD ? launch_kb_ring<WIN, KBW_RECORD>(f, a, st) : mode == KBW_DEPTH ? launch_kb_ring<WIN, KBW_DEPTH>(f, a, st) : \
+                            mode == KBW_FWD_INVD ? launch_kb_ring<WIN, KBW_FWD_INVD>(f, a, st) : mode == KBW_RECORD_INVD ? launch_kb_ring<WIN, KBW_RECORD_INVD>(f, a, st) : launch_kb_ring<WIN, KBW_FWD>(f, a, st)
     if (w <= 1) STP_KBW(1);
     if (w <= 2) STP_KBW(2);
     if (w <= 4) STP_KBW(4);

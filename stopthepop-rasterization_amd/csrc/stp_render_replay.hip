@@ -26,6 +26,8 @@
 #include "stp_internal.h"
 #include "stp_render_wave.h"
 
+#include <type_traits>
+
 namespace stp {
 
 #ifdef STP_REPLAY_STATS
@@ -77,12 +79,24 @@ constexpr int EXHAUSTED = 0x7fffffff; // "position" of a lane that has no record
 // maximum has no summation order, so it is the re-sorting kernels' value bit for bit.  The pair SET is the forward's too -- every record of
 // the log --, not the gradient terms': their lean transmittance may call a pixel saturated one record earlier than the forward did, and a
 // count has no tolerance.  STATS = false is the kernel as it was.
-template <bool LOG_BLOCKED, bool ABS, bool STATS>
-__global__ void __launch_bounds__(256, STATS ? (ABS ? STP_REPLAY_BOTH_OCC : STP_REPLAY_STATS_OCC) : ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC)
+// INVD: the inverse-depth request (stp_set_backward_invdepth).  (1 / z, D_final, dL/dD) joins the channel sums as a fourth channel -- one more
+// product in cd and in FD, CD follows -- and one more term per blend, alpha T dL/dD, passes through the merge levels, the window (the
+// gradient terms' fixed point: it is linear in dL/dD, which the tile's scale covers) and the flush into slot 14 of the record.  1 / z comes by
+// Gaussian id from the geometry buffer: requested at the END of the step that requested the entry's record (which has arrived by then), a
+// whole step ahead of its use.  The window grows by one row: ten .. fifteen terms are 40 .. 60 KB, three workgroups per CU up to thirteen
+// terms (52 KB), two beyond.  INVD = false is the kernel as it was.
+template <bool ABS, bool STATS, bool INVD> constexpr int replay_occupancy()
+{
+    if (!INVD) return STATS ? (ABS ? STP_REPLAY_BOTH_OCC : STP_REPLAY_STATS_OCC) : ABS ? STP_REPLAY_ABS_OCC : STP_REPLAY_OCC;
+    return ((ABS ? 11 : 9) + (STATS ? 3 : 0) + 1) * WINDOW * 8 <= 52 * 1024 ? 3 : 2; // (160 KB of LDS per CU)
+}
+template <bool LOG_BLOCKED, bool ABS, bool STATS, bool INVD>
+__global__ void __launch_bounds__(256, (replay_occupancy<ABS, STATS, INVD>()))
 render_replay_kernel(const RenderArgs a)
 {
     constexpr int SI = ABS ? 11 : 9;          // the gradient terms; with STATS also the first statistics term in g[] and s_acc (record slots GRAD_STATS .. + 2)
-    constexpr int NT = SI + (STATS ? 3 : 0);  // terms per list position
+    constexpr int ZI = SI + (STATS ? 3 : 0);  // INVD: the inverse-depth term in g[] and s_acc (record slot GRAD_INVDEPTH)
+    constexpr int NT = ZI + (INVD ? 1 : 0);   // terms per list position
     __shared__ unsigned long long s_acc[NT * WINDOW]; // [term][position - window start]
     __shared__ float s_md[4];
 
@@ -97,13 +111,15 @@ render_replay_kernel(const RenderArgs a)
     for (int i = (int)threadIdx.x; i < NT * WINDOW; i += 256) s_acc[i] = 0ull;
 
     BwdPixel bp;
-    init_bwd_pixel(bp, a, inside, px, py);
+    init_bwd_pixel<INVD>(bp, a, inside, px, py);
     // channel sums of the pixel (see blend_terms): final . dL, C . dL (running), -T_final (bg . dL)
-    const float FD = fmaf(bp.final_color[2], bp.dL_dpix[2], fmaf(bp.final_color[1], bp.dL_dpix[1], bp.final_color[0] * bp.dL_dpix[0]));
+    float FD_ = fmaf(bp.final_color[2], bp.dL_dpix[2], fmaf(bp.final_color[1], bp.dL_dpix[1], bp.final_color[0] * bp.dL_dpix[0]));
+    if constexpr (INVD) FD_ = fmaf(bp.D_final, bp.dL_dD, FD_);
+    const float FD = FD_;
     float CD = 0.0f;
     const float tfbg = -bp.T_final * bp.bg_dot;
     int n = inside ? (int)a.n_contrib[(size_t)a.W * py + px] : 0;
-    float md = bwd_pixel_scale(bp, a, inside, px, py);
+    float md = bwd_pixel_scale<INVD>(bp, a, inside, px, py);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) md = fmaxf(md, __shfl_xor(md, off));
     // fixed-point scale of the sums (stp_render_hier.inc: "on-chip gradient window"): one for the workgroup
@@ -148,18 +164,27 @@ render_replay_kernel(const RenderArgs a)
     const float4* const eC = a.entC + range.x; // list-ordered entry records: mean + Gaussian id, conic + opacity, colour
     const float4* const eD = a.entD + range.x;
     const float4* const eF = a.entF + range.x;
-    struct Entry { float4 c, d, f; };
+    struct EntryRows { float4 c, d, f; };
+    struct EntryZ : EntryRows { float z; }; // INVD: + 1 / z of the entry's Gaussian (fetch_z)
+    using Entry = std::conditional_t<INVD, EntryZ, EntryRows>;
+    auto make_entry = [&](const float4 c, const float4 d, const float4 f) __attribute__((always_inline)) {
+        Entry e; e.c = c; e.d = d; e.f = f;
+        if constexpr (INVD) e.z = 0.0f;
+        return e;
+    };
+    // INVD: 1 / z of an entry whose rows were requested a step ago (every row read is an entry of the list: a visible Gaussian's id)
+    auto fetch_z = [&](Entry& e) __attribute__((always_inline)) { if constexpr (INVD) e.z = a.invz[__float_as_int(e.c.w)]; };
     auto entry_at = [&](int p) __attribute__((always_inline)) { // (a harmless read of entry 0 where there is no record: no branch)
         const uint32_t off = (uint32_t)(p < list_len ? p : 0) << 4;
         auto at = [&](const float4* base) __attribute__((always_inline)) { return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + off); };
-        return Entry{at(eC), at(eD), at(eF)};
+        return make_entry(at(eC), at(eD), at(eF));
     };
 
     const uint32_t list_last = (uint32_t)(list_len - 1);
     auto entry_at_clamped = [&](uint32_t p) __attribute__((always_inline)) { // (p beyond the list -- a corrupt log word -- reads the last entry)
         const uint32_t off = min(p, list_last) << 4;
         auto at = [&](const float4* base) __attribute__((always_inline)) { return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + off); };
-        return Entry{at(eC), at(eD), at(eF)};
+        return make_entry(at(eC), at(eD), at(eF));
     };
 
     float Tx = 1.0f; // STATS: the pixel's transmittance as the forward chains it (bp.T follows the lean alpha)
@@ -190,7 +215,9 @@ render_replay_kernel(const RenderArgs a)
         const float dchannel_dcolor = alpha * Tm;
         const float rcp_test_T = __builtin_amdgcn_rcpf(test_T);
         const float rcp_1ma = rcp_test_T * bp.T;
-        const float cd = fmaf(cur.f.z, bp.dL_dpix[2], fmaf(cur.f.y, bp.dL_dpix[1], cur.f.x * bp.dL_dpix[0]));
+        float cd_ = fmaf(cur.f.z, bp.dL_dpix[2], fmaf(cur.f.y, bp.dL_dpix[1], cur.f.x * bp.dL_dpix[0]));
+        if constexpr (INVD) cd_ = fmaf(cur.z, bp.dL_dD, cd_);
+        const float cd = cd_;
         CD = fmaf(dchannel_dcolor, cd, CD);
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) g[ch] = dchannel_dcolor * bp.dL_dpix[ch];
@@ -208,6 +235,7 @@ render_replay_kernel(const RenderArgs a)
         g[7] = v * dy;
         g[8] = G * dL_dalpha;
         if constexpr (ABS) { g[9] = fabsf(g[3]); g[10] = fabsf(g[4]); } // (this lane's pair alone; exact zeros where the lane is switched off)
+        if constexpr (INVD) g[ZI] = dchannel_dcolor * bp.dL_dD;         // (alpha T dL/dD: like the colour terms, zero where the lane is switched off)
         if constexpr (STATS) {
             // The pair set is the FORWARD's: every record of the log (`act`), which is what the re-sorting kernels blend.  `ok` may end a
             // pixel one record early -- its lean transmittance is an ulp off the forward's, and the last record of a saturating pixel can
@@ -285,6 +313,10 @@ render_replay_kernel(const RenderArgs a)
                     const long long qv = __double_as_longlong(tq) - 0x4338000000000000ll;
                     atomicAdd(&s_acc[kk * WINDOW + slot], (unsigned long long)qv);
                 }
+                if constexpr (INVD) { // (alpha T dL/dD: below M like the colour terms, out of the range check)
+                    const double tq = fma((double)g[ZI], fx_scale, 6755399441055744.0);
+                    atomicAdd(&s_acc[ZI * WINDOW + slot], (unsigned long long)(__double_as_longlong(tq) - 0x4338000000000000ll));
+                }
                 if constexpr (STATS) {
                     const double tq = fma((double)g[SI], ST_SCALE, 6755399441055744.0);
                     atomicAdd(&s_acc[SI * WINDOW + slot], (unsigned long long)(__double_as_longlong(tq) - 0x4338000000000000ll));
@@ -294,6 +326,7 @@ render_replay_kernel(const RenderArgs a)
             } else { // a record the re-sort moved across a window boundary, or a term too large for the fixed point
 #pragma unroll
                 for (int kk = 0; kk < SI; kk++) atomicAdd(grad_slot(a, cur_id, kk), g[kk] * term_scale(kk));
+                if constexpr (INVD) add_invdepth(a, cur_id, g[ZI]);
                 if constexpr (STATS) {
                     atomicAdd(grad_slot(a, cur_id, GRAD_STATS), g[SI]);
                     max_blend_weight(a, cur_id, g[SI + 1]);
@@ -311,8 +344,8 @@ render_replay_kernel(const RenderArgs a)
         for (int pp = f0 + (int)(threadIdx.x >> 4); pp < f1; pp += 16) {
             const int p = pp & (WINDOW - 1);
             // (term = the record slot a lane writes; row = where its sum lives in s_acc: the statistics follow the gradient terms directly)
-            const int row = (STATS && term >= GRAD_STATS) ? term - GRAD_STATS + SI : term;
-            if (term < SI || (STATS && term >= GRAD_STATS && term < GRAD_STATS + 3)) {
+            const int row = (INVD && term == GRAD_INVDEPTH) ? ZI : (STATS && term >= GRAD_STATS) ? term - GRAD_STATS + SI : term;
+            if (term < SI || (STATS && term >= GRAD_STATS && term < GRAD_STATS + 3) || (INVD && term == GRAD_INVDEPTH)) {
                 const long long v = (long long)s_acc[row * WINDOW + p];
                 if (v != 0) {
                     s_acc[row * WINDOW + p] = 0ull;
@@ -359,6 +392,7 @@ render_replay_kernel(const RenderArgs a)
         int pos = (0 < n && off == 0) ? log_at(0) : -1;
         int raw1 = log_at(min((uint32_t)max(1 - off, 0), log_last_rec));
         Entry en = entry_at(max(pos, 0));
+        fetch_z(en);
         // one step: blends `cur` (loaded an iteration ago), loads the entry of the next step into `nxt`
         auto one_step = [&](const int k, const Entry& cur, Entry& nxt) __attribute__((always_inline)) {
             const int kr = k - off; // my record index
@@ -378,6 +412,7 @@ render_replay_kernel(const RenderArgs a)
                 if (have && !ok) n = kr; // (an ulp of difference against the forward's transmittance: stop where it says so)
                 merge_and_add(ok, cur_pos, cur_id, g, 0, dense, true);
             }
+            fetch_z(nxt); // (INVD: the next step's 1 / z, behind this step's work: nxt's rows have arrived)
         };
         // two copies of the step, the entry registers alternating between them (no copy of the ten entry words at the back edge)
         Entry en2 = en;
@@ -394,6 +429,7 @@ render_replay_kernel(const RenderArgs a)
     int pos = (0 < n) ? log_at(0) : EXHAUSTED;
     int pos1 = (1 < n) ? log_at(1) : EXHAUSTED;
     Entry en = entry_at(pos);
+    fetch_z(en);
     // (Lanes are not de-phased here: measured slower with hard and with sliding windows, profiles/EXPERIMENTS.md, round 3.)
     // The window slides in HALF steps: a phase covers positions [lo, lo + WINDOW), position p lives in slot p mod WINDOW,
     // and the phase ends when every lane has left its LOWER half -- lanes that are ahead keep blending in the upper half meanwhile and
@@ -428,6 +464,7 @@ render_replay_kernel(const RenderArgs a)
                 if (act && !ok) { n = k; pos = EXHAUSTED; pos1 = EXHAUSTED; } // (saturated one record earlier than the forward said)
                 merge_and_add(ok, cur_pos, cur_id, g, lo, same_start, false);
             }
+            fetch_z(en);
         }
         flush_range(lo, last ? list_len : lo + STEP);
         if (last) break;
@@ -462,23 +499,25 @@ hipError_t launch_hier_replay(const FrameParams& f, const RenderArgs& a, hipStre
 {
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(256);
     const bool blocked = log_blocked(f.s);
-    switch (a.requests & (REQ_ABSGRAD | REQ_BLEND_STATS)) {
-    case REQ_ABSGRAD | REQ_BLEND_STATS: // (both requests: fourteen terms per position)
-        if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((render_replay_kernel<false, true, true>), grid, block, 0, st, a);
-        break;
-    case REQ_BLEND_STATS: // (the blend-statistics request: twelve)
-        if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, false, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((render_replay_kernel<false, false, true>), grid, block, 0, st, a);
-        break;
-    case REQ_ABSGRAD: // (the absgrad request: eleven)
-        if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, true, false>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((render_replay_kernel<false, true, false>), grid, block, 0, st, a);
-        break;
-    default:
-        if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, false, false>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((render_replay_kernel<false, false, false>), grid, block, 0, st, a);
+    // one instantiation per log layout and set of requests (absgrad, blend statistics, inverse depth)
+#define STP_REPLAY(ABS, STATS, INVD)                                                                                   \
+    do {                                                                                                               \
+        if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, ABS, STATS, INVD>), grid, block, 0, st, a);       \
+        else hipLaunchKernelGGL((render_replay_kernel<false, ABS, STATS, INVD>), grid, block, 0, st, a);              \
+    } while (0)
+    const bool abs_ = (a.requests & REQ_ABSGRAD) != 0, stats_ = (a.requests & REQ_BLEND_STATS) != 0, invd_ = (a.requests & REQ_INVDEPTH) != 0;
+    if (invd_) {
+        if (abs_ && stats_) STP_REPLAY(true, true, true);     // (fifteen terms per position)
+        else if (stats_) STP_REPLAY(false, true, true);       // (thirteen)
+        else if (abs_) STP_REPLAY(true, false, true);         // (twelve)
+        else STP_REPLAY(false, false, true);                  // (ten)
+    } else {
+        if (abs_ && stats_) STP_REPLAY(true, true, false);    // (both requests: fourteen terms per position)
+        else if (stats_) STP_REPLAY(false, true, false);      // (the blend-statistics request: twelve)
+        else if (abs_) STP_REPLAY(true, false, false);        // (the absgrad request: eleven)
+        else STP_REPLAY(false, false, false);
     }
+#undef STP_REPLAY
     return hipGetLastError();
 }
 

@@ -69,8 +69,12 @@ __device__ __forceinline__ TileCtx tile_ctx(const RenderArgs& a)
 // ------------------------------------------------------------------------------------------------
 // GLOBAL forward
 // ------------------------------------------------------------------------------------------------
+// INVD: the inverse-depth request (stp_set_forward_invdepth) -- a fourth accumulator D += alpha T / z, written to out_invdepth; INVD = false
+// is the kernel as it was
+template <bool INVD>
 __global__ void __launch_bounds__(BLOCK) render_global_fwd_kernel(const RenderArgs a)
 {
+    __shared__ float s_invz[INVD ? BLOCK : 1];
     __shared__ float2 s_xy[BLOCK];
     __shared__ float4 s_co[BLOCK];
     __shared__ float s_col[3][BLOCK];
@@ -84,6 +88,7 @@ __global__ void __launch_bounds__(BLOCK) render_global_fwd_kernel(const RenderAr
     int todo = total;
 
     float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, depth_acc = 0.0f;
+    float Dz = 0.0f; // (INVD)
     uint32_t contributor = 0, last_contributor = 0;
 
     for (int i = 0; i < rounds; i++, todo -= BLOCK) {
@@ -96,6 +101,7 @@ __global__ void __launch_bounds__(BLOCK) render_global_fwd_kernel(const RenderAr
             s_col[0][threadIdx.x] = a.features[3 * (size_t)id + 0];
             s_col[1][threadIdx.x] = a.features[3 * (size_t)id + 1];
             s_col[2][threadIdx.x] = a.features[3 * (size_t)id + 2];
+            if constexpr (INVD) s_invz[threadIdx.x] = a.invz[id];
             if (a.debug_depth) { // reference forward.cu:337-341
                 const float ddx = a.cam[0] - a.means3D[3 * (size_t)id], ddy = a.cam[1] - a.means3D[3 * (size_t)id + 1], ddz = a.cam[2] - a.means3D[3 * (size_t)id + 2];
                 s_dist[threadIdx.x] = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
@@ -118,6 +124,7 @@ __global__ void __launch_bounds__(BLOCK) render_global_fwd_kernel(const RenderAr
             C1 += s_col[1][j] * alpha * T;
             C2 += s_col[2][j] * alpha * T;
             if (a.debug_depth) depth_acc += s_dist[j] * alpha * T;
+            if constexpr (INVD) Dz += s_invz[j] * alpha * T;
             T = test_T;
             last_contributor = contributor;
         }
@@ -126,6 +133,7 @@ __global__ void __launch_bounds__(BLOCK) render_global_fwd_kernel(const RenderAr
         const size_t N = (size_t)a.W * a.H, pid = (size_t)a.W * c.py + c.px;
         a.final_T[pid] = T;
         a.n_contrib[pid] = last_contributor;
+        if constexpr (INVD) a.out_invdepth[pid] = Dz;
         if (a.debug_depth) { // reference outputDebugVis, stopthepop_common.cuh:297-301
             a.out_color[pid] = depth_acc;
             a.out_color[N + pid] = T;
@@ -147,6 +155,8 @@ __global__ void __launch_bounds__(BLOCK) render_global_fwd_kernel(const RenderAr
 // ------------------------------------------------------------------------------------------------
 // GLOBAL backward: back-to-front with the stored n_contrib / final_T
 // ------------------------------------------------------------------------------------------------
+// INVD: the inverse-depth request (stp_set_backward_invdepth); INVD = false is the kernel as it was
+template <bool INVD>
 __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderArgs a)
 {
     __shared__ int s_id[BLOCK];
@@ -157,6 +167,10 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
     const TileCtx c = tile_ctx(a);
     const float pxf = (float)c.px, pyf = (float)c.py;
     const size_t N = (size_t)a.W * a.H, pid = (size_t)a.W * c.py + c.px;
+    // inverse-depth request: (1 / z, D, dL/dD) is a fourth channel of the back-to-front recurrence, without a background share
+    constexpr bool invd = INVD;
+    float dL_dD = 0.0f, accum_rec_z = 0.0f, last_z = 0.0f;
+    if constexpr (INVD) dL_dD = c.inside ? a.dL_dinvdepth[pid] : 0.0f;
     const int total = (int)(c.range.y - c.range.x);
     const int rounds = (total + BLOCK - 1) / BLOCK;
     int todo = total;
@@ -220,6 +234,12 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
                     dL_dalpha += (col - accum_rec[ch]) * dL_dpixel[ch];
                     g_col[ch] = dchannel_dcolor * dL_dpixel[ch];
                 }
+                if constexpr (INVD) {
+                    const float zc = a.invz[s_id[j]]; // (one address for the wave)
+                    accum_rec_z = last_alpha * last_z + (1.f - last_alpha) * accum_rec_z;
+                    last_z = zc;
+                    dL_dalpha += (zc - accum_rec_z) * dL_dD;
+                }
                 dL_dalpha *= T;
                 last_alpha = alpha;
                 dL_dalpha += (-T_final / (1.f - alpha)) * bg_dot;
@@ -245,8 +265,11 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
             const bool stats = (a.requests & REQ_BLEND_STATS) != 0;
             float r11 = 0.0f, r12 = 0.0f, r13 = 0.0f;
             if (stats) { r11 = wave_sum(g_w); r12 = wave_max(g_w); r13 = wave_sum(use ? 1.0f : 0.0f); }
-            // lane k hands over term k: nine (eleven, twelve, fourteen) lanes, one 64-byte record
-            if (lane < 9 || ((a.requests & REQ_ABSGRAD) && lane < 11) || (stats && lane >= GRAD_STATS && lane < GRAD_STATS + 3)) {
+            // inverse-depth request: the wave's sum of alpha T dL/dD rides in lane 14
+            float r14 = 0.0f;
+            if constexpr (INVD) r14 = wave_sum(g_w * dL_dD);
+            // lane k hands over term k: nine (eleven, twelve, fourteen, ...) lanes, one 64-byte record
+            if (lane < 9 || ((a.requests & REQ_ABSGRAD) && lane < 11) || (stats && lane >= GRAD_STATS && lane < GRAD_STATS + 3) || (invd && lane == GRAD_INVDEPTH)) {
                 float v = r0;
                 switch (lane) {
                 case 1: v = r1; break;
@@ -262,6 +285,7 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
                 case 11: v = r11; break;
                 case 12: v = r12; break;
                 case 13: v = r13; break;
+                case 14: v = r14; break;
                 default: break;
                 }
                 if (lane == GRAD_STATS + 1) max_blend_weight(a, s_id[j], v);
@@ -280,13 +304,15 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
 // 2 = training forward: additionally records every pixel's blend order in the blend log, so that the backward is the
 // replay kernel of stp_render_replay.hip (the same log format and thread -> pixel mapping as the hierarchical mode).
 constexpr int KB_FWD = 0, KB_BWD = 1, KB_FWD_RECORD = 2, KB_FWD_DEPTH = 3; // 3: forward of the debug depth visualisation
+constexpr int KB_FWD_INVD = 4, KB_FWD_RECORD_INVD = 5, KB_BWD_INVD = 6;    // forward, recording forward and re-sorting backward under the inverse-depth request
 
 template <int WIN, int MODE>
 __global__ void __launch_bounds__(BLOCK) render_kbuffer_kernel(const RenderArgs a)
 {
-    constexpr bool BACKWARD = MODE == KB_BWD;
-    constexpr bool RECORD = MODE == KB_FWD_RECORD;
+    constexpr bool BACKWARD = MODE == KB_BWD || MODE == KB_BWD_INVD;
+    constexpr bool RECORD = MODE == KB_FWD_RECORD || MODE == KB_FWD_RECORD_INVD;
     constexpr bool DEPTHVIZ = MODE == KB_FWD_DEPTH;
+    constexpr bool INVD = MODE == KB_FWD_INVD || MODE == KB_FWD_RECORD_INVD || MODE == KB_BWD_INVD; // forward: D += alpha T / z beside the colour; backward: the fourth channel
     // one staging round = BLOCK entry records (A, B, C, D of BinningState), read with unit stride from the list-ordered
     // entry arrays; the forward passes carry the list position through the window, the backward pass the Gaussian id
     __shared__ float4 s_A[BLOCK];
@@ -325,10 +351,11 @@ __global__ void __launch_bounds__(BLOCK) render_kbuffer_kernel(const RenderArgs 
     win.init();
     FwdPixel fp;
     BwdPixel bp;
-    if constexpr (BACKWARD) init_bwd_pixel(bp, a, c.inside, c.px, c.py);
+    if constexpr (BACKWARD) init_bwd_pixel<INVD>(bp, a, c.inside, c.px, c.py);
     else init_fwd_pixel(fp);
     uint32_t contributor = 0;
     float depth_acc = 0.0f;
+    FwdDepth fz;
     char* const log_base = RECORD ? log_wave_slice(a.blend_log, c.tile, w, a.log_depth) : nullptr; // [record / 8][lane][record % 8], stp_blend.h
     int nrec = 0;
     const float4* const eF = a.entF + c.range.x;
@@ -338,7 +365,7 @@ __global__ void __launch_bounds__(BLOCK) render_kbuffer_kernel(const RenderArgs 
     auto blend_one = [&]() {
         if (win.num == 0) return;
         bool ok;
-        if constexpr (BACKWARD) ok = blend_backward(bp, a, c.px, c.py, win.id[0], win.store[0]);
+        if constexpr (BACKWARD) ok = blend_backward<INVD>(bp, a, c.px, c.py, win.id[0], win.store[0]);
         else {
             // The forward windows do not carry alpha (two selects per slot and insertion less): it is evaluated again here,
             // from the same entry record with the same instructions, hence to the same bits as when the entry passed the
@@ -350,6 +377,7 @@ __global__ void __launch_bounds__(BLOCK) render_kbuffer_kernel(const RenderArgs 
             const float T_before = fp.T;
             ok = blend_forward_c(fp, col, alpha0);
             if constexpr (DEPTHVIZ) { if (ok) depth_acc += win.depth[0] * alpha0 * T_before; } // reference resorted_render.cuh:107
+            if constexpr (INVD) { if (ok) fz.D = fmaf(alpha0 * T_before, a.invz[__float_as_int(eCp.w)], fz.D); } // (the wave64 kernels' expression, stp_render_kbuf.hip: the same bits)
             if constexpr (RECORD) {
                 if (ok) {
                     if (nrec < a.log_depth) *reinterpret_cast<log_t*>(log_base + log_record_offset<true>(2u * (uint32_t)nrec, (uint32_t)lane << LOG_PIECE_SHIFT)) = (log_t)pos;
@@ -405,6 +433,7 @@ __global__ void __launch_bounds__(BLOCK) render_kbuffer_kernel(const RenderArgs 
 
     if constexpr (!BACKWARD) {
         if (c.inside) write_forward_pixel<DEPTHVIZ, true>(a, c.px, c.py, fp, depth_acc, RECORD ? (uint32_t)nrec : contributor); // (recording forward: the pixel's number of log records)
+        if constexpr (INVD) { if (c.inside) a.out_invdepth[(size_t)a.W * c.py + c.px] = fz.D; }
         if constexpr (RECORD) finish_blend_log(a, c.tile, nrec, total);
     }
 }
@@ -430,6 +459,7 @@ static RenderArgs make_args(const FrameParams& f, const GeometryState& g, const 
     a.gather.gx = f.gx; a.gather.cull_mask = subtile_mask_kind(f.s);
     a.gather.entA = b.entA; a.gather.entB = b.entB; a.gather.entC = b.entC; a.gather.entD = b.entD; a.gather.entF = b.entF;
     a.bg_image = f.bg_image; a.out_alpha = f.out_alpha; a.dL_dalpha = nullptr; // (forward: stp_set_forward_background; the backward sets its own)
+    a.invz = g.invz; a.out_invdepth = f.out_invdepth; a.invdepth = nullptr; a.dL_dinvdepth = nullptr; // (stp_set_forward_invdepth; the backward sets its own)
     return a;
 }
 
@@ -438,6 +468,9 @@ hipError_t launch_hier_fwd(const FrameParams& f, const RenderArgs& a, hipStream_
 hipError_t launch_hier_bwd(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
 hipError_t launch_hier_rec(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
 hipError_t launch_hier_dbg(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
+hipError_t launch_hier_fwd_invd(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err); // (the two forwards with the inverse-depth output)
+hipError_t launch_hier_rec_invd(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
+hipError_t launch_hier_bwd_invd(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
 hipError_t launch_depth_colormap(float* out_color, int N, uint32_t* minmax, hipStream_t st); // stp_debug_viz.hip
 hipError_t launch_hier_replay(const FrameParams& f, const RenderArgs& a, hipStream_t st);
 hipError_t launch_full_fwd(const FrameParams& f, const RenderArgs& a, hipStream_t st);
@@ -465,11 +498,13 @@ hipError_t launch_render_forward(const FrameParams& f, const GeometryState& g, c
 {
     RenderArgs a = make_args(f, g, b, img);
     a.out_color = out_color;
+    const bool invd = a.out_invdepth != nullptr; // (stp_set_forward_invdepth: the kernels' INVD variants; never with the debug depth visualisation)
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(BLOCK);
     if (grid.x == 0) return hipSuccess;
     switch (f.s.sort_mode) {
     case MODE_GLOBAL:
-        hipLaunchKernelGGL(render_global_fwd_kernel, grid, block, 0, st, a);
+        if (invd) hipLaunchKernelGGL(render_global_fwd_kernel<true>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(render_global_fwd_kernel<false>, grid, block, 0, st, a);
         return hipGetLastError();
     case MODE_KBUFFER: {
         // the wave64 kernel of stp_render_kbuf.hip (STP_KBUFFER=tile keeps the one-entry-per-wave kernel of this file for
@@ -477,16 +512,19 @@ hipError_t launch_render_forward(const FrameParams& f, const GeometryState& g, c
         const bool kb_tile = switches().kbuffer == Switches::KBUFFER_TILE;
         if (!kb_tile) {
             bool handled = false;
-            const hipError_t e = launch_kbuffer_wave(a.debug_depth ? KB_FWD_DEPTH : uses_blend_log(f.s) ? KB_FWD_RECORD : KB_FWD, f, a, st, &handled);
+            const int mode = a.debug_depth ? KB_FWD_DEPTH : uses_blend_log(f.s) ? (invd ? KB_FWD_RECORD_INVD : KB_FWD_RECORD) : (invd ? KB_FWD_INVD : KB_FWD);
+            const hipError_t e = launch_kbuffer_wave(mode, f, a, st, &handled);
             if (handled) return e;
         }
         if (a.debug_depth) return launch_kbuffer<KB_FWD_DEPTH>(f, a, st);
+        if (invd) return uses_blend_log(f.s) ? launch_kbuffer<KB_FWD_RECORD_INVD>(f, a, st) : launch_kbuffer<KB_FWD_INVD>(f, a, st);
         return uses_blend_log(f.s) ? launch_kbuffer<KB_FWD_RECORD>(f, a, st) : launch_kbuffer<KB_FWD>(f, a, st);
     }
     case MODE_FULL: return launch_full_fwd(f, a, st);
     case MODE_HIER:
         if (a.debug_depth) return launch_hier_dbg(f, a, st, err);
         a.fused_gather = f.fused_gather; // (the forward and recording forward sort + gather their tiles of up to TS_SMALL entries themselves)
+        if (invd) return uses_blend_log(f.s) ? launch_hier_rec_invd(f, a, st, err) : launch_hier_fwd_invd(f, a, st, err);
         return uses_blend_log(f.s) ? launch_hier_rec(f, a, st, err) : launch_hier_fwd(f, a, st, err);
     default: if (err) *err = "invalid sort mode"; return hipErrorInvalidValue;
     }
@@ -507,13 +545,16 @@ hipError_t launch_render_backward(const FrameParams& f, const GeometryState& g, 
     RenderArgs a = make_args(f, g, b, img);
     a.pixel_colors = bw.pixel_colors; a.dL_dpix = bw.dL_dpix; a.grad_rec = bw.grad_rec; a.grad_stride = bw.grad_stride;
     // (the caller has refused compact records with either request: slots 9 .. 13 exist)
-    a.requests = (bw.absgrad != nullptr ? REQ_ABSGRAD : 0) | (bw.blend_stats != nullptr ? REQ_BLEND_STATS : 0);
+    a.requests = (bw.absgrad != nullptr ? REQ_ABSGRAD : 0) | (bw.blend_stats != nullptr ? REQ_BLEND_STATS : 0) | (bw.dL_dinvdepth != nullptr ? REQ_INVDEPTH : 0);
+    a.out_invdepth = nullptr; a.invdepth = bw.invdepth; a.dL_dinvdepth = bw.dL_dinvdepth; // stp_set_backward_invdepth
+    const bool invd = (a.requests & REQ_INVDEPTH) != 0; // (the kernels' INVD instantiations)
     a.bg_image = bw.bg_image; a.out_alpha = nullptr; a.dL_dalpha = bw.dL_dalpha; // stp_set_backward_background
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(BLOCK);
     if (grid.x == 0) return hipSuccess;
     switch (f.s.sort_mode) {
     case MODE_GLOBAL:
-        hipLaunchKernelGGL(render_global_bwd_kernel, grid, block, 0, st, a);
+        if (invd) hipLaunchKernelGGL(render_global_bwd_kernel<true>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(render_global_bwd_kernel<false>, grid, block, 0, st, a);
         return hipGetLastError();
     case MODE_KBUFFER:
         if (uses_blend_log(f.s)) { // replay the forward's blend log; the re-sorting kernel only takes overflowed tiles
@@ -521,14 +562,14 @@ hipError_t launch_render_backward(const FrameParams& f, const GeometryState& g, 
             if (e != hipSuccess) return e;
             a.flag_mode = 1;
         }
-        return launch_kbuffer<KB_BWD>(f, a, st);
+        return invd ? launch_kbuffer<KB_BWD_INVD>(f, a, st) : launch_kbuffer<KB_BWD>(f, a, st);
     case MODE_HIER:
         if (uses_blend_log(f.s)) { // replay the forward's blend log; the resorting kernel only takes overflowed tiles
             hipError_t e = launch_hier_replay(f, a, st);
             if (e != hipSuccess) return e;
             a.flag_mode = 1;
         }
-        return launch_hier_bwd(f, a, st, err);
+        return invd ? launch_hier_bwd_invd(f, a, st, err) : launch_hier_bwd(f, a, st, err);
     default: if (err) *err = "Backward not supported for full per-pixel sort"; return hipErrorInvalidValue;
     }
 }

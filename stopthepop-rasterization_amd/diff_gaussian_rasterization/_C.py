@@ -47,6 +47,8 @@ _OPTIONAL_SYMBOLS = {
     "stp_set_backward_blend_stats": ([ctypes.c_void_p], None),
     "stp_set_forward_background": ([ctypes.c_void_p] * 2, None),
     "stp_set_backward_background": ([ctypes.c_void_p] * 3, None),
+    "stp_set_forward_invdepth": ([ctypes.c_void_p], None),
+    "stp_set_backward_invdepth": ([ctypes.c_void_p] * 2, None),
     "stp_sparse_adam": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
                         ctypes.c_int),
     "stp_photometric_workspace_floats": ([ctypes.c_int] * 3, ctypes.c_size_t),
@@ -57,6 +59,7 @@ _OPTIONAL_SYMBOLS = {
 _SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blend_stats": "blend statistics",
                    "stp_set_forward_background": "the alpha output and per-pixel background",
                    "stp_set_backward_background": "the alpha output and per-pixel background",
+                   "stp_set_forward_invdepth": "the inverse-depth output", "stp_set_backward_invdepth": "the inverse-depth output",
                    "stp_sparse_adam": "the sparse Adam step",
                    "stp_photometric_workspace_floats": "the photometric loss", "stp_photometric_forward": "the photometric loss",
                    "stp_photometric_backward": "the photometric loss"}
@@ -344,23 +347,31 @@ def _records_log(d: dict) -> bool:
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, inv_viewprojmatrix, tan_fovx, tan_fovy, image_height, image_width,
-                        sh, degree, campos, prefiltered, settings_dict, render_depth, debug, alpha=False
+                        sh, degree, campos, prefiltered, settings_dict, render_depth, debug, alpha=False, invdepth=False
                         ) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """== RasterizeGaussiansCUDA (reference rasterize_points.cu:43-138).
     Returns (num_rendered, out_color (3,H,W), radii (P,) int32, geomBuffer, binningBuffer, imgBuffer).
 
     alpha=True (extension, include/stp_raster.h: stp_set_forward_background): one more tensor, LAST in the tuple: alpha = 1 - final_T,
     (1,H,W) float32 (zeros for P == 0).  A `background` of shape exactly (3,H,W) is composed per pixel, out = C + final_T * background;
-    every other background is read as three floats.  Neither is available with render_depth."""
+    every other background is read as three floats.  Neither is available with render_depth.
+
+    invdepth=True (extension, include/stp_raster.h: stp_set_forward_invdepth): one more tensor, LAST in the tuple (behind alpha's): the
+    inverse-depth image sum_i alpha_i T_i / z_i over the pairs the colour blends, z_i the view-space z of Gaussian i's centre; (1,H,W)
+    float32, no background term (zeros where nothing blended, and for P == 0).  Not available with render_depth."""
     if means3D.dim() != 2 or means3D.size(1) != 3:   # (the reference's first check, rasterize_points.cu:69-71)
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if alpha or _per_pixel_background(background, image_height, image_width):
         _require("stp_set_forward_background")
+    if invdepth:
+        _require("stp_set_forward_invdepth")
+        if render_depth:
+            raise RuntimeError("the inverse-depth output (_invdepth) is not available with render_depth (the debug depth visualisation)")
     out = (_host or _native()).rasterize_gaussians(
         background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         inv_viewprojmatrix, tan_fovx, tan_fovy, int(image_height), int(image_width), sh, int(degree), campos, bool(prefiltered),
-        settings_dict, bool(render_depth), bool(debug), _records_log(settings_dict), bool(alpha))
-    return tuple(out) if alpha else tuple(out[:6])
+        settings_dict, bool(render_depth), bool(debug), _records_log(settings_dict), bool(alpha), bool(invdepth))
+    return tuple(out[:6]) + ((out[6],) if alpha else ()) + ((out[7],) if invdepth else ())
 
 
 def _per_pixel_background(background, height, width) -> bool:
@@ -372,7 +383,8 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
                                  cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, tan_fovx, tan_fovy,
                                  pixel_colors, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                                  imageBuffer, settings_dict, debug, phases=3, partial=None, chunk=None, outputs=None,
-                                 camera_grads=False, absgrad=False, blend_stats=False, dL_dalpha=None, bg_grad=False):
+                                 camera_grads=False, absgrad=False, blend_stats=False, dL_dalpha=None, bg_grad=False,
+                                 dL_dinvdepth=None, invdepth=None):
     """== RasterizeGaussiansBackwardCUDA (reference rasterize_points.cu:140-232).
     Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
 
@@ -393,6 +405,11 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
     exactly (3,H,W), which must be the forward's).  The (3,) sum runs in a fixed order: equal inputs give bit-equal results.  Both need the
     render half (phases bit 0) and work with compact records; with phases=1 and bg_grad the result is (records, dL_dbackground).
 
+    dL_dinvdepth=(1,H,W) tensor with invdepth=the forward's inverse-depth output (extension, include/stp_raster.h:
+    stp_set_backward_invdepth): the gradient of that output joins the eight gradients (and the camera's) -- through the alphas like a colour
+    gradient, and through 1 / z to dL_dmeans3D (and dL_dviewmatrix).  dL_dcolors / dL_dsh get nothing from it.  No extra result.  Needs both
+    halves in one call and the padded records, like absgrad.
+
     Extension for tile-row sharding (not in the reference): phases=1 runs only the render half and
     returns its per-Gaussian partial sums as the library's (P,16) gradient records (stp_raster.h);
     phases=2 takes the records (after the caller's all-reduce) as `partial` and runs the preprocess half.
@@ -410,13 +427,15 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
         _require("stp_set_backward_absgrad")
     if blend_stats:
         _require("stp_set_backward_blend_stats")
+    if dL_dinvdepth is not None:
+        _require("stp_set_backward_invdepth")
     if dL_dalpha is not None or bg_grad or _per_pixel_background(background, dL_dout_color.shape[-2], dL_dout_color.shape[-1]):
         _require("stp_set_backward_background")
     out = (_host or _native()).rasterize_gaussians_backward(
         background, means3D, radii, opacities, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         inv_viewprojmatrix, tan_fovx, tan_fovy, pixel_colors, dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer,
         imageBuffer, settings_dict, bool(debug), _records_log(settings_dict), int(phases), partial, None if outputs is None else list(outputs),
-        bool(camera_grads), bool(absgrad), bool(blend_stats), dL_dalpha, bool(bg_grad))
+        bool(camera_grads), bool(absgrad), bool(blend_stats), dL_dalpha, bool(bg_grad), dL_dinvdepth, invdepth)
     return out[0] if (int(phases) & 3) == 1 and not bg_grad else tuple(out)
 
 
@@ -465,7 +484,7 @@ def photometric_backward(image, target, maps, grad_out2):
 _GEOM_TYPES = {"depths": torch.float32, "clamped": torch.uint8, "radii": torch.int32, "rects2D": torch.float32,
                "means2D": torch.float32, "cov3D": torch.float32, "cov3D_inv": torch.float32,
                "conic_opacity": torch.float32, "rgb": torch.float32, "tiles_touched": torch.int32,
-               "point_offsets": torch.int32}
+               "point_offsets": torch.int32, "invz": torch.float32}
 _BIN_TYPES = {"point_list": torch.int32, "point_list_unsorted": torch.int32, "keys": torch.int64, "keys_unsorted": torch.int64}
 _IMG_TYPES = {"final_T": torch.float32, "n_contrib": torch.int32, "ranges": torch.int32, "tile_flags": torch.int32,
               "blend_log": torch.int16}  # the last two exist only in a buffer of a recording forward

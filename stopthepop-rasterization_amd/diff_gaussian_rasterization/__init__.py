@@ -70,6 +70,12 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
         # (save_bg: a bg that requires grad -- final_T * dL_dout is not the gradient of that image)
         raise RuntimeError("the alpha output (settings._alpha), a per-pixel background and a background that requires grad are not available "
                            "with render_depth=True: the depth visualisation's image is not C + T * background")
+    # inverse-depth output (extension; include/stp_raster.h: stp_set_forward_invdepth): settings._invdepth = True adds
+    # invdepth = sum alpha T / z, (1, H, W), as one more differentiable output, behind alpha where both are asked for
+    ctx.invdepth = bool(sdict.get("_invdepth"))
+    if ctx.invdepth and rs.render_depth:
+        raise RuntimeError("the inverse-depth output (settings._invdepth) is not available with render_depth=True: the depth visualisation "
+                           "replaces the image and has no backward")
     ctx.log_lease = None
     # absgrad (extension, settings._absgrad = True; include/stp_raster.h: stp_set_backward_absgrad): the backward also leaves the per-Gaussian
     # sums of |each pixel's contribution to dL/dmean2D| in means2D.absgrad -- the densification statistic of AbsGS / gsplat.  The tensor
@@ -111,6 +117,8 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
             rs.image_width, sh, rs.sh_degree, campos, rs.prefiltered, sdict, rs.render_depth,
             rs.debug)
     kw = {"alpha": True} if ctx.alpha else {}   # (the alpha tensor comes last)
+    if ctx.invdepth:
+        kw["invdepth"] = True                   # (... and the inverse depth behind it)
     if rs.debug:
         cpu_args = cpu_deep_copy_tuple(args)  # snapshot before anything can corrupt them
         try:
@@ -130,12 +138,12 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
     ctx.bin_generation = _C.scratch_generation(binningBuffer)
     ctx.save_for_backward(colors_precomp, means3D, opacities, scales, rotations, cov3Ds_precomp, radii, sh, color,
                           geomBuffer, binningBuffer, imgBuffer, *((viewmatrix, projmatrix, campos) if save_camera else ()),
-                          *((bg,) if save_bg else ()))
+                          *((bg,) if save_bg else ()), *((extra[-1],) if ctx.invdepth else ()))   # (the inverse-depth output: LAST)
     # radii is an integer output: without these two lines autograd materialises a (P,) zero "gradient" for it in
     # every backward (a 4 MB fill kernel per step at 1 M Gaussians)
     ctx.mark_non_differentiable(radii)
     ctx.set_materialize_grads(False)
-    return (color, radii, extra[0]) if ctx.alpha else (color, radii)
+    return (color, radii, *extra)   # (alpha, invdepth: those that were asked for)
 
 
 def _grad_alpha(ctx, rest):
@@ -143,7 +151,13 @@ def _grad_alpha(ctx, rest):
     return rest[0] if ctx.alpha and rest else None
 
 
-def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_grads=False, grad_alpha=None, bg=None):
+def _grad_invdepth(ctx, rest):
+    """The same for the inverse-depth output, which follows alpha's."""
+    i = 1 if ctx.alpha else 0
+    return rest[i] if ctx.invdepth and len(rest) > i else None
+
+
+def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_grads=False, grad_alpha=None, bg=None, grad_invdepth=None):
     """The backward the autograd Functions share: the eight Gaussian gradients of _C.rasterize_gaussians_backward (+ the three camera
     gradients with camera_grads=True, + dL/dbg last with bg, the background Function's saved input)."""
     num_rendered = ctx.num_rendered
@@ -171,6 +185,9 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
         kw["dL_dalpha"] = grad_alpha
     if bg_grad:
         kw["bg_grad"] = True
+    if grad_invdepth is not None:   # (None: the inverse depth took no part in the loss -- no pointer is set, the backward is what it is without)
+        kw["dL_dinvdepth"] = grad_invdepth
+        kw["invdepth"] = ctx.saved_tensors[-1]
     if rs.debug:
         cpu_args = cpu_deep_copy_tuple(args)
         try:
@@ -214,7 +231,8 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, grad_out_color, _, *rest):   # (rest: the alpha output's gradient, with settings._alpha)
         rs = ctx.raster_settings
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _backward_body(ctx, grad_out_color, rs.viewmatrix, rs.projmatrix, rs.campos, grad_alpha=_grad_alpha(ctx, rest))
+         grad_rotations) = _backward_body(ctx, grad_out_color, rs.viewmatrix, rs.projmatrix, rs.campos, grad_alpha=_grad_alpha(ctx, rest),
+                                          grad_invdepth=_grad_invdepth(ctx, rest))
         # one gradient per forward input, in forward's order
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                 grad_cov3Ds_precomp, None)
@@ -238,7 +256,8 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
         viewmatrix, projmatrix, campos = ctx.saved_tensors[12:15]
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations, grad_view, grad_proj, grad_campos) = _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, True,
-                                                                             grad_alpha=_grad_alpha(ctx, rest))
+                                                                             grad_alpha=_grad_alpha(ctx, rest),
+                                                                             grad_invdepth=_grad_invdepth(ctx, rest))
         grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                  grad_cov3Ds_precomp, grad_view, grad_proj, grad_campos)
         # None for every input that does not require grad (frozen Gaussians: the camera's gradients only)
@@ -260,7 +279,8 @@ class _RasterizeGaussiansBackground(torch.autograd.Function):
     def backward(ctx, grad_out_color, _, *rest):
         viewmatrix, projmatrix, campos, bg = ctx.saved_tensors[12:16]
         camera_grads = any(ctx.needs_input_grad[9:12])
-        out = _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_grads, grad_alpha=_grad_alpha(ctx, rest), bg=bg)
+        out = _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_grads, grad_alpha=_grad_alpha(ctx, rest), bg=bg,
+                             grad_invdepth=_grad_invdepth(ctx, rest))
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales, grad_rotations) = out[:8]
         grad_view, grad_proj, grad_campos = out[8:11] if camera_grads else (None, None, None)
         grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
@@ -350,7 +370,9 @@ class ExtendedSettings(_Settable):
                 # (the same for `settings._blend_stats = True`: means2D.blend_stats, per Gaussian the sum, max and count of its blend weights)
                 **({"_blend_stats": True} if getattr(self, "_blend_stats", False) else {}),
                 # (and for `settings._alpha = True`: the rasterizer returns (color, radii, alpha), alpha = 1 - final_T a differentiable output)
-                **({"_alpha": True} if getattr(self, "_alpha", False) else {})}
+                **({"_alpha": True} if getattr(self, "_alpha", False) else {}),
+                # (and for `settings._invdepth = True`: one more differentiable output behind it, invdepth = sum alpha T / z)
+                **({"_invdepth": True} if getattr(self, "_invdepth", False) else {})}
 
     def to_json(self):
         return json.dumps(self.to_dict())

@@ -248,6 +248,10 @@ class _ShardedRasterize(torch.autograd.Function):
             raise RuntimeError("blend statistics (settings._blend_stats) are not available with tile-row sharding: the compact (P, 9) "
                                "gradient record that crosses the links between the two halves of the backward has no room for the three "
                                "extra terms")
+        if sdict.get("_invdepth"):
+            # (the strips exchange colour rows only, and slot 14 of the padded record is not in the compact one the ranks all-reduce)
+            raise RuntimeError("the inverse-depth output (settings._invdepth) is not available with tile-row sharding: the strips' "
+                               "inverse-depth rows are not exchanged between the ranks; render on one GPU")
         bg = rs.bg
         if (sdict.get("_alpha") or _C._per_pixel_background(bg, rs.image_height, rs.image_width)
                 or (isinstance(bg, torch.Tensor) and bg.requires_grad)):
