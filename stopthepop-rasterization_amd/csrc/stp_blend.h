@@ -6,6 +6,7 @@
 
 #include "stp_device.h"
 #include "stp_tilesort.h"
+#include "stp_render_pass.h"
 
 namespace stp {
 
@@ -54,7 +55,7 @@ struct RenderArgs {
     // sum(depth * alpha * T) to channel 0 and T to channel 1 of out_color instead of the colour
     int debug_depth;
     const float* means3D; // GLOBAL mode's visualised depth is |cam - mean| (reference forward.cu:337-341)
-    // hierarchical forwards (MODE_FWD, MODE_FWD_RECORD): 1 = the workgroup sorts its tile and gathers the tile's entry records itself, in front of
+    // hierarchical forwards (PASS_FWD, PASS_FWD_RECORD and their inverse-depth variants): 1 = the workgroup sorts its tile and gathers the tile's entry records itself, in front of
     // rendering it, when the list holds 1 .. TS_SMALL entries (tile_sort_gather_lds, stp_tilesort.h); 0 = tile_sort_gather_kernel has done so
     int fused_gather;
     EntryGather gather;

@@ -35,7 +35,7 @@ namespace stp {
 
 #ifdef STP_HIER_STATS
 static __device__ unsigned long long g_hier_stats[16]; // (one copy per translation unit: only the slice below exports its reader)
-#if defined(STP_INST_MODE) && STP_INST_MODE == 2 && STP_INST_MID == 8
+#if defined(STP_INST_MODE) && STP_INST_MODE == 2 && STP_INST_MID == 8 // (PASS_FWD_RECORD)
 extern "C" int stp_debug_hier_stats(unsigned long long* out16)
 {
     hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_hier_stats), sizeof(unsigned long long) * 16);
@@ -100,19 +100,12 @@ struct HierLds { // dynamic-LDS carve, per workgroup (16 sub-tiles)
     static __host__ __device__ constexpr size_t ring(int MID) { return dirty(MID) + (size_t)BWD_WIN * 4; }
     static __host__ __device__ constexpr size_t ring_cs(int MID) { return ring(MID) + (size_t)BWD_RING * 4; }
     static __host__ __device__ constexpr size_t wave_mask(int MID) { return ring_cs(MID) + (size_t)BWD_RING * 4; }
-    static __host__ __device__ constexpr size_t total(int MID, int mode) { return (mode == 1 || mode == 6) ? wave_mask(MID) + 16 : hfifo(MID) + 64 * (size_t)HF_CAP * 4; }
+    static __host__ __device__ constexpr size_t total(int MID, int mode) { return pass_backward(mode) ? wave_mask(MID) + 16 : hfifo(MID) + 64 * (size_t)HF_CAP * 4; }
 };
 
-// MODE: 0 = forward, 1 = backward by re-running the resort (the reference's scheme), 2 = forward that also records
-// every pixel's blend order (the training forward; its backward is the replay kernel of stp_render_replay.hip).
-// launch bounds: 4 waves per SIMD (<= 128 VGPRs) for the forward passes, 3 (<= 168) for the backward pass
-constexpr int MODE_FWD = 0, MODE_BWD = 1, MODE_FWD_RECORD = 2, MODE_FWD_DEPTH = 3; // 3: forward of the debug depth visualisation
-// 4 / 5: the forward / recording forward with the inverse-depth output (stp_set_forward_invdepth): a fourth accumulator D += alpha T / z.
-// Instantiations of their own, the default queue sizes' at four waves per SIMD (128 VGPRs): their five-wave build has no register to spare.
-// 6: the re-sorting backward with the fourth channel (stp_set_backward_invdepth).
-constexpr int MODE_FWD_INVD = 4, MODE_FWD_RECORD_INVD = 5, MODE_BWD_INVD = 6;
-constexpr bool mode_invd(int mode) { return mode == MODE_FWD_INVD || mode == MODE_FWD_RECORD_INVD || mode == MODE_BWD_INVD; }
-constexpr bool mode_bwd(int mode) { return mode == MODE_BWD || mode == MODE_BWD_INVD; }
+// MODE: a render pass of stp_render_pass.h (PASS_*; the predicates pass_backward / pass_records / pass_depthviz / pass_invdepth).
+// launch bounds: 4 waves per SIMD (<= 128 VGPRs) for the forward passes, 3 (<= 168) for the backward pass.  The passes with the inverse-depth
+// output are instantiations of their own, the default queue sizes' at four waves per SIMD (128 VGPRs): their five-wave build has no register to spare.
 // waves per SIMD of the forwards with the inverse-depth output: sized so that none of them spills (the four extra registers do not fit
 // the budgets the plain forwards of the larger queues already overrun)
 constexpr int invd_fwd_waves(int head, bool frcp) { return (head == 4 && frcp) ? 4 : head <= 8 ? 3 : 2; }
@@ -120,9 +113,9 @@ constexpr int invd_fwd_waves(int head, bool frcp) { return (head == 4 && frcp) ?
 // spill at three already (the variants do not).  Forward: five for the default queue sizes (STP_FWD_WAVES), otherwise four.
 constexpr int hier_waves(int head, int mid, int mode, bool frcp)
 {
-    if (mode == MODE_BWD_INVD) return head >= 12 ? 2 : STP_BWD_WAVES;
-    if (mode == MODE_BWD) return STP_BWD_WAVES;
-    if (mode_invd(mode)) return invd_fwd_waves(head, frcp);
+    if (mode == PASS_BWD_INVD) return head >= 12 ? 2 : STP_BWD_WAVES;
+    if (mode == PASS_BWD) return STP_BWD_WAVES;
+    if (pass_invdepth(mode)) return invd_fwd_waves(head, frcp);
     return (head == 4 && mid == 8 && frcp) ? STP_FWD_WAVES : 4;
 }
 
@@ -131,18 +124,18 @@ constexpr int hier_waves(int head, int mid, int mode, bool frcp)
 template <int HEAD, int MID, bool CULL, int MODE, bool FRCP>
 __global__ void __launch_bounds__(256, hier_waves(HEAD, MID, MODE, FRCP)) render_hier_kernel(const RenderArgs a)
 {
-    constexpr bool INVD = mode_invd(MODE);
+    constexpr bool INVD = pass_invdepth(MODE);
     // (the mid level's lane views from a fresh lane id: only where the register budget needs it -- five waves per SIMD WITH 4x4 culling, see STP_FWD_WAVES)
-    constexpr bool FRESH_QUAD = !mode_bwd(MODE) && !INVD && HEAD == 4 && MID == 8 && FRCP && STP_FWD_WAVES >= 5 && CULL;
-    constexpr bool BACKWARD = mode_bwd(MODE);
-    constexpr bool RECORD = MODE == MODE_FWD_RECORD || MODE == MODE_FWD_RECORD_INVD;
-    constexpr bool DEPTHVIZ = MODE == MODE_FWD_DEPTH; // accumulate depth * alpha * T instead of colour (reference :1005-1008, stopthepop_common.cuh:264-282)
+    constexpr bool FRESH_QUAD = !pass_backward(MODE) && !INVD && HEAD == 4 && MID == 8 && FRCP && STP_FWD_WAVES >= 5 && CULL;
+    constexpr bool BACKWARD = pass_backward(MODE);
+    constexpr bool RECORD = pass_records(MODE);
+    constexpr bool DEPTHVIZ = pass_depthviz(MODE); // accumulate depth * alpha * T instead of colour (reference :1005-1008, stopthepop_common.cuh:264-282)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int OLDN = (MID - 4) / 4; // old mid entries owned per lane
 
     // thread -> pixel: wave_pixel_map() of stp_render_wave.h, written out.  The one piece of the scaffold this kernel keeps local: taken from
     // the function (same statements, same order) the default recording forwards -- 96 VGPRs for five waves per SIMD -- spill one more
-    // register (<4, 8, true, MODE_FWD_RECORD, true>: 0 -> 1, without culling 4 -> 5; profiles/EXPERIMENTS.md, "shared scaffold").
+    // register (<4, 8, true, PASS_FWD_RECORD, true>: 0 -> 1, without culling 4 -> 5; profiles/EXPERIMENTS.md, "shared scaffold").
     const int lane = (int)(threadIdx.x & 63);
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // wave = sub-tile row inside the tile (wave-uniform: an SGPR)
     const int s = lane >> 4;               // sub-tile (DPP row) inside the wave
@@ -170,7 +163,7 @@ __global__ void __launch_bounds__(256, hier_waves(HEAD, MID, MODE, FRCP)) render
             return;
         }
     }
-    if constexpr (MODE == MODE_FWD || MODE == MODE_FWD_RECORD || MODE == MODE_FWD_INVD || MODE == MODE_FWD_RECORD_INVD) {
+    if constexpr (!BACKWARD && !DEPTHVIZ) {
         // Fused entry gather (RenderArgs::fused_gather): the workgroup sorts its tile's list and writes keys, list and entry records itself --
         // what tile_sort_gather_kernel<TS_SMALL> did in a launch of its own in front of this one, whose memory latency lay on the critical
         // path.  Here the other workgroups on the CU, busy blending, hide it.  The keys take the first 8 KB of the LDS carve, which nothing
@@ -442,7 +435,7 @@ __global__ void __launch_bounds__(256, hier_waves(HEAD, MID, MODE, FRCP)) render
         if (ok) accumulate(head.id[0], front_gid, g);
         // blend-statistics request (wave-uniform flag): this pair's blend weight goes to memory as it is, three atomics per blend
         if (ok && (a.requests & REQ_BLEND_STATS)) add_blend_stats(a, front_gid, blend_weight(T_before, front_fd.co.w, head.store[0]));
-        // inverse-depth request (MODE_BWD_INVD): alpha T dL/dD of this pair goes to memory as it is, one atomic per blend
+        // inverse-depth request (PASS_BWD_INVD): alpha T dL/dD of this pair goes to memory as it is, one atomic per blend
         if constexpr (INVD) if (ok) add_invdepth(a, front_gid, blend_weight(T_before, front_fd.co.w, head.store[0]) * bp.dL_dD);
         if (!ok) { active = false; head.num--; return; }
         head.pop();

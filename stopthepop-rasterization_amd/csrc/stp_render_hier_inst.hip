@@ -1,7 +1,5 @@
 // stp_render_hier_inst.hip -- one slice of the hierarchical kernel's instantiation ladder.
-// Compiled several times by the Makefile with -DSTP_INST_MID={8,12,20} -DSTP_INST_MODE={0,1,2}
-// (0 forward, 1 resorting backward, 2 recording forward, 3 depth-visualisation forward, 4 / 5 forward / recording forward with the
-// inverse-depth output, 6 resorting backward with the inverse-depth gradient), so the
+// Compiled once per (pass, MID) of stp_render_pass.h's list by the Makefile, with -DSTP_INST_MODE=<pass id> -DSTP_INST_MID={8,12,20}, so the
 // template instantiations (HEAD x CULL per slice) build in parallel.  Queue-size ladders follow the
 // reference: forward HEAD in {4,8,16} (forward.cu:465-472), backward HEAD in {4,8,12,16}
 // (backward.cu:745-752), MID in {8,12,20}.  -DSTP_FASTBUILD keeps only HEAD 4 (with MID 8), the
@@ -14,33 +12,20 @@
 #ifndef STP_INST_MODE
 #error "STP_INST_MODE must be defined"
 #endif
-
-#define STP_CAT2(a, b) a##b
-#define STP_CAT(a, b) STP_CAT2(a, b)
-#if STP_INST_MODE == 1
-#define STP_FN STP_CAT(launch_hier_bwd_mid, STP_INST_MID)
-#elif STP_INST_MODE == 2
-#define STP_FN STP_CAT(launch_hier_rec_mid, STP_INST_MID)
-#elif STP_INST_MODE == 3
-#define STP_FN STP_CAT(launch_hier_dbg_mid, STP_INST_MID)
-#elif STP_INST_MODE == 4
-#define STP_FN STP_CAT(launch_hier_fwdz_mid, STP_INST_MID)
-#elif STP_INST_MODE == 5
-#define STP_FN STP_CAT(launch_hier_recz_mid, STP_INST_MID)
-#elif STP_INST_MODE == 6
-#define STP_FN STP_CAT(launch_hier_bwdz_mid, STP_INST_MID)
-#else
-#define STP_FN STP_CAT(launch_hier_fwd_mid, STP_INST_MID)
+#define STP_SLICE(PASS, MID) || (STP_INST_MODE == PASS && STP_INST_MID == MID)
+#if !(0 STP_HIER_SLICES(STP_SLICE))
+#error "(STP_INST_MODE, STP_INST_MID) is not in STP_HIER_SLICES"
 #endif
+#undef STP_SLICE
 
 namespace stp {
 
 // returns hipErrorInvalidValue with *handled = false when this slice has no kernel for `head`
-hipError_t STP_FN(const FrameParams& f, const RenderArgs& a, hipStream_t st, bool* handled)
+hipError_t STP_HIER_SLICE_FN(STP_INST_MODE, STP_INST_MID)(const FrameParams& f, const RenderArgs& a, hipStream_t st, bool* handled)
 {
     constexpr int MID = STP_INST_MID;
     constexpr int MODE = STP_INST_MODE;
-    constexpr bool BWD = MODE == 1 || MODE == 6;
+    constexpr bool BWD = pass_backward(MODE);
     const int head = f.s.queue_per_pixel;
     const bool cull = f.s.hierarchical_4x4_culling != 0;
     *handled = true;
@@ -53,7 +38,7 @@ hipError_t STP_FN(const FrameParams& f, const RenderArgs& a, hipStream_t st, boo
     if (head == 4) STP_GO(4);
 #ifndef STP_FASTBUILD
     if (head == 8) STP_GO(8);
-    if (BWD && head == 12) STP_GO(12);
+    if constexpr (BWD) { if (head == 12) STP_GO(12); } // (the backward's ladder only: a forward slice has no HEAD = 12 kernel)
     if (head == 16) STP_GO(16);
 #endif
 #undef STP_GO

@@ -51,19 +51,18 @@ extern "C" int stp_debug_kb_stats(unsigned long long* out40)
 
 namespace {
 
-constexpr int KBW_FWD = 0, KBW_RECORD = 2, KBW_DEPTH = 3; // (the values of the hierarchical kernel's modes)
-constexpr int KBW_FWD_INVD = 4, KBW_RECORD_INVD = 5;      // the forward and the recording forward with the inverse-depth output (stp_set_forward_invdepth)
-
+// MODE (here and below): a forward pass of stp_render_pass.h.
 // What the kernel body and a window policy share of a pixel: its blend state, its lists' record rows, and the record rows of the entry
 // at the FRONT of its window.  Neither window carries alpha: it is evaluated again at the pop, from the same record with the same
 // operations, hence to the same bits as when the entry passed its tests.  What the pop needs of the front entry -- mean, conic +
 // opacity, colour -- is fetched when the entry BECOMES the front, one step earlier.
 template <int MODE> struct KbPixel {
-    static constexpr bool RECORD = MODE == KBW_RECORD || MODE == KBW_RECORD_INVD, DEPTHVIZ = MODE == KBW_DEPTH;
+    static_assert(!pass_backward(MODE), "the wave64 k-buffer kernels are forward passes");
+    static constexpr bool RECORD = pass_records(MODE), DEPTHVIZ = pass_depthviz(MODE);
     // INVD: a fourth accumulator D += alpha T / z.  1 / z comes by Gaussian id (the front entry's record row C carries it) from the geometry
     // buffer: the load is issued at the entry's blend and its product is added one blend later (or in the epilogue), like the hierarchical
     // kernel's colour.  A lane that does not blend keeps (0, 0): the row it read may be a stand-in's.
-    static constexpr bool INVD = MODE == KBW_FWD_INVD || MODE == KBW_RECORD_INVD;
+    static constexpr bool INVD = pass_invdepth(MODE);
     const float* invz;
     float D, pend_w, pend_z;
     int lane, px, py;
@@ -321,7 +320,7 @@ template <int MODE, class WINDOW>
 __device__ __forceinline__ void render_kbuffer_body(const RenderArgs& a, WINDOW& win, int* const s_stage /* [sub-tile][survivor] */, int* const s_fifo /* [quad][slot] */)
 {
     constexpr bool RECORD = KbPixel<MODE>::RECORD;
-    constexpr bool DEPTHVIZ = MODE == KBW_DEPTH;
+    constexpr bool DEPTHVIZ = KbPixel<MODE>::DEPTHVIZ;
     constexpr bool INVD = KbPixel<MODE>::INVD;
     constexpr int CAP = WINDOW::FIFO_CAP;
 
@@ -474,37 +473,36 @@ template <int WIN, int MODE> hipError_t launch_kb_win(const FrameParams& f, cons
     return hipGetLastError();
 }
 
-} // namespace
 
-// mode: 0 forward, 2 recording forward, 3 depth visualisation, 4 / 5 forward / recording forward with the inverse-depth output.  Every window size of the reference's ladder (forward.cu:409-425)
-// has a kernel here: four waves per SIMD up to 4 entries, three up to 16, two for 20 and 24 (164-187 VGPRs, no scratch)
-hipError_t launch_kbuffer_wave(int mode, const FrameParams& f, const RenderArgs& a, hipStream_t st, bool* handled)
+// One forward pass over the window ladder.  Every window size of the reference's ladder (forward.cu:409-425: the next supported window) has a
+// kernel here: four waves per SIMD up to 4 entries, three up to 16, two for 20 and 24 (164-187 VGPRs, no scratch).  Windows of 8 entries and
+// more: the ring-in-LDS kernel (STP_KBUFFER=wave keeps the register window for them too).
+template <int MODE> hipError_t launch_kb_pass(const FrameParams& f, const RenderArgs& a, hipStream_t st)
 {
-    const int w = f.s.queue_per_pixel; // reference forward.cu:409-425: the next supported window
-    *handled = true;
-    // windows of 8 .. 16 entries: the ring-in-LDS kernel (STP_KBUFFER=wave keeps the register window for them too)
+    const int w = f.s.queue_per_pixel;
     const bool ring = switches().kbuffer != Switches::KBUFFER_WAVE;
-#define STP_KBW(WIN) return mode == KBW_RECORD ? launch_kb_win<WIN, KBW_RECORD>(f, a, st) : mode == KBW_DEPTH ? launch_kb_win<WIN, KBW_DEPTH>(f, a, st) : \
-                            mode == KBW_FWD_INVD ? launch_kb_win<WIN, KBW_FWD_INVD>(f, a, st) : mode == KBW_RECORD_INVD ? launch_kb_win<WIN, KBW_RECORD_INVD>(f, a, st) : launch_kb_win<WIN, KBW_FWD>(f, a, st)
-#define STP_KBR(WIN) return mode == KBW_RECORD ? launch_kb_ring<WIN, KBW_RECORD>(f, a, st) : mode == KBW_DEPTH ? launch_kb_ring<WIN, KBW_DEPTH>(f, a, st) : \
-                            mode == KBW_FWD_INVD ? launch_kb_ring<WIN, KBW_FWD_INVD>(f, a, st) : mode == KBW_RECORD_INVD ? launch_kb_ring<WIN, KBW_RECORD_INVD>(f, a, st) : launch_kb_ring<WIN, KBW_FWD>(f, a, st)
-    if (w <= 1) STP_KBW(1);
-    if (w <= 2) STP_KBW(2);
-    if (w <= 4) STP_KBW(4);
-    if (ring) {
-        if (w <= 8) STP_KBR(8);
-        if (w <= 12) STP_KBR(12);
-        if (w <= 16) STP_KBR(16);
-        if (w <= 20) STP_KBR(20);
-        STP_KBR(24);
-    }
-    if (w <= 8) STP_KBW(8);
-    if (w <= 12) STP_KBW(12);
-    if (w <= 16) STP_KBW(16);
-    if (w <= 20) STP_KBW(20);
-    STP_KBW(24);
+#define STP_KBW(WIN) if (w <= WIN) return launch_kb_win<WIN, MODE>(f, a, st)
+#define STP_KBR(WIN) if (w <= WIN) return ring ? launch_kb_ring<WIN, MODE>(f, a, st) : launch_kb_win<WIN, MODE>(f, a, st)
+    STP_KBW(1); STP_KBW(2); STP_KBW(4);
+    STP_KBR(8); STP_KBR(12); STP_KBR(16); STP_KBR(20);
+    return ring ? launch_kb_ring<24, MODE>(f, a, st) : launch_kb_win<24, MODE>(f, a, st);
 #undef STP_KBW
 #undef STP_KBR
+}
+
+} // namespace
+
+// pass: a forward pass of stp_render_pass.h
+hipError_t launch_kbuffer_wave(int pass, const FrameParams& f, const RenderArgs& a, hipStream_t st)
+{
+    switch (pass) {
+    case PASS_FWD: return launch_kb_pass<PASS_FWD>(f, a, st);
+    case PASS_FWD_RECORD: return launch_kb_pass<PASS_FWD_RECORD>(f, a, st);
+    case PASS_FWD_DEPTH: return launch_kb_pass<PASS_FWD_DEPTH>(f, a, st);
+    case PASS_FWD_INVD: return launch_kb_pass<PASS_FWD_INVD>(f, a, st);
+    case PASS_FWD_RECORD_INVD: return launch_kb_pass<PASS_FWD_RECORD_INVD>(f, a, st);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 } // namespace stp

@@ -2,7 +2,7 @@
 //
 // No counterpart in the reference: its backward (hierarchical_render.cuh:1038-1175) re-runs the complete
 // three-level resort to rediscover the order in which every pixel blended its Gaussians.  MI355X has 288 GB of
-// HBM, so the training forward (render_hier_kernel<..., MODE_FWD_RECORD>, render_kbuffer_kernel<WIN, KB_FWD_RECORD>)
+// HBM, so the training forward (render_hier_kernel<..., PASS_FWD_RECORD>, render_kbuffer_kernel<WIN, PASS_FWD_RECORD>)
 // simply writes that order down -- 2 bytes (the tile-list position) per blended (pixel, Gaussian) pair,
 // as many records per pixel as the frames before it needed (RenderArgs::log_depth; 192 + eight spare rows = 400 B per pixel for a frame nothing
 // is known about, 304 B per pixel = 0.63 GB at 1080p once C2's 114 blends per pixel are known) -- and this kernel walks each pixel's log
@@ -495,29 +495,21 @@ int blend_log_clamp_depth(int d) // (a multiple of the block: a lane's records c
     return d < BLEND_LOG_DEPTH_MIN ? BLEND_LOG_DEPTH_MIN : d;
 }
 
+// one instantiation per log layout and set of requests, REQ = RenderArgs::requests (absgrad: two more terms per list position than the nine,
+// blend statistics: three, inverse depth: one -- fifteen with all of them)
+template <int REQ> static void launch_replay_one(const RenderArgs& a, bool blocked, dim3 grid, hipStream_t st)
+{
+    constexpr bool ABS = (REQ & REQ_ABSGRAD) != 0, STATS = (REQ & REQ_BLEND_STATS) != 0, INVD = (REQ & REQ_INVDEPTH) != 0;
+    if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, ABS, STATS, INVD>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((render_replay_kernel<false, ABS, STATS, INVD>), grid, dim3(256), 0, st, a);
+}
+
 hipError_t launch_hier_replay(const FrameParams& f, const RenderArgs& a, hipStream_t st)
 {
-    const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(256);
-    const bool blocked = log_blocked(f.s);
-    // one instantiation per log layout and set of requests (absgrad, blend statistics, inverse depth)
-#define STP_REPLAY(ABS, STATS, INVD)                                                                                   \
-    do {                                                                                                               \
-        if (blocked) hipLaunchKernelGGL((render_replay_kernel<true, ABS, STATS, INVD>), grid, block, 0, st, a);       \
-        else hipLaunchKernelGGL((render_replay_kernel<false, ABS, STATS, INVD>), grid, block, 0, st, a);              \
-    } while (0)
-    const bool abs_ = (a.requests & REQ_ABSGRAD) != 0, stats_ = (a.requests & REQ_BLEND_STATS) != 0, invd_ = (a.requests & REQ_INVDEPTH) != 0;
-    if (invd_) {
-        if (abs_ && stats_) STP_REPLAY(true, true, true);     // (fifteen terms per position)
-        else if (stats_) STP_REPLAY(false, true, true);       // (thirteen)
-        else if (abs_) STP_REPLAY(true, false, true);         // (twelve)
-        else STP_REPLAY(false, false, true);                  // (ten)
-    } else {
-        if (abs_ && stats_) STP_REPLAY(true, true, false);    // (both requests: fourteen terms per position)
-        else if (stats_) STP_REPLAY(false, true, false);      // (the blend-statistics request: twelve)
-        else if (abs_) STP_REPLAY(true, false, false);        // (the absgrad request: eleven)
-        else STP_REPLAY(false, false, false);
-    }
-#undef STP_REPLAY
+    static_assert((REQ_ABSGRAD | REQ_BLEND_STATS | REQ_INVDEPTH) == 7, "the table below is indexed by the three request bits");
+    static constexpr decltype(&launch_replay_one<0>) BY_REQUESTS[8] = {launch_replay_one<0>, launch_replay_one<1>, launch_replay_one<2>, launch_replay_one<3>,
+                                                                       launch_replay_one<4>, launch_replay_one<5>, launch_replay_one<6>, launch_replay_one<7>};
+    BY_REQUESTS[a.requests & 7](a, log_blocked(f.s), dim3(f.gx * (f.ty1 - f.ty0)), st);
     return hipGetLastError();
 }
 

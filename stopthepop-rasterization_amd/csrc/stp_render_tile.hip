@@ -300,19 +300,16 @@ __global__ void __launch_bounds__(BLOCK) render_global_bwd_kernel(const RenderAr
 // ------------------------------------------------------------------------------------------------
 // (min_power_rect: stp_device.h)
 
-// MODE 0 = forward, 1 = backward that re-runs the window sort (the reference's scheme; nine atomics per blended pair),
-// 2 = training forward: additionally records every pixel's blend order in the blend log, so that the backward is the
-// replay kernel of stp_render_replay.hip (the same log format and thread -> pixel mapping as the hierarchical mode).
-constexpr int KB_FWD = 0, KB_BWD = 1, KB_FWD_RECORD = 2, KB_FWD_DEPTH = 3; // 3: forward of the debug depth visualisation
-constexpr int KB_FWD_INVD = 4, KB_FWD_RECORD_INVD = 5, KB_BWD_INVD = 6;    // forward, recording forward and re-sorting backward under the inverse-depth request
-
+// MODE: a render pass of stp_render_pass.h.  The backward re-runs the window sort (the reference's scheme; nine atomics per blended pair); the
+// recording forward writes the same log format with the same thread -> pixel mapping as the hierarchical mode, so that its backward is the
+// replay kernel of stp_render_replay.hip.
 template <int WIN, int MODE>
 __global__ void __launch_bounds__(BLOCK) render_kbuffer_kernel(const RenderArgs a)
 {
-    constexpr bool BACKWARD = MODE == KB_BWD || MODE == KB_BWD_INVD;
-    constexpr bool RECORD = MODE == KB_FWD_RECORD || MODE == KB_FWD_RECORD_INVD;
-    constexpr bool DEPTHVIZ = MODE == KB_FWD_DEPTH;
-    constexpr bool INVD = MODE == KB_FWD_INVD || MODE == KB_FWD_RECORD_INVD || MODE == KB_BWD_INVD; // forward: D += alpha T / z beside the colour; backward: the fourth channel
+    constexpr bool BACKWARD = pass_backward(MODE);
+    constexpr bool RECORD = pass_records(MODE);
+    constexpr bool DEPTHVIZ = pass_depthviz(MODE);
+    constexpr bool INVD = pass_invdepth(MODE); // forward: D += alpha T / z beside the colour; backward: the fourth channel
     // one staging round = BLOCK entry records (A, B, C, D of BinningState), read with unit stride from the list-ordered
     // entry arrays; the forward passes carry the list position through the window, the backward pass the Gaussian id
     __shared__ float4 s_A[BLOCK];
@@ -463,20 +460,14 @@ static RenderArgs make_args(const FrameParams& f, const GeometryState& g, const 
     return a;
 }
 
-// implemented in stp_render_hier_fwd.hip / stp_render_hier_bwd.hip / stp_render_full.hip
-hipError_t launch_hier_fwd(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
-hipError_t launch_hier_bwd(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
-hipError_t launch_hier_rec(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
-hipError_t launch_hier_dbg(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
-hipError_t launch_hier_fwd_invd(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err); // (the two forwards with the inverse-depth output)
-hipError_t launch_hier_rec_invd(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
-hipError_t launch_hier_bwd_invd(const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err);
-hipError_t launch_depth_colormap(float* out_color, int N, uint32_t* minmax, hipStream_t st); // stp_debug_viz.hip
-hipError_t launch_hier_replay(const FrameParams& f, const RenderArgs& a, hipStream_t st);
-hipError_t launch_full_fwd(const FrameParams& f, const RenderArgs& a, hipStream_t st);
-hipError_t launch_kbuffer_wave(int mode, const FrameParams& f, const RenderArgs& a, hipStream_t st, bool* handled); // stp_render_kbuf.hip
+// implemented in the other render files
+hipError_t launch_hier(int pass, const FrameParams& f, const RenderArgs& a, hipStream_t st, std::string* err); // stp_render_hier.hip
+hipError_t launch_hier_replay(const FrameParams& f, const RenderArgs& a, hipStream_t st);                      // stp_render_replay.hip
+hipError_t launch_full_fwd(const FrameParams& f, const RenderArgs& a, hipStream_t st);                         // stp_render_full.hip
+hipError_t launch_kbuffer_wave(int pass, const FrameParams& f, const RenderArgs& a, hipStream_t st);           // stp_render_kbuf.hip
+hipError_t launch_depth_colormap(float* out_color, int N, uint32_t* minmax, hipStream_t st);                   // stp_debug_viz.hip
 
-template <int MODE> static hipError_t launch_kbuffer(const FrameParams& f, const RenderArgs& a, hipStream_t st)
+template <int MODE> static hipError_t launch_kbuffer_one(const FrameParams& f, const RenderArgs& a, hipStream_t st)
 {
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(BLOCK);
     const int w = f.s.queue_per_pixel; // reference forward.cu:409-425 / backward.cu:712-731
@@ -493,39 +484,45 @@ template <int MODE> static hipError_t launch_kbuffer(const FrameParams& f, const
     return hipGetLastError();
 }
 
+// the k-buffer kernel of this file: the re-sorting backward, and every forward pass under STP_KBUFFER=tile
+static hipError_t launch_kbuffer(int pass, const FrameParams& f, const RenderArgs& a, hipStream_t st)
+{
+    switch (pass) {
+    case PASS_FWD: return launch_kbuffer_one<PASS_FWD>(f, a, st);
+    case PASS_BWD: return launch_kbuffer_one<PASS_BWD>(f, a, st);
+    case PASS_FWD_RECORD: return launch_kbuffer_one<PASS_FWD_RECORD>(f, a, st);
+    case PASS_FWD_DEPTH: return launch_kbuffer_one<PASS_FWD_DEPTH>(f, a, st);
+    case PASS_FWD_INVD: return launch_kbuffer_one<PASS_FWD_INVD>(f, a, st);
+    case PASS_FWD_RECORD_INVD: return launch_kbuffer_one<PASS_FWD_RECORD_INVD>(f, a, st);
+    case PASS_BWD_INVD: return launch_kbuffer_one<PASS_BWD_INVD>(f, a, st);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_render_forward(const FrameParams& f, const GeometryState& g, const BinningState& b, const ImageState& img,
                                  float* out_color, hipStream_t st, std::string* err)
 {
     RenderArgs a = make_args(f, g, b, img);
     a.out_color = out_color;
-    const bool invd = a.out_invdepth != nullptr; // (stp_set_forward_invdepth: the kernels' INVD variants; never with the debug depth visualisation)
+    // (inverse depth: stp_set_forward_invdepth, the kernels' INVD variants; refused with the debug depth visualisation before this point)
+    const int pass = render_pass(false, uses_blend_log(f.s), a.debug_depth != 0, a.out_invdepth != nullptr);
+    if (pass < 0) { if (err) *err = "invalid render pass"; return hipErrorInvalidValue; }
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(BLOCK);
     if (grid.x == 0) return hipSuccess;
     switch (f.s.sort_mode) {
-    case MODE_GLOBAL:
-        if (invd) hipLaunchKernelGGL(render_global_fwd_kernel<true>, grid, block, 0, st, a);
+    case MODE_GLOBAL: // (one kernel for the plain forward and the depth visualisation: RenderArgs::debug_depth)
+        if (pass_invdepth(pass)) hipLaunchKernelGGL(render_global_fwd_kernel<true>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(render_global_fwd_kernel<false>, grid, block, 0, st, a);
         return hipGetLastError();
-    case MODE_KBUFFER: {
+    case MODE_KBUFFER:
         // the wave64 kernel of stp_render_kbuf.hip (STP_KBUFFER=tile keeps the one-entry-per-wave kernel of this file for
         // comparison; the results are the same)
-        const bool kb_tile = switches().kbuffer == Switches::KBUFFER_TILE;
-        if (!kb_tile) {
-            bool handled = false;
-            const int mode = a.debug_depth ? KB_FWD_DEPTH : uses_blend_log(f.s) ? (invd ? KB_FWD_RECORD_INVD : KB_FWD_RECORD) : (invd ? KB_FWD_INVD : KB_FWD);
-            const hipError_t e = launch_kbuffer_wave(mode, f, a, st, &handled);
-            if (handled) return e;
-        }
-        if (a.debug_depth) return launch_kbuffer<KB_FWD_DEPTH>(f, a, st);
-        if (invd) return uses_blend_log(f.s) ? launch_kbuffer<KB_FWD_RECORD_INVD>(f, a, st) : launch_kbuffer<KB_FWD_INVD>(f, a, st);
-        return uses_blend_log(f.s) ? launch_kbuffer<KB_FWD_RECORD>(f, a, st) : launch_kbuffer<KB_FWD>(f, a, st);
-    }
+        if (switches().kbuffer == Switches::KBUFFER_TILE) return launch_kbuffer(pass, f, a, st);
+        return launch_kbuffer_wave(pass, f, a, st);
     case MODE_FULL: return launch_full_fwd(f, a, st);
     case MODE_HIER:
-        if (a.debug_depth) return launch_hier_dbg(f, a, st, err);
-        a.fused_gather = f.fused_gather; // (the forward and recording forward sort + gather their tiles of up to TS_SMALL entries themselves)
-        if (invd) return uses_blend_log(f.s) ? launch_hier_rec_invd(f, a, st, err) : launch_hier_fwd_invd(f, a, st, err);
-        return uses_blend_log(f.s) ? launch_hier_rec(f, a, st, err) : launch_hier_fwd(f, a, st, err);
+        a.fused_gather = f.fused_gather; // (the forward and recording forward sort + gather their tiles of up to TS_SMALL entries themselves; 0 under the depth visualisation)
+        return launch_hier(pass, f, a, st, err);
     default: if (err) *err = "invalid sort mode"; return hipErrorInvalidValue;
     }
 }
@@ -547,29 +544,24 @@ hipError_t launch_render_backward(const FrameParams& f, const GeometryState& g, 
     // (the caller has refused compact records with either request: slots 9 .. 13 exist)
     a.requests = (bw.absgrad != nullptr ? REQ_ABSGRAD : 0) | (bw.blend_stats != nullptr ? REQ_BLEND_STATS : 0) | (bw.dL_dinvdepth != nullptr ? REQ_INVDEPTH : 0);
     a.out_invdepth = nullptr; a.invdepth = bw.invdepth; a.dL_dinvdepth = bw.dL_dinvdepth; // stp_set_backward_invdepth
-    const bool invd = (a.requests & REQ_INVDEPTH) != 0; // (the kernels' INVD instantiations)
+    // (a backward has no pass of the depth visualisation: that setting does not reach its kernels)
+    const int pass = render_pass(true, uses_blend_log(f.s), false, (a.requests & REQ_INVDEPTH) != 0);
     a.bg_image = bw.bg_image; a.out_alpha = nullptr; a.dL_dalpha = bw.dL_dalpha; // stp_set_backward_background
     const dim3 grid(f.gx * (f.ty1 - f.ty0)), block(BLOCK);
     if (grid.x == 0) return hipSuccess;
     switch (f.s.sort_mode) {
     case MODE_GLOBAL:
-        if (invd) hipLaunchKernelGGL(render_global_bwd_kernel<true>, grid, block, 0, st, a);
+        if (pass_invdepth(pass)) hipLaunchKernelGGL(render_global_bwd_kernel<true>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(render_global_bwd_kernel<false>, grid, block, 0, st, a);
         return hipGetLastError();
     case MODE_KBUFFER:
+    case MODE_HIER:
         if (uses_blend_log(f.s)) { // replay the forward's blend log; the re-sorting kernel only takes overflowed tiles
             hipError_t e = launch_hier_replay(f, a, st);
             if (e != hipSuccess) return e;
             a.flag_mode = 1;
         }
-        return invd ? launch_kbuffer<KB_BWD_INVD>(f, a, st) : launch_kbuffer<KB_BWD>(f, a, st);
-    case MODE_HIER:
-        if (uses_blend_log(f.s)) { // replay the forward's blend log; the resorting kernel only takes overflowed tiles
-            hipError_t e = launch_hier_replay(f, a, st);
-            if (e != hipSuccess) return e;
-            a.flag_mode = 1;
-        }
-        return invd ? launch_hier_bwd_invd(f, a, st, err) : launch_hier_bwd(f, a, st, err);
+        return f.s.sort_mode == MODE_HIER ? launch_hier(pass, f, a, st, err) : launch_kbuffer(pass, f, a, st);
     default: if (err) *err = "Backward not supported for full per-pixel sort"; return hipErrorInvalidValue;
     }
 }

@@ -169,6 +169,27 @@ def test_kbuffer_windows(window):
     check_against_oracle(scenes.make_scene(P=3000, W=80, H=64, sigma_min=2.0, sigma_max=12.0, seed=5), settings_dict(2, per_pixel=window))
 
 
+def test_kbuffer_tile_kernel_forward_passes():
+    """STP_KBUFFER=tile (read once per process: a child) sends the k-buffer forwards to the one-entry-per-wave kernel of stp_render_tile.hip
+    instead of the wave64 kernels: its recording forward (with the replay as its backward), its plain forward and its depth visualisation,
+    each against the oracle with the yardstick of the test that covers the same pass on the default path (test_kbuffer_windows and its scene,
+    test_n_contrib_of_the_plain_forward's image bound, test_render_depth_visualisation and its scene)."""
+    import os, subprocess, sys
+    code = ("import sys, numpy as np; sys.path[:0] = ['tests', 'stopthepop-rasterization_amd', '.']; import conftest;"
+            "from helpers import *; from diff_gaussian_rasterization import scenes; import test_gpu_parity as t;"
+            "sc = scenes.make_scene(P=3000, W=80, H=64, sigma_min=2.0, sigma_max=12.0, seed=5); sd = settings_dict(2, per_pixel=16);"
+            "g, f = t.check_against_oracle(sc, sd);"   # (backward mode 'replay', the default: the forward records the blend log)
+            "g = GpuRun(sc, sd, backward=False); f, _ = oracle_run(sc, sd, backward=False);"
+            "assert max_abs(g.color, f.color) <= 2e-6;"
+            "sc = scenes.make_scene(P=800, W=80, H=64, sigma_min=2.0, sigma_max=8.0, seed=9, camera='orbit', opacity_range=(0.5, 0.95));"
+            "g = GpuRun(sc, sd, backward=False, render_depth=True); f, _ = oracle_run(sc, sd, backward=False, render_depth=True);"
+            "assert np.ptp(f.color) > 0.5 and max_abs(g.color, f.color) <= 2e-4;"
+            "print('tile ok')")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, STP_KBUFFER="tile"), cwd=root)
+    assert r.returncode == 0 and r.stdout.endswith("tile ok\n"), r.stdout[-2000:] + r.stderr[-4000:]
+
+
 @pytest.mark.parametrize("mode,window", [(0, 4), (2, 1), (2, 4), (2, 8), (2, 12), (2, 16), (2, 24)])
 def test_n_contrib_of_the_plain_forward(mode, window):
     """n_contrib of a forward that records no blend log (inference): GLOBAL = the last contributing list entry + 1
@@ -261,8 +282,9 @@ def test_sh_degrees_and_coefficient_counts(degree, M):
 
 
 @pytest.mark.parametrize("sd", [settings_dict(0), settings_dict(0, order=1), settings_dict(2, per_pixel=16), settings_dict(1),
-                                settings_dict(3), settings_dict(**FULL_STP), settings_dict(3, per_pixel=8, tile_2x2=12, h44=True)],
-                         ids=["global_z", "global_dist", "kbuffer16", "ppx_full", "hier", "full_stp", "hier_8_12"])
+                                settings_dict(3), settings_dict(**FULL_STP), settings_dict(3, per_pixel=8, tile_2x2=12, h44=True),
+                                settings_dict(2, per_pixel=4)],   # (kbuffer4: the k-buffer's register window; kbuffer16 is the ring in LDS)
+                         ids=["global_z", "global_dist", "kbuffer16", "ppx_full", "hier", "full_stp", "hier_8_12", "kbuffer4"])
 def test_render_depth_visualisation(sd):
     """`render_depth=True` (reference rasterize_points.cu:104-107): sum(depth * alpha * T) per pixel, normalised by the
     frame's extrema, Turbo colormap -- in every sort mode, against the oracle."""

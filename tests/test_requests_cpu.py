@@ -1,5 +1,6 @@
-"""CPU tests of two host-only pieces of the library: the cache of what a scratch buffer was carved with (csrc/stp_layout_cache.h, run by
-tests/cpp/layout_cache_check.cpp under the address and undefined-behaviour sanitizers), and the rules by which a call consumes the one-shot
+"""CPU tests of three host-only pieces of the library: the cache of what a scratch buffer was carved with (csrc/stp_layout_cache.h, run by
+tests/cpp/layout_cache_check.cpp under the address and undefined-behaviour sanitizers), the render passes' ids, predicates and selector
+(csrc/stp_render_pass.h, run by tests/cpp/render_pass_check.cpp the same way), and the rules by which a call consumes the one-shot
 per-thread requests (csrc/stp_api.hip: take_forward_requests / take_backward_requests), seen through the C ABI on paths that return
 before any HIP call."""
 import ctypes
@@ -16,12 +17,23 @@ ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 STP_DEBUG_DEPTH = 1
 
 
-def test_layout_cache_hits_misses_and_evicts(tmp_path):
-    exe = str(tmp_path / "layout_cache_check")
+def _run_host_check(tmp_path, name):
+    """Build tests/cpp/<name>.cpp, a stand-alone program over one host-only header of csrc/, under the sanitizers and run it."""
+    exe = str(tmp_path / name)
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-fsanitize=address,undefined", "-I", os.path.join(ROOT, "stopthepop-rasterization_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "cpp", "layout_cache_check.cpp"), "-o", exe])
+                           os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout == "ok\n" and r.stderr == "", r.stdout + r.stderr
+
+
+def test_layout_cache_hits_misses_and_evicts(tmp_path):
+    _run_host_check(tmp_path, "layout_cache_check")
+
+
+def test_render_pass_selector_and_predicates(tmp_path):
+    """csrc/stp_render_pass.h: the selector over all 16 combinations of (backward, record, depth visualisation, inverse depth) and the four
+    predicates on the seven pass ids, against the tables of tests/cpp/render_pass_check.cpp."""
+    _run_host_check(tmp_path, "render_pass_check")
 
 
 def _lib():

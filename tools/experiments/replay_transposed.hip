@@ -25,7 +25,7 @@
 //
 // No counterpart in the reference: its backward (hierarchical_render.cuh:1038-1175) re-runs the complete
 // three-level resort to rediscover the order in which every pixel blended its Gaussians.  MI355X has 288 GB of
-// HBM, so the training forward (render_hier_kernel<..., MODE_FWD_RECORD>, render_kbuffer_kernel<WIN, KB_FWD_RECORD>)
+// HBM, so the training forward (render_hier_kernel<..., PASS_FWD_RECORD>, render_kbuffer_kernel<WIN, PASS_FWD_RECORD>)
 // simply writes that order down -- 2 bytes (the tile-list position) per blended (pixel, Gaussian) pair,
 // BLEND_LOG_DEPTH = 256 records per pixel, 512 B per pixel, 1.07 GB at 1080p -- and this kernel walks the logs.
 // The gradient maths per pair is the reference's (hierarchical_render.cuh:1094-1166); the result is the same sum
