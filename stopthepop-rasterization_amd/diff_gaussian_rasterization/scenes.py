@@ -185,6 +185,41 @@ def make_scene(P: int, W: int, H: int, sigma_min: float, sigma_max: float, seed:
                  meta=dict(seed=seed, sigma=(sigma_min, sigma_max), camera=camera))
 
 
+def vary_inputs(scene: "Scene", tanfov_scale=(1.0, 1.0), principal=(0.0, 0.0), roll: float = 0.0, scale_modifier: float = 1.0,
+                quat_norm=None, seed: int = 3) -> "Scene":
+    """A copy of `scene` with the inputs that make_scene holds constant varied; the Gaussians stay where they are in the world.
+
+    tanfov_scale = (sx, sy): tanfovx *= sx, tanfovy *= sy, so focal_x != focal_y unless sx == sy (a scale below 1 narrows the frustum:
+    Gaussians move into the 1.3 * tan_fov clamp band and beyond).
+    principal = (cx, cy): an off-centre principal point in NDC, projection[2, 0:2] of the row-vector layout: ndc_x = x / (z tanfovx) + cx.
+    roll: view space rotated about the optical axis by `roll` radians, V' = V @ Rz(roll); the camera centre, campos, does not move.
+    scale_modifier: the Scene field, as the API passes it through.
+    quat_norm = (lo, hi): each quaternion is multiplied by its own factor, uniform in [lo, hi] (stream 400 of `seed`): raw, not
+    normalised rotations as a trainer holds them.  None: as they are.
+    The matrices are formed in float64 from the scene's float32 viewmatrix and rounded once."""
+    import copy
+    sc = copy.deepcopy(scene)
+    sc.tanfovx = float(scene.tanfovx) * float(tanfov_scale[0])
+    sc.tanfovy = float(scene.tanfovy) * float(tanfov_scale[1])
+    proj = perspective(sc.tanfovx, sc.tanfovy)
+    proj[2, 0], proj[2, 1] = float(principal[0]), float(principal[1])
+    c, s = math.cos(roll), math.sin(roll)
+    Rz = np.eye(4)
+    Rz[0, 0], Rz[0, 1], Rz[1, 0], Rz[1, 1] = c, s, -s, c
+    view = np.asarray(scene.viewmatrix, np.float64) @ Rz
+    full = view @ proj
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    sc.viewmatrix, sc.projmatrix, sc.inv_viewprojmatrix = f32(view), f32(full), f32(np.linalg.inv(full))
+    sc.scale_modifier = float(scale_modifier)
+    if quat_norm is not None:
+        lo, hi = float(quat_norm[0]), float(quat_norm[1])
+        norm = lo + (hi - lo) * uniform(seed, 400, sc.P)
+        sc.rotations = f32(np.asarray(scene.rotations, np.float64) * norm[:, None])
+    sc.meta = dict(scene.meta, varied=dict(tanfov_scale=tuple(tanfov_scale), principal=tuple(principal), roll=roll,
+                                           scale_modifier=scale_modifier, quat_norm=quat_norm, seed=seed))
+    return sc
+
+
 def covariance_from_scale_rotation(scene: "Scene") -> np.ndarray:
     """(P,6) float32 world-space covariances [xx, xy, xz, yy, yz, zz] = R diag((mod*s)^2) R^T of the scene's scales and
     rotations, evaluated in float64 and rounded: a valid `cov3D_precomp` INPUT for the same Gaussians (ref:

@@ -43,19 +43,24 @@ def _rel(a, b):
     return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30)) if a.size else 0.0
 
 
-def _scene_hash(sc):
+def _scene_hash(sc, scalars=False):
+    """scalars: with tanfovx, tanfovy and scale_modifier, as the generator hashes the fixtures that carry inputs_json"""
     h = hashlib.sha256()
     for a in (sc.means3D, sc.scales, sc.rotations, sc.opacities, sc.shs, sc.colors_precomp, sc.viewmatrix, sc.projmatrix,
               sc.inv_viewprojmatrix, sc.campos, sc.bg, sc.dL_dout):
         if a is not None:
             h.update(np.ascontiguousarray(a).tobytes())
+    if scalars:
+        h.update(np.array([sc.tanfovx, sc.tanfovy, sc.scale_modifier], np.float64).tobytes())
     return h.hexdigest()
 
 
 def load_case(path):
     z = np.load(path)
     sc = scenes.make_scene(**json.loads(str(z["scene_json"])))
-    assert _scene_hash(sc) == str(z["scene_sha256"]), "the seeded scene generator no longer reproduces the fixture's inputs"
+    if "inputs_json" in z.files:   # scenes.vary_inputs arguments (tests/golden/make_ref_golden.py: a case's `inputs`)
+        sc = scenes.vary_inputs(sc, **json.loads(str(z["inputs_json"])))
+    assert _scene_hash(sc, scalars="inputs_json" in z.files) == str(z["scene_sha256"]), "the seeded scene generator no longer reproduces the fixture's inputs"
     sd = json.loads(str(z["settings_json"]))
     c3 = z["cov3D_precomp"] if "cov3D_precomp" in z.files else None
     return z, sc, sd, c3

@@ -173,10 +173,14 @@ def test_product_against_the_live_reference(name, sd, variant):
 @LIVE
 @pytest.mark.parametrize("name,sd", [
     ("kbuffer16", settings_dict(2, per_pixel=16)), ("hier", settings_dict(3)), ("hier_cull_h8_m12", settings_dict(3, per_pixel=8, tile_2x2=12, h44=True)),
-    ("ptd_max", settings_dict(0, order=3)), ("full_stp", settings_dict(**{**FULL_STP, "tight": False}))])
+    ("ptd_max", settings_dict(0, order=3)), ("full_stp", settings_dict(**{**FULL_STP, "tight": False})),
+    ("full_stp_varied_camera_mod06", settings_dict(**{**FULL_STP, "tight": False}))])
 def test_product_is_bit_exact_with_the_live_reference(name, sd):
-    """Fresh seed, dense scene (~700 entries per tile): the default library against the reference's IEEE build, live."""
+    """Fresh seed, dense scene (~700 entries per tile): the default library against the reference's IEEE build, live.  The last case
+    with fx != fy, an off-centre principal point, a rolled view and scale_modifier = 0.6 (scenes.vary_inputs)."""
     sc = scenes.make_scene(P=6000, W=96, H=80, sigma_min=2.0, sigma_max=14.0, seed=79, camera="orbit")
+    if name == "full_stp_varied_camera_mod06":
+        sc = scenes.vary_inputs(sc, tanfov_scale=(1.3, 1.0), principal=(0.3, -0.2), roll=0.6, scale_modifier=0.6)
     rf = ref.forward_scene(sc, sd, variant="ieee")
     rg = rf.backward(sc.dL_dout)
     g = GpuRun(sc, sd, backward=True)

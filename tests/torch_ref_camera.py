@@ -19,26 +19,37 @@ def render(scene, order="global", proper_ewa_scaling=False, use_cov3D_precomp=Fa
     return img, leaves
 
 
-def with_clamped_gaussians(scene, z=10.0, ratio=1.4, sigma_px=4.0, opacity=0.5):
+def with_clamped_gaussians(scene, z=10.0, ratio=1.4, sigma_px=4.0, opacity=0.5, y_band=False):
     """A copy of `scene` with two Gaussians appended whose view-space means lie in the clamped band (|x / z| = ratio * tan_fovx >
-    1.3 * tan_fovx, one on each side), wide enough (sigma_px pixels) that their footprints reach into the frame."""
+    1.3 * tan_fovx, one on each side), wide enough (sigma_px pixels) that their footprints reach into the frame.
+    y_band: two more behind them, in the band of the other axis (|y / z| = ratio * tan_fovy, one on each side, x inside the frame),
+    sized by the y focal length."""
     import copy
     sc = copy.deepcopy(scene)
     V = np.asarray(sc.viewmatrix, np.float64)
     focal = sc.W / (2.0 * sc.tanfovx)
     pts_view = np.array([[ratio * sc.tanfovx * z, 0.1 * sc.tanfovy * z, z], [-ratio * sc.tanfovx * z, -0.2 * sc.tanfovy * z, z]])
-    world = (pts_view - V[3, :3]) @ np.linalg.inv(V[:3, :3])
     s = sigma_px * z / focal
+    sizes = [[s, 0.8 * s, 0.9 * s], [0.9 * s, s, 0.7 * s]]
+    q = np.array([[0.9, 0.1, 0.3, 0.3], [0.8, -0.2, 0.4, 0.4]])
+    colors = [[0.8, 0.3, 0.2], [0.1, 0.6, 0.9]]
+    if y_band:
+        pts_view = np.concatenate([pts_view, [[0.15 * sc.tanfovx * z, ratio * sc.tanfovy * z, z], [-0.3 * sc.tanfovx * z, -ratio * sc.tanfovy * z, z]]])
+        sy = sigma_px * z / (sc.H / (2.0 * sc.tanfovy))
+        sizes += [[0.8 * sy, sy, 0.9 * sy], [sy, 0.7 * sy, 0.9 * sy]]
+        q = np.concatenate([q, [[0.7, 0.3, -0.1, 0.5], [0.6, -0.4, 0.2, -0.3]]])
+        colors += [[0.4, 0.9, 0.3], [0.7, 0.2, 0.6]]
+    n = len(pts_view)
+    world = (pts_view - V[3, :3]) @ np.linalg.inv(V[:3, :3])
     f32 = lambda a: np.asarray(a, np.float32)
     sc.means3D = f32(np.concatenate([sc.means3D, world]))
-    sc.scales = f32(np.concatenate([sc.scales, [[s, 0.8 * s, 0.9 * s], [0.9 * s, s, 0.7 * s]]]))
-    q = np.array([[0.9, 0.1, 0.3, 0.3], [0.8, -0.2, 0.4, 0.4]])
+    sc.scales = f32(np.concatenate([sc.scales, sizes]))
     sc.rotations = f32(np.concatenate([sc.rotations, q / np.linalg.norm(q, axis=1, keepdims=True)]))
-    sc.opacities = f32(np.concatenate([sc.opacities, [[opacity], [opacity]]]))
+    sc.opacities = f32(np.concatenate([sc.opacities, [[opacity]] * n]))
     if sc.shs is not None:
-        sc.shs = f32(np.concatenate([sc.shs, np.tile(sc.shs[:1], (2, 1, 1))]))
+        sc.shs = f32(np.concatenate([sc.shs, np.tile(sc.shs[:1], (n, 1, 1))]))
     if sc.colors_precomp is not None:
-        sc.colors_precomp = f32(np.concatenate([sc.colors_precomp, [[0.8, 0.3, 0.2], [0.1, 0.6, 0.9]]]))
+        sc.colors_precomp = f32(np.concatenate([sc.colors_precomp, colors]))
     return sc
 
 
