@@ -3,7 +3,7 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
@@ -22,8 +22,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "stopthepop-rasterization_amd"))
 from diff_gaussian_rasterization import (CullingSettings, ExtendedSettings, GaussianRasterizationSettings,  # noqa: E402
-                                         GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, SparseGaussianAdam, photometric_loss,
-                                         scenes)
+                                         GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, SparseGaussianAdam, compute_relocation,
+                                         mcmc_add_noise_, photometric_loss, scenes)
 
 
 def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, scaling_modifier: float = 1.0,
@@ -94,6 +94,34 @@ def camera_of(sc: scenes.Scene, device):
                            world_view_transform=t(sc.viewmatrix), full_proj_transform=t(sc.projmatrix), camera_center=t(sc.campos))
 
 
+def relocate_dead(model: ToyGaussians, opt: torch.optim.Optimizer, min_opacity: float = 0.005) -> int:
+    """3DGS-MCMC's relocate_gs: every Gaussian whose opacity has fallen to min_opacity or below moves onto a live one, drawn with probability
+    proportional to its opacity; a live Gaussian drawn k times is then there k + 1 times, and compute_relocation gives the opacity and scales
+    that leave the rendered image unchanged.  Sampling and row copies are torch's; the Adam moments of the touched rows start again from
+    zero.  Returns the number of Gaussians relocated."""
+    with torch.no_grad():
+        opacity = model.get_opacity.reshape(-1)
+        dead = opacity <= min_opacity
+        n_dead = int(dead.sum())
+        if n_dead == 0 or n_dead == dead.numel():
+            return 0
+        dead_idx, alive_idx = dead.nonzero()[:, 0], (~dead).nonzero()[:, 0]
+        sampled = alive_idx[torch.multinomial(opacity[alive_idx], n_dead, replacement=True)]
+        ratio = torch.bincount(sampled, minlength=dead.numel())[sampled] + 1
+        new_opacity, new_scaling = compute_relocation(model.get_opacity[sampled], model.get_scaling[sampled], ratio)   # (N is clamped to 50 inside)
+        new_opacity = new_opacity.clamp(min_opacity, 1.0 - torch.finfo(torch.float32).eps)
+        model._opacity[sampled] = torch.log(new_opacity / (1.0 - new_opacity))
+        model._scaling[sampled] = torch.log(new_scaling)
+        touched = torch.cat([sampled, dead_idx])
+        for param in (model._xyz, model._features, model._opacity, model._scaling, model._rotation):
+            param[dead_idx] = param[sampled]
+            state = opt.state.get(param)
+            if state:
+                state["exp_avg"][touched] = 0
+                state["exp_avg_sq"][touched] = 0
+    return n_dead
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
@@ -112,6 +140,9 @@ def main(argv=None):
                     help="sparse_adam: SparseGaussianAdam, one fused launch that steps only the Gaussians visible in the frame (INTEGRATION.md section 3i)")
     ap.add_argument("--loss", default="l1", choices=["l1", "l1_ssim"],
                     help="l1_ssim: the trainers' 0.8 * L1 + 0.2 * (1 - SSIM) from the fused photometric_loss (INTEGRATION.md section 3j)")
+    ap.add_argument("--strategy", default="none", choices=["none", "mcmc"],
+                    help="mcmc: 3DGS-MCMC -- the fused position noise after every optimizer step, dead Gaussians relocated every 10 iterations with "
+                         "compute_relocation, and the opacity / scale L1 regularisers (INTEGRATION.md section 3l)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
@@ -150,6 +181,13 @@ def main(argv=None):
     stat_abs = torch.zeros_like(stat_signed)
     first = last = None
     label = "L1" if args.loss == "l1" else "0.8 L1 + 0.2 (1 - SSIM)"
+    mcmc = args.strategy == "mcmc"
+    noise_scale = 5e5 * 1.6e-4   # upstream's noise_lr times its initial position learning rate (the positions themselves are not fitted here)
+    relocated = relocations = 0
+    if mcmc:
+        torch.manual_seed(0)   # (the noise and the sampling are torch's: a run is reproducible)
+        with torch.no_grad():  # every fiftieth Gaussian starts dead (opacity 0.002), so that the first relocation has work whatever the fit does
+            model._opacity[::50] = math.log(0.002 / 0.998)
     for it in range(args.iters):
         out = render(cam, model, bg, train_cfg)
         if args.loss == "l1_ssim":   # both terms from one fused kernel pair; the printed figure is this loss then
@@ -160,6 +198,8 @@ def main(argv=None):
             loss = loss + args.mask_weight * (out["alpha"] - target_alpha).abs().mean()
         if with_depth:   # (and so is the inverse depth: no second render)
             loss = loss + args.depth_weight * (out["invdepth"] - target_invdepth).abs().mean()
+        if mcmc:   # upstream's opacity_reg and scale_reg: L1 pressure that lets unneeded Gaussians die, to be relocated
+            loss = loss + 0.01 * model.get_opacity.mean() + 0.01 * model.get_scaling.mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
         grad2d = out["viewspace_points"].grad  # what densification accumulates
@@ -171,12 +211,20 @@ def main(argv=None):
             opt.step(out["radii"], model.get_xyz.shape[0])
         else:
             opt.step()
+        if mcmc:
+            if it > 0 and it % 10 == 0:
+                relocated += relocate_dead(model, opt)
+                relocations += 1
+            # xyz += Sigma (randn * op_sigmoid(1 - opacity) * noise_lr * xyz_lr) in one kernel, from the raw parameters the step just moved
+            mcmc_add_noise_(model._xyz, model._scaling, model._rotation, model._opacity, torch.randn_like(model._xyz), noise_scale, raw=True)
         last = float(loss.detach())
         first = last if first is None else first
         if it % 10 == 0 or it == args.iters - 1:
             print(f"iter {it:3d}  {label} {last:.5f}  visible {int(out['visibility_filter'].sum())}  |grad2D| max {float(grad2d.norm(dim=1).max()):.3e}")
     with torch.no_grad():
         depth = render(cam, model, bg, cfg, render_depth=True)["render"]
+    if mcmc:
+        print(f"mcmc: relocated {relocated} Gaussians in {relocations} relocation steps (opacity <= 0.005), position noise after each of {args.iters} steps")
     if args.absgrad:
         print(f"densification statistic, mean over Gaussians: signed {float(stat_signed.mean()):.3e}, absolute {float(stat_abs.mean()):.3e} "
               f"(absolute >= signed for {float((stat_abs >= stat_signed * (1 - 1e-5)).float().mean()) * 100:.1f} % of them)")

@@ -325,6 +325,27 @@ typedef struct { float* param; const float* grad; float* exp_avg; float* exp_avg
 int stp_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind /* 0: N bytes, non-zero = visible; 1: N int32, > 0 = visible */,
                     float beta1, float beta2, void* stream);
 
+/* Extension (not in the reference): the two kernels of a 3DGS-MCMC trainer ("3D Gaussian Splatting as Markov Chain Monte Carlo").
+   stp_mcmc_relocation is that project's compute_relocation: Gaussian i of opacity o and scales s, to be replaced by N_i copies of itself, gets
+       o_new = 1 - (1 - o)^(1/N)     denom = sum_{j=1..N} sum_{k=0..j-1} C(j-1, k) (-1)^k o_new^(k+1) / sqrt(k+1)     s_new = (o / denom) s
+   with N_i clamped to [1, n_max - 1] (the inputs are not modified).  The sum is evaluated in float64 in its collapsed form
+   sum_{k=0..N-1} C(N, k+1) (-1)^k o_new^(k+1) / sqrt(k+1), o_new as -expm1(log1p(-o) / N); the results are rounded to float32 once.
+   opacity_old, opacity_new: n floats; scale_old, scale_new: n x 3 floats; N: n int32 (n_kind 0) or n int64 (n_kind 1), naturally aligned.
+   stp_mcmc_add_noise is the trainer's per-iteration position noise in one pass, in place on xyz:
+       o = raw ? sigmoid(opacities[i]) : opacities[i]      s = raw ? exp(scales[i]) : scales[i]      q = rotations[i] / |rotations[i]|  (w, x, y, z)
+       g = 1 / (1 + exp(-k ((1 - o) - x0)))                xyz[i] += R(q) diag(s^2) R(q)^T (noise[i] * g * noise_scale)
+   in float32 IEEE arithmetic: a gate whose exp overflows is 0, a zero quaternion gives NaN in its own row only.  xyz, scales, noise: P x 3
+   floats; rotations: P x 4; opacities: P.  Where all five pointers are 16-byte aligned the streams move 16 bytes per lane, otherwise one float
+   per access; the arithmetic is the same.  No atomics: equal inputs give equal bits.
+   Each call returns the number of kernel launches made (1; 0 for n == 0 / P == 0: nothing is touched), or a negative StpStatus with the reason
+   in the last-error text.  Refused BEFORE anything is launched (STP_ERR_INVALID_ARGUMENT): a negative count, an n_kind other than 0 or 1, an
+   n_max outside [2, 51], a raw other than 0 or 1, a null pointer.  Plain calls: no host synchronisation, no allocation, no per-thread request
+   state.  All pointers are device pointers to contiguous data. */
+int stp_mcmc_relocation(int n, const float* opacity_old, const float* scale_old, const void* N, int n_kind /* 0: int32, 1: int64 */, int n_max,
+                        float* opacity_new, float* scale_new, void* stream);
+int stp_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise,
+                       float noise_scale, float k, float x0, int raw, void* stream);
+
 /* Extension (not in the reference): the fused photometric loss of 3DGS trainers, (1 - lambda) * L1 + lambda * (1 - SSIM) -- upstream's
    l1_loss and ssim() with window_size = 11 and size_average = True, the pair the `fused-ssim` extension replaces.  `image` (x) and `target`
    (y) are `planes` contiguous float32 planes of H x W (a (C, H, W) or (B, C, H, W) tensor: planes = B * C), n = planes * H * W.  With

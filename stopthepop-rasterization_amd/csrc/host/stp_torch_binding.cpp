@@ -75,6 +75,8 @@ struct Api {
     decltype(&stp_set_forward_invdepth) set_forward_invdepth = nullptr;
     decltype(&stp_set_backward_invdepth) set_backward_invdepth = nullptr;
     decltype(&stp_sparse_adam) sparse_adam = nullptr;
+    decltype(&stp_mcmc_relocation) mcmc_relocation = nullptr;
+    decltype(&stp_mcmc_add_noise) mcmc_add_noise = nullptr;
     decltype(&stp_photometric_workspace_floats) photometric_workspace_floats = nullptr;
     decltype(&stp_photometric_forward) photometric_forward = nullptr;
     decltype(&stp_photometric_backward) photometric_backward = nullptr;
@@ -104,6 +106,8 @@ int load_library(const std::string& path)
     a.set_forward_invdepth = reinterpret_cast<decltype(a.set_forward_invdepth)>(dlsym(h, "stp_set_forward_invdepth"));
     a.set_backward_invdepth = reinterpret_cast<decltype(a.set_backward_invdepth)>(dlsym(h, "stp_set_backward_invdepth"));
     a.sparse_adam = reinterpret_cast<decltype(a.sparse_adam)>(dlsym(h, "stp_sparse_adam"));
+    a.mcmc_relocation = reinterpret_cast<decltype(a.mcmc_relocation)>(dlsym(h, "stp_mcmc_relocation"));
+    a.mcmc_add_noise = reinterpret_cast<decltype(a.mcmc_add_noise)>(dlsym(h, "stp_mcmc_add_noise"));
     a.photometric_workspace_floats = reinterpret_cast<decltype(a.photometric_workspace_floats)>(dlsym(h, "stp_photometric_workspace_floats"));
     a.photometric_forward = reinterpret_cast<decltype(a.photometric_forward)>(dlsym(h, "stp_photometric_forward"));
     a.photometric_backward = reinterpret_cast<decltype(a.photometric_backward)>(dlsym(h, "stp_photometric_backward"));
@@ -590,6 +594,96 @@ int sparse_adam(const std::vector<torch::Tensor>& params, const std::vector<torc
     return rc;
 }
 
+// == the 3DGS-MCMC kernels (extension, include/stp_raster.h: stp_mcmc_relocation / stp_mcmc_add_noise; compute_relocation and mcmc_add_noise_ in
+// __init__.py), on the caller's current stream.  What is wrong with the tensors themselves is refused first, where they live last: every refusal
+// can be met without a GPU.
+static void mcmc_check_float(const char* who, const char* name, const torch::Tensor& t)
+{
+    TORCH_CHECK(t.defined(), who, ": ", name, " must be a tensor");
+    TORCH_CHECK(t.scalar_type() == torch::kFloat32, who, ": ", name, ": expected float32 tensor, got ", t.scalar_type());
+}
+static void mcmc_check_rows(const char* who, const char* name, const torch::Tensor& t, const int64_t rows, const int64_t width)
+{
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && t.size(1) == width, who, ": ", name, " must be (", rows, ", ", width, "), got ", t.sizes());
+}
+static void mcmc_check_column(const char* who, const char* name, const torch::Tensor& t)
+{
+    TORCH_CHECK(t.dim() == 1 || (t.dim() == 2 && t.size(1) == 1), who, ": ", name, " must be (n,) or (n, 1), got ", t.sizes());
+}
+static void mcmc_check_device(const char* who, const char* name, const torch::Tensor& t, const torch::Tensor& first)
+{
+    TORCH_CHECK(t.device() == first.device(), who, ": ", name, ": expected all tensors on ", first.device(), ", got one on ", t.device());
+    TORCH_CHECK(t.is_cuda(), who, ": ", name, ": diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
+}
+
+// -> (opacity_new of opacity_old's shape, scale_new (n, 3)); upstream's name and argument order.  binoms: checked for its shape only -- the kernel
+// has its own binomials -- and n_max is the clamp's upper bound plus one.  N is NOT clamped in place (upstream's is).
+std::tuple<torch::Tensor, torch::Tensor> compute_relocation(const torch::Tensor& opacity_old, const torch::Tensor& scale_old, const torch::Tensor& N,
+                                                            const c10::optional<torch::Tensor>& binoms_in, const int64_t n_max)
+{
+    static const char* const who = "compute_relocation";
+    need_library();
+    if (!g_api.mcmc_relocation)
+        throw std::runtime_error("compute_relocation: the loaded libstp_raster.so does not export stp_mcmc_relocation (a library built before the 3DGS-MCMC kernels): rebuild it");
+    mcmc_check_float(who, "opacity_old", opacity_old);
+    mcmc_check_float(who, "scale_old", scale_old);
+    TORCH_CHECK(N.defined() && (N.scalar_type() == torch::kInt32 || N.scalar_type() == torch::kInt64), who, ": N: expected int32 or int64 tensor, got ", N.scalar_type());
+    TORCH_CHECK(n_max >= 2 && n_max <= 51, who, ": n_max must be in [2, 51], got ", n_max);
+    if (binoms_in.has_value()) {
+        const torch::Tensor& binoms = *binoms_in;
+        mcmc_check_float(who, "binoms", binoms);
+        TORCH_CHECK(binoms.dim() == 2 && binoms.size(0) == n_max && binoms.size(1) == n_max, who, ": binoms must be (n_max, n_max) = (", n_max, ", ", n_max, "), got ", binoms.sizes());
+    }
+    mcmc_check_column(who, "opacity_old", opacity_old);
+    mcmc_check_column(who, "N", N);
+    const int64_t n = opacity_old.size(0);
+    TORCH_CHECK(n < (1ll << 31), who, ": opacity_old: ", n, " rows >= 2^31");
+    mcmc_check_rows(who, "scale_old", scale_old, n, 3);
+    TORCH_CHECK(N.size(0) == n, who, ": N has ", N.size(0), " rows, opacity_old has ", n);
+    mcmc_check_device(who, "scale_old", scale_old, opacity_old);
+    mcmc_check_device(who, "N", N, opacity_old);
+    mcmc_check_device(who, "opacity_old", opacity_old, opacity_old);
+    const torch::Tensor o = opacity_old.contiguous(), s = scale_old.contiguous(), cnt = N.contiguous();
+    const c10::hip::HIPGuard guard(o.device().index());
+    torch::Tensor o_new = torch::empty(o.sizes(), o.options()), s_new = torch::empty(s.sizes(), s.options());
+    if (n == 0) return {o_new, s_new};
+    const int rc = g_api.mcmc_relocation((int)n, o.data_ptr<float>(), s.data_ptr<float>(), cnt.data_ptr(), cnt.scalar_type() == torch::kInt64 ? 1 : 0, (int)n_max,
+                                         o_new.data_ptr<float>(), s_new.data_ptr<float>(), (void*)c10::hip::getCurrentHIPStream(o.device().index()).stream());
+    if (rc < 0) raise_last(rc);
+    return {o_new, s_new};
+}
+
+// in place on xyz (which must be contiguous: it is updated where it lies); the other four are made contiguous.  Returns the launches made.
+int mcmc_add_noise(const torch::Tensor& xyz, const torch::Tensor& scales, const torch::Tensor& rotations, const torch::Tensor& opacities,
+                   const torch::Tensor& noise, const double noise_scale, const double k, const double x0, const bool raw)
+{
+    static const char* const who = "mcmc_add_noise";
+    need_library();
+    if (!g_api.mcmc_add_noise)
+        throw std::runtime_error("mcmc_add_noise: the loaded libstp_raster.so does not export stp_mcmc_add_noise (a library built before the 3DGS-MCMC kernels): rebuild it");
+    const torch::Tensor* all[5] = {&xyz, &scales, &rotations, &opacities, &noise};
+    static const char* const names[5] = {"xyz", "scales", "rotations", "opacities", "noise"};
+    for (int j = 0; j < 5; j++) mcmc_check_float(who, names[j], *all[j]);
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, who, ": xyz must be (P, 3), got ", xyz.sizes());
+    const int64_t P = xyz.size(0);
+    TORCH_CHECK(P < (1ll << 31), who, ": xyz: ", P, " rows >= 2^31");
+    mcmc_check_rows(who, "scales", scales, P, 3);
+    mcmc_check_rows(who, "rotations", rotations, P, 4);
+    mcmc_check_rows(who, "noise", noise, P, 3);
+    mcmc_check_column(who, "opacities", opacities);
+    TORCH_CHECK(opacities.size(0) == P, who, ": opacities has ", opacities.size(0), " rows, xyz has ", P);
+    for (int j = 1; j < 5; j++) mcmc_check_device(who, names[j], *all[j], xyz);
+    mcmc_check_device(who, "xyz", xyz, xyz);
+    TORCH_CHECK(xyz.is_contiguous(), who, ": xyz must be contiguous (it is updated in place)");
+    if (P == 0) return 0;
+    const torch::Tensor s = scales.contiguous(), q = rotations.contiguous(), o = opacities.contiguous(), w = noise.contiguous();
+    const c10::hip::HIPGuard guard(xyz.device().index());
+    const int rc = g_api.mcmc_add_noise((int)P, xyz.data_ptr<float>(), s.data_ptr<float>(), q.data_ptr<float>(), o.data_ptr<float>(), w.data_ptr<float>(),
+                                        (float)noise_scale, (float)k, (float)x0, raw ? 1 : 0, (void*)c10::hip::getCurrentHIPStream(xyz.device().index()).stream());
+    if (rc < 0) raise_last(rc);
+    return rc;
+}
+
 // == the fused photometric loss (extension, include/stp_raster.h: stp_photometric_forward / _backward; photometric_loss and fused_ssim in
 // __init__.py), on the caller's current stream.  image, target: float32 (C, H, W) or (B, C, H, W) on one GPU, made contiguous here.
 struct PhotometricShape { int planes, H, W; };
@@ -725,6 +819,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward);
     m.def("mark_visible", &mark_visible);
     m.def("sparse_adam", &sparse_adam);
+    m.def("compute_relocation", &compute_relocation);
+    m.def("mcmc_add_noise", &mcmc_add_noise);
     m.def("photometric_forward", &photometric_forward);
     m.def("photometric_backward", &photometric_backward);
     m.def("scratch_generation", &scratch_generation);

@@ -1,6 +1,6 @@
 // stp_api.hip -- the C ABI of libstp_raster.so (declared in include/stp_raster.h): the per-thread error state, the argument checks
 // and frame description that forward and backward share, the one-shot per-thread requests, and the backward, mark-visible, sparse
-// Adam and photometric-loss calls.  Replaces CudaRasterizer::Rasterizer::{backward,markVisible} (reference cuda_rasterizer/rasterizer_impl.cu:417-526,
+// Adam, 3DGS-MCMC and photometric-loss calls.  Replaces CudaRasterizer::Rasterizer::{backward,markVisible} (reference cuda_rasterizer/rasterizer_impl.cu:417-526,
 // 161-173).  The forward is stp_forward.hip, the scratch buffers and their queries stp_buffers.hip, the stage timer stp_timer.hip.
 //
 // The calls are re-entrant: the scratch buffers belong to the caller, stp_last_error and the requests are per thread, and the
@@ -312,6 +312,36 @@ int stp_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const vo
     hipError_t e;
     const int launches = launch_sparse_adam(n_tensors, tensors, N, visible, visible_kind, beta1, beta2, (hipStream_t)stream, &e);
     if (e != hipSuccess) return fail_hip(e, "sparse_adam launch");
+    return launches;
+}
+
+int stp_mcmc_relocation(int n, const float* opacity_old, const float* scale_old, const void* N, int n_kind, int n_max, float* opacity_new,
+                        float* scale_new, void* stream)
+{
+    // everything is checked before the launch
+    if (n < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mcmc_relocation: negative n");
+    if (n_kind != 0 && n_kind != 1)
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_mcmc_relocation: unknown n_kind " + std::to_string(n_kind) + " (0: int32, 1: int64)");
+    if (n_max < 2 || n_max > 51)
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_mcmc_relocation: n_max " + std::to_string(n_max) + " outside [2, 51] (N is clamped to [1, n_max - 1])");
+    if (n == 0) return 0;
+    if (!opacity_old || !scale_old || !N || !opacity_new || !scale_new) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mcmc_relocation: null pointer");
+    hipError_t e;
+    const int launches = launch_mcmc_relocation(n, opacity_old, scale_old, N, n_kind, n_max, opacity_new, scale_new, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "mcmc_relocation launch");
+    return launches;
+}
+
+int stp_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise, float noise_scale,
+                       float k, float x0, int raw, void* stream)
+{
+    if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mcmc_add_noise: negative P");
+    if (raw != 0 && raw != 1) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mcmc_add_noise: raw must be 0 or 1, got " + std::to_string(raw));
+    if (P == 0) return 0;
+    if (!xyz || !scales || !rotations || !opacities || !noise) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mcmc_add_noise: null pointer");
+    hipError_t e;
+    const int launches = launch_mcmc_add_noise(P, xyz, scales, rotations, opacities, noise, noise_scale, k, x0, raw, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "mcmc_add_noise launch");
     return launches;
 }
 

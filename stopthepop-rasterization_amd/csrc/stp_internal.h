@@ -275,6 +275,12 @@ hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmat
 // the launches made, *err = the launch error that ended them early (or hipSuccess)
 int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind, float beta1, float beta2,
                        hipStream_t st, hipError_t* err);
+// the 3DGS-MCMC kernels (stp_mcmc.hip) over arguments stp_mcmc_relocation / stp_mcmc_add_noise have validated (n, P in [1, 2^31)): one launch
+// each; both return the launches made, *err = the launch error (or hipSuccess)
+int launch_mcmc_relocation(int n, const float* opacity_old, const float* scale_old, const void* N, int n_kind, int n_max, float* opacity_new,
+                           float* scale_new, hipStream_t st, hipError_t* err);
+int launch_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise, float noise_scale,
+                          float k, float x0, int raw, hipStream_t st, hipError_t* err);
 // the fused photometric loss (stp_loss.hip) over arguments stp_photometric_* have validated (planes * H * W in [1, 2^31)): workgroups of the
 // tiled kernels (= rows of two partial sums in the workspace); the forward = tile kernel (with the three derivative maps when `maps`) + the
 // one-workgroup sum, the backward = one tile kernel.  Both return the launches made, *err = the launch error that ended them early

@@ -51,6 +51,8 @@ _OPTIONAL_SYMBOLS = {
     "stp_set_backward_invdepth": ([ctypes.c_void_p] * 2, None),
     "stp_sparse_adam": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
                         ctypes.c_int),
+    "stp_mcmc_relocation": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3, ctypes.c_int),
+    "stp_mcmc_add_noise": ([ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_float] * 3 + [ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "stp_photometric_workspace_floats": ([ctypes.c_int] * 3, ctypes.c_size_t),
     "stp_photometric_forward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int),
     "stp_photometric_backward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int),
@@ -61,6 +63,7 @@ _SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blen
                    "stp_set_backward_background": "the alpha output and per-pixel background",
                    "stp_set_forward_invdepth": "the inverse-depth output", "stp_set_backward_invdepth": "the inverse-depth output",
                    "stp_sparse_adam": "the sparse Adam step",
+                   "stp_mcmc_relocation": "the 3DGS-MCMC kernels", "stp_mcmc_add_noise": "the 3DGS-MCMC kernels",
                    "stp_photometric_workspace_floats": "the photometric loss", "stp_photometric_forward": "the photometric loss",
                    "stp_photometric_backward": "the photometric loss"}
 
@@ -460,6 +463,29 @@ def adamUpdate(param, grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps, N, M)
     if int(N) * int(M) != param.numel():
         raise RuntimeError(f"adamUpdate: param has {param.numel()} elements, N * M = {int(N) * int(M)}")
     sparse_adam([param], [grad], [exp_avg], [exp_avg_sq], visible, [lr], [eps], b1, b2, N)
+
+
+RELOCATION_N_MAX = 51   # upstream's N_max: N is clamped to [1, N_max - 1]
+
+
+def compute_relocation(opacity_old, scale_old, N, binoms=None, n_max=RELOCATION_N_MAX):
+    """The opacity and scales of each of N copies that replace a Gaussian (extension, include/stp_raster.h: stp_mcmc_relocation), under the
+    name and argument order of the 3DGS-MCMC rasterizer's `_C.compute_relocation`: -> (opacity_new of opacity_old's shape, scale_new (n, 3)),
+    float32, on the current stream.  opacity_old (n,) or (n, 1) and scale_old (n, 3) float32, N (n,) or (n, 1) int32 / int64, clamped to
+    [1, n_max - 1] WITHOUT being modified.  binoms: upstream's (n_max, n_max) float32 table, n_max <= 51; its shape is checked and its
+    CONTENTS ARE NOT READ -- the kernel forms its own binomials (exactly, in float64) -- so only n_max, the clamp's upper bound plus one, has
+    an effect.  binoms=None: no table."""
+    _require("stp_mcmc_relocation")
+    return tuple((_host or _native()).compute_relocation(opacity_old, scale_old, N, binoms, int(n_max)))
+
+
+def mcmc_add_noise(xyz, scales, rotations, opacities, noise, noise_scale, k, x0, raw) -> int:
+    """The 3DGS-MCMC position noise in one pass, IN PLACE on xyz (extension, include/stp_raster.h: stp_mcmc_add_noise), on the current stream:
+    xyz[i] += R diag(s^2) R^T (noise[i] * g * noise_scale), g = 1 / (1 + exp(-k ((1 - o) - x0))); raw: scales and opacities are the model's
+    raw parameters (exp and sigmoid are applied in the kernel).  xyz (P, 3) contiguous, scales (P, 3), rotations (P, 4), opacities (P,) or
+    (P, 1), noise (P, 3), all float32 on one GPU.  Returns the kernel launches made (1; 0 for P == 0)."""
+    _require("stp_mcmc_add_noise")
+    return int((_host or _native()).mcmc_add_noise(xyz, scales, rotations, opacities, noise, float(noise_scale), float(k), float(x0), bool(raw)))
 
 
 def photometric_forward(image, target, want_maps):

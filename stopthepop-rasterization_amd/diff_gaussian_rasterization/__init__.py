@@ -26,7 +26,7 @@ from . import _C
 
 __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes", "SortSettings", "CullingSettings",
            "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam",
-           "photometric_terms", "fused_ssim", "photometric_loss"]
+           "photometric_terms", "fused_ssim", "photometric_loss", "compute_relocation", "mcmc_add_noise_"]
 
 
 def enum_dict_factory(data):
@@ -558,3 +558,31 @@ def photometric_loss(image: torch.Tensor, target: torch.Tensor, lambda_dssim: fl
     composed on the two device scalars of photometric_terms (which see for shapes, refusals and the gradient rules)."""
     terms = _photometric(image, target)
     return (1.0 - lambda_dssim) * terms[0] + lambda_dssim * (1.0 - terms[1])
+
+
+def compute_relocation(opacity_old: torch.Tensor, scale_old: torch.Tensor, N: torch.Tensor):
+    """3DGS-MCMC's relocation rule (extension; include/stp_raster.h: stp_mcmc_relocation; the function a 3DGS-MCMC code base imports from its
+    rasterizer package): a Gaussian of opacity o and scales s that is replaced by N copies of itself gives each copy
+        o_new = 1 - (1 - o)^(1/N),    s_new = (o / denom) s,    denom = sum_{i=1..N} sum_{k=0..i-1} C(i-1, k) (-1)^k o_new^(k+1) / sqrt(k+1)
+    -> (opacity_new, scale_new), float32.  opacity_old: (n,) or (n, 1) float32, and opacity_new keeps its shape; scale_old: (n, 3) float32;
+    N: (n,) or (n, 1) int32 or int64, clamped to [1, 50] -- WITHOUT being modified (upstream clamps its N in place).  Non-contiguous inputs
+    are made contiguous.  The sum is evaluated in float64; equal inputs give equal bits.  No autograd (the inputs are detached).
+    Refused with a RuntimeError naming the argument: CPU tensors ("no CPU path"), other dtypes, shapes or row counts that do not match,
+    tensors on different devices."""
+    return _C.compute_relocation(opacity_old.detach(), scale_old.detach(), N, None, _C.RELOCATION_N_MAX)
+
+
+def mcmc_add_noise_(xyz: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor, noise: torch.Tensor,
+                    noise_scale: float, *, raw: bool = False, k: float = 100.0, x0: float = 0.995) -> torch.Tensor:
+    """3DGS-MCMC's per-iteration position noise in ONE kernel, in place (extension; include/stp_raster.h: stp_mcmc_add_noise):
+        xyz[i] += R diag(s^2) R^T (noise[i] * g * noise_scale),    g = 1 / (1 + exp(-k ((1 - o) - x0)))
+    with R the rotation of rotations[i] / |rotations[i]| (w, x, y, z), s = scales[i], o = opacities[i]; raw=True reads the model's raw
+    _scaling and _opacity and applies exp and sigmoid in the kernel.  noise is the caller's torch.randn_like(xyz) (random numbers stay
+    torch's), noise_scale the trainer's noise_lr * xyz_lr; noise_scale, k and x0 are rounded to float32 once.  xyz (P, 3) contiguous,
+    scales (P, 3), rotations (P, 4), opacities (P,) or (P, 1), noise (P, 3): float32 on one GPU.  Works on xyz's storage like an optimizer
+    step: nothing is recorded in autograd, a leaf that requires grad is fine, and the SAME tensor is returned.  Float32 IEEE arithmetic: a
+    gate whose exp overflows is 0, a zero quaternion gives NaN in its own row only.  Equal inputs give equal bits.  Refused with a
+    RuntimeError naming the argument: CPU tensors ("no CPU path"), other dtypes than float32, shapes or row counts that do not match, tensors
+    on different devices, an xyz that is not contiguous."""
+    _C.mcmc_add_noise(xyz.detach(), scales.detach(), rotations.detach(), opacities.detach(), noise.detach(), noise_scale, k, x0, raw)
+    return xyz
