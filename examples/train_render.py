@@ -3,7 +3,7 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
@@ -23,7 +23,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "stopthepop-rasterization_amd"))
 from diff_gaussian_rasterization import (CullingSettings, ExtendedSettings, GaussianRasterizationSettings,  # noqa: E402
                                          GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, SparseGaussianAdam, compute_relocation,
-                                         mcmc_add_noise_, photometric_loss, scenes)
+                                         densification_stats_, densify_and_prune, densify_plan, mcmc_add_noise_, photometric_loss, scenes)
 
 
 def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, scaling_modifier: float = 1.0,
@@ -140,9 +140,11 @@ def main(argv=None):
                     help="sparse_adam: SparseGaussianAdam, one fused launch that steps only the Gaussians visible in the frame (INTEGRATION.md section 3i)")
     ap.add_argument("--loss", default="l1", choices=["l1", "l1_ssim"],
                     help="l1_ssim: the trainers' 0.8 * L1 + 0.2 * (1 - SSIM) from the fused photometric_loss (INTEGRATION.md section 3j)")
-    ap.add_argument("--strategy", default="none", choices=["none", "mcmc"],
+    ap.add_argument("--strategy", default="none", choices=["none", "mcmc", "adc"],
                     help="mcmc: 3DGS-MCMC -- the fused position noise after every optimizer step, dead Gaussians relocated every 10 iterations with "
-                         "compute_relocation, and the opacity / scale L1 regularisers (INTEGRATION.md section 3l)")
+                         "compute_relocation, and the opacity / scale L1 regularisers (INTEGRATION.md section 3l).  adc: 3DGS adaptive density control "
+                         "-- the fused densification statistics after every backward, densify_plan + densify_and_prune every 10 iterations "
+                         "(INTEGRATION.md section 3m)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
@@ -164,7 +166,12 @@ def main(argv=None):
     with torch.no_grad():
         model._features.mul_(0.3)
         model._opacity.sub_(1.0)
-    if args.optimizer == "sparse_adam":   # one group per tensor, as the trainers' training_setup() builds them
+    adc = args.strategy == "adc"
+    if adc and args.optimizer != "sparse_adam":   # densify_and_prune wants the trainers' layout: one named group per tensor
+        opt = torch.optim.Adam([{"params": [model._features], "lr": 2e-2, "name": "f"}, {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
+                                {"params": [model._xyz], "lr": 0.0, "name": "xyz"}, {"params": [model._scaling], "lr": 0.0, "name": "scaling"},
+                                {"params": [model._rotation], "lr": 0.0, "name": "rotation"}], lr=0.0, eps=1e-15)
+    elif args.optimizer == "sparse_adam":   # one group per tensor, as the trainers' training_setup() builds them
         opt = SparseGaussianAdam([{"params": [model._features], "lr": 2e-2, "name": "f"}, {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
                                   {"params": [model._xyz], "lr": 0.0, "name": "xyz"}, {"params": [model._scaling], "lr": 0.0, "name": "scaling"},
                                   {"params": [model._rotation], "lr": 0.0, "name": "rotation"}], lr=0.0, eps=1e-15)
@@ -179,6 +186,10 @@ def main(argv=None):
     # Gaussian -- signed (3DGS: pulls from opposite sides cancel) and, with --absgrad, absolute (AbsGS: they add up)
     stat_signed = torch.zeros(model.get_xyz.shape[0], device=dev)
     stat_abs = torch.zeros_like(stat_signed)
+    # --strategy adc: the same sums from the fused statistics kernel, with the trainer's denom and max_radii2D beside them
+    stat_denom, stat_radii, abs_denom = torch.zeros_like(stat_signed), torch.zeros_like(stat_signed), torch.zeros_like(stat_signed)
+    extent = 1.1 * float((model.get_xyz.detach() - model.get_xyz.detach().mean(dim=0)).norm(dim=1).max())   # (a trainer's cameras_extent)
+    grown = pruned = 0
     first = last = None
     label = "L1" if args.loss == "l1" else "0.8 L1 + 0.2 (1 - SSIM)"
     mcmc = args.strategy == "mcmc"
@@ -204,9 +215,14 @@ def main(argv=None):
         loss.backward()
         grad2d = out["viewspace_points"].grad  # what densification accumulates
         vis = out["visibility_filter"]
-        stat_signed[vis] += grad2d[vis, :2].norm(dim=-1)
-        if args.absgrad:   # assigned by every backward, never accumulated: the running sum is the trainer's
-            stat_abs[vis] += out["viewspace_points"].absgrad[vis, :2].norm(dim=-1)
+        if adc:   # one kernel, no mask indexing and no synchronisation: the forward's radii are the visibility
+            densification_stats_(stat_signed, stat_denom, stat_radii, grad2d, out["radii"])
+            if args.absgrad:
+                densification_stats_(stat_abs, abs_denom, None, out["viewspace_points"].absgrad, out["radii"])
+        else:
+            stat_signed[vis] += grad2d[vis, :2].norm(dim=-1)
+            if args.absgrad:   # assigned by every backward, never accumulated: the running sum is the trainer's
+                stat_abs[vis] += out["viewspace_points"].absgrad[vis, :2].norm(dim=-1)
         if args.optimizer == "sparse_adam":   # the forward's radii are the visibility: no mask tensor on the way
             opt.step(out["radii"], model.get_xyz.shape[0])
         else:
@@ -217,12 +233,26 @@ def main(argv=None):
                 relocations += 1
             # xyz += Sigma (randn * op_sigmoid(1 - opacity) * noise_lr * xyz_lr) in one kernel, from the raw parameters the step just moved
             mcmc_add_noise_(model._xyz, model._scaling, model._rotation, model._opacity, torch.randn_like(model._xyz), noise_scale, raw=True)
+        if adc and it > 0 and it % 10 == 0:
+            # upstream's densify_and_prune: the decision as one byte per Gaussian, then one scan and one apply over every tensor and both
+            # Adam moments; the optimizer's groups get the new Parameters and the model takes them from the returned dict
+            plan = densify_plan(stat_signed, stat_denom, model._scaling, model._opacity, None, grad_threshold=0.0002, extent=extent, max_screen_size=20)
+            before = plan.numel()
+            new = densify_and_prune(opt, plan)
+            model._features, model._opacity, model._xyz, model._scaling, model._rotation = (new[n] for n in ("f", "opacity", "xyz", "scaling", "rotation"))
+            after = model.get_xyz.shape[0]
+            kept, cloned, split = (int(((plan >> b) & 1).sum()) for b in range(3))
+            grown, pruned = grown + cloned + 2 * split, pruned + before - kept
+            print(f"iter {it:3d}  adc: {before} rows -> {after} (kept {kept}, cloned {cloned}, split {split} into {2 * split})")
+            stat_signed, stat_abs, stat_denom, stat_radii, abs_denom = (torch.zeros(after, device=dev) for _ in range(5))   # (upstream's densification_postfix)
         last = float(loss.detach())
         first = last if first is None else first
         if it % 10 == 0 or it == args.iters - 1:
             print(f"iter {it:3d}  {label} {last:.5f}  visible {int(out['visibility_filter'].sum())}  |grad2D| max {float(grad2d.norm(dim=1).max()):.3e}")
     with torch.no_grad():
         depth = render(cam, model, bg, cfg, render_depth=True)["render"]
+    if adc:
+        print(f"adc: {grown} rows appended and {pruned} originals removed over the run, {model.get_xyz.shape[0]} Gaussians at the end")
     if mcmc:
         print(f"mcmc: relocated {relocated} Gaussians in {relocations} relocation steps (opacity <= 0.005), position noise after each of {args.iters} steps")
     if args.absgrad:

@@ -346,6 +346,55 @@ int stp_mcmc_relocation(int n, const float* opacity_old, const float* scale_old,
 int stp_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise,
                        float noise_scale, float k, float x0, int raw, void* stream);
 
+/* Extension (not in the reference): adaptive density control of a 3DGS / StopThePop trainer -- the per-step statistics and densify_and_prune --
+   in four calls.  All data is float32, all pointers are device pointers to contiguous data (stp_densify_scan's `counts` excepted), every call
+   runs on the caller's stream and allocates nothing; no atomics: equal inputs give equal bits.
+   stp_densify_stats, in place, one lane per Gaussian: for every visible i (visible_kind as in stp_sparse_adam: 0 = P bytes, non-zero = visible;
+       1 = the P int32 radii of the forward, > 0 = visible)
+       grad_accum[i] += sqrtf(gx * gx + gy * gy)  (the first two floats of row i of grad2d, rows of grad_stride = 2 or 3 floats; uncontracted)
+       denom[i] += 1          max_radii2D[i] = max(max_radii2D[i], (float)radii[i])  where max_radii2D is given (visible_kind 1 only)
+   Invisible rows keep their bits and their gradient is never read.  No host synchronisation.
+   stp_densify_plan writes one byte per Gaussian.  With s = the three scales (exp of `scaling` where rule->raw) and o = the opacity (its sigmoid
+   where rule->raw):
+       g = denom > 0 ? grad_accum / denom : 0        smax = max(s)        hot = g >= grad_threshold
+       clone = hot && smax <= split_size             split = hot && smax > split_size           low = o < min_opacity
+       ws(x) = prune_big && x > max_world_size       vs = prune_big && max_radii2D != null && max_radii2D[i] > max_screen_size
+       K = !split && !(low || ws(smax) || vs)        C = clone && !(low || ws(smax))            S = split && !(low || ws(smax / split_shrink))
+       plan[i] = K | C << 1 | S << 2
+   K: the original stays, C: one copy is appended, S: two children are appended.  The bits are independent: every value 0..7 is a legal plan
+   (bits 3..7 are ignored), so a plan may as well be written by the caller.  With max_radii2D == null the surviving rows and their order are
+   those of upstream's densify_and_prune (whose screen-size test never fires: it zeroes max_radii2D before its prune); with max_radii2D
+   given the test applies to the originals.  No host synchronisation.
+   stp_densify_scan: one exclusive sum over the 3P flags [K bits | C bits | S bits]: offsets[i], offsets[P + i], offsets[2P + i] are the
+   destination rows of Gaussian i's original, copy and first child in the output order below; counts = (nK, nC, nS) is written to HOST memory,
+   and THE CALL SYNCHRONISES THE STREAM -- the one host synchronisation of a densification (the caller must learn the new row count to
+   allocate the outputs).  scratch: stp_densify_scratch_bytes(P) bytes (a function of P alone; 0 for a P the scan refuses), 4-byte aligned.
+   stp_densify_apply writes the new model: for each of n_tensors entries (row = floats per Gaussian; exp_avg and exp_avg_sq both given or both
+   null, and then their outputs too) the M = nK + nC + 2 nS output rows are, in this order, the K rows in index order, the C rows, the first
+   children of the S rows, their second children -- what upstream's cat, cat, mask sequence leaves.  K rows copy the parameter and both
+   moments bit for bit; C rows and children copy the parameter and get zero moments, except that child j of the r-th split Gaussian i has
+       xyz' = xyz[i] + R(q / |q|) (s * noise[j * nS + r])          scaling' = raw ? logf(s / split_shrink) : s / split_shrink
+   in the tensors of role 1 (xyz, row 3) and 2 (scaling, row 3), with q the row of the role-3 tensor (rotation, (w, x, y, z), row 4), s the
+   activated scales (expf of the role-2 rows where raw) and noise the caller's 2 nS x 3 standard normal floats.  Role 0: a plain tensor.
+   Inputs are not modified; outputs must not overlap inputs.  A tensor whose rows are multiples of 16 bytes and whose pointers are all
+   16-byte aligned moves 16 bytes per lane, others one float at a time, with equal bits.  Up to eight entries go in one launch.
+   stats / plan / scan / apply return the number of kernel launches made (0 for P == 0 or nothing to write: nothing is touched, counts = 0), or
+   a negative StpStatus with the reason in the last-error text.  Refused BEFORE anything is launched (STP_ERR_INVALID_ARGUMENT): a negative P
+   or one with 3P >= 2^31, null pointers (of anything that would be read or written), a grad_stride other than 2 or 3, an unknown visible_kind,
+   max_radii2D with visible_kind 0 (there are no radii to read), a scratch that is too small or misaligned; and by apply: counts outside
+   [0, P], more than 64 entries, row <= 0 or P * row >= 2^31, an unknown role, one moment pointer without the other, raw other than 0 or 1,
+   nS > 0 without exactly one entry of each of the roles 1, 2, 3 with rows 3, 3, 4 or without noise. */
+typedef struct { float grad_threshold, split_size, min_opacity, max_screen_size, max_world_size, split_shrink; int32_t raw, prune_big; } StpDensifyRule;
+typedef struct { const float *param, *exp_avg, *exp_avg_sq; float *param_out, *exp_avg_out, *exp_avg_sq_out; int32_t row; int32_t role; } StpDensifyTensor;
+int stp_densify_stats(int P, float* grad_accum, float* denom, float* max_radii2D /* may be null */, const float* grad2d, int grad_stride /* 2 or 3 */,
+                      const void* visible, int visible_kind, void* stream);
+int stp_densify_plan(int P, const float* grad_accum, const float* denom, const float* scaling, const float* opacity,
+                     const float* max_radii2D /* may be null */, const StpDensifyRule* rule, uint8_t* plan, void* stream);
+size_t stp_densify_scratch_bytes(int P);
+int stp_densify_scan(int P, const uint8_t* plan, void* scratch, size_t scratch_bytes, uint32_t* offsets /* 3P */, int64_t counts[3] /* host */, void* stream);
+int stp_densify_apply(int P, const uint8_t* plan, const uint32_t* offsets, const int64_t counts[3], int n_tensors, const StpDensifyTensor* tensors,
+                      const float* noise /* (2 nS, 3) */, float split_shrink, int raw, void* stream);
+
 /* Extension (not in the reference): the fused photometric loss of 3DGS trainers, (1 - lambda) * L1 + lambda * (1 - SSIM) -- upstream's
    l1_loss and ssim() with window_size = 11 and size_average = True, the pair the `fused-ssim` extension replaces.  `image` (x) and `target`
    (y) are `planes` contiguous float32 planes of H x W (a (C, H, W) or (B, C, H, W) tensor: planes = B * C), n = planes * H * W.  With

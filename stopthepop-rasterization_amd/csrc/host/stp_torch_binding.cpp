@@ -77,6 +77,11 @@ struct Api {
     decltype(&stp_sparse_adam) sparse_adam = nullptr;
     decltype(&stp_mcmc_relocation) mcmc_relocation = nullptr;
     decltype(&stp_mcmc_add_noise) mcmc_add_noise = nullptr;
+    decltype(&stp_densify_stats) densify_stats = nullptr;
+    decltype(&stp_densify_plan) densify_plan = nullptr;
+    decltype(&stp_densify_scratch_bytes) densify_scratch_bytes = nullptr;
+    decltype(&stp_densify_scan) densify_scan = nullptr;
+    decltype(&stp_densify_apply) densify_apply = nullptr;
     decltype(&stp_photometric_workspace_floats) photometric_workspace_floats = nullptr;
     decltype(&stp_photometric_forward) photometric_forward = nullptr;
     decltype(&stp_photometric_backward) photometric_backward = nullptr;
@@ -108,6 +113,11 @@ int load_library(const std::string& path)
     a.sparse_adam = reinterpret_cast<decltype(a.sparse_adam)>(dlsym(h, "stp_sparse_adam"));
     a.mcmc_relocation = reinterpret_cast<decltype(a.mcmc_relocation)>(dlsym(h, "stp_mcmc_relocation"));
     a.mcmc_add_noise = reinterpret_cast<decltype(a.mcmc_add_noise)>(dlsym(h, "stp_mcmc_add_noise"));
+    a.densify_stats = reinterpret_cast<decltype(a.densify_stats)>(dlsym(h, "stp_densify_stats"));
+    a.densify_plan = reinterpret_cast<decltype(a.densify_plan)>(dlsym(h, "stp_densify_plan"));
+    a.densify_scratch_bytes = reinterpret_cast<decltype(a.densify_scratch_bytes)>(dlsym(h, "stp_densify_scratch_bytes"));
+    a.densify_scan = reinterpret_cast<decltype(a.densify_scan)>(dlsym(h, "stp_densify_scan"));
+    a.densify_apply = reinterpret_cast<decltype(a.densify_apply)>(dlsym(h, "stp_densify_apply"));
     a.photometric_workspace_floats = reinterpret_cast<decltype(a.photometric_workspace_floats)>(dlsym(h, "stp_photometric_workspace_floats"));
     a.photometric_forward = reinterpret_cast<decltype(a.photometric_forward)>(dlsym(h, "stp_photometric_forward"));
     a.photometric_backward = reinterpret_cast<decltype(a.photometric_backward)>(dlsym(h, "stp_photometric_backward"));
@@ -684,6 +694,204 @@ int mcmc_add_noise(const torch::Tensor& xyz, const torch::Tensor& scales, const 
     return rc;
 }
 
+// == densification (extension, include/stp_raster.h: stp_densify_stats / _plan / _scan / _apply; densification_stats_, densify_plan,
+// densify_tensors and densify_and_prune in __init__.py), on the caller's current stream.  As above, what is wrong with the tensors themselves is
+// refused first and where they live last.  Only densify_scan synchronises with the host (inside the library: the new row count).
+static const char* const DENSIFY_REBUILD = " (a library built before the densification kernels): rebuild it";
+static void densify_check_column(const char* who, const char* name, const torch::Tensor& t, const int64_t P)
+{
+    mcmc_check_float(who, name, t);
+    mcmc_check_column(who, name, t);
+    TORCH_CHECK(t.size(0) == P, who, ": ", name, " has ", t.size(0), " rows, expected ", P);
+}
+static void densify_check_P(const char* who, const int64_t P) { TORCH_CHECK(3 * P < (1ll << 31), who, ": ", P, " rows: 3 P >= 2^31"); }
+
+// in place on the accumulators (which must be contiguous); max_radii2D may be None.  radii: the forward's int32 radii, or a bool / uint8 mask.
+int densify_stats(const torch::Tensor& grad_accum, const torch::Tensor& denom, const c10::optional<torch::Tensor>& max_radii2D, const torch::Tensor& grad2d,
+                  const torch::Tensor& radii)
+{
+    static const char* const who = "densification_stats_";
+    need_library();
+    if (!g_api.densify_stats) throw std::runtime_error(std::string("densify_stats: the loaded libstp_raster.so does not export stp_densify_stats") + DENSIFY_REBUILD);
+    mcmc_check_float(who, "grad2d", grad2d);
+    TORCH_CHECK(grad2d.dim() == 2 && (grad2d.size(1) == 2 || grad2d.size(1) == 3), who, ": grad2d must be (P, 3) or (P, 2), got ", grad2d.sizes());
+    const int64_t P = grad2d.size(0);
+    densify_check_P(who, P);
+    densify_check_column(who, "xyz_gradient_accum", grad_accum, P);
+    densify_check_column(who, "denom", denom, P);
+    if (max_radii2D.has_value()) densify_check_column(who, "max_radii2D", *max_radii2D, P);
+    TORCH_CHECK(radii.defined(), who, ": radii must be a tensor");
+    const auto vt = radii.scalar_type();
+    TORCH_CHECK(vt == torch::kBool || vt == torch::kByte || vt == torch::kInt32, who, ": radii must be int32 (the forward's radii) or a bool / uint8 mask, got ", vt);
+    TORCH_CHECK(radii.numel() == P, who, ": radii has ", radii.numel(), " elements, expected ", P);
+    TORCH_CHECK(!max_radii2D.has_value() || vt == torch::kInt32, who, ": max_radii2D needs the forward's int32 radii, not a mask (pass max_radii2D=None)");
+    mcmc_check_device(who, "xyz_gradient_accum", grad_accum, grad2d);
+    mcmc_check_device(who, "denom", denom, grad2d);
+    if (max_radii2D.has_value()) mcmc_check_device(who, "max_radii2D", *max_radii2D, grad2d);
+    mcmc_check_device(who, "radii", radii, grad2d);
+    mcmc_check_device(who, "grad2d", grad2d, grad2d);
+    TORCH_CHECK(grad_accum.is_contiguous() && denom.is_contiguous() && (!max_radii2D.has_value() || max_radii2D->is_contiguous()), who,
+                ": the accumulators must be contiguous (they are updated in place)");
+    if (P == 0) return 0;
+    const torch::Tensor g = grad2d.contiguous(), vis = radii.contiguous();
+    const c10::hip::HIPGuard guard(g.device().index());
+    const int rc = g_api.densify_stats((int)P, grad_accum.data_ptr<float>(), denom.data_ptr<float>(), max_radii2D.has_value() ? max_radii2D->data_ptr<float>() : nullptr,
+                                       g.data_ptr<float>(), (int)g.size(1), vis.data_ptr(), vt == torch::kInt32 ? 1 : 0,
+                                       (void*)c10::hip::getCurrentHIPStream(g.device().index()).stream());
+    if (rc < 0) raise_last(rc);
+    return rc;
+}
+
+// -> the plan, uint8 (P,).  rule: (grad_threshold, split_size, min_opacity, max_screen_size, max_world_size, split_shrink), rounded to float32 here.
+torch::Tensor densify_plan(const torch::Tensor& grad_accum, const torch::Tensor& denom, const torch::Tensor& scaling, const torch::Tensor& opacity,
+                           const c10::optional<torch::Tensor>& max_radii2D, const std::vector<double>& rule_in, const bool raw, const bool prune_big)
+{
+    static const char* const who = "densify_plan";
+    need_library();
+    if (!g_api.densify_plan) throw std::runtime_error(std::string("densify_plan: the loaded libstp_raster.so does not export stp_densify_plan") + DENSIFY_REBUILD);
+    TORCH_CHECK(rule_in.size() == 6, who, ": the rule has six numbers");
+    mcmc_check_float(who, "scaling", scaling);
+    TORCH_CHECK(scaling.dim() == 2 && scaling.size(1) == 3, who, ": scaling must be (P, 3), got ", scaling.sizes());
+    const int64_t P = scaling.size(0);
+    densify_check_P(who, P);
+    densify_check_column(who, "xyz_gradient_accum", grad_accum, P);
+    densify_check_column(who, "denom", denom, P);
+    densify_check_column(who, "opacity", opacity, P);
+    if (max_radii2D.has_value()) densify_check_column(who, "max_radii2D", *max_radii2D, P);
+    mcmc_check_device(who, "xyz_gradient_accum", grad_accum, scaling);
+    mcmc_check_device(who, "denom", denom, scaling);
+    mcmc_check_device(who, "opacity", opacity, scaling);
+    if (max_radii2D.has_value()) mcmc_check_device(who, "max_radii2D", *max_radii2D, scaling);
+    mcmc_check_device(who, "scaling", scaling, scaling);
+    const c10::hip::HIPGuard guard(scaling.device().index());
+    torch::Tensor plan = torch::empty({P}, scaling.options().dtype(torch::kByte));
+    if (P == 0) return plan;
+    const torch::Tensor ga = grad_accum.contiguous(), de = denom.contiguous(), sc = scaling.contiguous(), op = opacity.contiguous();
+    torch::Tensor mr;
+    if (max_radii2D.has_value()) mr = max_radii2D->contiguous();
+    const StpDensifyRule rule = {(float)rule_in[0], (float)rule_in[1], (float)rule_in[2], (float)rule_in[3], (float)rule_in[4], (float)rule_in[5], raw ? 1 : 0, prune_big ? 1 : 0};
+    const int rc = g_api.densify_plan((int)P, ga.data_ptr<float>(), de.data_ptr<float>(), sc.data_ptr<float>(), op.data_ptr<float>(), mr.defined() ? mr.data_ptr<float>() : nullptr,
+                                      &rule, plan.data_ptr<uint8_t>(), (void*)c10::hip::getCurrentHIPStream(scaling.device().index()).stream());
+    if (rc < 0) raise_last(rc);
+    return plan;
+}
+
+static void densify_check_plan(const char* who, const torch::Tensor& plan)
+{
+    TORCH_CHECK(plan.defined() && plan.scalar_type() == torch::kByte, who, ": plan: expected uint8 tensor, got ", plan.scalar_type());
+    TORCH_CHECK(plan.dim() == 1, who, ": plan must be (P,), got ", plan.sizes());
+    densify_check_P(who, plan.size(0));
+    TORCH_CHECK(plan.is_cuda(), who, ": plan: diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
+}
+
+// -> (offsets (3P,) int32, nK, nC, nS).  SYNCHRONISES the current stream (in the library): the caller needs the counts to allocate.
+std::tuple<torch::Tensor, int64_t, int64_t, int64_t> densify_scan(const torch::Tensor& plan_in)
+{
+    static const char* const who = "densify_scan";
+    need_library();
+    if (!g_api.densify_scan || !g_api.densify_scratch_bytes)
+        throw std::runtime_error(std::string("densify_scan: the loaded libstp_raster.so does not export stp_densify_scan") + DENSIFY_REBUILD);
+    densify_check_plan(who, plan_in);
+    const torch::Tensor plan = plan_in.contiguous();
+    const int64_t P = plan.size(0);
+    const c10::hip::HIPGuard guard(plan.device().index());
+    torch::Tensor offsets = torch::empty({3 * P}, plan.options().dtype(torch::kInt32));
+    int64_t counts[3] = {0, 0, 0};
+    if (P == 0) return {offsets, 0, 0, 0};
+    const size_t bytes = g_api.densify_scratch_bytes((int)P);
+    torch::Tensor scratch = torch::empty({(int64_t)bytes}, plan.options());
+    const int rc = g_api.densify_scan((int)P, plan.data_ptr<uint8_t>(), scratch.data_ptr(), bytes, reinterpret_cast<uint32_t*>(offsets.data_ptr<int32_t>()), counts,
+                                      (void*)c10::hip::getCurrentHIPStream(plan.device().index()).stream());
+    if (rc < 0) raise_last(rc);
+    return {offsets, counts[0], counts[1], counts[2]};
+}
+
+// -> (new tensors, new exp_avgs, new exp_avg_sqs): lists as long as `tensors`, the moment lists holding None where none was given.  Tensor k
+// is (P, ...) of any trailing shape; the outputs are (nK + nC + 2 nS, ...).  No host synchronisation.
+std::tuple<std::vector<torch::Tensor>, std::vector<c10::optional<torch::Tensor>>, std::vector<c10::optional<torch::Tensor>>>
+densify_apply(const torch::Tensor& plan_in, const torch::Tensor& offsets, const std::vector<int64_t>& counts_in, const std::vector<torch::Tensor>& tensors,
+              const std::vector<int64_t>& roles, const std::vector<c10::optional<torch::Tensor>>& exp_avgs, const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs,
+              const c10::optional<torch::Tensor>& noise_in, const double split_shrink, const bool raw)
+{
+    static const char* const who = "densify_apply";
+    need_library();
+    if (!g_api.densify_apply) throw std::runtime_error(std::string("densify_apply: the loaded libstp_raster.so does not export stp_densify_apply") + DENSIFY_REBUILD);
+    const size_t n = tensors.size();
+    TORCH_CHECK(roles.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n, who, ": tensors, roles, exp_avgs and exp_avg_sqs must have one entry per tensor");
+    TORCH_CHECK(n <= 64, who, ": ", n, " tensors, at most 64 in one call");
+    TORCH_CHECK(counts_in.size() == 3, who, ": counts must be (nK, nC, nS)");
+    TORCH_CHECK(plan_in.defined() && plan_in.scalar_type() == torch::kByte && plan_in.dim() == 1, who, ": plan: expected a uint8 (P,) tensor");
+    const int64_t P = plan_in.size(0);
+    densify_check_P(who, P);
+    const int64_t counts[3] = {counts_in[0], counts_in[1], counts_in[2]};
+    for (int j = 0; j < 3; j++) TORCH_CHECK(counts[j] >= 0 && counts[j] <= P, who, ": counts[", j, "] = ", counts[j], " outside [0, P]");
+    const int64_t nS = counts[2], M = counts[0] + counts[1] + 2 * nS;
+    TORCH_CHECK(offsets.defined() && offsets.scalar_type() == torch::kInt32 && offsets.dim() == 1 && offsets.size(0) == 3 * P, who, ": offsets: expected an int32 (3 P,) tensor");
+    for (size_t k = 0; k < n; k++) {
+        const torch::Tensor& t = tensors[k];
+        TORCH_CHECK(t.defined(), who, ": tensor ", k, " is undefined");
+        TORCH_CHECK(t.scalar_type() == torch::kFloat32, who, ": tensor ", k, ": expected float32 tensor, got ", t.scalar_type());
+        TORCH_CHECK(t.dim() >= 1 && t.size(0) == P, who, ": tensor ", k, " must have ", P, " rows (the plan's), got ", t.sizes());
+        TORCH_CHECK(P == 0 || t.numel() > 0, who, ": tensor ", k, ": rows without elements, ", t.sizes());
+        TORCH_CHECK(roles[k] >= 0 && roles[k] <= 3, who, ": tensor ", k, ": unknown role ", roles[k], " (0 plain, 1 xyz, 2 scaling, 3 rotation)");
+        TORCH_CHECK(exp_avgs[k].has_value() == exp_avg_sqs[k].has_value(), who, ": tensor ", k, ": exp_avg and exp_avg_sq must both be given or both be None");
+        if (exp_avgs[k].has_value())
+            for (const torch::Tensor* m : {&*exp_avgs[k], &*exp_avg_sqs[k]}) {
+                TORCH_CHECK(m->defined() && m->scalar_type() == torch::kFloat32, who, ": tensor ", k, ": moments: expected float32 tensors");
+                TORCH_CHECK(m->sizes() == t.sizes(), who, ": tensor ", k, ": a moment has shape ", m->sizes(), ", the parameter has ", t.sizes());
+            }
+    }
+    if (nS > 0) {
+        TORCH_CHECK(noise_in.has_value(), who, ": nS = ", nS, " needs noise");
+        mcmc_check_float(who, "noise", *noise_in);
+        mcmc_check_rows(who, "noise", *noise_in, 2 * nS, 3);
+    }
+    TORCH_CHECK(plan_in.is_cuda(), who, ": plan: diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
+    mcmc_check_device(who, "offsets", offsets, plan_in);
+    for (size_t k = 0; k < n; k++) {
+        mcmc_check_device(who, "a tensor", tensors[k], plan_in);
+        if (exp_avgs[k].has_value()) {
+            mcmc_check_device(who, "an exp_avg", *exp_avgs[k], plan_in);
+            mcmc_check_device(who, "an exp_avg_sq", *exp_avg_sqs[k], plan_in);
+        }
+    }
+    if (nS > 0) mcmc_check_device(who, "noise", *noise_in, plan_in);
+    const torch::Tensor plan = plan_in.contiguous(), off = offsets.contiguous();
+    const c10::hip::HIPGuard guard(plan.device().index());
+    std::vector<torch::Tensor> held; // the contiguous inputs, alive until the launches are made
+    std::vector<torch::Tensor> out_p(n);
+    std::vector<c10::optional<torch::Tensor>> out_m(n), out_v(n);
+    std::vector<StpDensifyTensor> table(n);
+    for (size_t k = 0; k < n; k++) {
+        std::vector<int64_t> shape = tensors[k].sizes().vec();
+        int64_t row = 1;
+        for (size_t d = 1; d < shape.size(); d++) row *= shape[d];
+        TORCH_CHECK(row > 0 && P * row < (1ll << 31), who, ": tensor ", k, ": ", P, " rows of ", row, " floats: outside (0, 2^31)");
+        shape[0] = M;
+        held.push_back(tensors[k].contiguous());
+        out_p[k] = torch::empty(shape, held.back().options());
+        StpDensifyTensor& t = table[k];
+        t = StpDensifyTensor{held.back().data_ptr<float>(), nullptr, nullptr, out_p[k].data_ptr<float>(), nullptr, nullptr, (int32_t)row, (int32_t)roles[k]};
+        if (exp_avgs[k].has_value()) {
+            held.push_back(exp_avgs[k]->contiguous());
+            t.exp_avg = held.back().data_ptr<float>();
+            held.push_back(exp_avg_sqs[k]->contiguous());
+            t.exp_avg_sq = held.back().data_ptr<float>();
+            out_m[k] = torch::empty(shape, held.back().options());
+            out_v[k] = torch::empty(shape, held.back().options());
+            t.exp_avg_out = out_m[k]->data_ptr<float>();
+            t.exp_avg_sq_out = out_v[k]->data_ptr<float>();
+        }
+    }
+    torch::Tensor noise;
+    if (nS > 0) noise = noise_in->contiguous();
+    const int rc = g_api.densify_apply((int)P, plan.data_ptr<uint8_t>(), reinterpret_cast<const uint32_t*>(off.data_ptr<int32_t>()), counts, (int)n, table.data(),
+                                       noise.defined() ? noise.data_ptr<float>() : nullptr, (float)split_shrink, raw ? 1 : 0,
+                                       (void*)c10::hip::getCurrentHIPStream(plan.device().index()).stream());
+    if (rc < 0) raise_last(rc);
+    return {out_p, out_m, out_v};
+}
+
 // == the fused photometric loss (extension, include/stp_raster.h: stp_photometric_forward / _backward; photometric_loss and fused_ssim in
 // __init__.py), on the caller's current stream.  image, target: float32 (C, H, W) or (B, C, H, W) on one GPU, made contiguous here.
 struct PhotometricShape { int planes, H, W; };
@@ -821,6 +1029,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("sparse_adam", &sparse_adam);
     m.def("compute_relocation", &compute_relocation);
     m.def("mcmc_add_noise", &mcmc_add_noise);
+    m.def("densify_stats", &densify_stats);
+    m.def("densify_plan", &densify_plan);
+    m.def("densify_scan", &densify_scan);
+    m.def("densify_apply", &densify_apply);
     m.def("photometric_forward", &photometric_forward);
     m.def("photometric_backward", &photometric_backward);
     m.def("scratch_generation", &scratch_generation);

@@ -1,6 +1,6 @@
 // stp_api.hip -- the C ABI of libstp_raster.so (declared in include/stp_raster.h): the per-thread error state, the argument checks
 // and frame description that forward and backward share, the one-shot per-thread requests, and the backward, mark-visible, sparse
-// Adam, 3DGS-MCMC and photometric-loss calls.  Replaces CudaRasterizer::Rasterizer::{backward,markVisible} (reference cuda_rasterizer/rasterizer_impl.cu:417-526,
+// Adam, 3DGS-MCMC, densification and photometric-loss calls.  Replaces CudaRasterizer::Rasterizer::{backward,markVisible} (reference cuda_rasterizer/rasterizer_impl.cu:417-526,
 // 161-173).  The forward is stp_forward.hip, the scratch buffers and their queries stp_buffers.hip, the stage timer stp_timer.hip.
 //
 // The calls are re-entrant: the scratch buffers belong to the caller, stp_last_error and the requests are per thread, and the
@@ -342,6 +342,113 @@ int stp_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rota
     hipError_t e;
     const int launches = launch_mcmc_add_noise(P, xyz, scales, rotations, opacities, noise, noise_scale, k, x0, raw, (hipStream_t)stream, &e);
     if (e != hipSuccess) return fail_hip(e, "mcmc_add_noise launch");
+    return launches;
+}
+
+// ---- densification (stp_densify.hip): everything is checked before the first launch
+static int check_densify_P(const char* who, int P)
+{
+    if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative P");
+    if (3ll * P >= (1ll << 31)) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": 3 P = " + std::to_string(3ll * P) + " >= 2^31");
+    return 0;
+}
+
+int stp_densify_stats(int P, float* grad_accum, float* denom, float* max_radii2D, const float* grad2d, int grad_stride, const void* visible,
+                      int visible_kind, void* stream)
+{
+    if (const int rc = check_densify_P("stp_densify_stats", P)) return rc;
+    if (grad_stride != 2 && grad_stride != 3)
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_stats: grad_stride must be 2 or 3, got " + std::to_string(grad_stride));
+    if (visible_kind != 0 && visible_kind != 1)
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_stats: unknown visible_kind " + std::to_string(visible_kind) + " (0: P bytes, 1: P int32 radii)");
+    if (max_radii2D && visible_kind == 0)
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_stats: max_radii2D needs the radii (visible_kind 1): bytes hold no radius to read");
+    if (P == 0) return 0;
+    if (!grad_accum || !denom || !grad2d || !visible) return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_stats: null pointer");
+    hipError_t e;
+    const int launches = launch_densify_stats(P, grad_accum, denom, max_radii2D, grad2d, grad_stride, visible, visible_kind, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "densify_stats launch");
+    return launches;
+}
+
+int stp_densify_plan(int P, const float* grad_accum, const float* denom, const float* scaling, const float* opacity, const float* max_radii2D,
+                     const StpDensifyRule* rule, uint8_t* plan, void* stream)
+{
+    if (const int rc = check_densify_P("stp_densify_plan", P)) return rc;
+    if (!rule) return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_plan: null rule");
+    if (P == 0) return 0;
+    if (!grad_accum || !denom || !scaling || !opacity || !plan) return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_plan: null pointer");
+    hipError_t e;
+    const int launches = launch_densify_plan(P, grad_accum, denom, scaling, opacity, max_radii2D, *rule, plan, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "densify_plan launch");
+    return launches;
+}
+
+size_t stp_densify_scratch_bytes(int P)
+{
+    if (P < 0 || 3ll * P >= (1ll << 31)) return 0;
+    return densify_scratch_bytes(P);
+}
+
+int stp_densify_scan(int P, const uint8_t* plan, void* scratch, size_t scratch_bytes, uint32_t* offsets, int64_t counts[3], void* stream)
+{
+    if (const int rc = check_densify_P("stp_densify_scan", P)) return rc;
+    if (!counts) return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_scan: null counts");
+    if (P == 0) {
+        counts[0] = counts[1] = counts[2] = 0;
+        return 0;
+    }
+    if (!plan || !scratch || !offsets) return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_scan: null pointer");
+    if (scratch_bytes < densify_scratch_bytes(P))
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_scan: scratch of " + std::to_string(scratch_bytes) + " bytes, stp_densify_scratch_bytes(P) = " +
+                                                  std::to_string(densify_scratch_bytes(P)));
+    if (reinterpret_cast<uintptr_t>(scratch) & 3u) return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_scan: scratch is not 4-byte aligned");
+    hipError_t e;
+    const int launches = launch_densify_scan(P, plan, scratch, offsets, counts, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "densify_scan");
+    return launches;
+}
+
+int stp_densify_apply(int P, const uint8_t* plan, const uint32_t* offsets, const int64_t counts[3], int n_tensors, const StpDensifyTensor* tensors,
+                      const float* noise, float split_shrink, int raw, void* stream)
+{
+    static const char* const who = "stp_densify_apply";
+    if (const int rc = check_densify_P(who, P)) return rc;
+    if (n_tensors < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative n_tensors");
+    if (n_tensors > 64) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(n_tensors) + " tensors, at most 64 in one call");
+    if (raw != 0 && raw != 1) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": raw must be 0 or 1, got " + std::to_string(raw));
+    if (!counts) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null counts");
+    for (int j = 0; j < 3; j++)
+        if (counts[j] < 0 || counts[j] > P)
+            return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": counts[" + std::to_string(j) + "] = " + std::to_string((long long)counts[j]) + " outside [0, P]");
+    if (n_tensors > 0 && !tensors) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null tensor table");
+    const int64_t nS = counts[2], M = counts[0] + counts[1] + 2 * nS;
+    int of_role[4] = {0, 0, 0, 0};
+    bool rows_fit = true;
+    for (int k = 0; k < n_tensors; k++) {
+        const StpDensifyTensor& t = tensors[k];
+        const std::string which = std::string(who) + ": tensor " + std::to_string(k);
+        if (t.row <= 0) return fail(STP_ERR_INVALID_ARGUMENT, which + ": row " + std::to_string(t.row) + " <= 0");
+        if ((long long)P * t.row >= (1ll << 31)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": P * row = " + std::to_string((long long)P * t.row) + " >= 2^31");
+        if (t.role < 0 || t.role > 3) return fail(STP_ERR_INVALID_ARGUMENT, which + ": unknown role " + std::to_string(t.role) + " (0 plain, 1 xyz, 2 scaling, 3 rotation)");
+        if ((t.exp_avg == nullptr) != (t.exp_avg_sq == nullptr)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": exp_avg and exp_avg_sq must both be given or both be null");
+        of_role[t.role]++;
+        if (t.role != 0 && t.row != (t.role == 3 ? 4 : 3)) rows_fit = false;
+        if (M > 0) {
+            if (!t.param || !t.param_out) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer");
+            if (t.exp_avg && (!t.exp_avg_out || !t.exp_avg_sq_out)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer (moment output)");
+        }
+    }
+    if (nS > 0) {
+        if (of_role[1] != 1 || of_role[2] != 1 || of_role[3] != 1 || !rows_fit)
+            return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": a split needs exactly one tensor of each of the roles 1 (xyz, row 3), 2 (scaling, row 3) and 3 (rotation, row 4)");
+        if (!noise) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null noise with nS = " + std::to_string((long long)nS));
+    }
+    if (P == 0 || M == 0 || n_tensors == 0) return 0;
+    if (!plan || !offsets) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    hipError_t e;
+    const int launches = launch_densify_apply(P, plan, offsets, counts, n_tensors, tensors, noise, split_shrink, raw, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "densify_apply launch");
     return launches;
 }
 

@@ -281,6 +281,17 @@ int launch_mcmc_relocation(int n, const float* opacity_old, const float* scale_o
                            float* scale_new, hipStream_t st, hipError_t* err);
 int launch_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise, float noise_scale,
                           float k, float x0, int raw, hipStream_t st, hipError_t* err);
+// densification (stp_densify.hip) over arguments stp_densify_* have validated (P in [1, 2^31 / 3), every P * row < 2^31): each returns the
+// launches made, *err = the error that ended it early (or hipSuccess).  launch_densify_scan copies the three counts to the host and
+// SYNCHRONISES the stream; its scratch holds densify_scratch_bytes(P) bytes, 4-byte aligned.
+int launch_densify_stats(int P, float* grad_accum, float* denom, float* max_radii2D, const float* grad2d, int grad_stride, const void* visible,
+                         int visible_kind, hipStream_t st, hipError_t* err);
+int launch_densify_plan(int P, const float* grad_accum, const float* denom, const float* scaling, const float* opacity, const float* max_radii2D,
+                        const StpDensifyRule& rule, uint8_t* plan, hipStream_t st, hipError_t* err);
+size_t densify_scratch_bytes(int P);
+int launch_densify_scan(int P, const uint8_t* plan, void* scratch, uint32_t* offsets, int64_t counts[3], hipStream_t st, hipError_t* err);
+int launch_densify_apply(int P, const uint8_t* plan, const uint32_t* offsets, const int64_t counts[3], int n_tensors, const StpDensifyTensor* tensors,
+                         const float* noise, float split_shrink, int raw, hipStream_t st, hipError_t* err);
 // the fused photometric loss (stp_loss.hip) over arguments stp_photometric_* have validated (planes * H * W in [1, 2^31)): workgroups of the
 // tiled kernels (= rows of two partial sums in the workspace); the forward = tile kernel (with the three derivative maps when `maps`) + the
 // one-workgroup sum, the backward = one tile kernel.  Both return the launches made, *err = the launch error that ended them early

@@ -53,6 +53,12 @@ _OPTIONAL_SYMBOLS = {
                         ctypes.c_int),
     "stp_mcmc_relocation": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3, ctypes.c_int),
     "stp_mcmc_add_noise": ([ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_float] * 3 + [ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "stp_densify_stats": ([ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "stp_densify_plan": ([ctypes.c_int] + [ctypes.c_void_p] * 8, ctypes.c_int),
+    "stp_densify_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t),
+    "stp_densify_scan": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3, ctypes.c_int),
+    "stp_densify_apply": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p],
+                          ctypes.c_int),
     "stp_photometric_workspace_floats": ([ctypes.c_int] * 3, ctypes.c_size_t),
     "stp_photometric_forward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int),
     "stp_photometric_backward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int),
@@ -64,6 +70,9 @@ _SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blen
                    "stp_set_forward_invdepth": "the inverse-depth output", "stp_set_backward_invdepth": "the inverse-depth output",
                    "stp_sparse_adam": "the sparse Adam step",
                    "stp_mcmc_relocation": "the 3DGS-MCMC kernels", "stp_mcmc_add_noise": "the 3DGS-MCMC kernels",
+                   "stp_densify_stats": "the densification kernels", "stp_densify_plan": "the densification kernels",
+                   "stp_densify_scratch_bytes": "the densification kernels", "stp_densify_scan": "the densification kernels",
+                   "stp_densify_apply": "the densification kernels",
                    "stp_photometric_workspace_floats": "the photometric loss", "stp_photometric_forward": "the photometric loss",
                    "stp_photometric_backward": "the photometric loss"}
 
@@ -486,6 +495,54 @@ def mcmc_add_noise(xyz, scales, rotations, opacities, noise, noise_scale, k, x0,
     (P, 1), noise (P, 3), all float32 on one GPU.  Returns the kernel launches made (1; 0 for P == 0)."""
     _require("stp_mcmc_add_noise")
     return int((_host or _native()).mcmc_add_noise(xyz, scales, rotations, opacities, noise, float(noise_scale), float(k), float(x0), bool(raw)))
+
+
+class StpDensifyRule(ctypes.Structure):
+    """include/stp_raster.h: StpDensifyRule (for callers of the C ABI through ctypes; the native module builds its own)"""
+    _fields_ = [(name, ctypes.c_float) for name in ("grad_threshold", "split_size", "min_opacity", "max_screen_size", "max_world_size", "split_shrink")] + \
+               [("raw", ctypes.c_int32), ("prune_big", ctypes.c_int32)]
+
+
+class StpDensifyTensor(ctypes.Structure):
+    """include/stp_raster.h: StpDensifyTensor"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("param", "exp_avg", "exp_avg_sq", "param_out", "exp_avg_out", "exp_avg_sq_out")] + \
+               [("row", ctypes.c_int32), ("role", ctypes.c_int32)]
+
+
+DENSIFY_ROLES = {"plain": 0, "xyz": 1, "scaling": 2, "rotation": 3}
+
+
+def densify_stats(xyz_gradient_accum, denom, max_radii2D, grad2d, radii) -> int:
+    """A trainer's add_densification_stats in one launch, IN PLACE on the accumulators (extension, include/stp_raster.h: stp_densify_stats), on
+    the current stream, without host synchronisation.  Returns the kernel launches made."""
+    _require("stp_densify_stats")
+    return int((_host or _native()).densify_stats(xyz_gradient_accum, denom, max_radii2D, grad2d, radii))
+
+
+def densify_plan(xyz_gradient_accum, denom, scaling, opacity, max_radii2D, rule, raw, prune_big):
+    """The plan byte of every Gaussian (extension, include/stp_raster.h: stp_densify_plan): uint8 (P,), bit 0 keep, bit 1 clone, bit 2 split.
+    rule: the six floats of StpDensifyRule in its order.  No host synchronisation."""
+    _require("stp_densify_plan")
+    return (_host or _native()).densify_plan(xyz_gradient_accum, denom, scaling, opacity, max_radii2D, [float(x) for x in rule], bool(raw), bool(prune_big))
+
+
+def densify_scan(plan):
+    """plan -> (offsets, (nK, nC, nS)) (extension, include/stp_raster.h: stp_densify_scan): offsets is the int32 (3P,) tensor of destination rows
+    densify_apply reads.  THIS CALL SYNCHRONISES the current stream with the host -- the one synchronisation of a densification: the new row
+    count has to be known to allocate the outputs."""
+    _require("stp_densify_scan")
+    offsets, nK, nC, nS = (_host or _native()).densify_scan(plan)
+    return offsets, (int(nK), int(nC), int(nS))
+
+
+def densify_apply(plan, offsets, counts, tensors, roles, exp_avgs, exp_avg_sqs, noise, split_shrink, raw):
+    """The new tensors and Adam moments of a plan (extension, include/stp_raster.h: stp_densify_apply) -> (new_tensors, new_exp_avgs,
+    new_exp_avg_sqs), lists as long as `tensors`; exp_avgs / exp_avg_sqs hold None where a tensor has no moments, and so do the results.
+    roles: 0 plain, 1 xyz, 2 scaling, 3 rotation.  noise: (2 nS, 3), may be None where nS == 0.  No host synchronisation."""
+    _require("stp_densify_apply")
+    out = (_host or _native()).densify_apply(plan, offsets, [int(c) for c in counts], list(tensors), [int(r) for r in roles], list(exp_avgs),
+                                             list(exp_avg_sqs), noise, float(split_shrink), bool(raw))
+    return list(out[0]), list(out[1]), list(out[2])
 
 
 def photometric_forward(image, target, want_maps):

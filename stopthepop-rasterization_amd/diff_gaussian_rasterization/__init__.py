@@ -17,7 +17,7 @@ from __future__ import annotations
 import json
 from dataclasses import asdict, dataclass, field, fields
 from enum import IntEnum
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -26,7 +26,8 @@ from . import _C
 
 __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes", "SortSettings", "CullingSettings",
            "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam",
-           "photometric_terms", "fused_ssim", "photometric_loss", "compute_relocation", "mcmc_add_noise_"]
+           "photometric_terms", "fused_ssim", "photometric_loss", "compute_relocation", "mcmc_add_noise_",
+           "densification_stats_", "densify_plan", "densify_tensors", "densify_and_prune"]
 
 
 def enum_dict_factory(data):
@@ -586,3 +587,96 @@ def mcmc_add_noise_(xyz: torch.Tensor, scales: torch.Tensor, rotations: torch.Te
     on different devices, an xyz that is not contiguous."""
     _C.mcmc_add_noise(xyz.detach(), scales.detach(), rotations.detach(), opacities.detach(), noise.detach(), noise_scale, k, x0, raw)
     return xyz
+
+
+def _f32(x) -> float:
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def densification_stats_(xyz_gradient_accum: torch.Tensor, denom: torch.Tensor, max_radii2D: Optional[torch.Tensor], grad2d: torch.Tensor,
+                         radii: torch.Tensor) -> None:
+    """A trainer's per-step densification statistics in ONE kernel, in place, without host synchronisation (extension; include/stp_raster.h:
+    stp_densify_stats) -- what `stat[vis] += grad2d[vis, :2].norm(dim=-1, keepdim=True); denom[vis] += 1; max_radii2D[vis] =
+    max(max_radii2D[vis], radii[vis])` does with a `nonzero` and a synchronisation per indexed tensor.  For every i with radii[i] > 0:
+        xyz_gradient_accum[i] += sqrt(gx^2 + gy^2)      denom[i] += 1      max_radii2D[i] = max(max_radii2D[i], radii[i])
+    grad2d: viewspace_points.grad or .absgrad, (P, 3) or (P, 2) float32 (only the first two columns are read).  The accumulators: (P,) or
+    (P, 1) float32, contiguous.  radii: the forward's int32 radii; a bool / uint8 mask is accepted where max_radii2D is None.  Rows that are
+    not visible keep their bits and their gradient is never read (a NaN there changes nothing).  Equal inputs give equal bits.  Refused with a
+    RuntimeError naming the argument: CPU tensors ("no CPU path"), other dtypes, shapes or row counts that do not match."""
+    _C.densify_stats(xyz_gradient_accum.detach(), denom.detach(), None if max_radii2D is None else max_radii2D.detach(), grad2d.detach(), radii)
+
+
+def densify_plan(xyz_gradient_accum: torch.Tensor, denom: torch.Tensor, scaling: torch.Tensor, opacity: torch.Tensor,
+                 max_radii2D: Optional[torch.Tensor] = None, *, grad_threshold: float, percent_dense: float = 0.01, extent: float,
+                 min_opacity: float = 0.005, max_screen_size: Optional[float] = None, raw: bool = True) -> torch.Tensor:
+    """The decision of 3DGS adaptive density control as one byte per Gaussian, in ONE kernel without host synchronisation (extension;
+    include/stp_raster.h: stp_densify_plan): uint8 (P,), bit 0 = the original stays, bit 1 = one copy is appended, bit 2 = two children are
+    appended.  With s the scales (exp(scaling) where raw), o the opacity (its sigmoid where raw) and g = accum / denom (0 where denom == 0):
+        hot = g >= grad_threshold       clone = hot and max(s) <= percent_dense * extent       split = hot and max(s) > percent_dense * extent
+        pruned = o < min_opacity  or, where max_screen_size is not None,  max(s) > 0.1 * extent  or  max_radii2D > max_screen_size
+    where a split's children are tested with max(s) / 1.6.  With max_radii2D=None the rows densify_tensors / densify_and_prune leave and
+    their order are exactly those of upstream's densify_and_prune (which zeroes max_radii2D before its prune: its screen-size test never
+    fires); with max_radii2D given the test applies to the originals.  The bits are independent, so a plan can also be written with torch:
+    keep.to(torch.uint8) prunes, 1 | 2 grows.  The thresholds are rounded to float32 once."""
+    big = max_screen_size is not None
+    rule = (_f32(grad_threshold), _f32(float(percent_dense) * float(extent)), _f32(min_opacity), _f32(max_screen_size if big else 0.0),
+            _f32(0.1 * float(extent)), _f32(0.8 * 2))
+    return _C.densify_plan(xyz_gradient_accum.detach(), denom.detach(), scaling.detach(), opacity.detach(),
+                           None if max_radii2D is None else max_radii2D.detach(), rule, raw, big)
+
+
+def densify_tensors(plan: torch.Tensor, tensors, roles=None, exp_avgs=None, exp_avg_sqs=None, noise: Optional[torch.Tensor] = None, *,
+                    split_shrink: float = 1.6, raw: bool = True):
+    """Clone, split and prune a model by a plan (densify_plan's, or one written with torch) in one scan and one apply (extension;
+    include/stp_raster.h: stp_densify_scan, stp_densify_apply) -> (new_tensors, new_exp_avgs, new_exp_avg_sqs, (nK, nC, nS)).
+    tensors: float32 (P, ...) of any trailing shape; roles: per tensor "plain" / "xyz" / "scaling" / "rotation" (or 0..3; None: all plain);
+    exp_avgs / exp_avg_sqs: the Adam moments per tensor, None where there are none (None: no moments at all).  The output has
+    nK + nC + 2 nS rows: the kept rows in index order, the copies, the first children of the split rows, their second children -- the order
+    upstream's cat, cat, mask sequence leaves.  Kept rows copy parameter and moments bit for bit; copies and children get zero moments;
+    child j of the r-th split Gaussian i has xyz + R(q / |q|) (s * noise[j * nS + r]) and scaling log(s / split_shrink) (s / split_shrink
+    where raw is False), s = exp(scaling) where raw.  noise: (2 nS, 3) standard normal (random numbers stay torch's); None draws
+    torch.randn.  A split needs exactly one tensor of each of the roles xyz (P, 3), scaling (P, 3), rotation (P, 4).
+    ONE host synchronisation, in the scan: the counts have to be known to allocate.  Inputs are not modified."""
+    tensors = [t.detach() for t in tensors]
+    n = len(tensors)
+    roles = [0] * n if roles is None else [_C.DENSIFY_ROLES[r] if isinstance(r, str) else int(r) for r in roles]
+    exp_avgs = [None] * n if exp_avgs is None else [None if m is None else m.detach() for m in exp_avgs]
+    exp_avg_sqs = [None] * n if exp_avg_sqs is None else [None if v is None else v.detach() for v in exp_avg_sqs]
+    offsets, counts = _C.densify_scan(plan)
+    if noise is None and counts[2] > 0:
+        noise = torch.randn(2 * counts[2], 3, device=plan.device, dtype=torch.float32)
+    new_t, new_m, new_v = _C.densify_apply(plan, offsets, counts, tensors, roles, exp_avgs, exp_avg_sqs, noise, split_shrink, raw)
+    return new_t, new_m, new_v, counts
+
+
+def densify_and_prune(optimizer, plan: torch.Tensor, *, noise: Optional[torch.Tensor] = None, split_shrink: float = 1.6, raw: bool = True,
+                      names=("xyz", "scaling", "rotation")):
+    """upstream's densify_and_prune on an optimizer, by a plan (extension): every group of `optimizer` (a torch.optim.Adam or a
+    SparseGaussianAdam whose groups hold one tensor each and carry "name") goes through ONE densify_tensors call; the groups named
+    names = (xyz, scaling, rotation) play those roles.  Each group gets a new nn.Parameter in group["params"][0], optimizer.state moves onto
+    it with the new exp_avg and exp_avg_sq (a group whose state is still empty stays empty; other entries, "step", are kept), and
+    {name: new Parameter} -- upstream's optimizable_tensors -- is returned for the model to take.  One host synchronisation."""
+    role_of = dict(zip(names, ("xyz", "scaling", "rotation")))
+    groups = list(optimizer.param_groups)
+    params, roles, ms, vs = [], [], [], []
+    for group in groups:
+        if len(group["params"]) != 1 or "name" not in group:
+            raise ValueError("densify_and_prune: every group must hold one tensor and carry a \"name\"")
+        p = group["params"][0]
+        state = optimizer.state.get(p, {})
+        params.append(p)
+        roles.append(role_of.get(group["name"], "plain"))
+        ms.append(state.get("exp_avg"))
+        vs.append(state.get("exp_avg_sq"))
+    new_t, new_m, new_v, _ = densify_tensors(plan, params, roles, ms, vs, noise, split_shrink=split_shrink, raw=raw)
+    out = {}
+    for group, old, t, m, v in zip(groups, params, new_t, new_m, new_v):
+        new = torch.nn.Parameter(t.requires_grad_(old.requires_grad))
+        state = optimizer.state.pop(old, None)
+        if state is not None and len(state) > 0:
+            if m is not None:
+                state["exp_avg"], state["exp_avg_sq"] = m, v
+            optimizer.state[new] = state
+        group["params"][0] = new
+        out[group["name"]] = new
+    return out
