@@ -3,11 +3,12 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--split-sh]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
   model  : get_xyz, get_opacity, get_scaling, get_rotation, get_features, active_sh_degree
+           (a model with `split_sh` set also has get_features_dc and get_features_rest, which are then passed as they are)
 and returns the trainer's usual dict (render, viewspace_points, visibility_filter, radii; "alpha" and "invdepth" too when asked for).
 """
 from __future__ import annotations
@@ -34,7 +35,9 @@ def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, 
     `bg_color` is three floats or a (3, H, W) image the frame is composed onto; where it requires grad it gets one.  With
     `splat_args._alpha = True` the dict also carries "alpha", the pixel's opacity (1, H, W), differentiable like the image
     (INTEGRATION.md section 3h); with `splat_args._invdepth = True` "invdepth", the blended inverse depth sum alpha T / z (1, H, W) that
-    upstream's rasterizer returns as `invdepths`, differentiable too."""
+    upstream's rasterizer returns as `invdepths`, differentiable too.
+    A model with `split_sh` hands its two SH parameters over as they are -- dc=_features_dc, shs=_features_rest -- where a trainer
+    otherwise concatenates them every step."""
     screenspace_points = torch.zeros_like(model.get_xyz, requires_grad=True)
     raster_settings = GaussianRasterizationSettings(
         image_height=int(camera.image_height), image_width=int(camera.image_width),
@@ -43,9 +46,11 @@ def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, 
         inv_viewprojmatrix=camera.full_proj_transform.inverse(), sh_degree=model.active_sh_degree,
         campos=camera.camera_center, prefiltered=False, settings=splat_args, render_depth=render_depth, debug=debug)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
-    shs, colors = (None, override_color) if override_color is not None else (model.get_features, None)
+    shs, colors, dc = (None, override_color, None) if override_color is not None else (model.get_features, None, None)
+    if override_color is None and getattr(model, "split_sh", False):   # no torch.cat: the two leaves go in, their two .grad come out
+        shs, dc = model.get_features_rest, model.get_features_dc
     image, radii, *extra = rasterizer(means3D=model.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors,
-                                      opacities=model.get_opacity, scales=model.get_scaling, rotations=model.get_rotation)
+                                      opacities=model.get_opacity, scales=model.get_scaling, rotations=model.get_rotation, dc=dc)
     out = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
     if getattr(splat_args, "_alpha", False):      # (the extra outputs in their order: alpha, then the inverse depth)
         out["alpha"] = extra.pop(0)
@@ -70,22 +75,45 @@ def splat_config(name: str) -> ExtendedSettings:
 class ToyGaussians(torch.nn.Module):
     """The part of the trainer's GaussianModel that render() touches (activations included)."""
 
-    def __init__(self, sc: scenes.Scene, device):
+    def __init__(self, sc: scenes.Scene, device, split_sh: bool = False):
         super().__init__()
+        self.split_sh = split_sh
         t = lambda a: torch.nn.Parameter(torch.tensor(a, device=device))
         self._xyz = t(sc.means3D)
         self._scaling = torch.nn.Parameter(torch.log(torch.tensor(sc.scales, device=device)))
         self._rotation = t(sc.rotations)
         op = torch.tensor(sc.opacities, device=device).clamp(1e-4, 1 - 1e-4)
         self._opacity = torch.nn.Parameter(torch.log(op / (1 - op)))
-        self._features = t(sc.shs)
+        if split_sh:   # the trainers' two parameters, with their two learning rates
+            self._features_dc, self._features_rest = t(sc.shs[:, :1].copy()), t(sc.shs[:, 1:].copy())
+        else:
+            self._features = t(sc.shs)
         self.active_sh_degree = sc.sh_degree
 
     get_xyz = property(lambda s: s._xyz)
     get_scaling = property(lambda s: torch.exp(s._scaling))
     get_rotation = property(lambda s: torch.nn.functional.normalize(s._rotation))
     get_opacity = property(lambda s: torch.sigmoid(s._opacity))
-    get_features = property(lambda s: s._features)
+    get_features = property(lambda s: torch.cat((s._features_dc, s._features_rest), dim=1) if s.split_sh else s._features)
+    get_features_dc = property(lambda s: s._features_dc)
+    get_features_rest = property(lambda s: s._features_rest)
+
+    def feature_groups(self, lr: float):
+        """The optimizer groups of the SH coefficients: one, or upstream's two with feature_lr / 20 for the rest; named as
+        densify_and_prune carries them."""
+        if self.split_sh:
+            return [{"params": [self._features_dc], "lr": lr, "name": "f_dc"}, {"params": [self._features_rest], "lr": lr / 20.0, "name": "f_rest"}]
+        return [{"params": [self._features], "lr": lr, "name": "f"}]
+
+    def feature_params(self):
+        return [self._features_dc, self._features_rest] if self.split_sh else [self._features]
+
+    def take_features(self, new: dict):
+        """the Parameters densify_and_prune returned, by group name"""
+        if self.split_sh:
+            self._features_dc, self._features_rest = new["f_dc"], new["f_rest"]
+        else:
+            self._features = new["f"]
 
 
 def camera_of(sc: scenes.Scene, device):
@@ -113,7 +141,7 @@ def relocate_dead(model: ToyGaussians, opt: torch.optim.Optimizer, min_opacity: 
         model._opacity[sampled] = torch.log(new_opacity / (1.0 - new_opacity))
         model._scaling[sampled] = torch.log(new_scaling)
         touched = torch.cat([sampled, dead_idx])
-        for param in (model._xyz, model._features, model._opacity, model._scaling, model._rotation):
+        for param in (model._xyz, *model.feature_params(), model._opacity, model._scaling, model._rotation):
             param[dead_idx] = param[sampled]
             state = opt.state.get(param)
             if state:
@@ -145,6 +173,9 @@ def main(argv=None):
                          "compute_relocation, and the opacity / scale L1 regularisers (INTEGRATION.md section 3l).  adc: 3DGS adaptive density control "
                          "-- the fused densification statistics after every backward, densify_plan + densify_and_prune every 10 iterations "
                          "(INTEGRATION.md section 3m)")
+    ap.add_argument("--split-sh", action="store_true",
+                    help="the model keeps _features_dc and _features_rest as two parameters (two optimizer groups, the rest at a twentieth of the "
+                         "learning rate, as upstream) and renders with dc=: no torch.cat per step (INTEGRATION.md section 3n)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
@@ -162,21 +193,22 @@ def main(argv=None):
         target, target_alpha, target_invdepth = target_out["render"], target_out.get("alpha"), target_out.get("invdepth")
 
     # start from perturbed colours and opacities and fit them back
-    model = ToyGaussians(target_scene, dev)
+    model = ToyGaussians(target_scene, dev, split_sh=args.split_sh)
     with torch.no_grad():
-        model._features.mul_(0.3)
+        for f in model.feature_params():
+            f.mul_(0.3)
         model._opacity.sub_(1.0)
     adc = args.strategy == "adc"
     if adc and args.optimizer != "sparse_adam":   # densify_and_prune wants the trainers' layout: one named group per tensor
-        opt = torch.optim.Adam([{"params": [model._features], "lr": 2e-2, "name": "f"}, {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
+        opt = torch.optim.Adam([*model.feature_groups(2e-2), {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
                                 {"params": [model._xyz], "lr": 0.0, "name": "xyz"}, {"params": [model._scaling], "lr": 0.0, "name": "scaling"},
                                 {"params": [model._rotation], "lr": 0.0, "name": "rotation"}], lr=0.0, eps=1e-15)
     elif args.optimizer == "sparse_adam":   # one group per tensor, as the trainers' training_setup() builds them
-        opt = SparseGaussianAdam([{"params": [model._features], "lr": 2e-2, "name": "f"}, {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
+        opt = SparseGaussianAdam([*model.feature_groups(2e-2), {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
                                   {"params": [model._xyz], "lr": 0.0, "name": "xyz"}, {"params": [model._scaling], "lr": 0.0, "name": "scaling"},
                                   {"params": [model._rotation], "lr": 0.0, "name": "rotation"}], lr=0.0, eps=1e-15)
     else:
-        opt = torch.optim.Adam([{"params": [model._features], "lr": 2e-2}, {"params": [model._opacity], "lr": 5e-2},
+        opt = torch.optim.Adam([*model.feature_groups(2e-2), {"params": [model._opacity], "lr": 5e-2},
                                 {"params": [model._xyz, model._scaling, model._rotation], "lr": 0.0}])
     train_cfg = splat_config(args.config)
     train_cfg._alpha = masked
@@ -239,7 +271,8 @@ def main(argv=None):
             plan = densify_plan(stat_signed, stat_denom, model._scaling, model._opacity, None, grad_threshold=0.0002, extent=extent, max_screen_size=20)
             before = plan.numel()
             new = densify_and_prune(opt, plan)
-            model._features, model._opacity, model._xyz, model._scaling, model._rotation = (new[n] for n in ("f", "opacity", "xyz", "scaling", "rotation"))
+            model.take_features(new)
+            model._opacity, model._xyz, model._scaling, model._rotation = (new[n] for n in ("opacity", "xyz", "scaling", "rotation"))
             after = model.get_xyz.shape[0]
             kept, cloned, split = (int(((plan >> b) & 1).sum()) for b in range(3))
             grown, pruned = grown + cloned + 2 * split, pruned + before - kept

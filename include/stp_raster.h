@@ -301,6 +301,27 @@ void stp_set_backward_background(const float* bg_image /* the forward's, or NULL
 void stp_set_forward_invdepth(float* out_invdepth /* H x W */);
 void stp_set_backward_invdepth(const float* invdepth /* the forward's, H x W */, const float* dL_dinvdepth /* H x W */);
 
+/* Extension (the `dc` / `shs` pair of the official 3DGS rasterizer's accelerated branch): SH coefficients as the two tensors a trainer keeps
+   them in -- `dc`, the (P, 3) first coefficient (a trainer's _features_dc), and the (P, M-1, 3) rest (_features_rest) -- without a
+   concatenated (P, M, 3) copy going in or a full-size dL_dsh coming out.  M stays the TOTAL number of coefficients per Gaussian.
+   stp_set_forward_split_sh -- the NEXT stp_forward of the calling thread reads coefficient 0 of Gaussian i at dc + 3 i and coefficients
+       1 .. M-1 at shs + 3 (M-1) i: `shs` is the rest.  With M == 1 `shs` is not read and may be NULL.
+   stp_set_backward_split_sh -- the NEXT stp_backward / stp_backward_phases of the calling thread that runs the per-Gaussian half (phases
+       bit 1) reads the coefficients the same way and writes dL_ddc (P x 3) and dL_dsh as P x (M-1) x 3 (not written, may be NULL, for
+       M == 1).  Both are written in full, zeros for Gaussians with radii <= 0, as dL_dsh is.  A chunked per-Gaussian half (phases bits
+       8-23) is fine: every chunk writes its own rows of both.
+   Only the SH kernels' staging between global memory and LDS differs (two source / destination spans per workgroup instead of one); the
+   arithmetic reads the same values, so every output of a call with the request -- the image, radii, num_rendered, all gradients, dL_ddc
+   and dL_dsh against the two slices of the concatenated call's dL_dsh -- is bit-identical to that of a call on the concatenated tensor.
+   The pointers need only the 4-byte alignment of their element type (rows 1.. of a larger tensor are fine): 16-byte aligned ones are
+   moved 16 bytes per lane, others one float at a time.  With colors_precomp given the precomputed colours win, as without the request:
+   no SH coefficient is read and the backward writes neither SH gradient.
+   A NULL dc clears a pending request.  The forward request is consumed by the next stp_forward of the thread whatever its outcome; the
+   backward request by the next backward with phases bit 1, whatever its outcome -- a render-only call (phases = 1) leaves it pending, as
+   it does the camera request.  STP_ERR_INVALID_ARGUMENT: a backward request without dL_ddc, or M > 1 with a NULL shs / dL_dsh. */
+void stp_set_forward_split_sh(const float* dc /* P x 3 */);
+void stp_set_backward_split_sh(const float* dc /* P x 3 */, float* dL_ddc /* P x 3 */);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:188-193, rasterizer_impl.cu:161-173).
    `present` is P bytes (bool). */
 int stp_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

@@ -74,6 +74,8 @@ struct Api {
     decltype(&stp_set_backward_background) set_backward_background = nullptr;
     decltype(&stp_set_forward_invdepth) set_forward_invdepth = nullptr;
     decltype(&stp_set_backward_invdepth) set_backward_invdepth = nullptr;
+    decltype(&stp_set_forward_split_sh) set_forward_split_sh = nullptr;
+    decltype(&stp_set_backward_split_sh) set_backward_split_sh = nullptr;
     decltype(&stp_sparse_adam) sparse_adam = nullptr;
     decltype(&stp_mcmc_relocation) mcmc_relocation = nullptr;
     decltype(&stp_mcmc_add_noise) mcmc_add_noise = nullptr;
@@ -110,6 +112,8 @@ int load_library(const std::string& path)
     a.set_backward_background = reinterpret_cast<decltype(a.set_backward_background)>(dlsym(h, "stp_set_backward_background"));
     a.set_forward_invdepth = reinterpret_cast<decltype(a.set_forward_invdepth)>(dlsym(h, "stp_set_forward_invdepth"));
     a.set_backward_invdepth = reinterpret_cast<decltype(a.set_backward_invdepth)>(dlsym(h, "stp_set_backward_invdepth"));
+    a.set_forward_split_sh = reinterpret_cast<decltype(a.set_forward_split_sh)>(dlsym(h, "stp_set_forward_split_sh"));
+    a.set_backward_split_sh = reinterpret_cast<decltype(a.set_backward_split_sh)>(dlsym(h, "stp_set_backward_split_sh"));
     a.sparse_adam = reinterpret_cast<decltype(a.sparse_adam)>(dlsym(h, "stp_sparse_adam"));
     a.mcmc_relocation = reinterpret_cast<decltype(a.mcmc_relocation)>(dlsym(h, "stp_mcmc_relocation"));
     a.mcmc_add_noise = reinterpret_cast<decltype(a.mcmc_add_noise)>(dlsym(h, "stp_mcmc_add_noise"));
@@ -298,23 +302,45 @@ bool per_pixel_background(const torch::Tensor& bg, int H, int W)
                              " (a library built before the alpha output and per-pixel background): rebuild it");
 }
 
+// dc (extension, include/stp_raster.h: stp_set_forward_split_sh / stp_set_backward_split_sh): the first SH coefficient as a tensor of its own,
+// (P,1,3) or (P,3); `sh` is then the rest, (P,M-1,3), possibly empty.  Returns M, the total coefficient count.  Checked before any device work.
+int split_sh_total(const torch::Tensor& dc, const torch::Tensor& sh, const torch::Tensor& means3D, const char* symbol, bool exported)
+{
+    if (!exported)
+        throw std::runtime_error(std::string("dc: the loaded libstp_raster.so does not export ") + symbol + " (a library built before split SH inputs): rebuild it");
+    const int64_t P = means3D.size(0);
+    if (!((dc.dim() == 3 && dc.size(1) == 1 && dc.size(2) == 3) || (dc.dim() == 2 && dc.size(1) == 3)))
+        throw std::runtime_error("dc must have dimensions (num_points, 1, 3) or (num_points, 3)");
+    if (dc.size(0) != P) throw std::runtime_error("dc must have one row per Gaussian: " + std::to_string(dc.size(0)) + " rows for " + std::to_string(P) + " points");
+    if (dc.scalar_type() != torch::kFloat32) throw std::runtime_error("dc must be a float32 tensor");
+    if (dc.device() != means3D.device()) throw std::runtime_error("dc must be on the device of means3D");
+    if (sh.numel() == 0) return 1;
+    if (!(sh.dim() == 3 && sh.size(0) == P && sh.size(2) == 3))
+        throw std::runtime_error("with dc, shs is the rest of the coefficients and must have dimensions (num_points, M - 1, 3)");
+    if (sh.scalar_type() != torch::kFloat32 || sh.device() != means3D.device()) throw std::runtime_error("with dc, shs must be a float32 tensor on the device of means3D");
+    return (int)sh.size(1) + 1;
+}
+
 // == RasterizeGaussiansCUDA (reference rasterize_points.cu:43-138).
 // Returns (num_rendered, out_color (3,H,W), radii (P,) int32, geomBuffer, binningBuffer, imgBuffer, alpha).
 // alpha (extension, include/stp_raster.h: stp_set_forward_background): with alpha = true the last element is 1 - final_T, (1,H,W); an
 // undefined tensor otherwise.  A background of shape exactly (3,H,W) is composed per pixel.
 // invdepth (extension, include/stp_raster.h: stp_set_forward_invdepth): with invdepth = true one more element behind alpha's: sum alpha T / z,
 // (1,H,W); an undefined tensor otherwise.
+// dc (keyword, extension): see split_sh_total; `sh` is then the (P,M-1,3) rest.  Ignored with precomputed colours.
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors, const torch::Tensor& opacity,
                     const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier, const torch::Tensor& cov3D_precomp,
                     const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const torch::Tensor& inv_viewprojmatrix, const float tan_fovx,
                     const float tan_fovy, const int image_height, const int image_width, const torch::Tensor& sh, const int degree,
                     const torch::Tensor& campos, const bool prefiltered, const py::dict& settings, const bool render_depth, const bool debug,
-                    const bool record_log, const bool alpha, const bool invdepth)
+                    const bool record_log, const bool alpha, const bool invdepth, const c10::optional<torch::Tensor>& dc)
 {
     need_library();
     TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must have dimensions (num_points, 3)");
     TORCH_CHECK(means3D.is_cuda(), "diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
+    const bool split = dc.has_value() && dc->defined() && colors.numel() == 0; // (precomputed colours win)
+    const int M_split = split ? split_sh_total(*dc, sh, means3D, "stp_set_forward_split_sh", g_api.set_forward_split_sh != nullptr) : 0;
     const torch::Device dev = means3D.device();
     const int P = (int)means3D.size(0), H = image_height, W = image_width;
     const bool windowed = settings.contains("_tile_rows") && !settings["_tile_rows"].is_none();
@@ -338,7 +364,7 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
     Resizer geom{torch::empty({0}, bopt), false, false, 0}, binning{torch::empty({0}, bopt), true, false, 1}, img{torch::empty({0}, bopt), true, false, 2};
     int rendered = 0;
     if (P != 0) {
-        const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
+        const int M = split ? M_split : sh.numel() != 0 ? (int)sh.size(1) : 0;
         StpSettings s = settings_from_dict(settings, record_log);
         if (render_depth) { // DebugVisualization::Depth (reference rasterize_points.cu:104-107); no log: it has no backward
             s.debug_visualization = STP_DEBUG_DEPTH;
@@ -347,6 +373,8 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
         const torch::Tensor bg_ = prep(background, dev), m3_ = prep(means3D, dev), sh_ = prep(sh, dev), col_ = prep(colors, dev), op_ = prep(opacity, dev),
                             sc_ = prep(scales, dev), ro_ = prep(rotations, dev), c3_ = prep(cov3D_precomp, dev), vm_ = prep(viewmatrix, dev),
                             pm_ = prep(projmatrix, dev), inv_ = prep(inv_viewprojmatrix, dev), cam_ = prep(campos, dev);
+        torch::Tensor dc_;
+        if (split) dc_ = prep(*dc, dev);
         const c10::hip::HIPGuard guard(dev.index());
         hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
         int rc;
@@ -355,6 +383,7 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
             if (alpha || bg_pixels) // (consumed by the call below, on this thread)
                 g_api.set_forward_background(bg_pixels ? fptr(bg_) : nullptr, alpha ? out_alpha.data_ptr<float>() : nullptr);
             if (invdepth) g_api.set_forward_invdepth(out_invdepth.data_ptr<float>());
+            if (split) g_api.set_forward_split_sh(dc_.data_ptr<float>());
             rc = g_api.forward(&Resizer::call, &geom, &Resizer::call, &binning, &Resizer::call, &img, P, degree, M, fptr(bg_), W, H, &s, fptr(m3_),
                              fptr(sh_), fptr(col_), fptr(op_), fptr(sc_), scale_modifier, fptr(ro_), fptr(c3_), fptr(vm_), fptr(pm_), fptr(inv_),
                              fptr(cam_), tan_fovx, tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(), radii.data_ptr<int>(), debug ? 1 : 0,
@@ -384,6 +413,11 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
 // dL_dinvdepth / invdepth (extension, include/stp_raster.h: stp_set_backward_invdepth): the gradient of the forward's inverse-depth output and
 // that output itself, both (1,H,W).  No extra result: the gradient arrives in the eight (and the camera's three).  Whole backwards on padded
 // records only.
+// dc (keyword, extension, include/stp_raster.h: stp_set_backward_split_sh): the first SH coefficient, (P,1,3) or (P,3); `sh` is then the (P,M-1,3)
+// rest.  dL_dsh, in its usual slot, is (P,M-1,3), and dL_ddc, (P,3), is the LAST tensor of the result.  The full order of the result is
+//   [the eight] [dL_dview, dL_dproj, dL_dcam] [absgrad] [blend_stats] [dL_dbackground] [dL_ddc]
+// each bracket present when asked for.  Calls with the per-Gaussian half (phases bit 1); with `outputs` (a later chunk) a ninth tensor in it is
+// the dL_ddc of the first chunk.  Ignored with precomputed colours.
 std::vector<torch::Tensor>
 rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& opacities,
                              const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
@@ -394,10 +428,13 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const py::dict& settings, const bool debug, const bool record_log, const int phases, const c10::optional<torch::Tensor>& partial,
                              const c10::optional<std::vector<torch::Tensor>>& outputs, const bool camera_grads, const bool absgrad, const bool blend_stats,
                              const c10::optional<torch::Tensor>& dL_dalpha, const bool bg_grad,
-                             const c10::optional<torch::Tensor>& dL_dinvdepth, const c10::optional<torch::Tensor>& invdepth)
+                             const c10::optional<torch::Tensor>& dL_dinvdepth, const c10::optional<torch::Tensor>& invdepth,
+                             const c10::optional<torch::Tensor>& dc)
 {
     need_library();
     TORCH_CHECK(means3D.is_cuda(), "diff_gaussian_rasterization (MI355X build) needs tensors on a GPU device; there is no CPU path in the product");
+    const bool split = dc.has_value() && dc->defined() && colors.numel() == 0 && (phases & 2); // (precomputed colours win; the render half reads no SH)
+    const int M_split = split ? split_sh_total(*dc, sh, means3D, "stp_set_backward_split_sh", g_api.set_backward_split_sh != nullptr) : 0;
     if (camera_grads) {
         if (!g_api.set_backward_camera_grads || !g_api.camera_grad_workspace_bytes)
             throw std::runtime_error(std::string("camera gradients: the loaded libstp_raster.so does not export ") +
@@ -434,7 +471,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         TORCH_CHECK(invdepth.has_value() && invdepth->defined(), "dL_dinvdepth needs the forward's invdepth");
         TORCH_CHECK(dL_dinvdepth->numel() == (int64_t)H * W && invdepth->numel() == (int64_t)H * W, "dL_dinvdepth and invdepth must have H * W elements");
     }
-    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
+    const int M = split ? M_split : sh.numel() != 0 ? (int)sh.size(1) : 0;
     const auto fopt = means3D.options().dtype(torch::kFloat32);
     const int rec_floats = (phases & 4) ? STP_GRAD_RECORD_USED : STP_GRAD_RECORD_FLOATS; // (bit 2: compact records, the tile-row shard's wire format)
     // STP_KEEP_RECORDS=1 (MEASURED, round 4, off): a whole backward keeps its record buffer between steps and the per-Gaussian half clears what
@@ -456,10 +493,16 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
     if (!records.defined()) records = partial.has_value() ? *partial : torch::zeros({P, rec_floats}, fopt);
     TORCH_CHECK(records.dim() == 2 && records.size(0) == P && records.size(1) == rec_floats && records.scalar_type() == torch::kFloat32 &&
                     records.is_contiguous(), "partial must be a contiguous float32 (P,", rec_floats, ") tensor");
-    torch::Tensor dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations;
+    torch::Tensor dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_ddc;
     if ((phases & 2) && outputs.has_value()) {
         // a chunked per-Gaussian half (phases bits 8-23): the later chunks write into the tensors the first one allocated
-        TORCH_CHECK(outputs->size() == 8, "outputs: the eight gradient tensors of an earlier chunk");
+        TORCH_CHECK(outputs->size() == (split ? 9u : 8u), "outputs: the eight gradient tensors of an earlier chunk (and its dL_ddc behind them with dc)");
+        if (split) {
+            dL_ddc = (*outputs)[8];
+            TORCH_CHECK(dL_ddc.scalar_type() == torch::kFloat32 && dL_ddc.is_contiguous() && dL_ddc.numel() == (int64_t)P * 3 &&
+                            (*outputs)[5].is_contiguous() && (*outputs)[5].numel() == (int64_t)P * (M - 1) * 3,
+                        "outputs: dL_dsh must be a contiguous (P,M-1,3) and dL_ddc a contiguous (P,3) float32 tensor with dc");
+        }
         dL_dmeans2D = (*outputs)[0]; dL_dcolors = (*outputs)[1]; dL_dopacity = (*outputs)[2]; dL_dmeans3D = (*outputs)[3];
         dL_dcov3D = (*outputs)[4]; dL_dsh = (*outputs)[5]; dL_dscales = (*outputs)[6]; dL_drotations = (*outputs)[7];
     } else if (phases & 2) {
@@ -467,7 +510,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         // except for the scale/rotation gradients when a precomputed covariance is used (then they are not touched)
         const bool have_scales = scales.numel() != 0;
         dL_dmeans2D = torch::empty({P, 3}, fopt); dL_dcolors = torch::empty({P, 3}, fopt); dL_dopacity = torch::empty({P, 1}, fopt);
-        dL_dmeans3D = torch::empty({P, 3}, fopt); dL_dcov3D = torch::empty({P, 6}, fopt); dL_dsh = torch::empty({P, M, 3}, fopt);
+        dL_dmeans3D = torch::empty({P, 3}, fopt); dL_dcov3D = torch::empty({P, 6}, fopt); dL_dsh = torch::empty({P, split ? M - 1 : M, 3}, fopt);
+        if (split) dL_ddc = torch::empty({P, 3}, fopt); // (written in full by the library, like dL_dsh)
         dL_dscales = have_scales ? torch::empty({P, 3}, fopt) : torch::zeros({P, 3}, fopt);
         dL_drotations = have_scales ? torch::empty({P, 4}, fopt) : torch::zeros({P, 4}, fopt);
     }
@@ -492,11 +536,14 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
     if (bg_pixels) bgpix_ = prep(background, dev);
     torch::Tensor dinv_, inv_out_;
     if (have_dinv) { dinv_ = prep(*dL_dinvdepth, dev); inv_out_ = prep(*invdepth, dev); }
+    torch::Tensor dc_;
+    if (split && P != 0) dc_ = prep(*dc, dev);
     auto make_requests = [&] { // (all are consumed by the library call that follows, on this thread)
         if ((bg_pixels || have_dalpha || bg_grad) && P != 0)
             g_api.set_backward_background(bg_pixels ? bgpix_.data_ptr<float>() : nullptr, have_dalpha ? dal_.data_ptr<float>() : nullptr,
                                           bg_grad ? dL_dbg.data_ptr<float>() : nullptr);
         if (have_dinv && P != 0) g_api.set_backward_invdepth(inv_out_.data_ptr<float>(), dinv_.data_ptr<float>());
+        if (split && P != 0) g_api.set_backward_split_sh(dc_.data_ptr<float>(), dL_ddc.data_ptr<float>());
         if (blend_stats && P != 0) g_api.set_backward_blend_stats(stats.data_ptr<float>());
         if (absgrad && P != 0) g_api.set_backward_absgrad(dL_dmeans2D_abs.data_ptr<float>());
         if (camera_grads) g_api.set_backward_camera_grads(dL_dview.data_ptr<float>(), dL_dproj.data_ptr<float>(), dL_dcam.data_ptr<float>(), cam_ws.data_ptr(), (size_t)cam_ws.numel());
@@ -541,6 +588,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
     if (absgrad) result.push_back(dL_dmeans2D_abs);
     if (blend_stats) result.push_back(stats);
     if (bg_grad) result.push_back(dL_dbg);
+    if (split) result.push_back(dL_ddc);
     return result;
 }
 

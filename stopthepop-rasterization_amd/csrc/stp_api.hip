@@ -56,7 +56,8 @@ void fill_frame(FrameParams& f, int P, int D, int M, const float* background, in
 // ---- them live in this one struct, and the two functions below are the only ones that take them.
 struct BackwardBackground { const float* bg_image = nullptr; const float* dL_dalpha = nullptr; float* dL_dbackground = nullptr; }; // stp_set_backward_background
 struct BackwardInvdepth { const float* invdepth = nullptr; const float* dL_dinvdepth = nullptr; }; // stp_set_backward_invdepth
-struct BackwardRequests { CameraGradRequest cam; float* absgrad = nullptr; float* blend_stats = nullptr; BackwardBackground background; BackwardInvdepth invdepth; };
+struct BackwardSplitSh { const float* dc = nullptr; float* dL_ddc = nullptr; }; // stp_set_backward_split_sh
+struct BackwardRequests { CameraGradRequest cam; float* absgrad = nullptr; float* blend_stats = nullptr; BackwardBackground background; BackwardInvdepth invdepth; BackwardSplitSh split_sh; };
 struct PendingRequests { ForwardRequests forward; BackwardRequests backward; };
 static thread_local PendingRequests t_pending;
 
@@ -64,7 +65,7 @@ static thread_local PendingRequests t_pending;
 // outcome.  stp_forward calls this in front of its very first check, so a call refused there has consumed them too.
 ForwardRequests take_forward_requests() { return std::exchange(t_pending.forward, ForwardRequests{}); }
 // What a backward with these `phases` takes; what it does not take stays pending.
-//   camera gradients: consumed by the next backward that runs the per-Gaussian half (phases bit 1), whatever its outcome.  A call without
+//   camera gradients and split SH: consumed by the next backward that runs the per-Gaussian half (phases bit 1), whatever its outcome.  A call without
 //       bit 1 leaves them pending.
 //   backward background: consumed by the next backward that runs the render half (phases bit 0), whatever its outcome.  A call without
 //       bit 0 leaves it pending (nothing of it lives in the gradient records).
@@ -76,7 +77,7 @@ static BackwardRequests take_backward_requests(int phases)
 {
     BackwardRequests& p = t_pending.backward;
     BackwardRequests r;
-    if (phases & 2) r.cam = std::exchange(p.cam, CameraGradRequest{});
+    if (phases & 2) { r.cam = std::exchange(p.cam, CameraGradRequest{}); r.split_sh = std::exchange(p.split_sh, BackwardSplitSh{}); }
     r.absgrad = std::exchange(p.absgrad, nullptr); r.blend_stats = std::exchange(p.blend_stats, nullptr);
     r.invdepth = std::exchange(p.invdepth, BackwardInvdepth{});
     if (phases & 1) r.background = std::exchange(p.background, BackwardBackground{});
@@ -111,6 +112,8 @@ void stp_set_backward_blend_stats(float* blend_stats) { t_pending.backward.blend
 void stp_set_backward_background(const float* bg_image, const float* dL_dalpha, float* dL_dbackground) { t_pending.backward.background = BackwardBackground{bg_image, dL_dalpha, dL_dbackground}; }
 void stp_set_forward_invdepth(float* out_invdepth) { t_pending.forward.out_invdepth = out_invdepth; }
 void stp_set_backward_invdepth(const float* invdepth, const float* dL_dinvdepth) { t_pending.backward.invdepth = BackwardInvdepth{invdepth, dL_dinvdepth}; }
+void stp_set_forward_split_sh(const float* dc) { t_pending.forward.sh_dc = dc; }
+void stp_set_backward_split_sh(const float* dc, float* dL_ddc) { t_pending.backward.split_sh = dc ? BackwardSplitSh{dc, dL_ddc} : BackwardSplitSh{}; }
 
 namespace {
 // Scratch of the uniform background gradient's two-stage sum (stp_background.hip): a small ring of partial-row buffers per device, made at the
@@ -180,6 +183,12 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
         if (((phases >> 8) & 0xFF) > 1)
             return fail(STP_ERR_INVALID_ARGUMENT, "the inverse-depth gradient is not available from a chunked per-Gaussian half (phases bits 8-23)");
     }
+    const BackwardSplitSh& bsh = req.split_sh;
+    if (bsh.dc && colors_precomp) shs = nullptr; // precomputed colours win, as in the forward: no SH coefficient is read, neither SH gradient is written
+    if (bsh.dc && !colors_precomp) {
+        if (!bsh.dL_ddc) return fail(STP_ERR_INVALID_ARGUMENT, "split SH: dL_ddc must be given with dc");
+        if (M > 1 && (!shs || !dL_dsh)) return fail(STP_ERR_INVALID_ARGUMENT, "split SH: M > 1 needs the rest of the coefficients (shs) and their gradient (dL_dsh)");
+    }
     if (cam.dL_dview) {
         if (!cam.workspace || (reinterpret_cast<uintptr_t>(cam.workspace) & 15) != 0 || cam.workspace_bytes < camera_grad_workspace_bytes(P))
             return fail(STP_ERR_INVALID_ARGUMENT, "camera gradients: the workspace is null, not 16-byte aligned or smaller than stp_camera_grad_workspace_bytes(P)");
@@ -219,6 +228,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     bw.blend_stats = blend_stats;
     bw.bg_image = bbg.bg_image; bw.dL_dalpha = bbg.dL_dalpha; bw.dL_dbackground = bbg.dL_dbackground;
     bw.invdepth = binv.invdepth; bw.dL_dinvdepth = binv.dL_dinvdepth;
+    if (bsh.dc && !colors_precomp) { f.sh_dc = bsh.dc; bw.dL_ddc = bsh.dL_ddc; }
     bw.pixel_colors = pixel_colors; bw.dL_dpix = dL_dpix; bw.dL_dmean2D = dL_dmean2D; bw.grad_rec = grad_records;
     bw.grad_stride = (phases & 4) ? STP_GRAD_RECORD_USED : STP_GRAD_RECORD_FLOATS;
     bw.clear_rec = (phases & 8) ? 1 : 0;

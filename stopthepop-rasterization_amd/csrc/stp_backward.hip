@@ -43,6 +43,8 @@ struct BwdPreArgs {
     float* dL_dscale;
     float* dL_drot;
     float* cam_rows;       // CAM only: one kCamRow-float row of camera-gradient partial sums per workgroup (camera_grad_* below)
+    const float* dc;       // SPLIT only: the (P, 3) first SH coefficient; `shs` is then the (P, M-1, 3) rest (not read for M == 1, never nullptr)
+    float* dL_ddc;         // SPLIT only: P x 3; dL_dsh is then P x (M-1) x 3
 };
 
 // Camera-gradient contributions of one Gaussian (CAM instantiation), in the order of a workspace row:
@@ -397,7 +399,9 @@ __device__ __forceinline__ float wave_sum(float v) // every lane ends with the s
     return v;
 }
 
-template <bool CAM, bool INVD>
+// SPLIT (stp_set_backward_split_sh): the LDS rows come from two global spans (a.dc, a.shs) and leave as two (a.dL_ddc, a.dL_dsh), see stp_device.h:
+// split SH rows; everything between the two stagings is the SPLIT = false kernel's.
+template <bool CAM, bool INVD, bool SPLIT>
 __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreArgs a)
 {
     extern __shared__ float s_rows[]; // [256][3M + 1]
@@ -413,9 +417,20 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreAr
         for (int k = 0; k < kCamTerms; k++) cg[k] = 0.0f;
     }
     if (have_sh) {
-        const float* __restrict__ src = a.shs + (size_t)base * row_len;
+        const float* __restrict__ src = a.shs + (size_t)base * (SPLIT ? row_len - 3 : row_len);
         const int total = rows * row_len;
-        if (row_len == 48 && rows == 256) { // SH degree 3 (M = 16), full block: every load in flight at once (stp_device.h)
+        if constexpr (SPLIT) {
+            const float* __restrict__ src_dc = a.dc + (size_t)base * 3;
+            const bool vec = aligned16(a.dc, row_len > 3 ? a.shs : nullptr); // (views such as rest[1:] are 4-byte aligned only)
+            if (row_len == 48 && rows == 256 && vec) {
+                float4 v[12];
+                split48_load(src_dc, src, tid, v);
+                split48_store(s_rows, tid, v);
+            } else {
+                stage_span_in<256>(src_dc, s_rows, tid, rows, 3, 0, row_stride, vec);
+                stage_span_in<256>(src, s_rows, tid, rows, row_len - 3, 3, row_stride, vec);
+            }
+        } else if (row_len == 48 && rows == 256) { // SH degree 3 (M = 16), full block: every load in flight at once (stp_device.h)
             stage_rows_in<256, 48>(src, s_rows, tid);
         } else if ((row_len & 3) == 0) {
             for (int f = 4 * tid; f < total; f += 4 * 256) {
@@ -461,9 +476,18 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreAr
     }
     if (have_sh) {
         __syncthreads();
-        float* __restrict__ dst = a.dL_dsh + (size_t)base * row_len;
+        float* __restrict__ dst = a.dL_dsh + (size_t)base * (SPLIT ? row_len - 3 : row_len);
         const int total = rows * row_len;
-        if (row_len == 48 && rows == 256) {
+        if constexpr (SPLIT) {
+            float* __restrict__ dst_dc = a.dL_ddc + (size_t)base * 3;
+            const bool vec = aligned16(a.dL_ddc, row_len > 3 ? a.dL_dsh : nullptr);
+            if (row_len == 48 && rows == 256 && vec) {
+                split48_out(dst_dc, dst, s_rows, tid);
+            } else {
+                stage_span_out<256>(dst_dc, s_rows, tid, rows, 3, 0, row_stride, vec);
+                stage_span_out<256>(dst, s_rows, tid, rows, row_len - 3, 3, row_stride, vec);
+            }
+        } else if (row_len == 48 && rows == 256) {
             stage_rows_out<256, 48>(dst, s_rows, tid);
         } else if ((row_len & 3) == 0) {
             for (int f = 4 * tid; f < total; f += 4 * 256) {
@@ -621,12 +645,20 @@ hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState&
     a.dL_dmean2D = bw.dL_dmean2D; a.grad_rec = bw.grad_rec; a.grad_stride = bw.grad_stride; a.clear_rec = bw.clear_rec; a.dL_dopacity = bw.dL_dopacity; a.dL_dcolor = bw.dL_dcolor;
     a.dL_dmean3D = bw.dL_dmean3D; a.dL_dcov3D = bw.dL_dcov3D; a.dL_dsh = bw.dL_dsh; a.dL_dscale = bw.dL_dscale; a.dL_drot = bw.dL_drot;
     a.cam_rows = cam ? reinterpret_cast<float*>(bw.cam.workspace) : nullptr;
+    const bool split = f.sh_dc != nullptr && bw.dL_ddc != nullptr; // stp_set_backward_split_sh
+    a.dc = f.sh_dc; a.dL_ddc = bw.dL_ddc;
+    if (split && a.shs == nullptr) a.shs = a.dc; // M == 1: no rest; the kernel's "have SH" test wants a pointer and reads nothing through this one
     const bool invd = bw.dL_dinvdepth != nullptr; // (stp_set_backward_invdepth; the caller has refused a chunked half and compact records with it: slot 14 exists)
-    const void* kernel = cam ? (invd ? reinterpret_cast<const void*>(preprocess_backward_kernel<true, true>) : reinterpret_cast<const void*>(preprocess_backward_kernel<true, false>))
-                             : (invd ? reinterpret_cast<const void*>(preprocess_backward_kernel<false, true>) : reinterpret_cast<const void*>(preprocess_backward_kernel<false, false>));
+    using Kernel = void (*)(const BwdPreArgs);
+    static const Kernel kernels[8] = {
+        preprocess_backward_kernel<false, false, false>, preprocess_backward_kernel<false, false, true>,
+        preprocess_backward_kernel<false, true, false>,  preprocess_backward_kernel<false, true, true>,
+        preprocess_backward_kernel<true, false, false>,  preprocess_backward_kernel<true, false, true>,
+        preprocess_backward_kernel<true, true, false>,   preprocess_backward_kernel<true, true, true>};
+    const Kernel kernel = kernels[(cam ? 4 : 0) + (invd ? 2 : 0) + (split ? 1 : 0)];
     const size_t lds = (a.shs != nullptr && a.M > 0) ? (size_t)256 * (3 * a.M + 1) * sizeof(float) : 0;
     if (lds > 64 * 1024) { // above the default dynamic-LDS limit (M > 21: no SH degree the reference knows)
-        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     const int n_blocks = (f.P + 255) / 256;
@@ -648,14 +680,12 @@ hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState&
         if (e != hipSuccess) return e;
     }
     if (cam) {
-        if (invd) hipLaunchKernelGGL((preprocess_backward_kernel<true, true>), dim3(b1 - b0), dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((preprocess_backward_kernel<true, false>), dim3(b1 - b0), dim3(256), lds, st, a);
+        hipLaunchKernelGGL(kernel, dim3(b1 - b0), dim3(256), lds, st, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         return launch_camera_grad_finalize(f.P, bw.cam, st);
     }
-    if (invd) hipLaunchKernelGGL((preprocess_backward_kernel<false, true>), dim3(b1 - b0), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((preprocess_backward_kernel<false, false>), dim3(b1 - b0), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(kernel, dim3(b1 - b0), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

@@ -534,4 +534,101 @@ __device__ __forceinline__ void stage_rows_out(float* __restrict__ dst, const fl
     }
 }
 
+// ---- Split SH rows (stp_set_forward_split_sh / stp_set_backward_split_sh): an LDS row of 3M + 1 words is fed from TWO global spans, columns
+// 0..2 from `dc` (3 floats per row) and columns 3..3M-1 from `rest` (3(M-1) floats per row).  A 16-byte piece of either span can straddle two
+// rows (3 and 45 are no multiples of 4), so every element is placed by its own row and column.
+// The generic form, any row length and row count: `rows` rows of `len` floats at src <-> columns [col0, col0 + len) of LDS rows of `stride`
+// words.  vec: src / dst is 16-byte aligned -- whole 16-byte pieces move as one access, the total's last 1..3 floats one at a time; else all
+// of it one float at a time (no unaligned vector access).  len == 0 moves nothing.
+template <int BLOCK>
+__device__ __forceinline__ void stage_span_in(const float* __restrict__ src, float* __restrict__ s_rows, int tid, int rows, int len, int col0, int stride, bool vec)
+{
+    const int total = rows * len, nvec = vec ? (total & ~3) : 0;
+    for (int f = 4 * tid; f < nvec; f += 4 * BLOCK) {
+        const float4 v = *reinterpret_cast<const float4*>(src + f);
+        const float e[4] = {v.x, v.y, v.z, v.w};
+        int r = f / len, j = f - r * len;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            s_rows[r * stride + col0 + j] = e[i];
+            if (++j == len) { j = 0; r++; }
+        }
+    }
+    for (int f = nvec + tid; f < total; f += BLOCK) {
+        const int r = f / len, j = f - r * len;
+        s_rows[r * stride + col0 + j] = src[f];
+    }
+}
+template <int BLOCK>
+__device__ __forceinline__ void stage_span_out(float* __restrict__ dst, const float* __restrict__ s_rows, int tid, int rows, int len, int col0, int stride, bool vec)
+{
+    const int total = rows * len, nvec = vec ? (total & ~3) : 0;
+    for (int f = 4 * tid; f < nvec; f += 4 * BLOCK) {
+        float e[4];
+        int r = f / len, j = f - r * len;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            e[i] = s_rows[r * stride + col0 + j];
+            if (++j == len) { j = 0; r++; }
+        }
+        *reinterpret_cast<float4*>(dst + f) = make_float4(e[0], e[1], e[2], e[3]);
+    }
+    for (int f = nvec + tid; f < total; f += BLOCK) {
+        const int r = f / len, j = f - r * len;
+        dst[f] = s_rows[r * stride + col0 + j];
+    }
+}
+// The unrolled form for M = 16 on a FULL block of 256 rows with 16-byte aligned spans, every load in flight before the first LDS write (see
+// stage_rows_load).  rest: 256 x 45 floats = 2880 pieces = 11 per thread + 64; dc: 256 x 3 floats = 192 pieces.  The twelfth piece of a
+// thread is therefore rest piece 2816 + tid in wave 0 and dc piece tid - 64 in waves 1..3: twelve loads per thread, as the concatenated row has.
+constexpr int SPLIT48_REST = 45, SPLIT48_STRIDE = 49, SPLIT48_FULL = 11;
+__device__ __forceinline__ void split48_lds(int piece, bool is_dc, int (&w)[4]) // LDS words of the four elements of a 16-byte piece
+{
+    const int len = is_dc ? 3 : SPLIT48_REST, e = 4 * piece; // (one division per piece; the elements behind the first step along, wrapping into the next row)
+    const int r = is_dc ? e / 3 : e / SPLIT48_REST;
+    int j = e - len * r, row = r * SPLIT48_STRIDE + (is_dc ? 0 : 3);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        w[i] = row + j;
+        if (++j == len) { j = 0; row += SPLIT48_STRIDE; }
+    }
+}
+__device__ __forceinline__ void split48_load(const float* __restrict__ dc, const float* __restrict__ rest, int tid, float4 (&v)[12])
+{
+#pragma unroll
+    for (int k = 0; k < SPLIT48_FULL; k++) v[k] = reinterpret_cast<const float4*>(rest)[tid + k * 256];
+    v[SPLIT48_FULL] = tid < 64 ? reinterpret_cast<const float4*>(rest)[tid + SPLIT48_FULL * 256] : reinterpret_cast<const float4*>(dc)[tid - 64];
+}
+__device__ __forceinline__ void split48_store(float* __restrict__ s_rows, int tid, const float4 (&v)[12])
+{
+#pragma unroll
+    for (int k = 0; k <= SPLIT48_FULL; k++) {
+        const bool is_dc = k == SPLIT48_FULL && tid >= 64;
+        const int piece = is_dc ? tid - 64 : tid + k * 256;
+        const float e[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+        int w[4];
+        split48_lds(piece, is_dc, w);
+#pragma unroll
+        for (int i = 0; i < 4; i++) s_rows[w[i]] = e[i];
+    }
+}
+__device__ __forceinline__ void split48_out(float* __restrict__ dL_ddc, float* __restrict__ dL_drest, const float* __restrict__ s_rows, int tid)
+{
+#pragma unroll
+    for (int k = 0; k <= SPLIT48_FULL; k++) {
+        const bool is_dc = k == SPLIT48_FULL && tid >= 64;
+        const int piece = is_dc ? tid - 64 : tid + k * 256;
+        float e[4];
+        int w[4];
+        split48_lds(piece, is_dc, w);
+#pragma unroll
+        for (int i = 0; i < 4; i++) e[i] = s_rows[w[i]];
+        reinterpret_cast<float4*>(is_dc ? dL_ddc : dL_drest)[piece] = make_float4(e[0], e[1], e[2], e[3]);
+    }
+}
+__device__ __forceinline__ bool aligned16(const void* a, const void* b) // (a null pointer counts as aligned: a span nobody moves)
+{
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
+
 } // namespace stp

@@ -423,7 +423,9 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
         return fail(STP_ERR_INVALID_ARGUMENT, "alpha output / per-pixel background (stp_set_forward_background) are not available with the debug depth visualisation: its image is not C + T * background");
     if (req.out_invdepth && settings->debug_visualization == STP_DEBUG_DEPTH)
         return fail(STP_ERR_INVALID_ARGUMENT, "the inverse-depth output (stp_set_forward_invdepth) is not available with the debug depth visualisation");
-    if (!colors_precomp && !shs) return fail(STP_ERR_INVALID_ARGUMENT, "neither SHs nor precomputed colours given");
+    const float* const sh_dc = colors_precomp ? nullptr : req.sh_dc; // stp_set_forward_split_sh (precomputed colours win)
+    if (sh_dc && M > 1 && !shs) return fail(STP_ERR_INVALID_ARGUMENT, "split SH (stp_set_forward_split_sh): M > 1 needs the rest of the coefficients in shs");
+    if (!colors_precomp && !shs && !sh_dc) return fail(STP_ERR_INVALID_ARGUMENT, "neither SHs nor precomputed colours given");
     if (!cov3D_precomp && !(scales && rotations)) return fail(STP_ERR_INVALID_ARGUMENT, "neither scale/rotation nor precomputed covariance given");
     const bool with_inv = requires_depth_along_ray(*settings);
     if (with_inv && !(scales && rotations)) return fail(STP_ERR_NEEDS_SCALE_ROTATION, "sorted modes need scales and rotations");
@@ -432,6 +434,7 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
     fill_frame(f, P, D, M, background, width, height, *settings, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
                rotations, cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered);
     f.out_invdepth = req.out_invdepth;
+    f.sh_dc = sh_dc;
     f.bg_image = fbg.bg_image; f.out_alpha = fbg.out_alpha; // (every render launch of the call: both halves of a split forward, a redone run-ahead frame)
     if (int rc = c.carve_geometry_and_image(geometry_alloc, geometry_user, image_alloc, image_user, with_inv)) return rc;
 

@@ -178,6 +178,7 @@ struct FrameParams {
     const float* bg_image = nullptr; // forward, stp_set_forward_background: per-pixel background (3 x H x W) in the place of `background`
     float* out_alpha = nullptr;      // ... and where the render kernels also write alpha = 1 - final_T (H x W)
     float* out_invdepth = nullptr;   // forward, stp_set_forward_invdepth: the render kernels' INVD variants also write sum(alpha T / z) (H x W); preprocess keeps 1 / z
+    const float* sh_dc = nullptr;    // stp_set_forward_split_sh / stp_set_backward_split_sh: the (P, 3) first SH coefficient; `shs` is then the (P, M-1, 3) rest (nullptr allowed for M == 1)
     int wild_cov; // forward, after the status read-back: some visible Gaussian has a Sigma^-1 entry >= 1e36 or not finite (depth keys then take the reciprocal with its domain check)
 };
 
@@ -219,6 +220,7 @@ struct BackwardParams {
     float* dL_dsh;
     float* dL_dscale;
     float* dL_drot;
+    float* dL_ddc = nullptr; // stp_set_backward_split_sh (with FrameParams::sh_dc): P x 3, the first coefficient's gradient; dL_dsh is then P x (M-1) x 3
 };
 
 // ---- argument checks and frame description shared by the forward and the backward (stp_api.hip) ----
@@ -231,7 +233,7 @@ void fill_frame(FrameParams& f, int P, int D, int M, const float* background, in
 // ---- the one-shot per-thread requests (stp_api.hip: the stp_set_* setters, and the rules by which a call takes them) ----
 struct ForwardSplit { int row = 0; hipEvent_t event = nullptr; bool armed = false; };      // stp_set_forward_split
 struct ForwardBackground { const float* bg_image = nullptr; float* out_alpha = nullptr; }; // stp_set_forward_background
-struct ForwardRequests { ForwardSplit split; ForwardBackground background; float* out_invdepth = nullptr; /* stp_set_forward_invdepth */ };
+struct ForwardRequests { ForwardSplit split; ForwardBackground background; float* out_invdepth = nullptr; /* stp_set_forward_invdepth */ const float* sh_dc = nullptr; /* stp_set_forward_split_sh */ };
 ForwardRequests take_forward_requests();
 
 // ---- launchers (one per stage; each returns hipSuccess or the launch error) ----

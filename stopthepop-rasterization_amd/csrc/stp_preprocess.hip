@@ -378,6 +378,7 @@ struct ShArgs {
     const int* radii;
     uint8_t* clamped;
     float* rgb;
+    const float* dc; // SPLIT only: the (P, 3) first coefficient; `shs` is then the (P, M-1, 3) rest (not read for M == 1)
 };
 
 #ifndef STP_SH_BLOCK
@@ -385,6 +386,9 @@ struct ShArgs {
 #endif
 constexpr int SH_BLOCK = STP_SH_BLOCK; // Gaussians (= threads) per workgroup: its LDS staging area is SH_BLOCK x (3M + 1) words
 
+// SPLIT (stp_set_forward_split_sh): the same LDS rows from two global spans, columns 0..2 from a.dc and 3..3M-1 from a.shs (stp_device.h: split SH
+// rows); everything behind the staging is the SPLIT = false kernel's.
+template <bool SPLIT>
 __global__ void __launch_bounds__(SH_BLOCK) sh_color_kernel(const ShArgs a)
 {
     extern __shared__ float s_rows[]; // [SH_BLOCK][3M + 1]
@@ -396,16 +400,30 @@ __global__ void __launch_bounds__(SH_BLOCK) sh_color_kernel(const ShArgs a)
     // Order of the loads matters: the coefficient rows FIRST (twelve 16-byte loads per thread in flight), the Gaussian's
     // radius and mean behind them -- one memory latency per workgroup instead of three dependent ones.  (No early exit on
     // "nobody visible" either: it would put the radius in front again.)
-    const float* __restrict__ src = a.shs + (size_t)base * row_len;
+    const float* __restrict__ src = a.shs + (size_t)base * (SPLIT ? row_len - 3 : row_len);
+    const float* __restrict__ src_dc = SPLIT ? a.dc + (size_t)base * 3 : nullptr;
     const int total = rows * row_len;
-    const bool fast = row_len == 48 && rows == SH_BLOCK; // SH degree 3 (M = 16), full block
+    const bool vec = SPLIT ? aligned16(a.dc, row_len > 3 ? a.shs : nullptr) : true; // (SPLIT: views such as rest[1:] are 4-byte aligned only)
+    const bool fast = row_len == 48 && rows == SH_BLOCK && vec; // SH degree 3 (M = 16), full block
     float4 v48[12];
-    if (fast) stage_rows_load<SH_BLOCK, 48>(src, tid, v48);
+    if constexpr (SPLIT) {
+        static_assert(!SPLIT || SH_BLOCK == 256, "split48_* are written for 256 rows");
+        if (fast) split48_load(src_dc, src, tid, v48);
+    } else {
+        if (fast) stage_rows_load<SH_BLOCK, 48>(src, tid, v48);
+    }
     const int ic = min(idx, a.P - 1); // (clamped, unconditional loads: no branch between them, both in flight together)
     const int radius_ic = a.radii[ic];
     const float3 mean = make_float3(a.means3D[3 * (size_t)ic], a.means3D[3 * (size_t)ic + 1], a.means3D[3 * (size_t)ic + 2]);
     const int my_radius = idx < a.P ? radius_ic : 0;
-    if (fast) {
+    if constexpr (SPLIT) {
+        if (fast) {
+            split48_store(s_rows, tid, v48);
+        } else {
+            stage_span_in<SH_BLOCK>(src_dc, s_rows, tid, rows, 3, 0, row_stride, vec);
+            stage_span_in<SH_BLOCK>(src, s_rows, tid, rows, row_len - 3, 3, row_stride, vec);
+        }
+    } else if (fast) {
         stage_rows_store<SH_BLOCK, 48>(s_rows, tid, v48);
     } else if ((row_len & 3) == 0) {
         for (int f = 4 * tid; f < total; f += 4 * SH_BLOCK) {
@@ -700,15 +718,19 @@ hipError_t launch_duplicate(const FrameParams& f, const GeometryState& g, const 
 
 hipError_t launch_sh_color(const FrameParams& f, const GeometryState& g, const int* radii, hipStream_t st)
 {
-    if (f.colors_precomp != nullptr || f.shs == nullptr || f.M <= 0) return hipSuccess; // reference forward.cu:200: precomputed colours win
+    const bool split = f.sh_dc != nullptr; // stp_set_forward_split_sh: f.shs is the rest (nullptr allowed for M == 1)
+    if (f.colors_precomp != nullptr || (f.shs == nullptr && !split) || f.M <= 0) return hipSuccess; // reference forward.cu:200: precomputed colours win
     ShArgs a;
     a.P = f.P; a.D = f.D; a.M = f.M; a.means3D = f.means3D; a.shs = f.shs; a.cam = f.cam_pos; a.radii = radii; a.clamped = g.clamped; a.rgb = g.rgb;
+    a.dc = f.sh_dc;
+    const void* kernel = split ? reinterpret_cast<const void*>(sh_color_kernel<true>) : reinterpret_cast<const void*>(sh_color_kernel<false>);
     const size_t lds = (size_t)SH_BLOCK * (3 * a.M + 1) * sizeof(float);
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sh_color_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(sh_color_kernel, dim3((f.P + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), lds, st, a);
+    if (split) hipLaunchKernelGGL(sh_color_kernel<true>, dim3((f.P + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), lds, st, a);
+    else hipLaunchKernelGGL(sh_color_kernel<false>, dim3((f.P + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), lds, st, a);
     return hipGetLastError();
 }
 

@@ -49,6 +49,8 @@ _OPTIONAL_SYMBOLS = {
     "stp_set_backward_background": ([ctypes.c_void_p] * 3, None),
     "stp_set_forward_invdepth": ([ctypes.c_void_p], None),
     "stp_set_backward_invdepth": ([ctypes.c_void_p] * 2, None),
+    "stp_set_forward_split_sh": ([ctypes.c_void_p], None),
+    "stp_set_backward_split_sh": ([ctypes.c_void_p] * 2, None),
     "stp_sparse_adam": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
                         ctypes.c_int),
     "stp_mcmc_relocation": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3, ctypes.c_int),
@@ -68,6 +70,7 @@ _SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blen
                    "stp_set_forward_background": "the alpha output and per-pixel background",
                    "stp_set_backward_background": "the alpha output and per-pixel background",
                    "stp_set_forward_invdepth": "the inverse-depth output", "stp_set_backward_invdepth": "the inverse-depth output",
+                   "stp_set_forward_split_sh": "split SH inputs", "stp_set_backward_split_sh": "split SH inputs",
                    "stp_sparse_adam": "the sparse Adam step",
                    "stp_mcmc_relocation": "the 3DGS-MCMC kernels", "stp_mcmc_add_noise": "the 3DGS-MCMC kernels",
                    "stp_densify_stats": "the densification kernels", "stp_densify_plan": "the densification kernels",
@@ -359,8 +362,8 @@ def _records_log(d: dict) -> bool:
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, inv_viewprojmatrix, tan_fovx, tan_fovy, image_height, image_width,
-                        sh, degree, campos, prefiltered, settings_dict, render_depth, debug, alpha=False, invdepth=False
-                        ) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                        sh, degree, campos, prefiltered, settings_dict, render_depth, debug, alpha=False, invdepth=False,
+                        dc=None) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """== RasterizeGaussiansCUDA (reference rasterize_points.cu:43-138).
     Returns (num_rendered, out_color (3,H,W), radii (P,) int32, geomBuffer, binningBuffer, imgBuffer).
 
@@ -370,7 +373,11 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 
     invdepth=True (extension, include/stp_raster.h: stp_set_forward_invdepth): one more tensor, LAST in the tuple (behind alpha's): the
     inverse-depth image sum_i alpha_i T_i / z_i over the pairs the colour blends, z_i the view-space z of Gaussian i's centre; (1,H,W)
-    float32, no background term (zeros where nothing blended, and for P == 0).  Not available with render_depth."""
+    float32, no background term (zeros where nothing blended, and for P == 0).  Not available with render_depth.
+
+    dc=(P,1,3) or (P,3) tensor (keyword; extension, include/stp_raster.h: stp_set_forward_split_sh): the first SH coefficient as a tensor of
+    its own (a trainer's _features_dc); `sh` is then the rest, (P,M-1,3) (_features_rest; empty for a degree-0 model).  No concatenated copy
+    is made, and every output equals that of the call on torch.cat((dc, rest), 1) bit for bit.  Ignored with precomputed colours."""
     if means3D.dim() != 2 or means3D.size(1) != 3:   # (the reference's first check, rasterize_points.cu:69-71)
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if alpha or _per_pixel_background(background, image_height, image_width):
@@ -379,10 +386,12 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
         _require("stp_set_forward_invdepth")
         if render_depth:
             raise RuntimeError("the inverse-depth output (_invdepth) is not available with render_depth (the debug depth visualisation)")
+    if dc is not None:
+        _require("stp_set_forward_split_sh")
     out = (_host or _native()).rasterize_gaussians(
         background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         inv_viewprojmatrix, tan_fovx, tan_fovy, int(image_height), int(image_width), sh, int(degree), campos, bool(prefiltered),
-        settings_dict, bool(render_depth), bool(debug), _records_log(settings_dict), bool(alpha), bool(invdepth))
+        settings_dict, bool(render_depth), bool(debug), _records_log(settings_dict), bool(alpha), bool(invdepth), dc)
     return tuple(out[:6]) + ((out[6],) if alpha else ()) + ((out[7],) if invdepth else ())
 
 
@@ -396,7 +405,7 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
                                  pixel_colors, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                                  imageBuffer, settings_dict, debug, phases=3, partial=None, chunk=None, outputs=None,
                                  camera_grads=False, absgrad=False, blend_stats=False, dL_dalpha=None, bg_grad=False,
-                                 dL_dinvdepth=None, invdepth=None):
+                                 dL_dinvdepth=None, invdepth=None, dc=None):
     """== RasterizeGaussiansBackwardCUDA (reference rasterize_points.cu:140-232).
     Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
 
@@ -422,6 +431,11 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
     gradient, and through 1 / z to dL_dmeans3D (and dL_dviewmatrix).  dL_dcolors / dL_dsh get nothing from it.  No extra result.  Needs both
     halves in one call and the padded records, like absgrad.
 
+    dc=(P,1,3) or (P,3) tensor (keyword; extension, include/stp_raster.h: stp_set_backward_split_sh): the forward's split SH input; `sh` is the
+    (P,M-1,3) rest.  dL_dsh, in its usual slot, is then (P,M-1,3), and one more tensor, dL_ddc (P,3), is LAST in the tuple, behind every
+    extra above: (the eight) (the camera's three) (absgrad) (blend_stats) (dL_dbackground) (dL_ddc).  Both equal the two slices of the
+    concatenated call's dL_dsh bit for bit.  Per-Gaussian half (phases bit 1); works chunked, `outputs` then carries nine tensors.
+
     Extension for tile-row sharding (not in the reference): phases=1 runs only the render half and
     returns its per-Gaussian partial sums as the library's (P,16) gradient records (stp_raster.h);
     phases=2 takes the records (after the caller's all-reduce) as `partial` and runs the preprocess half.
@@ -441,13 +455,15 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
         _require("stp_set_backward_blend_stats")
     if dL_dinvdepth is not None:
         _require("stp_set_backward_invdepth")
+    if dc is not None:
+        _require("stp_set_backward_split_sh")
     if dL_dalpha is not None or bg_grad or _per_pixel_background(background, dL_dout_color.shape[-2], dL_dout_color.shape[-1]):
         _require("stp_set_backward_background")
     out = (_host or _native()).rasterize_gaussians_backward(
         background, means3D, radii, opacities, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         inv_viewprojmatrix, tan_fovx, tan_fovy, pixel_colors, dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer,
         imageBuffer, settings_dict, bool(debug), _records_log(settings_dict), int(phases), partial, None if outputs is None else list(outputs),
-        bool(camera_grads), bool(absgrad), bool(blend_stats), dL_dalpha, bool(bg_grad), dL_dinvdepth, invdepth)
+        bool(camera_grads), bool(absgrad), bool(blend_stats), dL_dalpha, bool(bg_grad), dL_dinvdepth, invdepth, dc)
     return out[0] if (int(phases) & 3) == 1 and not bg_grad else tuple(out)
 
 

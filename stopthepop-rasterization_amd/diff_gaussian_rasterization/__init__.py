@@ -40,26 +40,28 @@ def cpu_deep_copy_tuple(input_tuple):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
+                        raster_settings, dc=None):
+    """dc (extension, include/stp_raster.h: stp_set_forward_split_sh): the first SH coefficient, (P, 1, 3) or (P, 3), as a tensor of its own;
+    `sh` is then the rest, (P, M-1, 3).  It rides behind raster_settings in every Function, so that the inputs in front keep their places."""
     rs = raster_settings
     if torch.is_grad_enabled() and isinstance(rs.bg, torch.Tensor) and rs.bg.requires_grad:
         # a learnable background: bg -- and the camera tensors, which get their gradients here too where they require them -- become explicit
         # inputs of a third Function
         return _RasterizeGaussiansBackground.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                                   rs.bg, rs.viewmatrix, rs.projmatrix, rs.campos, raster_settings)
+                                                   rs.bg, rs.viewmatrix, rs.projmatrix, rs.campos, raster_settings, dc)
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (rs.viewmatrix, rs.projmatrix, rs.campos)):
         # camera gradients (pose refinement): the camera tensors become explicit inputs of a second Function
         return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                               rs.viewmatrix, rs.projmatrix, rs.campos, raster_settings)
+                                               rs.viewmatrix, rs.projmatrix, rs.campos, raster_settings, dc)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings)
+                                     cov3Ds_precomp, raster_settings, dc)
 
 
 def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos, rs,
-                  save_camera=False, bg=None):
+                  save_camera=False, bg=None, dc=None):
     """The forward the autograd Functions share (the camera tensors are rs's own, or the camera Function's explicit inputs, which
     save_camera=True saves for the backward behind the twelve tensors every Function saves; bg: the background Function's explicit input,
-    saved behind them)."""
+    saved behind them; dc: the split SH input, saved behind those -- sh is then the rest --; the inverse-depth output stays LAST)."""
     sdict = rs.settings.to_dict()
     save_bg = bg is not None
     if bg is None:
@@ -120,8 +122,13 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
     kw = {"alpha": True} if ctx.alpha else {}   # (the alpha tensor comes last)
     if ctx.invdepth:
         kw["invdepth"] = True                   # (... and the inverse depth behind it)
+    # split SH (extension; include/stp_raster.h: stp_set_forward_split_sh): precomputed colours win, as in the library
+    ctx.dc_index = None
+    if dc is not None and colors_precomp.numel() == 0:
+        kw["dc"] = dc
+        ctx.dc_index = 12 + (3 if save_camera else 0) + (1 if save_bg else 0)
     if rs.debug:
-        cpu_args = cpu_deep_copy_tuple(args)  # snapshot before anything can corrupt them
+        cpu_args = cpu_deep_copy_tuple(args + ((dc,) if "dc" in kw else ()))  # snapshot before anything can corrupt them (dc: behind the 22)
         try:
             num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, *extra = _C.rasterize_gaussians(*args, **kw)
         except Exception as ex:
@@ -139,7 +146,8 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
     ctx.bin_generation = _C.scratch_generation(binningBuffer)
     ctx.save_for_backward(colors_precomp, means3D, opacities, scales, rotations, cov3Ds_precomp, radii, sh, color,
                           geomBuffer, binningBuffer, imgBuffer, *((viewmatrix, projmatrix, campos) if save_camera else ()),
-                          *((bg,) if save_bg else ()), *((extra[-1],) if ctx.invdepth else ()))   # (the inverse-depth output: LAST)
+                          *((bg,) if save_bg else ()), *((dc,) if ctx.dc_index is not None else ()),
+                          *((extra[-1],) if ctx.invdepth else ()))   # (the inverse-depth output: LAST)
     # radii is an integer output: without these two lines autograd materialises a (P,) zero "gradient" for it in
     # every backward (a 4 MB fill kernel per step at 1 M Gaussians)
     ctx.mark_non_differentiable(radii)
@@ -160,7 +168,8 @@ def _grad_invdepth(ctx, rest):
 
 def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_grads=False, grad_alpha=None, bg=None, grad_invdepth=None):
     """The backward the autograd Functions share: the eight Gaussian gradients of _C.rasterize_gaussians_backward (+ the three camera
-    gradients with camera_grads=True, + dL/dbg last with bg, the background Function's saved input)."""
+    gradients with camera_grads=True, + dL/dbg last with bg, the background Function's saved input).  With a split SH input the sixth
+    gradient is the rest's, (P, M-1, 3), and ctx.grad_dc receives dc's in dc's own shape (None otherwise)."""
     num_rendered = ctx.num_rendered
     rs = ctx.raster_settings
     (colors_precomp, means3D, opacities, scales, rotations, cov3Ds_precomp, radii, sh, color, geomBuffer,
@@ -189,8 +198,11 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
     if grad_invdepth is not None:   # (None: the inverse depth took no part in the loss -- no pointer is set, the backward is what it is without)
         kw["dL_dinvdepth"] = grad_invdepth
         kw["invdepth"] = ctx.saved_tensors[-1]
+    dc = ctx.saved_tensors[ctx.dc_index] if ctx.dc_index is not None else None
+    if dc is not None:
+        kw["dc"] = dc
     if rs.debug:
-        cpu_args = cpu_deep_copy_tuple(args)
+        cpu_args = cpu_deep_copy_tuple(args + ((dc,) if dc is not None else ()))
         try:
             out = _C.rasterize_gaussians_backward(*args, **kw)
         except Exception as ex:
@@ -202,7 +214,12 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
     _C.release_scratch(imgBuffer); _C.release_scratch(binningBuffer)  # the blend log goes back to the library's free list
     if ctx.log_lease is not None:
         ctx.log_lease.release()
-    # (the extra tensors come last, the statistics behind absgrad's, dL/dbg behind both; assigned, not accumulated: the trainer keeps its own statistic)
+    # (the extra tensors come last, the statistics behind absgrad's, dL/dbg behind both, dL/ddc behind all; assigned, not accumulated: the
+    # trainer keeps its own statistic)
+    ctx.grad_dc = None
+    if dc is not None:
+        ctx.grad_dc = out[-1].view(dc.shape)   # ((P, 3) from the library: a fresh contiguous tensor in the input's own shape)
+        out = out[:-1]
     grad_bg = None
     if bg_grad:
         grad_bg = out[-1]
@@ -220,13 +237,23 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
     return out + (grad_bg,) if bg_grad else out
 
 
+def _split_grad_sh(ctx, grad_sh):
+    """The rest's gradient of a split SH backward: None where the rest does not require grad."""
+    return grad_sh if ctx.needs_input_grad[2] else None
+
+
+def _split_grad_dc(ctx):
+    """dc's gradient (dc is the LAST input of every Function): None where dc is absent or does not require grad."""
+    return ctx.grad_dc if ctx.dc_index is not None and ctx.needs_input_grad[-1] else None
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
+                raster_settings, dc=None):
         rs = raster_settings
         return _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.viewmatrix,
-                             rs.projmatrix, rs.campos, rs)
+                             rs.projmatrix, rs.campos, rs, dc=dc)
 
     @staticmethod
     def backward(ctx, grad_out_color, _, *rest):   # (rest: the alpha output's gradient, with settings._alpha)
@@ -235,8 +262,12 @@ class _RasterizeGaussians(torch.autograd.Function):
          grad_rotations) = _backward_body(ctx, grad_out_color, rs.viewmatrix, rs.projmatrix, rs.campos, grad_alpha=_grad_alpha(ctx, rest),
                                           grad_invdepth=_grad_invdepth(ctx, rest))
         # one gradient per forward input, in forward's order
-        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, None)
+        if ctx.dc_index is None:
+            return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
+                    grad_cov3Ds_precomp, None, None)
+        # split SH: None for a frozen dc or rest
+        return (grad_means3D, grad_means2D, _split_grad_sh(ctx, grad_sh), grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
+                grad_cov3Ds_precomp, None, _split_grad_dc(ctx))
 
 
 class _RasterizeGaussiansCamera(torch.autograd.Function):
@@ -246,11 +277,11 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix, campos,
-                raster_settings):
+                raster_settings, dc=None):
         # (needs_input_grad counts the camera inputs: a frame where only the camera requires grad records the blend log too; the
         # camera tensors are saved like the Gaussians: an in-place change before the backward raises instead of giving wrong gradients)
         return _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix,
-                             campos, raster_settings, save_camera=True)
+                             campos, raster_settings, save_camera=True, dc=dc)
 
     @staticmethod
     def backward(ctx, grad_out_color, _, *rest):
@@ -262,7 +293,7 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
         grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                  grad_cov3Ds_precomp, grad_view, grad_proj, grad_campos)
         # None for every input that does not require grad (frozen Gaussians: the camera's gradients only)
-        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad)) + (None,)
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad)) + (None, _split_grad_dc(ctx))
 
 
 class _RasterizeGaussiansBackground(torch.autograd.Function):
@@ -272,9 +303,9 @@ class _RasterizeGaussiansBackground(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, bg, viewmatrix, projmatrix, campos,
-                raster_settings):
+                raster_settings, dc=None):
         return _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix,
-                             campos, raster_settings, save_camera=True, bg=bg)
+                             campos, raster_settings, save_camera=True, bg=bg, dc=dc)
 
     @staticmethod
     def backward(ctx, grad_out_color, _, *rest):
@@ -286,7 +317,7 @@ class _RasterizeGaussiansBackground(torch.autograd.Function):
         grad_view, grad_proj, grad_campos = out[8:11] if camera_grads else (None, None, None)
         grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                  grad_cov3Ds_precomp, out[-1], grad_view, grad_proj, grad_campos)
-        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad)) + (None,)
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad)) + (None, _split_grad_dc(ctx))
 
 
 class SortMode(IntEnum):
@@ -414,6 +445,25 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
+def _check_split_sh(dc, shs, means3D):
+    """GaussianRasterizer.forward's checks of a split SH input, before any device work: RuntimeError naming the argument."""
+    if not isinstance(dc, torch.Tensor):
+        raise RuntimeError(f"dc must be a tensor, got {type(dc).__name__}")
+    P = means3D.shape[0]
+    if not ((dc.dim() == 3 and dc.shape[1] == 1 and dc.shape[2] == 3) or (dc.dim() == 2 and dc.shape[1] == 3)):
+        raise RuntimeError(f"dc must have dimensions (num_points, 1, 3) or (num_points, 3), got {tuple(dc.shape)}")
+    if dc.shape[0] != P:
+        raise RuntimeError(f"dc must have one row per Gaussian: {dc.shape[0]} rows for {P} points")
+    if dc.dtype != torch.float32:
+        raise RuntimeError(f"dc must be a float32 tensor, got {dc.dtype}")
+    if dc.device != means3D.device:
+        raise RuntimeError(f"dc must be on the device of means3D ({means3D.device}), got {dc.device}")
+    if shs is not None and shs.numel() != 0:
+        if shs.dim() != 3 or shs.shape[0] != P or shs.shape[2] != 3 or shs.dtype != torch.float32 or shs.device != means3D.device:
+            raise RuntimeError(f"with dc, shs is the rest of the coefficients: a float32 (num_points, M - 1, 3) tensor on the device of "
+                               f"means3D, got {tuple(shs.shape)} {shs.dtype} on {shs.device}")
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings):
         super().__init__()
@@ -426,16 +476,22 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, dc=None):
+        """dc (extension; include/stp_raster.h: stp_set_forward_split_sh): a trainer's _features_dc, (P, 1, 3) or (P, 3), with shs = its
+        _features_rest, (P, M-1, 3) (None or (P, 0, 3) for a degree-0 model) -- no torch.cat going in, and dc.grad / shs.grad come back as
+        two fresh contiguous tensors in the inputs' shapes.  Results equal those of shs = torch.cat((dc, rest), dim=1)."""
         rs = self.raster_settings
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
+        have_sh = shs is not None or dc is not None
+        if (not have_sh and colors_precomp is None) or (have_sh and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+        if dc is not None:
+            _check_split_sh(dc, shs, means3D)
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         empty = lambda t: torch.Tensor([]) if t is None else t  # absent optional input == empty CPU tensor
         return rasterize_gaussians(means3D, means2D, empty(shs), empty(colors_precomp), opacities, empty(scales),
-                                   empty(rotations), empty(cov3D_precomp), rs)
+                                   empty(rotations), empty(cov3D_precomp), rs, dc)
 
 
 class SparseGaussianAdam(torch.optim.Adam):

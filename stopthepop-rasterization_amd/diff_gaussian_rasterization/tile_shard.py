@@ -397,7 +397,10 @@ class TileRowShardedRasterizer(torch.nn.Module):
         self.shard = (dist, rank, world, self.parts, to_all)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, dc=None):
+        if dc is not None:   # (GaussianRasterizer.forward's split SH input: a shard cannot be tested on one GPU, so it is left out on purpose)
+            raise RuntimeError("dc= (split SH inputs) is not wired through the tile-row shard: pass torch.cat((dc, rest), dim=1) as shs, or "
+                               "render on one GPU")
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
