@@ -135,7 +135,10 @@ void stp_set_forward_split(int tile_row, void* event);
        [14] dL/d(1/z) (only with the inverse-depth request)   [15] unused
    (one atomic instruction / one L2 request per flush instead of nine into four arrays: 9x the flush rate on
    MI355X, tools/global_atomic_bench.hip); the per-Gaussian half reads the record and writes dL_dmean2D,
-   dL_dopacity and dL_dcolor in the reference's layouts along with the remaining gradients. */
+   dL_dopacity and dL_dcolor in the reference's layouts along with the remaining gradients.
+   OPTIONAL OUTPUTS: dL_dcolor and dL_dcov3D may be NULL -- "not wanted": the gradients of colors_precomp and cov3D_precomp, which a caller
+   that renders from SH coefficients and scale / rotation has no receiver for.  The per-Gaussian half then skips those stores (24 + 12 bytes
+   per Gaussian); every other output is what it is with them (dL_dscale / dL_drot are formed from dL_dcov3D in registers either way). */
 int stp_backward(int P, int D, int M, int R,
                  const float* background, int width, int height,
                  const StpSettings* settings,
@@ -322,6 +325,25 @@ void stp_set_backward_invdepth(const float* invdepth /* the forward's, H x W */,
 void stp_set_forward_split_sh(const float* dc /* P x 3 */);
 void stp_set_backward_split_sh(const float* dc /* P x 3 */, float* dL_ddc /* P x 3 */);
 
+/* Extension: the SH stash.  The per-Gaussian half of the backward needs the SH coefficients of a Gaussian (192 B at degree 3) for nine
+   numbers only: the derivative of each colour channel with respect to the unit view direction.  They depend on the coefficients, the mean
+   and the camera position -- all of which the forward's SH -> RGB kernel holds -- and on nothing the backward adds.
+   stp_set_forward_sh_stash(1) -- the NEXT stp_forward of the calling thread, if it evaluates SH colours (shs or a split dc given, M > 0, no
+       colors_precomp), also writes those nine floats per visible Gaussian into one more sub-array at the END of its geometry buffer -- nine
+       planes of P floats, "sh_stash" of stp_geometry_layout, plane 3 c + {0, 1, 2} = d(channel c) / d(direction x, y, z) -- and asks
+       geometry_alloc for stp_geometry_buffer_size_stash(P, settings) bytes: 36 P more (rounded up to the carve's alignment); no other
+       offset moves.  A forward that does not ask, or has no SH colours to evaluate, writes and allocates nothing new and runs the kernels it
+       always ran.  Consumed by the next stp_forward of the thread whatever its outcome; 0 clears a pending request.
+   The backward needs no request: the buffer says whether it carries a stash (three words of its first 256 bytes: a magic, P, ~P, written by
+   the stashing kernel; the library also remembers it per buffer address, like the binning layout, and stp_forget_buffer forgets it), and a
+   per-Gaussian half handed one reads it in the place of the SH rows -- 36 B for 192 B per visible Gaussian.  A buffer without one (no
+   request, a forward of an older library) takes the path it always took.  A call with a camera request still reads the SH rows for its
+   camera terms (dL_dcampos is a function of the nine numbers).  The stashed values are formed by the backward's own expressions, compiled
+   with the backward's contraction setting: every gradient is the legacy path's bit for bit except dL_dmean3D above SH degree 1, which is
+   within 3.5e-8 of its largest entry of it (the two kernels fuse the shared expressions differently; against a float64 evaluation both
+   paths have the same error: tests/test_gpu_sh_stash.py).  The image, radii, colours and clamp flags of the forward do not change. */
+void stp_set_forward_sh_stash(int enable);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:188-193, rasterizer_impl.cu:161-173).
    `present` is P bytes (bool). */
 int stp_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
@@ -443,6 +465,7 @@ int stp_photometric_backward(int planes, int H, int W, const float* image, const
 
 /* Sizes of the three scratch buffers (the reference's `required<State>()`, rasterizer_impl.h:68-75). */
 size_t stp_geometry_buffer_size(int P, const StpSettings* settings);
+size_t stp_geometry_buffer_size_stash(int P, const StpSettings* settings); /* of a forward with stp_set_forward_sh_stash: the above + the nine planes of P floats */
 size_t stp_binning_buffer_size(int R);
 size_t stp_image_buffer_size(int width, int height); /* without the optional blend log */
 /* Bytes the blend log adds to the image buffer of a forward with StpSettings.record_blend_log = 1 in the hierarchical / k-buffer modes,

@@ -76,6 +76,7 @@ struct Api {
     decltype(&stp_set_backward_invdepth) set_backward_invdepth = nullptr;
     decltype(&stp_set_forward_split_sh) set_forward_split_sh = nullptr;
     decltype(&stp_set_backward_split_sh) set_backward_split_sh = nullptr;
+    decltype(&stp_set_forward_sh_stash) set_forward_sh_stash = nullptr; // (a library with it also takes NULL for dL_dcolor / dL_dcov3D)
     decltype(&stp_sparse_adam) sparse_adam = nullptr;
     decltype(&stp_mcmc_relocation) mcmc_relocation = nullptr;
     decltype(&stp_mcmc_add_noise) mcmc_add_noise = nullptr;
@@ -114,6 +115,7 @@ int load_library(const std::string& path)
     a.set_backward_invdepth = reinterpret_cast<decltype(a.set_backward_invdepth)>(dlsym(h, "stp_set_backward_invdepth"));
     a.set_forward_split_sh = reinterpret_cast<decltype(a.set_forward_split_sh)>(dlsym(h, "stp_set_forward_split_sh"));
     a.set_backward_split_sh = reinterpret_cast<decltype(a.set_backward_split_sh)>(dlsym(h, "stp_set_backward_split_sh"));
+    a.set_forward_sh_stash = reinterpret_cast<decltype(a.set_forward_sh_stash)>(dlsym(h, "stp_set_forward_sh_stash"));
     a.sparse_adam = reinterpret_cast<decltype(a.sparse_adam)>(dlsym(h, "stp_sparse_adam"));
     a.mcmc_relocation = reinterpret_cast<decltype(a.mcmc_relocation)>(dlsym(h, "stp_mcmc_relocation"));
     a.mcmc_add_noise = reinterpret_cast<decltype(a.mcmc_add_noise)>(dlsym(h, "stp_mcmc_add_noise"));
@@ -361,6 +363,12 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
     }
     torch::Tensor out_invdepth; // (like the image: every pixel of the rendered tile rows is written)
     if (invdepth) out_invdepth = zero ? torch::zeros({1, H, W}, fopt) : torch::empty({1, H, W}, fopt);
+    // The SH stash (include/stp_raster.h: stp_set_forward_sh_stash) is asked for exactly when a backward can follow -- the autograd layer's
+    // condition for asking for the blend log, settings._record_blend_log, or, where its policy or the sort mode rules the log out, its
+    // settings._sh_stash -- and the library exports the request; settings._no_sh_stash = True keeps a differentiable forward on the legacy
+    // path (tests compare the two).  An inference forward asks for nothing.
+    auto flag = [&](const char* key) { return settings.contains(key) && !settings[key].is_none() && settings[key].cast<bool>(); };
+    const bool sh_stash = (flag("_record_blend_log") || flag("_sh_stash")) && !flag("_no_sh_stash") && !render_depth && g_api.set_forward_sh_stash != nullptr;
     Resizer geom{torch::empty({0}, bopt), false, false, 0}, binning{torch::empty({0}, bopt), true, false, 1}, img{torch::empty({0}, bopt), true, false, 2};
     int rendered = 0;
     if (P != 0) {
@@ -384,6 +392,7 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
                 g_api.set_forward_background(bg_pixels ? fptr(bg_) : nullptr, alpha ? out_alpha.data_ptr<float>() : nullptr);
             if (invdepth) g_api.set_forward_invdepth(out_invdepth.data_ptr<float>());
             if (split) g_api.set_forward_split_sh(dc_.data_ptr<float>());
+            if (sh_stash) g_api.set_forward_sh_stash(1);
             rc = g_api.forward(&Resizer::call, &geom, &Resizer::call, &binning, &Resizer::call, &img, P, degree, M, fptr(bg_), W, H, &s, fptr(m3_),
                              fptr(sh_), fptr(col_), fptr(op_), fptr(sc_), scale_modifier, fptr(ro_), fptr(c3_), fptr(vm_), fptr(pm_), fptr(inv_),
                              fptr(cam_), tan_fovx, tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(), radii.data_ptr<int>(), debug ? 1 : 0,
@@ -391,6 +400,7 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
         }
         if (rc < 0) raise_last(rc);
         rendered = rc;
+        remember_storage(geom.t);
         remember_storage(binning.t);
         remember_storage(img.t);
     }
@@ -508,9 +518,14 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
     } else if (phases & 2) {
         // the per-Gaussian half writes every row of its outputs (zeros for invisible Gaussians): no zero-fill needed,
         // except for the scale/rotation gradients when a precomputed covariance is used (then they are not touched)
+        // settings._no_grad_colors / _no_grad_cov3D (set by the autograd layer where colors_precomp / cov3D_precomp are absent): nobody receives
+        // that gradient, so it is neither allocated nor written (include/stp_raster.h: optional outputs) and its slot of the result is None.
+        // A direct caller without the keys gets all eight, written in full.
         const bool have_scales = scales.numel() != 0;
-        dL_dmeans2D = torch::empty({P, 3}, fopt); dL_dcolors = torch::empty({P, 3}, fopt); dL_dopacity = torch::empty({P, 1}, fopt);
-        dL_dmeans3D = torch::empty({P, 3}, fopt); dL_dcov3D = torch::empty({P, 6}, fopt); dL_dsh = torch::empty({P, split ? M - 1 : M, 3}, fopt);
+        auto omitted = [&](const char* key) { return g_api.set_forward_sh_stash != nullptr && settings.contains(key) && settings[key].cast<bool>(); };
+        const bool no_dcolors = omitted("_no_grad_colors") && colors.numel() == 0, no_dcov3D = omitted("_no_grad_cov3D") && cov3D_precomp.numel() == 0;
+        dL_dmeans2D = torch::empty({P, 3}, fopt); if (!no_dcolors) dL_dcolors = torch::empty({P, 3}, fopt); dL_dopacity = torch::empty({P, 1}, fopt);
+        dL_dmeans3D = torch::empty({P, 3}, fopt); if (!no_dcov3D) dL_dcov3D = torch::empty({P, 6}, fopt); dL_dsh = torch::empty({P, split ? M - 1 : M, 3}, fopt);
         if (split) dL_ddc = torch::empty({P, 3}, fopt); // (written in full by the library, like dL_dsh)
         dL_dscales = have_scales ? torch::empty({P, 3}, fopt) : torch::zeros({P, 3}, fopt);
         dL_drotations = have_scales ? torch::empty({P, 4}, fopt) : torch::zeros({P, 4}, fopt);
@@ -567,6 +582,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
         auto optb = [](const torch::Tensor& t) -> char* { return t.defined() && t.numel() != 0 ? reinterpret_cast<char*>(t.data_ptr()) : nullptr; };
         const c10::hip::HIPGuard guard(dev.index());
         hipStream_t stream = c10::hip::getCurrentHIPStream(dev.index()).stream();
+        forget_unless_same_storage(geomBuffer); // (whether it carries an SH stash)
         forget_unless_same_storage(binningBuffer); // (a clone, a copy or a recycled address: the library then reads the buffer's own header)
         forget_unless_same_storage(imageBuffer);
         make_requests(); // (consumed by the call below, on this thread)

@@ -113,6 +113,7 @@ void stp_set_backward_background(const float* bg_image, const float* dL_dalpha, 
 void stp_set_forward_invdepth(float* out_invdepth) { t_pending.forward.out_invdepth = out_invdepth; }
 void stp_set_backward_invdepth(const float* invdepth, const float* dL_dinvdepth) { t_pending.backward.invdepth = BackwardInvdepth{invdepth, dL_dinvdepth}; }
 void stp_set_forward_split_sh(const float* dc) { t_pending.forward.sh_dc = dc; }
+void stp_set_forward_sh_stash(int enable) { t_pending.forward.sh_stash = enable != 0; }
 void stp_set_backward_split_sh(const float* dc, float* dL_ddc) { t_pending.backward.split_sh = dc ? BackwardSplitSh{dc, dL_ddc} : BackwardSplitSh{}; }
 
 namespace {
@@ -206,14 +207,19 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer)) return fail(STP_ERR_INVALID_ARGUMENT, "null scratch buffer");
     if (!grad_records) return fail(STP_ERR_INVALID_ARGUMENT, "null gradient record buffer");
     if ((phases & 1) && (!dL_dpix || !pixel_colors)) return fail(STP_ERR_INVALID_ARGUMENT, "null image gradient");
-    if ((phases & 2) && (!dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot))
+    // (dL_dcolor and dL_dcov3D may be NULL: outputs the caller has no receiver for -- colors_precomp / cov3D_precomp absent -- are then not written)
+    if ((phases & 2) && (!dL_dmean2D || !dL_dopacity || !dL_dmean3D || !dL_dscale || !dL_drot))
         return fail(STP_ERR_INVALID_ARGUMENT, "null gradient buffer");
 
     FrameParams f;
     fill_frame(f, P, D, M, background, width, height, *settings, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
                rotations, cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, cam_pos, tan_fovx, tan_fovy, 0);
     const bool with_inv = requires_depth_along_ray(*settings);
-    GeometryState g = carve_geometry(geom_buffer, (size_t)P, with_inv, nullptr);
+    // an SH stash (stp_set_forward_sh_stash) is asked for only where the per-Gaussian half would read SH rows; a buffer without one: the legacy path
+    bool with_stash = false;
+    if ((phases & 2) && !colors_precomp && (shs || bsh.dc) && M > 0) { if (int rc = stash_of(geom_buffer, P, (int64_t)R, &with_stash, (hipStream_t)stream, true)) return rc; }
+    float* sh_stash = nullptr;
+    GeometryState g = carve_geometry(geom_buffer, (size_t)P, with_inv, nullptr, nullptr, nullptr, with_stash ? &sh_stash : nullptr);
     // what the buffers were carved with travels with them (cache of this process, else the buffers' own headers): a buffer that carries none is refused
     uint32_t bin_cap = 0, log_depth = 0;
     if (R > 0) { if (int rc = layout_of(binning_buffer, (uint32_t)R, &bin_cap, (hipStream_t)stream, true)) return rc; } // (a run-ahead forward carved it for its capacity)
@@ -228,6 +234,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     bw.blend_stats = blend_stats;
     bw.bg_image = bbg.bg_image; bw.dL_dalpha = bbg.dL_dalpha; bw.dL_dbackground = bbg.dL_dbackground;
     bw.invdepth = binv.invdepth; bw.dL_dinvdepth = binv.dL_dinvdepth;
+    bw.sh_stash = sh_stash;
     if (bsh.dc && !colors_precomp) { f.sh_dc = bsh.dc; bw.dL_ddc = bsh.dL_ddc; }
     bw.pixel_colors = pixel_colors; bw.dL_dpix = dL_dpix; bw.dL_dmean2D = dL_dmean2D; bw.grad_rec = grad_records;
     bw.grad_stride = (phases & 4) ? STP_GRAD_RECORD_USED : STP_GRAD_RECORD_FLOATS;

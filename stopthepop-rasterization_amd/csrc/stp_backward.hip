@@ -11,6 +11,7 @@
 // rows written once.
 #include "stp_internal.h"
 #include "stp_device.h"
+#include "stp_sh_dir.h"
 
 namespace stp {
 
@@ -45,6 +46,7 @@ struct BwdPreArgs {
     float* cam_rows;       // CAM only: one kCamRow-float row of camera-gradient partial sums per workgroup (camera_grad_* below)
     const float* dc;       // SPLIT only: the (P, 3) first SH coefficient; `shs` is then the (P, M-1, 3) rest (not read for M == 1, never nullptr)
     float* dL_ddc;         // SPLIT only: P x 3; dL_dsh is then P x (M-1) x 3
+    const float* sh_stash; // STASH only: the forward's nine planes of P floats (stp_sh_dir.h; stp_set_forward_sh_stash)
 };
 
 // Camera-gradient contributions of one Gaussian (CAM instantiation), in the order of a workspace row:
@@ -70,7 +72,10 @@ __device__ __forceinline__ float opaque(float v)
 // INVD: the inverse-depth request (stp_set_backward_invdepth): slot STP_GRAD_RECORD_INVDEPTH of the record holds dL/d(1/z) of the Gaussian,
 // z = t.z the view-space depth of its centre; -slot / z^2 joins dL/dt_z in front of dL/dmean and the camera terms.  INVD = false is the
 // function as it was.
-template <bool TERMS, bool INVD>
+// STASH: the direction derivatives of the three colour channels come from the forward's stash (a.sh_stash, stp_sh_dir.h); sh_row holds zeros
+// in the place of the coefficients.  STASH = false is the function as it was.
+// a.dL_dcolor / a.dL_dcov3D may be null (outputs nobody receives): a wave-uniform test skips their stores, dcov[] stays in registers.
+template <bool TERMS, bool INVD, bool STASH>
 __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, float* sh_row, float* cg)
 {
     const float* __restrict__ view = a.view;
@@ -119,9 +124,10 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         }
     }
     if constexpr (!TERMS) {
-        a.dL_dcolor[3 * (size_t)idx] = rec0.x; a.dL_dcolor[3 * (size_t)idx + 1] = rec0.y; a.dL_dcolor[3 * (size_t)idx + 2] = rec0.z;
+        if (a.dL_dcolor != nullptr) { a.dL_dcolor[3 * (size_t)idx] = rec0.x; a.dL_dcolor[3 * (size_t)idx + 1] = rec0.y; a.dL_dcolor[3 * (size_t)idx + 2] = rec0.z; }
         a.dL_dmean2D[3 * (size_t)idx] = rec0.w; a.dL_dmean2D[3 * (size_t)idx + 1] = rec1.x;
     }
+    float dcov[6]; // dL/dcov3D: stored where somebody receives it, and handed in registers to the scale / rotation path below
 
     // ---- dL/dconic -> dL/dcov2D -> dL/dcov3D and dL/dmean (covariance path) ----
     {
@@ -182,7 +188,6 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         }
         const float denom = c_xx * c_yy - c_xy * c_xy;
         const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-        float dcov[6];
         if (denom2inv != 0) {
             dL_dc_xx += denom2inv * (-c_yy * c_yy * dcx + 2 * c_xy * c_yy * dcy + (denom - c_xx * c_yy) * dcz);
             dL_dc_yy += denom2inv * (-c_xx * c_xx * dcz + 2 * c_xx * c_xy * dcy + (denom - c_xx * c_yy) * dcx);
@@ -197,8 +202,12 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
 #pragma unroll
             for (int i = 0; i < 6; i++) dcov[i] = 0;
         }
+        if constexpr (!TERMS) {
+            if (a.dL_dcov3D != nullptr) {
 #pragma unroll
-        for (int i = 0; i < 6; i++) if constexpr (!TERMS) a.dL_dcov3D[6 * (size_t)idx + i] = dcov[i];
+                for (int i = 0; i < 6; i++) a.dL_dcov3D[6 * (size_t)idx + i] = dcov[i];
+            }
+        }
 
         const float dL_dT00 = 2 * (T.m[0][0] * Vrk.m[0][0] + T.m[0][1] * Vrk.m[0][1] + T.m[0][2] * Vrk.m[0][2]) * dL_dc_xx +
                               (T.m[1][0] * Vrk.m[0][0] + T.m[1][1] * Vrk.m[0][1] + T.m[1][2] * Vrk.m[0][2]) * dL_dc_xy;
@@ -266,8 +275,8 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         float3 cam = make_float3(a.cam[0], a.cam[1], a.cam[2]);
         if constexpr (TERMS) cam = make_float3(opaque(cam.x), opaque(cam.y), opaque(cam.z));
         const float3 v = make_float3(mean.x - cam.x, mean.y - cam.y, mean.z - cam.z);
-        const float len = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z);
-        const float x = v.x / len, y = v.y / len, z = v.z / len;
+        float x, y, z;
+        sh_unit_dir(v, x, y, z);
         float* const dsh = sh_row; // in place: gradient row over coefficient row
         float dRGB[3];
 #pragma unroll
@@ -288,16 +297,14 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
             }
             if (D > 0) {
                 if constexpr (!TERMS) { dsh[3 + ch] = (-kSH_C1 * y) * g; dsh[6 + ch] = (kSH_C1 * z) * g; dsh[9 + ch] = (-kSH_C1 * x) * g; }
-                dx = -kSH_C1 * sh[3]; dy = -kSH_C1 * sh[1]; dz = kSH_C1 * sh[2];
+                sh_dir_deg1(sh, dx, dy, dz);
                 if (D > 1) {
                     const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
                     if constexpr (!TERMS) {
                         dsh[12 + ch] = (kSH_C2[0] * xy) * g; dsh[15 + ch] = (kSH_C2[1] * yz) * g; dsh[18 + ch] = (kSH_C2[2] * (2.f * zz - xx - yy)) * g;
                         dsh[21 + ch] = (kSH_C2[3] * xz) * g; dsh[24 + ch] = (kSH_C2[4] * (xx - yy)) * g;
                     }
-                    dx += kSH_C2[0] * y * sh[4] + kSH_C2[2] * 2.f * -x * sh[6] + kSH_C2[3] * z * sh[7] + kSH_C2[4] * 2.f * x * sh[8];
-                    dy += kSH_C2[0] * x * sh[4] + kSH_C2[1] * z * sh[5] + kSH_C2[2] * 2.f * -y * sh[6] + kSH_C2[4] * 2.f * -y * sh[8];
-                    dz += kSH_C2[1] * y * sh[5] + kSH_C2[2] * 2.f * 2.f * z * sh[6] + kSH_C2[3] * x * sh[7];
+                    sh_dir_deg2(x, y, z, sh, dx, dy, dz);
                     if (D > 2) {
                         if constexpr (!TERMS) {
                             dsh[27 + ch] = (kSH_C3[0] * y * (3.f * xx - yy)) * g; dsh[30 + ch] = (kSH_C3[1] * xy * z) * g;
@@ -305,16 +312,18 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
                             dsh[39 + ch] = (kSH_C3[4] * x * (4.f * zz - xx - yy)) * g; dsh[42 + ch] = (kSH_C3[5] * z * (xx - yy)) * g;
                             dsh[45 + ch] = (kSH_C3[6] * x * (xx - 3.f * yy)) * g;
                         }
-                        dx += (kSH_C3[0] * sh[9] * 3.f * 2.f * xy + kSH_C3[1] * sh[10] * yz + kSH_C3[2] * sh[11] * -2.f * xy +
-                               kSH_C3[3] * sh[12] * -3.f * 2.f * xz + kSH_C3[4] * sh[13] * (-3.f * xx + 4.f * zz - yy) +
-                               kSH_C3[5] * sh[14] * 2.f * xz + kSH_C3[6] * sh[15] * 3.f * (xx - yy));
-                        dy += (kSH_C3[0] * sh[9] * 3.f * (xx - yy) + kSH_C3[1] * sh[10] * xz + kSH_C3[2] * sh[11] * (-3.f * yy + 4.f * zz - xx) +
-                               kSH_C3[3] * sh[12] * -3.f * 2.f * yz + kSH_C3[4] * sh[13] * -2.f * xy + kSH_C3[5] * sh[14] * -2.f * yz +
-                               kSH_C3[6] * sh[15] * -3.f * 2.f * xy);
-                        dz += (kSH_C3[1] * sh[10] * xy + kSH_C3[2] * sh[11] * 4.f * 2.f * yz + kSH_C3[3] * sh[12] * 3.f * (2.f * zz - xx - yy) +
-                               kSH_C3[4] * sh[13] * 4.f * 2.f * xz + kSH_C3[5] * sh[14] * (xx - yy));
+                        sh_dir_deg3(xx, yy, zz, xy, yz, xz, sh, dx, dy, dz);
                     }
                 }
+            }
+            if constexpr (STASH) {
+                // The row holds ZEROS here (the kernel filled it: no coefficient was read), so dx, dy, dz are zeros so far, and the forward's
+                // values join them.  The arithmetic above is kept on purpose: with it the compiler sees the block it sees in the STASH = false
+                // kernel and makes the same fusion choices (-ffp-contract=fast) for the dsh[] terms and the normalisation below -- without it
+                // dL_dsh and the camera terms came out an ulp apart from the legacy path's (profiles/EXPERIMENTS.md).  The kernel is bound by
+                // its memory traffic; the extra multiplications cost it nothing measurable.
+                float sx = a.sh_stash[(size_t)(3 * ch + 0) * a.P + idx], sy = a.sh_stash[(size_t)(3 * ch + 1) * a.P + idx], sz = a.sh_stash[(size_t)(3 * ch + 2) * a.P + idx];
+                dx += sx; dy += sy; dz += sz;
             }
             ddir[0] += dx * g; ddir[1] += dy * g; ddir[2] += dz * g;
         }
@@ -345,7 +354,7 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         const float sx = a.scale_modifier * a.scales[3 * (size_t)idx], sy = a.scale_modifier * a.scales[3 * (size_t)idx + 1],
                     sz = a.scale_modifier * a.scales[3 * (size_t)idx + 2];
         const Mat3 Mm = mat_mul(mat_diag(sx, sy, sz), R);
-        const float* d = a.dL_dcov3D + 6 * (size_t)idx;
+        const float* d = dcov;
         Mat3 dSig;
         dSig.m[0][0] = d[0];        dSig.m[0][1] = 0.5f * d[1]; dSig.m[0][2] = 0.5f * d[2];
         dSig.m[1][0] = 0.5f * d[1]; dSig.m[1][1] = d[3];        dSig.m[1][2] = 0.5f * d[4];
@@ -401,7 +410,10 @@ __device__ __forceinline__ float wave_sum(float v) // every lane ends with the s
 
 // SPLIT (stp_set_backward_split_sh): the LDS rows come from two global spans (a.dc, a.shs) and leave as two (a.dL_ddc, a.dL_dsh), see stp_device.h:
 // split SH rows; everything between the two stagings is the SPLIT = false kernel's.
-template <bool CAM, bool INVD, bool SPLIT>
+// STASH (a forward with stp_set_forward_sh_stash wrote a.sh_stash): no SH row is read from global memory; the LDS rows are filled with zeros
+// in the place of the stage-in and are otherwise the staging area of the coalesced dL_dsh / dL_ddc stores.  a.shs / a.dc are not read -- except
+// with CAM, whose camera-terms pass keeps reading the coefficients (a camera request saves the dcov round trip and the unwanted outputs only).
+template <bool CAM, bool INVD, bool SPLIT, bool STASH>
 __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreArgs a)
 {
     extern __shared__ float s_rows[]; // [256][3M + 1]
@@ -416,7 +428,14 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreAr
 #pragma unroll
         for (int k = 0; k < kCamTerms; k++) cg[k] = 0.0f;
     }
-    if (have_sh) {
+    // CAM with STASH: the camera terms depend on the nine numbers too (dL/dcampos), and they stay the legacy path's bit for bit: the rows ARE staged
+    // in, the camera-terms pass reads them as it always did, and each thread clears its own row in front of its gradient pass (below).
+    constexpr bool STAGE_IN = !STASH || CAM;
+    if (have_sh && !STAGE_IN) { // zeros in the place of the coefficients (gaussian_backward: STASH)
+        for (int f = tid; f < rows * row_stride; f += 256) s_rows[f] = 0.0f;
+        __syncthreads();
+    }
+    if (have_sh && STAGE_IN) {
         const float* __restrict__ src = a.shs + (size_t)base * (SPLIT ? row_len - 3 : row_len);
         const int total = rows * row_len;
         if constexpr (SPLIT) {
@@ -454,15 +473,21 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(const BwdPreAr
                 // opaque branch: the gradient pass below is the CAM = false kernel's, arithmetic for arithmetic
                 int go = 1;
                 asm volatile("" : "+s"(go));
-                if (go) gaussian_backward<true, INVD>(a, idx, s_rows + tid * row_stride, cg);
+                if (go) gaussian_backward<true, INVD, false>(a, idx, s_rows + tid * row_stride, cg);
+                if constexpr (STASH) { // (its own row, which no other thread reads before the barrier in front of the stores)
+                    if (have_sh) for (int j = 0; j < row_len; j++) s_rows[tid * row_stride + j] = 0.0f;
+                    asm volatile("" ::: "memory"); // the gradient pass loads the zeros as it loads coefficients: values the compiler does not know
+                }
             }
-            gaussian_backward<false, INVD>(a, idx, s_rows + tid * row_stride, cg);
+            gaussian_backward<false, INVD, STASH>(a, idx, s_rows + tid * row_stride, cg);
         } else { // invisible: all gradients are zero
-            a.dL_dcolor[3 * (size_t)idx] = 0.0f; a.dL_dcolor[3 * (size_t)idx + 1] = 0.0f; a.dL_dcolor[3 * (size_t)idx + 2] = 0.0f;
+            if (a.dL_dcolor != nullptr) { a.dL_dcolor[3 * (size_t)idx] = 0.0f; a.dL_dcolor[3 * (size_t)idx + 1] = 0.0f; a.dL_dcolor[3 * (size_t)idx + 2] = 0.0f; }
             a.dL_dmean2D[3 * (size_t)idx] = 0.0f; a.dL_dmean2D[3 * (size_t)idx + 1] = 0.0f;
             a.dL_dopacity[idx] = 0.0f;
+            if (a.dL_dcov3D != nullptr) {
 #pragma unroll
-            for (int i = 0; i < 6; i++) a.dL_dcov3D[6 * (size_t)idx + i] = 0.0f;
+                for (int i = 0; i < 6; i++) a.dL_dcov3D[6 * (size_t)idx + i] = 0.0f;
+            }
 #pragma unroll
             for (int i = 0; i < 3; i++) a.dL_dmean3D[3 * (size_t)idx + i] = 0.0f;
             if (a.scales != nullptr) {
@@ -649,13 +674,20 @@ hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState&
     a.dc = f.sh_dc; a.dL_ddc = bw.dL_ddc;
     if (split && a.shs == nullptr) a.shs = a.dc; // M == 1: no rest; the kernel's "have SH" test wants a pointer and reads nothing through this one
     const bool invd = bw.dL_dinvdepth != nullptr; // (stp_set_backward_invdepth; the caller has refused a chunked half and compact records with it: slot 14 exists)
+    // the forward's stash (carve_geometry; stp_api.hip has asked the buffer whether one was written): only where there are SH rows to spare
+    const bool stash = bw.sh_stash != nullptr && a.shs != nullptr && a.M > 0;
+    a.sh_stash = stash ? bw.sh_stash : nullptr;
     using Kernel = void (*)(const BwdPreArgs);
-    static const Kernel kernels[8] = {
-        preprocess_backward_kernel<false, false, false>, preprocess_backward_kernel<false, false, true>,
-        preprocess_backward_kernel<false, true, false>,  preprocess_backward_kernel<false, true, true>,
-        preprocess_backward_kernel<true, false, false>,  preprocess_backward_kernel<true, false, true>,
-        preprocess_backward_kernel<true, true, false>,   preprocess_backward_kernel<true, true, true>};
-    const Kernel kernel = kernels[(cam ? 4 : 0) + (invd ? 2 : 0) + (split ? 1 : 0)];
+    static const Kernel kernels[16] = {
+        preprocess_backward_kernel<false, false, false, false>, preprocess_backward_kernel<false, false, true, false>,
+        preprocess_backward_kernel<false, true, false, false>,  preprocess_backward_kernel<false, true, true, false>,
+        preprocess_backward_kernel<true, false, false, false>,  preprocess_backward_kernel<true, false, true, false>,
+        preprocess_backward_kernel<true, true, false, false>,   preprocess_backward_kernel<true, true, true, false>,
+        preprocess_backward_kernel<false, false, false, true>,  preprocess_backward_kernel<false, false, true, true>,
+        preprocess_backward_kernel<false, true, false, true>,   preprocess_backward_kernel<false, true, true, true>,
+        preprocess_backward_kernel<true, false, false, true>,   preprocess_backward_kernel<true, false, true, true>,
+        preprocess_backward_kernel<true, true, false, true>,    preprocess_backward_kernel<true, true, true, true>};
+    const Kernel kernel = kernels[(stash ? 8 : 0) + (cam ? 4 : 0) + (invd ? 2 : 0) + (split ? 1 : 0)];
     const size_t lds = (a.shs != nullptr && a.M > 0) ? (size_t)256 * (3 * a.M + 1) * sizeof(float) : 0;
     if (lds > 64 * 1024) { // above the default dynamic-LDS limit (M > 21: no SH degree the reference knows)
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

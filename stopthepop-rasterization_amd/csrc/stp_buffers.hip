@@ -10,7 +10,7 @@
 
 namespace stp {
 
-GeometryState carve_geometry(char* base, size_t P, bool with_inv, size_t* total, NamedOffset* names, int* n_names)
+GeometryState carve_geometry(char* base, size_t P, bool with_inv, size_t* total, NamedOffset* names, int* n_names, float** sh_stash)
 {
     Carver c(base);
     GeometryState g{};
@@ -35,6 +35,14 @@ GeometryState carve_geometry(char* base, size_t P, bool with_inv, size_t* total,
     g.scan_temp_bytes = scan_temp_bytes(P);
     g.scan_temp = c.take<char>(g.scan_temp_bytes);
     g.invz = c.take<float>(P, &off); note("invz", off, P); // (behind everything else: the other sub-arrays are where they were)
+    // the SH stash (stp_set_forward_sh_stash), LAST: a buffer carved without it ends here, and its size is the one it has always been.  A layout query
+    // names the place in either case (the sub-array exists only in a buffer of a forward that asked)
+    {
+        const Carver before_stash = c;
+        float* const stash = c.take<float>(9 * P, &off); note("sh_stash", off, 9 * P);
+        if (sh_stash) *sh_stash = stash;
+        else c = before_stash;
+    }
     if (total) *total = c.total();
     if (n_names) *n_names = n;
     return g;
@@ -132,9 +140,10 @@ void clamp_tile_rows(int height, int& y0, int& y1)
 // does not know -- a buffer that was cloned, copied, moved, or whose entry was dropped -- is looked up in the buffer's own header (one blocking
 // 16-byte copy: the rare path); a buffer without a valid header is REFUSED (STP_ERR_INVALID_ARGUMENT) instead of being carved on a guess.
 static std::mutex g_layout_mutex;
-static LayoutCache g_layout, g_log_depth;
+static LayoutCache g_layout, g_log_depth, g_stash;
 void remember_layout(const void* binning, uint32_t count, int64_t R) { std::lock_guard<std::mutex> l(g_layout_mutex); g_layout.put(binning, count, R); }
 void remember_log_depth(const void* image, uint32_t depth, int64_t R) { std::lock_guard<std::mutex> l(g_layout_mutex); g_log_depth.put(image, depth, R); }
+void remember_stash(const void* geometry, bool stash, int64_t R) { std::lock_guard<std::mutex> l(g_layout_mutex); g_stash.put(geometry, stash ? 1u : 0u, R); }
 // the header a forward left in the buffer: 0 and *value on success, else a negative STP_ERR_* (message set)
 // (the copy is ordered on the CALLER's stream -- a clone made on a non-blocking stream is not visible to the null stream's copy -- and waited for;
 //  introspection calls have no stream: they wait for the device first)
@@ -175,6 +184,24 @@ int log_depth_of(const char* image, int64_t R, uint32_t* depth, hipStream_t st, 
     return 0;
 }
 
+// does the geometry buffer carry an SH stash (stp_set_forward_sh_stash): cache, else the three words the stashing forward left in the buffer's status
+// block.  A buffer without them -- a forward that did not ask, a library that did not know -- has none and takes the legacy path: nothing is refused.
+int stash_of(const char* geometry, int P, int64_t R, bool* stash, hipStream_t st, bool have_stream)
+{
+    uint32_t v = 0;
+    {
+        std::lock_guard<std::mutex> l(g_layout_mutex);
+        if (g_stash.get(geometry, R, &v)) { *stash = v != 0u; return 0; }
+    }
+    uint32_t h[4] = {0, 0, 0, 0};
+    if (!have_stream) (void)hipDeviceSynchronize();
+    if (hipMemcpyAsync(h, reinterpret_cast<const uint32_t*>(geometry) + STP_STASH_WORD, sizeof(h), hipMemcpyDeviceToHost, have_stream ? st : nullptr) != hipSuccess ||
+        hipStreamSynchronize(have_stream ? st : nullptr) != hipSuccess) { (void)hipGetLastError(); return fail(STP_ERR_HIP, "could not read the status block of the geometry buffer"); }
+    *stash = h[0] == STP_HEADER_MAGIC_STASH && h[1] == (uint32_t)P && h[2] == ~(uint32_t)P;
+    remember_stash(geometry, *stash, R);
+    return 0;
+}
+
 } // namespace stp
 
 using namespace stp;
@@ -185,6 +212,13 @@ size_t stp_geometry_buffer_size(int P, const StpSettings* settings)
 {
     size_t total = 0;
     carve_geometry(nullptr, (size_t)P, settings ? requires_depth_along_ray(*settings) : true, &total);
+    return total;
+}
+size_t stp_geometry_buffer_size_stash(int P, const StpSettings* settings)
+{
+    size_t total = 0;
+    float* stash = nullptr;
+    carve_geometry(nullptr, (size_t)P, settings ? requires_depth_along_ray(*settings) : true, &total, nullptr, nullptr, &stash);
     return total;
 }
 size_t stp_binning_buffer_size(int R)
@@ -246,6 +280,7 @@ void stp_forget_buffer(const void* buffer)
     std::lock_guard<std::mutex> l(g_layout_mutex);
     g_layout.map.erase(buffer);
     g_log_depth.map.erase(buffer);
+    g_stash.map.erase(buffer);
 }
 int stp_blend_log_depth(const void* image_buffer)
 {

@@ -127,7 +127,7 @@ int acquire_mailbox(Mailbox* out)
 struct ForwardCall {
     const hipStream_t st; const int debug; // (under the names STP_DEBUG_SYNC uses)
     FrameParams f;
-    GeometryState g{}; ImageState img{}; char* img_ptr = nullptr;
+    GeometryState g{}; ImageState img{}; char* img_ptr = nullptr; char* geom_base = nullptr; float* sh_stash = nullptr; // (sh_stash: stp_set_forward_sh_stash, else nullptr)
     Mailbox mb;
     SizeGuess* gslot = nullptr; uint64_t gkey = 0; // the guess slot of this kind of frame
     uint32_t* log_need_word = nullptr; uint32_t log_tag = 0; int log_depth = 0; bool with_log = false;
@@ -144,20 +144,21 @@ struct ForwardCall {
 
     ForwardCall(hipStream_t stream, int debug_, const ForwardSplit& split_, int* radii_, float* out_color_)
         : st(stream), debug(debug_), radii(radii_), out_color(out_color_), split{split_, stream, false}, colours{nullptr, stream, false} {}
-    int carve_geometry_and_image(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn image_alloc, void* image_user, bool with_inv);
+    int carve_geometry_and_image(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn image_alloc, void* image_user, bool with_inv, bool with_stash);
     int launch_up_to_mailbox(); int colour_on_side();
     int request_binning(stp_alloc_fn binning_alloc, void* binning_user);
     int wait_mailbox(); int read_mailbox(int* R_out, bool* wild_out);
     int binning_and_render(const GeometryState& gd, const BinningState& b, int L, uint32_t dup_cap);
 };
 
-int ForwardCall::carve_geometry_and_image(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn image_alloc, void* image_user, bool with_inv)
+int ForwardCall::carve_geometry_and_image(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn image_alloc, void* image_user, bool with_inv, bool with_stash)
 {
     size_t geom_bytes = 0;
-    carve_geometry(nullptr, (size_t)f.P, with_inv, &geom_bytes);
+    carve_geometry(nullptr, (size_t)f.P, with_inv, &geom_bytes, nullptr, nullptr, with_stash ? &sh_stash : nullptr);
     char* geom_ptr = (char*)geometry_alloc(geometry_user, geom_bytes);
     if (!geom_ptr) return fail(STP_ERR_ALLOC, "geometry allocator returned NULL");
-    g = carve_geometry(geom_ptr, (size_t)f.P, with_inv, nullptr);
+    g = carve_geometry(geom_ptr, (size_t)f.P, with_inv, nullptr, nullptr, nullptr, with_stash ? &sh_stash : nullptr);
+    geom_base = geom_ptr;
     if (!radii) radii = g.internal_radii;
 
     // (the mailbox is taken here already: the device's guess slots size the blend log)
@@ -211,14 +212,14 @@ int ForwardCall::launch_up_to_mailbox()
     colour_started = !(side && switches().colour_late);
     if (side) {
         if (colour_started) { if (int rc = colour_on_side()) return rc; }
-    } else STP_TRY(launch_sh_color(f, g, radii, st), "SH colour launch");
+    } else STP_TRY(launch_sh_color(f, g, radii, sh_stash, st), "SH colour launch");
     return 0;
 }
 
 int ForwardCall::colour_on_side()
 {
     STP_TRY(hipStreamWaitEvent(side->stream, mb.ev, 0), "side stream wait");
-    STP_TRY(launch_sh_color(f, g, radii, side->stream), "SH colour launch");
+    STP_TRY(launch_sh_color(f, g, radii, sh_stash, side->stream), "SH colour launch");
     // from here on the side stream works on the caller's buffers: every return path joins it (SideJoin); should the
     // event that the join waits for fail to record, the side stream is drained on the spot instead
     if (hipError_t e = hipEventRecord(mb.done, side->stream); e != hipSuccess) {
@@ -436,7 +437,9 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
     f.out_invdepth = req.out_invdepth;
     f.sh_dc = sh_dc;
     f.bg_image = fbg.bg_image; f.out_alpha = fbg.out_alpha; // (every render launch of the call: both halves of a split forward, a redone run-ahead frame)
-    if (int rc = c.carve_geometry_and_image(geometry_alloc, geometry_user, image_alloc, image_user, with_inv)) return rc;
+    // stp_set_forward_sh_stash: only a forward that runs the SH colour kernel has anything to stash (launch_sh_color's own test)
+    const bool with_stash = req.sh_stash && !colors_precomp && (shs || sh_dc) && M > 0;
+    if (int rc = c.carve_geometry_and_image(geometry_alloc, geometry_user, image_alloc, image_user, with_inv, with_stash)) return rc;
 
     // How the (tile, depth) order is established:
     //   default           device-wide radix sort on the tile bits only (two passes), then the tile's own workgroup sorts its
@@ -471,6 +474,7 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
         if (int rc = c.binning_and_render(g_dup, b, (int)c.cap, c.cap)) return rc;
         if (int rc = c.read_mailbox(&R, &wild)) return rc;
         if ((uint32_t)R <= c.cap && !wild) {
+            remember_stash(c.geom_base, with_stash, R);
             remember_layout(c.bin_ptr, c.cap, R);
             remember_log_depth(c.img_ptr, (uint32_t)c.log_depth, R);
             return R;
@@ -478,6 +482,7 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
         // the frame did not fit its guess (or needs the checked reciprocal): once more from duplicate_kernel on, exact this time
         g_dup.block_prefix = nullptr; g_dup.block_sums = nullptr;
         STP_TRY(launch_frame_init(c.g, c.img, f.gx * f.ty0, f.gx * (f.ty1 - f.ty0), c.with_log, sw.atomic_bin, st), "frame init launch"); // ranges and tile flags of the discarded pass
+        STP_TRY(launch_stash_mark(f, c.g, c.sh_stash, st), "stash mark launch"); // (... and the status block, where a stashing colour kernel had left its mark)
     } else { // the hand-over: the host waits for num_rendered
         if (int rc = c.read_mailbox(&R, &wild)) return rc;
         STP_DEBUG_SYNC("SH colour");
@@ -492,6 +497,7 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
     }
     const BinningState b = carve_binning(c.bin_ptr, (size_t)R, nullptr);
     if (int rc = c.binning_and_render(g_dup, b, R, 0xFFFFFFFFu)) return rc;
+    remember_stash(c.geom_base, with_stash, R);
     if (c.bin_ptr) remember_layout(c.bin_ptr, (uint32_t)R, R);
     remember_log_depth(c.img_ptr, (uint32_t)c.log_depth, R);
     return R;

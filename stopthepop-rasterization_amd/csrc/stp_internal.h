@@ -84,6 +84,13 @@ struct GeometryState {
     size_t scan_temp_bytes;
     float* invz;             // P: 1 / view-space z of the visible Gaussians; written only by a forward with the inverse-depth request (LAST in the carve)
 };
+// The SH stash (stp_set_forward_sh_stash) is one more sub-array behind invz, carved only on request (carve_geometry's sh_stash): nine planes of P
+// floats, plane 3 ch + {0, 1, 2} = d(colour channel ch) / d(unit view direction x, y, z) of the visible Gaussians (stp_sh_dir.h).  It is NOT a member
+// of GeometryState, which kernels take by value: their arguments, and with them the kernels, stay what they are.
+// Whether a geometry buffer carries a stash travels with it: words STP_STASH_WORD .. + 2 of the status block (the buffer's first 256 bytes) hold
+// {STP_HEADER_MAGIC_STASH, P, ~P}, written by the stashing sh_color_kernel; frame_init_kernel zeroes them in every forward.
+constexpr int STP_STASH_WORD = 8;
+constexpr uint32_t STP_HEADER_MAGIC_STASH = 0x53505453u; // "STPS"
 
 struct ImageState { // reference ImageState, rasterizer_impl.cu:195-202 (ranges sized per tile, not per pixel)
     float* final_T;      // N
@@ -123,7 +130,7 @@ struct BinningState { // reference BinningState, rasterizer_impl.cu:204-217
 constexpr uint32_t STP_HEADER_MAGIC_BINNING = 0x42505453u, STP_HEADER_MAGIC_IMAGE = 0x49505453u; // "STPB", "STPI"
 struct NamedOffset { const char* name; size_t offset; size_t count; };
 
-GeometryState carve_geometry(char* base, size_t P, bool with_inv, size_t* total, NamedOffset* names = nullptr, int* n_names = nullptr);
+GeometryState carve_geometry(char* base, size_t P, bool with_inv, size_t* total, NamedOffset* names = nullptr, int* n_names = nullptr, float** sh_stash = nullptr); // sh_stash: carve the stash too, *sh_stash = where
 ImageState carve_image(char* base, int W, int H, int ty0, int ty1, int log_depth /* 0: no blend log */, size_t* total, NamedOffset* names = nullptr, int* n_names = nullptr); // the tile-row window's share, frame-coordinate indexing
 BinningState carve_binning(char* base, size_t R, size_t* total, NamedOffset* names = nullptr, int* n_names = nullptr);
 void clamp_tile_rows(int height, int& y0, int& y1); // StpSettings::tile_y0 / tile_y1 -> the frame's tile-row window (y1 <= 0: the whole frame)
@@ -141,6 +148,8 @@ void timer_mark(int i, hipStream_t st); // events 0..4: forward stage boundaries
 
 // ---- what a buffer was carved with (stp_buffers.hip: buffer headers): cache of this process, else the buffer's own header ----
 void remember_layout(const void* binning, uint32_t count, int64_t R);
+void remember_stash(const void* geometry, bool stash, int64_t R); // every forward says whether its geometry buffer carries an SH stash ...
+int stash_of(const char* geometry, int P, int64_t R, bool* stash, hipStream_t st, bool have_stream); // ... the backward asks: cache, else the buffer's own status block
 void remember_log_depth(const void* image, uint32_t depth, int64_t R);
 int layout_of(const char* binning, uint32_t R, uint32_t* cap, hipStream_t st = nullptr, bool have_stream = false);
 int log_depth_of(const char* image, int64_t R, uint32_t* depth, hipStream_t st = nullptr, bool have_stream = false);
@@ -220,6 +229,7 @@ struct BackwardParams {
     float* dL_dsh;
     float* dL_dscale;
     float* dL_drot;
+    const float* sh_stash = nullptr; // the forward's SH stash, where the geometry buffer carries one (stp_api.hip: stash_of): the per-Gaussian half reads it in the place of the SH rows
     float* dL_ddc = nullptr; // stp_set_backward_split_sh (with FrameParams::sh_dc): P x 3, the first coefficient's gradient; dL_dsh is then P x (M-1) x 3
 };
 
@@ -233,7 +243,7 @@ void fill_frame(FrameParams& f, int P, int D, int M, const float* background, in
 // ---- the one-shot per-thread requests (stp_api.hip: the stp_set_* setters, and the rules by which a call takes them) ----
 struct ForwardSplit { int row = 0; hipEvent_t event = nullptr; bool armed = false; };      // stp_set_forward_split
 struct ForwardBackground { const float* bg_image = nullptr; float* out_alpha = nullptr; }; // stp_set_forward_background
-struct ForwardRequests { ForwardSplit split; ForwardBackground background; float* out_invdepth = nullptr; /* stp_set_forward_invdepth */ const float* sh_dc = nullptr; /* stp_set_forward_split_sh */ };
+struct ForwardRequests { ForwardSplit split; ForwardBackground background; float* out_invdepth = nullptr; /* stp_set_forward_invdepth */ const float* sh_dc = nullptr; /* stp_set_forward_split_sh */ bool sh_stash = false; /* stp_set_forward_sh_stash */ };
 ForwardRequests take_forward_requests();
 
 // ---- launchers (one per stage; each returns hipSuccess or the launch error) ----
@@ -248,7 +258,8 @@ inline bool tile_order_used(const FrameParams& f) { return tile_order_enabled() 
 bool gather_order_enabled();
 int gather_order_mode();
 hipError_t launch_tile_order(const FrameParams& f, const ImageState& img, hipStream_t st);
-hipError_t launch_sh_color(const FrameParams& f, const GeometryState& g, const int* radii, hipStream_t st); // SH -> RGB of the visible Gaussians (after preprocess)
+hipError_t launch_sh_color(const FrameParams& f, const GeometryState& g, const int* radii, float* sh_stash, hipStream_t st); // SH -> RGB of the visible Gaussians (after preprocess); with sh_stash also the stash and its mark
+hipError_t launch_stash_mark(const FrameParams& f, const GeometryState& g, float* sh_stash, hipStream_t st); // the mark alone, once more (a redone run-ahead frame: frame_init_kernel has cleared the status block again)
 hipError_t launch_mailbox(const uint32_t* last_offset, const uint32_t* status, uint32_t* mailbox_dev, uint32_t ticket, uint32_t* log_need, hipStream_t st);
 hipError_t launch_block_prefix_mailbox(const FrameParams& f, const GeometryState& g, uint32_t* mailbox_dev, uint32_t ticket, uint32_t* log_need, hipStream_t st); // second level of the scan + the hand-over
 hipError_t launch_duplicate(const FrameParams& f, const GeometryState& g, const int* radii, const BinningState& b, uint32_t* tile_cursor, uint32_t cap, uint32_t header_cap, uint32_t* zero_ptr, size_t zero_words, hipStream_t st); // header_cap: entries the buffer was carved for (its header); tile_cursor: nullptr = by point_offsets into the unsorted arrays; cap: slots of a run-ahead launch (0xFFFFFFFF = exact)

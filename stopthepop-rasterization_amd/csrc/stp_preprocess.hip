@@ -13,6 +13,7 @@
 // never results; here every Gaussian's tile loop is per-thread.
 #include "stp_internal.h"
 #include "stp_device.h"
+#include "stp_sh_dir.h"
 
 namespace stp {
 
@@ -379,6 +380,8 @@ struct ShArgs {
     uint8_t* clamped;
     float* rgb;
     const float* dc; // SPLIT only: the (P, 3) first coefficient; `shs` is then the (P, M-1, 3) rest (not read for M == 1)
+    float* stash;     // STASH only: nine planes of P floats (GeometryState::sh_stash) ...
+    uint32_t* mark;   // ... and the three words of the status block that say so (stp_internal.h: STP_STASH_WORD)
 };
 
 #ifndef STP_SH_BLOCK
@@ -388,7 +391,11 @@ constexpr int SH_BLOCK = STP_SH_BLOCK; // Gaussians (= threads) per workgroup: i
 
 // SPLIT (stp_set_forward_split_sh): the same LDS rows from two global spans, columns 0..2 from a.dc and 3..3M-1 from a.shs (stp_device.h: split SH
 // rows); everything behind the staging is the SPLIT = false kernel's.
-template <bool SPLIT>
+// STASH (stp_set_forward_sh_stash): behind the colour, every visible Gaussian also keeps d(colour channel) / d(unit view direction) of its three
+// channels -- nine floats, from the row, the mean and the camera position this kernel holds anyway -- for the per-Gaussian backward, which then
+// reads 36 B in the place of the 192 B row.  The expressions are the backward's own (stp_sh_dir.h), compiled here with the contraction the
+// backward compiles them with, NOT with sh_to_rgb's; the colour and clamp outputs are those of the STASH = false kernel.
+template <bool SPLIT, bool STASH>
 __global__ void __launch_bounds__(SH_BLOCK) sh_color_kernel(const ShArgs a)
 {
     extern __shared__ float s_rows[]; // [SH_BLOCK][3M + 1]
@@ -442,8 +449,27 @@ __global__ void __launch_bounds__(SH_BLOCK) sh_color_kernel(const ShArgs a)
     if (my_radius > 0) {
         const float3 cam = make_float3(a.cam[0], a.cam[1], a.cam[2]);
         sh_to_rgb(idx, a.D, mean, cam, s_rows + tid * row_stride, a.clamped, a.rgb);
+        if constexpr (STASH) {
+            const float* __restrict__ sh_row = s_rows + tid * row_stride;
+            float x, y, z;
+            sh_unit_dir(make_float3(mean.x - cam.x, mean.y - cam.y, mean.z - cam.z), x, y, z);
+            const int D = a.D;
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                float sh[16], dx, dy, dz;
+#pragma unroll
+                for (int k = 1; k < 16; k++) sh[k] = (k < a.M && k < (D + 1) * (D + 1)) ? sh_row[3 * k + ch] : 0.0f; // (the backward's own guard)
+                sh_dir_derivative(D, x, y, z, sh, dx, dy, dz);
+                a.stash[(size_t)(3 * ch + 0) * a.P + idx] = dx; a.stash[(size_t)(3 * ch + 1) * a.P + idx] = dy; a.stash[(size_t)(3 * ch + 2) * a.P + idx] = dz;
+            }
+        }
+    }
+    if constexpr (STASH) {
+        if (idx == 0) { a.mark[0] = STP_HEADER_MAGIC_STASH; a.mark[1] = (uint32_t)a.P; a.mark[2] = ~(uint32_t)a.P; }
     }
 }
+
+__global__ void stash_mark_kernel(uint32_t* mark, uint32_t P) { mark[0] = STP_HEADER_MAGIC_STASH; mark[1] = P; mark[2] = ~P; }
 
 struct DupArgs {
     int P, W, H, gx, gy, ty0, ty1;
@@ -716,21 +742,31 @@ hipError_t launch_duplicate(const FrameParams& f, const GeometryState& g, const 
     return hipGetLastError();
 }
 
-hipError_t launch_sh_color(const FrameParams& f, const GeometryState& g, const int* radii, hipStream_t st)
+hipError_t launch_sh_color(const FrameParams& f, const GeometryState& g, const int* radii, float* sh_stash, hipStream_t st)
 {
     const bool split = f.sh_dc != nullptr; // stp_set_forward_split_sh: f.shs is the rest (nullptr allowed for M == 1)
     if (f.colors_precomp != nullptr || (f.shs == nullptr && !split) || f.M <= 0) return hipSuccess; // reference forward.cu:200: precomputed colours win
     ShArgs a;
     a.P = f.P; a.D = f.D; a.M = f.M; a.means3D = f.means3D; a.shs = f.shs; a.cam = f.cam_pos; a.radii = radii; a.clamped = g.clamped; a.rgb = g.rgb;
     a.dc = f.sh_dc;
-    const void* kernel = split ? reinterpret_cast<const void*>(sh_color_kernel<true>) : reinterpret_cast<const void*>(sh_color_kernel<false>);
+    const bool stash = sh_stash != nullptr; // stp_set_forward_sh_stash (stp_forward carves the sub-array only for a forward that runs this kernel)
+    a.stash = sh_stash; a.mark = g.status + STP_STASH_WORD;
+    using Kernel = void (*)(const ShArgs);
+    static const Kernel kernels[4] = {sh_color_kernel<false, false>, sh_color_kernel<true, false>, sh_color_kernel<false, true>, sh_color_kernel<true, true>};
+    const Kernel kernel = kernels[(stash ? 2 : 0) + (split ? 1 : 0)];
     const size_t lds = (size_t)SH_BLOCK * (3 * a.M + 1) * sizeof(float);
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    if (split) hipLaunchKernelGGL(sh_color_kernel<true>, dim3((f.P + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), lds, st, a);
-    else hipLaunchKernelGGL(sh_color_kernel<false>, dim3((f.P + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), lds, st, a);
+    hipLaunchKernelGGL(kernel, dim3((f.P + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_stash_mark(const FrameParams& f, const GeometryState& g, float* sh_stash, hipStream_t st)
+{
+    if (sh_stash == nullptr) return hipSuccess;
+    hipLaunchKernelGGL(stash_mark_kernel, dim3(1), dim3(1), 0, st, g.status + STP_STASH_WORD, (uint32_t)f.P);
     return hipGetLastError();
 }
 

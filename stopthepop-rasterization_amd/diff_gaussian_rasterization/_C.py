@@ -51,6 +51,8 @@ _OPTIONAL_SYMBOLS = {
     "stp_set_backward_invdepth": ([ctypes.c_void_p] * 2, None),
     "stp_set_forward_split_sh": ([ctypes.c_void_p], None),
     "stp_set_backward_split_sh": ([ctypes.c_void_p] * 2, None),
+    "stp_set_forward_sh_stash": ([ctypes.c_int], None),
+    "stp_geometry_buffer_size_stash": ([ctypes.c_int, ctypes.POINTER(StpSettings)], ctypes.c_size_t),
     "stp_sparse_adam": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
                         ctypes.c_int),
     "stp_mcmc_relocation": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3, ctypes.c_int),
@@ -71,6 +73,7 @@ _SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blen
                    "stp_set_backward_background": "the alpha output and per-pixel background",
                    "stp_set_forward_invdepth": "the inverse-depth output", "stp_set_backward_invdepth": "the inverse-depth output",
                    "stp_set_forward_split_sh": "split SH inputs", "stp_set_backward_split_sh": "split SH inputs",
+                   "stp_set_forward_sh_stash": "the SH stash", "stp_geometry_buffer_size_stash": "the SH stash",
                    "stp_sparse_adam": "the sparse Adam step",
                    "stp_mcmc_relocation": "the 3DGS-MCMC kernels", "stp_mcmc_add_noise": "the 3DGS-MCMC kernels",
                    "stp_densify_stats": "the densification kernels", "stp_densify_plan": "the densification kernels",
@@ -583,7 +586,8 @@ def photometric_backward(image, target, maps, grad_out2):
 _GEOM_TYPES = {"depths": torch.float32, "clamped": torch.uint8, "radii": torch.int32, "rects2D": torch.float32,
                "means2D": torch.float32, "cov3D": torch.float32, "cov3D_inv": torch.float32,
                "conic_opacity": torch.float32, "rgb": torch.float32, "tiles_touched": torch.int32,
-               "point_offsets": torch.int32, "invz": torch.float32}
+               "point_offsets": torch.int32, "invz": torch.float32,
+               "sh_stash": torch.float32}  # (9, P) planes; only in the buffer of a forward that stashed (stp_set_forward_sh_stash)
 _BIN_TYPES = {"point_list": torch.int32, "point_list_unsorted": torch.int32, "keys": torch.int64, "keys_unsorted": torch.int64}
 _IMG_TYPES = {"final_T": torch.float32, "n_contrib": torch.int32, "ranges": torch.int32, "tile_flags": torch.int32,
               "blend_log": torch.int16}  # the last two exist only in a buffer of a recording forward
@@ -602,7 +606,17 @@ def _view(buf: torch.Tensor, off: int, count: int, dtype) -> torch.Tensor:
     return buf[off:off + nbytes].view(dtype)
 
 
+def has_sh_stash(geomBuffer, P, settings_dict) -> bool:
+    """Does this geometry buffer carry an SH stash (include/stp_raster.h: stp_set_forward_sh_stash)?  Read from the three words the stashing
+    forward leaves in the buffer's first 256 bytes (magic, P, ~P)."""
+    if geomBuffer.numel() < 48:
+        return False
+    w = geomBuffer[32:44].view(torch.int32).cpu().tolist()
+    return (w[0] & 0xFFFFFFFF) == 0x53505453 and (w[1] & 0xFFFFFFFF) == int(P) and (w[2] & 0xFFFFFFFF) == (~int(P) & 0xFFFFFFFF)
+
+
 def geometry_array(geomBuffer, P, settings_dict, name):
+    """Named view of a sub-array of the geometry buffer ("sh_stash": nine planes of P floats, present only where has_sh_stash says so)."""
     s = settings_from_dict(settings_dict)
     off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
     if _load().stp_geometry_layout(int(P), ctypes.byref(s), name.encode(), ctypes.byref(off), ctypes.byref(cnt)) != 0:

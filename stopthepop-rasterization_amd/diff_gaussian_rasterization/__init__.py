@@ -113,6 +113,15 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
             ctx.log_lease = _C.LogLease(_C._device_index(means3D.device), _C.blend_log_bytes(rs.image_width, rs.image_height))
         else:
             sdict["_backward_mode"] = "resort"
+        # ... and, whatever the backward mode, let the SH colour kernel keep the nine direction derivatives the per-Gaussian backward would
+        # otherwise re-read the SH rows for (include/stp_raster.h: stp_set_forward_sh_stash)
+        sdict["_sh_stash"] = True
+    # gradients nobody receives (include/stp_raster.h: optional outputs of stp_backward): with SH coefficients / scale and rotation as inputs the
+    # backward neither allocates nor writes dL_dcolors / dL_dcov3D (their slots of its result are None)
+    if colors_precomp.numel() == 0:
+        sdict["_no_grad_colors"] = True
+    if cov3Ds_precomp.numel() == 0:
+        sdict["_no_grad_cov3D"] = True
     ctx.settings_dict = sdict
     # positional layout of _C.rasterize_gaussians (22 arguments)
     args = (bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
