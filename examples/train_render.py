@@ -3,7 +3,7 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--split-sh]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--split-sh] [--init-scales scene|knn]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
@@ -176,6 +176,10 @@ def main(argv=None):
     ap.add_argument("--split-sh", action="store_true",
                     help="the model keeps _features_dc and _features_rest as two parameters (two optimizer groups, the rest at a twentieth of the "
                          "learning rate, as upstream) and renders with dc=: no torch.cat per step (INTEGRATION.md section 3n)")
+    ap.add_argument("--init-scales", default="scene", choices=["scene", "knn"],
+                    help="knn: the model's initial _scaling comes from the points alone, as the trainers' GaussianModel.create_from_pcd sets it: "
+                         "log(sqrt(clamp_min(distCUDA2(xyz), 1e-7))) on all three axes, with `from simple_knn._C import distCUDA2` "
+                         "(INTEGRATION.md section 3p)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
@@ -198,6 +202,11 @@ def main(argv=None):
         for f in model.feature_params():
             f.mul_(0.3)
         model._opacity.sub_(1.0)
+        if args.init_scales == "knn":   # create_from_pcd's three lines, import included
+            from simple_knn._C import distCUDA2
+            dist2 = torch.clamp_min(distCUDA2(model._xyz.detach().float()), 0.0000001)
+            model._scaling.copy_(torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3))
+            print(f"initial scales from distCUDA2 over {dist2.numel()} points: mean 3-NN distance {float(torch.sqrt(dist2).mean()):.4f}")
     adc = args.strategy == "adc"
     if adc and args.optimizer != "sparse_adam":   # densify_and_prune wants the trainers' layout: one named group per tensor
         opt = torch.optim.Adam([*model.feature_groups(2e-2), {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},

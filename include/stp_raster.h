@@ -438,6 +438,24 @@ int stp_densify_scan(int P, const uint8_t* plan, void* scratch, size_t scratch_b
 int stp_densify_apply(int P, const uint8_t* plan, const uint32_t* offsets, const int64_t counts[3], int n_tensors, const StpDensifyTensor* tensors,
                       const float* noise /* (2 nS, 3) */, float split_shrink, int raw, void* stream);
 
+/* Extension (not in the reference): simple_knn's distCUDA2, the call 3DGS code bases initialise their scales with.  For `points`, P x 3
+   contiguous float32 on the device, mean_dist2[i] is the mean of the three smallest squared distances from point i to the points j != i
+   (by index: an exact duplicate of i is a neighbour at distance 0), in input order.  The search is exact and the result fixed to the bit:
+       dx = xj - xi, dy = yj - yi, dz = zj - zi      d2 = (dx * dx + dy * dy) + dz * dz      out[i] = ((b0 + b1) + b2) / 3.0f
+   in float32, every operation rounded to nearest once and none contracted, b0 <= b1 <= b2 the three smallest d2: the bits of a brute-force
+   evaluation in that order, whatever the cloud (the three smallest values of a multiset do not depend on ties or on the search order).
+   The points are sorted by 30-bit Morton codes over 1024 cells of equal count per axis (rocPRIM sorts), cut into boxes of STP_KNN_BOX,
+   and a workgroup per box searches the other boxes behind float32-conservative box tests.  No atomics: equal inputs give equal bits.  No host synchronisation and no allocation:
+   `scratch` is stp_knn_scratch_bytes(P) bytes of device memory, 16-byte aligned, free again when the kernels have run.
+   stp_knn_scratch_bytes is a function of P alone, 0 for P <= 0, non-decreasing in P, and does not overflow up to INT_MAX (32 bytes per
+   point and a little).  stp_knn_mean_dist2 returns the number of launches made (the library's sort counting as one; 0 for P == 0: nothing is
+   touched), or a negative StpStatus with the reason in the last-error text.  Refused BEFORE anything is launched
+   (STP_ERR_INVALID_ARGUMENT): a negative P, 1 <= P <= 3 (there are no three neighbours), a null pointer, a scratch that is too small or
+   misaligned. */
+#define STP_KNN_BOX 256
+size_t stp_knn_scratch_bytes(int P);
+int stp_knn_mean_dist2(int P, const float* points /* P x 3 */, void* scratch, size_t scratch_bytes, float* mean_dist2 /* P */, void* stream);
+
 /* Extension (not in the reference): the fused photometric loss of 3DGS trainers, (1 - lambda) * L1 + lambda * (1 - SSIM) -- upstream's
    l1_loss and ssim() with window_size = 11 and size_average = True, the pair the `fused-ssim` extension replaces.  `image` (x) and `target`
    (y) are `planes` contiguous float32 planes of H x W (a (C, H, W) or (B, C, H, W) tensor: planes = B * C), n = planes * H * W.  With

@@ -5,7 +5,8 @@
 builds libstp_raster.so (and the second library, libstp_raster_fma.so: INTEGRATION.md section 5) with hipcc for gfx950
 (make -C stopthepop-rasterization_amd/csrc [FMA_DEPTH=1]) and the native torch binding
 _stp_host with g++ (csrc/host/build_host.py: host code only -- no kernel goes through a torch extension, hence no hipify
-pass) and installs the package `diff_gaussian_rasterization` with both as package data.
+pass) and installs the package `diff_gaussian_rasterization` with both as package data, and beside it the package `simple_knn`
+(`from simple_knn._C import distCUDA2`, the import of every 3DGS trainer), which holds no binary of its own.
 The repository's test-side directories (oracle/, tests/, tools/) are not installed."""
 import os
 import subprocess
@@ -33,7 +34,7 @@ setup(
     name="diff_gaussian_rasterization",
     version="0.4.0",
     description="MI355X-native sorted Gaussian-splat rasterizer behind the StopThePop diff_gaussian_rasterization API",
-    packages=["diff_gaussian_rasterization"],
+    packages=["diff_gaussian_rasterization", "simple_knn"],
     package_dir={"": PKG_PARENT},
     package_data={"diff_gaussian_rasterization": ["libstp_raster.so", "libstp_raster_fma.so", "_stp_host*.so"]},
     cmdclass={"build_py": BuildWithLibrary},

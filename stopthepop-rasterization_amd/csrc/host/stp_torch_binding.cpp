@@ -80,6 +80,8 @@ struct Api {
     decltype(&stp_sparse_adam) sparse_adam = nullptr;
     decltype(&stp_mcmc_relocation) mcmc_relocation = nullptr;
     decltype(&stp_mcmc_add_noise) mcmc_add_noise = nullptr;
+    decltype(&stp_knn_scratch_bytes) knn_scratch_bytes = nullptr;
+    decltype(&stp_knn_mean_dist2) knn_mean_dist2 = nullptr;
     decltype(&stp_densify_stats) densify_stats = nullptr;
     decltype(&stp_densify_plan) densify_plan = nullptr;
     decltype(&stp_densify_scratch_bytes) densify_scratch_bytes = nullptr;
@@ -119,6 +121,8 @@ int load_library(const std::string& path)
     a.sparse_adam = reinterpret_cast<decltype(a.sparse_adam)>(dlsym(h, "stp_sparse_adam"));
     a.mcmc_relocation = reinterpret_cast<decltype(a.mcmc_relocation)>(dlsym(h, "stp_mcmc_relocation"));
     a.mcmc_add_noise = reinterpret_cast<decltype(a.mcmc_add_noise)>(dlsym(h, "stp_mcmc_add_noise"));
+    a.knn_scratch_bytes = reinterpret_cast<decltype(a.knn_scratch_bytes)>(dlsym(h, "stp_knn_scratch_bytes"));
+    a.knn_mean_dist2 = reinterpret_cast<decltype(a.knn_mean_dist2)>(dlsym(h, "stp_knn_mean_dist2"));
     a.densify_stats = reinterpret_cast<decltype(a.densify_stats)>(dlsym(h, "stp_densify_stats"));
     a.densify_plan = reinterpret_cast<decltype(a.densify_plan)>(dlsym(h, "stp_densify_plan"));
     a.densify_scratch_bytes = reinterpret_cast<decltype(a.densify_scratch_bytes)>(dlsym(h, "stp_densify_scratch_bytes"));
@@ -758,6 +762,34 @@ int mcmc_add_noise(const torch::Tensor& xyz, const torch::Tensor& scales, const 
     return rc;
 }
 
+// == simple_knn's distCUDA2 (extension, include/stp_raster.h: stp_knn_mean_dist2; knn_mean_dist2 in __init__.py and simple_knn._C.distCUDA2), on the
+// caller's current stream: -> (P,) float32, the mean of the three smallest squared distances to the other points, in input order.  The scratch is
+// a torch tensor of the caching allocator, returned to it when this function leaves (the allocator keeps it for the stream until the kernels
+// have run).  No host synchronisation.
+torch::Tensor knn_mean_dist2(const torch::Tensor& points_in)
+{
+    static const char* const who = "knn_mean_dist2";
+    need_library();
+    if (!g_api.knn_mean_dist2 || !g_api.knn_scratch_bytes)
+        throw std::runtime_error("knn_mean_dist2: the loaded libstp_raster.so does not export stp_knn_mean_dist2 (a library built before the nearest-neighbour kernels): rebuild it");
+    mcmc_check_float(who, "points", points_in);
+    TORCH_CHECK(points_in.dim() == 2 && points_in.size(1) == 3, who, ": points must be (P, 3), got ", points_in.sizes());
+    const int64_t P = points_in.size(0);
+    TORCH_CHECK(P < (1ll << 31), who, ": points: ", P, " rows >= 2^31");
+    TORCH_CHECK(P == 0 || P >= 4, who, ": points: ", P, " rows: the mean over three neighbours needs at least 4 points");
+    mcmc_check_device(who, "points", points_in, points_in);
+    const torch::Tensor points = points_in.detach().contiguous();
+    const c10::hip::HIPGuard guard(points.device().index());
+    torch::Tensor out = torch::empty({P}, points.options());
+    if (P == 0) return out;
+    const size_t bytes = g_api.knn_scratch_bytes((int)P);
+    torch::Tensor scratch = torch::empty({(int64_t)bytes}, points.options().dtype(torch::kByte));
+    const int rc = g_api.knn_mean_dist2((int)P, points.data_ptr<float>(), scratch.data_ptr(), bytes, out.data_ptr<float>(),
+                                        (void*)c10::hip::getCurrentHIPStream(points.device().index()).stream());
+    if (rc < 0) raise_last(rc);
+    return out;
+}
+
 // == densification (extension, include/stp_raster.h: stp_densify_stats / _plan / _scan / _apply; densification_stats_, densify_plan,
 // densify_tensors and densify_and_prune in __init__.py), on the caller's current stream.  As above, what is wrong with the tensors themselves is
 // refused first and where they live last.  Only densify_scan synchronises with the host (inside the library: the new row count).
@@ -1093,6 +1125,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("sparse_adam", &sparse_adam);
     m.def("compute_relocation", &compute_relocation);
     m.def("mcmc_add_noise", &mcmc_add_noise);
+    m.def("knn_mean_dist2", &knn_mean_dist2);
     m.def("densify_stats", &densify_stats);
     m.def("densify_plan", &densify_plan);
     m.def("densify_scan", &densify_scan);

@@ -1,6 +1,6 @@
 // stp_api.hip -- the C ABI of libstp_raster.so (declared in include/stp_raster.h): the per-thread error state, the argument checks
 // and frame description that forward and backward share, the one-shot per-thread requests, and the backward, mark-visible, sparse
-// Adam, 3DGS-MCMC, densification and photometric-loss calls.  Replaces CudaRasterizer::Rasterizer::{backward,markVisible} (reference cuda_rasterizer/rasterizer_impl.cu:417-526,
+// Adam, 3DGS-MCMC, nearest-neighbour, densification and photometric-loss calls.  Replaces CudaRasterizer::Rasterizer::{backward,markVisible} (reference cuda_rasterizer/rasterizer_impl.cu:417-526,
 // 161-173).  The forward is stp_forward.hip, the scratch buffers and their queries stp_buffers.hip, the stage timer stp_timer.hip.
 //
 // The calls are re-entrant: the scratch buffers belong to the caller, stp_last_error and the requests are per thread, and the
@@ -359,6 +359,26 @@ int stp_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rota
     hipError_t e;
     const int launches = launch_mcmc_add_noise(P, xyz, scales, rotations, opacities, noise, noise_scale, k, x0, raw, (hipStream_t)stream, &e);
     if (e != hipSuccess) return fail_hip(e, "mcmc_add_noise launch");
+    return launches;
+}
+
+size_t stp_knn_scratch_bytes(int P) { return knn_scratch_bytes(P); }
+
+int stp_knn_mean_dist2(int P, const float* points, void* scratch, size_t scratch_bytes, float* mean_dist2, void* stream)
+{
+    // everything is checked before the first launch
+    if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_knn_mean_dist2: negative P");
+    if (P == 0) return 0;
+    if (P < 4)
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_knn_mean_dist2: P = " + std::to_string(P) + ": the mean over three neighbours needs at least 4 points");
+    if (!points || !scratch || !mean_dist2) return fail(STP_ERR_INVALID_ARGUMENT, "stp_knn_mean_dist2: null pointer");
+    const size_t need = knn_scratch_bytes(P);
+    if (scratch_bytes < need)
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_knn_mean_dist2: scratch of " + std::to_string(scratch_bytes) + " bytes, stp_knn_scratch_bytes(P) = " + std::to_string(need));
+    if (reinterpret_cast<uintptr_t>(scratch) & 15u) return fail(STP_ERR_INVALID_ARGUMENT, "stp_knn_mean_dist2: scratch is not 16-byte aligned");
+    hipError_t e;
+    const int launches = launch_knn_mean_dist2(P, points, scratch, mean_dist2, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "knn_mean_dist2");
     return launches;
 }
 

@@ -314,6 +314,12 @@ int launch_photometric_forward(int planes, int H, int W, const float* image, con
 int launch_photometric_backward(int planes, int H, int W, const float* image, const float* target, const float* maps, const float* dL_dout2,
                                 float* dL_dimage, hipStream_t st, hipError_t* err);
 
+// the 3-nearest-neighbour mean squared distance (stp_knn.hip) over arguments stp_knn_mean_dist2 has validated (P in [4, 2^31), a scratch of
+// knn_scratch_bytes(P) bytes, 16-byte aligned): returns the launches made (the library's sort counting as one), *err = the error that ended
+// them early (or hipSuccess).  knn_scratch_bytes: 0 for P <= 0, non-decreasing in P, no overflow up to INT_MAX.
+size_t knn_scratch_bytes(int P);
+int launch_knn_mean_dist2(int P, const float* points, void* scratch, float* mean_dist2, hipStream_t st, hipError_t* err);
+
 uint32_t higher_msb(uint32_t n);
 
 } // namespace stp

@@ -57,6 +57,8 @@ _OPTIONAL_SYMBOLS = {
                         ctypes.c_int),
     "stp_mcmc_relocation": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3, ctypes.c_int),
     "stp_mcmc_add_noise": ([ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_float] * 3 + [ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "stp_knn_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t),
+    "stp_knn_mean_dist2": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2, ctypes.c_int),
     "stp_densify_stats": ([ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "stp_densify_plan": ([ctypes.c_int] + [ctypes.c_void_p] * 8, ctypes.c_int),
     "stp_densify_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t),
@@ -76,6 +78,7 @@ _SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blen
                    "stp_set_forward_sh_stash": "the SH stash", "stp_geometry_buffer_size_stash": "the SH stash",
                    "stp_sparse_adam": "the sparse Adam step",
                    "stp_mcmc_relocation": "the 3DGS-MCMC kernels", "stp_mcmc_add_noise": "the 3DGS-MCMC kernels",
+                   "stp_knn_scratch_bytes": "the nearest-neighbour kernels", "stp_knn_mean_dist2": "the nearest-neighbour kernels",
                    "stp_densify_stats": "the densification kernels", "stp_densify_plan": "the densification kernels",
                    "stp_densify_scratch_bytes": "the densification kernels", "stp_densify_scan": "the densification kernels",
                    "stp_densify_apply": "the densification kernels",
@@ -514,6 +517,23 @@ def mcmc_add_noise(xyz, scales, rotations, opacities, noise, noise_scale, k, x0,
     (P, 1), noise (P, 3), all float32 on one GPU.  Returns the kernel launches made (1; 0 for P == 0)."""
     _require("stp_mcmc_add_noise")
     return int((_host or _native()).mcmc_add_noise(xyz, scales, rotations, opacities, noise, float(noise_scale), float(k), float(x0), bool(raw)))
+
+
+KNN_BOX = 256   # == STP_KNN_BOX (include/stp_raster.h): points per box of the search, and lanes per workgroup
+
+
+def knn_scratch_bytes(P: int) -> int:
+    """Bytes of device scratch stp_knn_mean_dist2 needs for P points (include/stp_raster.h): a function of P alone, non-decreasing in P."""
+    return int(_require("stp_knn_scratch_bytes")(int(P)))
+
+
+def knn_mean_dist2(points):
+    """simple_knn's distCUDA2 (extension, include/stp_raster.h: stp_knn_mean_dist2), on the current stream, without host synchronisation:
+    points (P, 3) float32 on a GPU -> (P,) float32, the mean of the three smallest squared distances from each point to the others, in
+    input order.  Exact, and the bits of a float32 brute force in the header's evaluation order.  P == 0 gives an empty tensor; P in 1..3
+    is refused (there are no three neighbours)."""
+    _require("stp_knn_mean_dist2")
+    return (_host or _native()).knn_mean_dist2(points)
 
 
 class StpDensifyRule(ctypes.Structure):

@@ -27,6 +27,7 @@ from . import _C
 __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes", "SortSettings", "CullingSettings",
            "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam",
            "photometric_terms", "fused_ssim", "photometric_loss", "compute_relocation", "mcmc_add_noise_",
+           "knn_mean_dist2", "distCUDA2", "dist_cuda2",
            "densification_stats_", "densify_plan", "densify_tensors", "densify_and_prune"]
 
 
@@ -652,6 +653,22 @@ def mcmc_add_noise_(xyz: torch.Tensor, scales: torch.Tensor, rotations: torch.Te
     on different devices, an xyz that is not contiguous."""
     _C.mcmc_add_noise(xyz.detach(), scales.detach(), rotations.detach(), opacities.detach(), noise.detach(), noise_scale, k, x0, raw)
     return xyz
+
+
+def knn_mean_dist2(points: torch.Tensor) -> torch.Tensor:
+    """simple_knn's distCUDA2 (extension; include/stp_raster.h: stp_knn_mean_dist2) -- what `GaussianModel.create_from_pcd` initialises the
+    scales with: for points (P, 3) float32 on a GPU, out[i] is the mean of the three smallest squared distances from point i to the points
+    j != i (by index: an exact duplicate is a neighbour at distance 0), float32, (P,), in input order, on the current stream and without
+    host synchronisation.  The search is exact (Morton-sorted boxes behind float32-conservative box tests) and the result is fixed to the
+    bit: d2 = (dx * dx + dy * dy) + dz * dz and ((b0 + b1) + b2) / 3 in float32 with every operation rounded once -- the bits of a brute
+    force in that order, whatever the cloud.  Equal inputs give equal bits.  A non-contiguous input is made contiguous; P == 0 gives an
+    empty (0,) tensor; the result never requires grad.  Refused with a RuntimeError naming the argument: another dtype ("points: expected
+    float32"), another shape ("points must be (P, 3)"), P in 1..3 ("needs at least 4 points"; upstream returns garbage there), a CPU
+    tensor ("no CPU path").  `simple_knn._C.distCUDA2` is this function."""
+    return _C.knn_mean_dist2(points.detach())
+
+
+dist_cuda2 = distCUDA2 = knn_mean_dist2
 
 
 def _f32(x) -> float:
