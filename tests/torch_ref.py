@@ -10,7 +10,8 @@ pixel's own depth-along-ray, i.e. what the resorting modes converge to at low de
 One dense renderer, render_core(), serves every float64 yardstick of the tests: render() / loss_and_grads() here, and through its hooks
 the camera gradients (torch_ref_camera.py), absgrad (torch_ref_absgrad.py), the blend statistics (torch_ref_blend_stats.py) and the
 per-Gaussian bound on the colour gradient (torch_ref_colour_bound.py).  A further yardstick is a further hook, not a copy;
-tests/test_yardstick_pin_cpu.py holds the first four to recorded values, tests/test_upstream_grad_cpu.py the fifth.
+tests/test_yardstick_pin_cpu.py holds the first four to recorded values, tests/test_upstream_grad_cpu.py the fifth.  The part of it that
+sees one Gaussian at a time is per_gaussian(), on which torch_ref_per_gaussian.py differentiates the per-Gaussian backward alone.
 """
 from __future__ import annotations
 
@@ -52,24 +53,17 @@ def eval_sh(deg, sh, dirs):
     return res + 0.5
 
 
-def render_core(scene, order="global", proper_ewa_scaling=False, use_cov3D_precomp=False, depth_key="z", camera_leaves=False,
-                offset_leaves=False):
-    """The one dense renderer.  Returns (image (3,H,W) float64 tensor, dict of leaf tensors with requires_grad, details).
-
-    camera_leaves: viewmatrix, projmatrix and campos are leaves too (torch_ref_camera.py), with two conventions where the camera enters:
-      * the three camera tensors are INDEPENDENT leaves, as the rasterizer reads them (it never checks that projmatrix = viewmatrix @ P
-        or that campos is the camera centre); culling, tile binning and every sort key see the detached camera;
-      * the 1.3 * tan_fov clamp of the view-space mean inside the EWA Jacobian is differentiated as the rasterizer differentiates it for
-        means3D (the reference's backward.cu): a clamped coordinate is a constant -- it carries no gradient to the view-space mean, and
-        its value enters J as a number.  Without the switch clamp(x / z) * z is differentiated, which also moves with z; the two agree
-        for every Gaussian inside the band, where the switch puts x itself into J and not (x / z) * z: an ulp or two on the image.
-    offset_leaves: two N x P zero leaves, "offsets_x" and "offsets_y", are added to the pixel offsets dx, dy (torch_ref_absgrad.py).
-    details: what torch_ref_blend_stats.py reads, without gradients.  Per (pixel, Gaussian) pair, N x P in the Gaussians' own order:
-    "w" the blend weight alpha * T (0 where the pair is not blended), "blended", "cand" (a candidate: in the tile rectangle, visible,
-    power <= 0 and, in the exact order, not behind the camera -- whatever its alpha) and "alpha"; in each pixel's sorted order, with the
-    sort index "idx": "test_T" = T * (1 - alpha) and "reached" (no entry in front of it saturated the pixel; the saturating entry
-    itself is reached); "T_final" (N,)."""
-    dd = torch.float64
+def per_gaussian(scene, proper_ewa_scaling=False, use_cov3D_precomp=False, camera_leaves=False, dtype=torch.float64, hooks=None):
+    """The per-Gaussian part of render_core, from the leaves to what the render half reads of a Gaussian: the NDC mean, the conic, the
+    opacity actually blended (with the proper_ewa_scaling factor) and the colour.  Returns (dict of leaf tensors with requires_grad, dict
+    of intermediates "ndc" (P,2), "conic" (three (P,) tensors: xx, xy, yy), "opacity" (P,), "colour" (P,3) and what render_core and
+    torch_ref_per_gaussian.py read besides).  No pixel enters, and no Gaussian reads another's row.
+    dtype: float64 for every yardstick; torch_ref_per_gaussian.py also evaluates this function in float32 to measure what float32 can do.
+    hooks: None for every yardstick of render_core.  torch_ref_per_gaussian.py passes the rasterizer's two conventions that are not
+    plain derivatives: "conic" (a function of the three conic entries and det) and "ewa_factor" (of a0, b0, c0, a, c); its scale() reads
+    the view matrix through "view_in_covariance" where it enters the covariance, to tell that path from the one through the mean."""
+    hooks = hooks or {}
+    dd = dtype
     t = lambda a: torch.tensor(np.asarray(a), dtype=dd)
     W, H = scene.W, scene.H
     V, PM, INV = t(scene.viewmatrix), t(scene.projmatrix), t(scene.inv_viewprojmatrix)
@@ -89,6 +83,8 @@ def render_core(scene, order="global", proper_ewa_scaling=False, use_cov3D_preco
     Sigma = Rm @ Sd @ Rm.transpose(1, 2)
     if use_cov3D_precomp:
         c6 = torch.stack([Sigma[:, 0, 0], Sigma[:, 0, 1], Sigma[:, 0, 2], Sigma[:, 1, 1], Sigma[:, 1, 2], Sigma[:, 2, 2]], 1)
+        if "cov3D_precomp" in scene.meta:   # the very array a caller passed, not the float64 one of the same Gaussians
+            c6 = t(scene.meta["cov3D_precomp"])
         c6 = c6.detach().clone().requires_grad_(True); leaves["cov3D_precomp"] = c6
         Sigma_used = torch.stack([c6[:, 0], c6[:, 1], c6[:, 2], c6[:, 1], c6[:, 3], c6[:, 4], c6[:, 2], c6[:, 4], c6[:, 5]], 1).reshape(-1, 3, 3)
     else:
@@ -96,7 +92,6 @@ def render_core(scene, order="global", proper_ewa_scaling=False, use_cov3D_preco
 
     pv = means @ V[:3, :3] + V[3, :3]                  # view-space means (row-vector convention)
     tz = pv[:, 2]
-    near_ok = (tz > 0.2).detach()
     fx, fy = W / (2 * scene.tanfovx), H / (2 * scene.tanfovy)
     limx, limy = 1.3 * scene.tanfovx, 1.3 * scene.tanfovy
     if camera_leaves:
@@ -111,16 +106,20 @@ def render_core(scene, order="global", proper_ewa_scaling=False, use_cov3D_preco
         tyc = torch.clamp(pv[:, 1] / tz, -limy, limy) * tz
     zero = torch.zeros_like(tz)
     J = torch.stack([fx / tz, zero, -fx * txc / (tz * tz), zero, fy / tz, -fy * tyc / (tz * tz)], 1).reshape(-1, 2, 3)
-    Wm = V[:3, :3].T  # p_view = Wm p + t
+    Wm = (hooks["view_in_covariance"](V) if "view_in_covariance" in hooks else V)[:3, :3].T  # p_view = Wm p + t
     JW = J @ Wm
     cov2 = JW @ Sigma_used @ JW.transpose(1, 2)
     a0, b0, c0 = cov2[:, 0, 0], cov2[:, 0, 1], cov2[:, 1, 1]
     a, b, c = a0 + 0.3, b0, c0 + 0.3
     det = a * c - b * b
     o = opac[:, 0]
-    if proper_ewa_scaling:
+    if proper_ewa_scaling and "ewa_factor" in hooks:
+        o = o * hooks["ewa_factor"](a0, b0, c0, a, c)
+    elif proper_ewa_scaling:
         o = o * torch.sqrt(torch.clamp((a0 * c0 - b0 * b0) / det, min=0.000025))
     cA, cB, cC = c / det, -b / det, a / det
+    if "conic" in hooks:
+        cA, cB, cC = hooks["conic"](cA, cB, cC, det)
 
     ph = torch.cat([means, torch.ones(P, 1, dtype=dd)], 1) @ PM
     ndc = ph[:, :2] / (ph[:, 3:4] + 1e-7) + ndc_shift
@@ -134,6 +133,36 @@ def render_core(scene, order="global", proper_ewa_scaling=False, use_cov3D_preco
         col = torch.clamp(eval_sh(scene.sh_degree, shs, d), min=0.0)
     else:
         col = t(scene.colors_precomp).requires_grad_(True); leaves["colors_precomp"] = col
+
+    return leaves, dict(ndc=ndc, conic=(cA, cB, cC), opacity=o, colour=col, means=means, scales=scales, Rm=Rm, Sigma=Sigma, pv=pv,
+                        a=a, c=c, det=det, mx=mx, my=my, cam=cam, bg=bg, INV=INV)
+
+
+def render_core(scene, order="global", proper_ewa_scaling=False, use_cov3D_precomp=False, depth_key="z", camera_leaves=False,
+                offset_leaves=False):
+    """The one dense renderer.  Returns (image (3,H,W) float64 tensor, dict of leaf tensors with requires_grad, details).
+
+    camera_leaves: viewmatrix, projmatrix and campos are leaves too (torch_ref_camera.py), with two conventions where the camera enters:
+      * the three camera tensors are INDEPENDENT leaves, as the rasterizer reads them (it never checks that projmatrix = viewmatrix @ P
+        or that campos is the camera centre); culling, tile binning and every sort key see the detached camera;
+      * the 1.3 * tan_fov clamp of the view-space mean inside the EWA Jacobian is differentiated as the rasterizer differentiates it for
+        means3D (the reference's backward.cu): a clamped coordinate is a constant -- it carries no gradient to the view-space mean, and
+        its value enters J as a number.  Without the switch clamp(x / z) * z is differentiated, which also moves with z; the two agree
+        for every Gaussian inside the band, where the switch puts x itself into J and not (x / z) * z: an ulp or two on the image.
+    offset_leaves: two N x P zero leaves, "offsets_x" and "offsets_y", are added to the pixel offsets dx, dy (torch_ref_absgrad.py).
+    details: what torch_ref_blend_stats.py reads, without gradients.  Per (pixel, Gaussian) pair, N x P in the Gaussians' own order:
+    "w" the blend weight alpha * T (0 where the pair is not blended), "blended", "cand" (a candidate: in the tile rectangle, visible,
+    power <= 0 and, in the exact order, not behind the camera -- whatever its alpha) and "alpha"; in each pixel's sorted order, with the
+    sort index "idx": "test_T" = T * (1 - alpha) and "reached" (no entry in front of it saturated the pixel; the saturating entry
+    itself is reached); "T_final" (N,).  And, WITH their graph, "per_gaussian": per_gaussian()'s intermediates, through which alone
+    the image depends on the leaves (torch_ref_per_gaussian.py)."""
+    dd = torch.float64
+    leaves, pg = per_gaussian(scene, proper_ewa_scaling, use_cov3D_precomp, camera_leaves)
+    means, scales, Rm, cam, bg, INV = pg["means"], pg["scales"], pg["Rm"], pg["cam"], pg["bg"], pg["INV"]
+    (cA, cB, cC), o, col, tz = pg["conic"], pg["opacity"], pg["colour"], pg["pv"][:, 2]
+    a, c, det, mx, my = pg["a"], pg["c"], pg["det"], pg["mx"], pg["my"]
+    W, H, P = scene.W, scene.H, means.shape[0]
+    near_ok = (tz > 0.2).detach()
 
     # binning, non-differentiable: 3.33 sigma rectangle of tiles (no culling options here)
     with torch.no_grad():
@@ -199,6 +228,7 @@ def render_core(scene, order="global", proper_ewa_scaling=False, use_cov3D_preco
         unsort = lambda m: torch.zeros_like(m).scatter(1, idx, m)
         details = {"w": unsort(wgt), "blended": unsort(alive & keep_s), "cand": cand, "alpha": alpha.detach(), "idx": idx,
                    "test_T": test_T, "reached": keep_s & ((stops - stop.to(torch.int64)) == 0), "T_final": T_final.detach()}
+    details["per_gaussian"] = pg
     return img.T.reshape(3, H, W), leaves, details
 
 
