@@ -33,8 +33,9 @@ def command():
 
 
 def up_to_date():
-    return os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(SRC), os.path.getmtime(os.path.join(HERE, "..", "..", "..", "include", "stp_raster.h")),
-                                                                os.path.getmtime(__file__))
+    # every file of this directory (the .cpp, the headers it includes, this script) and the C ABI's header
+    deps = [e.path for e in os.scandir(HERE) if e.is_file()] + [os.path.join(HERE, "..", "..", "..", "include", "stp_raster.h")]
+    return os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(p) for p in deps)
 
 
 def main():

@@ -1,0 +1,390 @@
+// stp_bind_train.h -- the training kernels beside the rasterizer: sparse Adam, 3DGS-MCMC, nearest neighbours, densification, the photometric loss.
+// All run on the caller's current stream.  What is wrong with the tensors themselves is refused first, where they live last (stp_tensor_checks.h).
+#pragma once
+
+#include <limits>
+#include <tuple>
+
+#include <c10/hip/HIPGuard.h>
+
+#include "stp_tensor_checks.h"
+
+namespace {
+// == the fused sparse Adam step (extension, include/stp_raster.h: stp_sparse_adam; the step of SparseGaussianAdam in __init__.py): one library call
+// for all quadruples (param, grad, exp_avg, exp_avg_sq), on the caller's current stream.  visible: bool / uint8 (non-zero = visible) or the
+// int32 radii of the forward (> 0 = visible), N elements, read as it is.  Returns the kernel launches the library made.
+int sparse_adam(const std::vector<torch::Tensor>& params, const std::vector<torch::Tensor>& grads, const std::vector<torch::Tensor>& exp_avgs,
+                const std::vector<torch::Tensor>& exp_avg_sqs, const torch::Tensor& visible, const std::vector<double>& lrs, const std::vector<double>& epss,
+                const double beta1, const double beta2, const int64_t N)
+{
+    need_library();
+    require(g_api.sparse_adam, "sparse_adam");
+    const size_t n = params.size();
+    TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n && lrs.size() == n && epss.size() == n,
+                "sparse_adam: params, grads, exp_avgs, exp_avg_sqs, lrs and epss must have one entry per tensor");
+    TORCH_CHECK(N >= 0 && N < (1ll << 31), "sparse_adam: N out of range");
+    TORCH_CHECK(visible.defined() && visible.is_cuda(), GPU_ONLY);
+    const torch::Device dev = visible.device();
+    const auto vt = visible.scalar_type();
+    TORCH_CHECK(vt == torch::kBool || vt == torch::kByte || vt == torch::kInt32, "sparse_adam: visible must be bool, uint8 or int32 (radii), got ", vt);
+    TORCH_CHECK(visible.numel() == N && visible.is_contiguous(), "sparse_adam: visible must be contiguous with N = ", N, " elements, got ", visible.numel());
+    std::vector<StpAdamTensor> table(n);
+    for (size_t k = 0; k < n; k++) {
+        const torch::Tensor* quad[4] = {&params[k], &grads[k], &exp_avgs[k], &exp_avg_sqs[k]};
+        static const char* const names[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
+        for (int j = 0; j < 4; j++) {
+            const torch::Tensor& t = *quad[j];
+            TORCH_CHECK(t.defined(), "sparse_adam: tensor ", k, ": ", names[j], " is undefined");
+            TORCH_CHECK(t.is_cuda(), GPU_ONLY);
+            TORCH_CHECK(t.device() == dev, "expected all tensors on ", dev, ", got one on ", t.device());
+            TORCH_CHECK(t.scalar_type() == torch::kFloat32, "expected float32 tensor, got ", t.scalar_type());
+            TORCH_CHECK(t.is_contiguous(), "sparse_adam: tensor ", k, ": ", names[j], " must be contiguous (it is updated in place)");
+            TORCH_CHECK(t.sizes() == params[k].sizes(), "sparse_adam: tensor ", k, ": ", names[j], " has shape ", t.sizes(), ", param has ", params[k].sizes());
+        }
+        table[k] = StpAdamTensor{params[k].data_ptr<float>(), grads[k].data_ptr<float>(), exp_avgs[k].data_ptr<float>(), exp_avg_sqs[k].data_ptr<float>(),
+                                 (long long)params[k].numel(), (float)lrs[k], (float)epss[k]};
+    }
+    const c10::hip::HIPGuard guard(dev.index());
+    return checked(g_api.sparse_adam((int)n, table.data(), (int)N, visible.data_ptr(), vt == torch::kInt32 ? 1 : 0, (float)beta1, (float)beta2, current_stream(dev)));
+}
+
+// == the 3DGS-MCMC kernels (extension, include/stp_raster.h: stp_mcmc_relocation / stp_mcmc_add_noise; compute_relocation and mcmc_add_noise_ in
+// __init__.py).
+// -> (opacity_new of opacity_old's shape, scale_new (n, 3)); upstream's name and argument order.  binoms: checked for its shape only -- the kernel
+// has its own binomials -- and n_max is the clamp's upper bound plus one.  N is NOT clamped in place (upstream's is).
+std::tuple<torch::Tensor, torch::Tensor> compute_relocation(const torch::Tensor& opacity_old, const torch::Tensor& scale_old, const torch::Tensor& N,
+                                                            const c10::optional<torch::Tensor>& binoms_in, const int64_t n_max)
+{
+    static const char* const who = "compute_relocation";
+    need_library();
+    require(g_api.mcmc_relocation, who);
+    check_float(who, "opacity_old", opacity_old);
+    check_float(who, "scale_old", scale_old);
+    TORCH_CHECK(N.defined() && (N.scalar_type() == torch::kInt32 || N.scalar_type() == torch::kInt64), who, ": N: expected int32 or int64 tensor, got ", N.scalar_type());
+    TORCH_CHECK(n_max >= 2 && n_max <= 51, who, ": n_max must be in [2, 51], got ", n_max);
+    if (binoms_in.has_value()) {
+        const torch::Tensor& binoms = *binoms_in;
+        check_float(who, "binoms", binoms);
+        TORCH_CHECK(binoms.dim() == 2 && binoms.size(0) == n_max && binoms.size(1) == n_max, who, ": binoms must be (n_max, n_max) = (", n_max, ", ", n_max, "), got ", binoms.sizes());
+    }
+    check_column(who, "opacity_old", opacity_old);
+    check_column(who, "N", N);
+    const int64_t n = opacity_old.size(0);
+    TORCH_CHECK(n < (1ll << 31), who, ": opacity_old: ", n, " rows >= 2^31");
+    check_rows(who, "scale_old", scale_old, n, 3);
+    TORCH_CHECK(N.size(0) == n, who, ": N has ", N.size(0), " rows, opacity_old has ", n);
+    check_device(who, "scale_old", scale_old, opacity_old);
+    check_device(who, "N", N, opacity_old);
+    check_device(who, "opacity_old", opacity_old, opacity_old);
+    const torch::Tensor o = opacity_old.contiguous(), s = scale_old.contiguous(), cnt = N.contiguous();
+    const c10::hip::HIPGuard guard(o.device().index());
+    torch::Tensor o_new = torch::empty(o.sizes(), o.options()), s_new = torch::empty(s.sizes(), s.options());
+    if (n == 0) return {o_new, s_new};
+    checked(g_api.mcmc_relocation((int)n, o.data_ptr<float>(), s.data_ptr<float>(), cnt.data_ptr(), cnt.scalar_type() == torch::kInt64 ? 1 : 0, (int)n_max,
+                                  o_new.data_ptr<float>(), s_new.data_ptr<float>(), current_stream(o.device())));
+    return {o_new, s_new};
+}
+
+// in place on xyz (which must be contiguous: it is updated where it lies); the other four are made contiguous.  Returns the launches made.
+int mcmc_add_noise(const torch::Tensor& xyz, const torch::Tensor& scales, const torch::Tensor& rotations, const torch::Tensor& opacities,
+                   const torch::Tensor& noise, const double noise_scale, const double k, const double x0, const bool raw)
+{
+    static const char* const who = "mcmc_add_noise";
+    need_library();
+    require(g_api.mcmc_add_noise, who);
+    const torch::Tensor* all[5] = {&xyz, &scales, &rotations, &opacities, &noise};
+    static const char* const names[5] = {"xyz", "scales", "rotations", "opacities", "noise"};
+    for (int j = 0; j < 5; j++) check_float(who, names[j], *all[j]);
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, who, ": xyz must be (P, 3), got ", xyz.sizes());
+    const int64_t P = xyz.size(0);
+    TORCH_CHECK(P < (1ll << 31), who, ": xyz: ", P, " rows >= 2^31");
+    check_rows(who, "scales", scales, P, 3);
+    check_rows(who, "rotations", rotations, P, 4);
+    check_rows(who, "noise", noise, P, 3);
+    check_column(who, "opacities", opacities);
+    TORCH_CHECK(opacities.size(0) == P, who, ": opacities has ", opacities.size(0), " rows, xyz has ", P);
+    for (int j = 1; j < 5; j++) check_device(who, names[j], *all[j], xyz);
+    check_device(who, "xyz", xyz, xyz);
+    TORCH_CHECK(xyz.is_contiguous(), who, ": xyz must be contiguous (it is updated in place)");
+    if (P == 0) return 0;
+    const torch::Tensor s = scales.contiguous(), q = rotations.contiguous(), o = opacities.contiguous(), w = noise.contiguous();
+    const c10::hip::HIPGuard guard(xyz.device().index());
+    return checked(g_api.mcmc_add_noise((int)P, xyz.data_ptr<float>(), s.data_ptr<float>(), q.data_ptr<float>(), o.data_ptr<float>(), w.data_ptr<float>(),
+                                        (float)noise_scale, (float)k, (float)x0, raw ? 1 : 0, current_stream(xyz.device())));
+}
+
+// == simple_knn's distCUDA2 (extension, include/stp_raster.h: stp_knn_mean_dist2; knn_mean_dist2 in __init__.py and simple_knn._C.distCUDA2), on the
+// caller's current stream: -> (P,) float32, the mean of the three smallest squared distances to the other points, in input order.  The scratch is
+// a torch tensor of the caching allocator, returned to it when this function leaves (the allocator keeps it for the stream until the kernels
+// have run).  No host synchronisation.
+torch::Tensor knn_mean_dist2(const torch::Tensor& points_in)
+{
+    static const char* const who = "knn_mean_dist2";
+    need_library();
+    require(g_api.knn_mean_dist2, who);
+    require(g_api.knn_scratch_bytes, who);
+    check_float(who, "points", points_in);
+    TORCH_CHECK(points_in.dim() == 2 && points_in.size(1) == 3, who, ": points must be (P, 3), got ", points_in.sizes());
+    const int64_t P = points_in.size(0);
+    TORCH_CHECK(P < (1ll << 31), who, ": points: ", P, " rows >= 2^31");
+    TORCH_CHECK(P == 0 || P >= 4, who, ": points: ", P, " rows: the mean over three neighbours needs at least 4 points");
+    check_device(who, "points", points_in, points_in);
+    const torch::Tensor points = points_in.detach().contiguous();
+    const c10::hip::HIPGuard guard(points.device().index());
+    torch::Tensor out = torch::empty({P}, points.options());
+    if (P == 0) return out;
+    const size_t bytes = g_api.knn_scratch_bytes((int)P);
+    torch::Tensor scratch = torch::empty({(int64_t)bytes}, points.options().dtype(torch::kByte));
+    checked(g_api.knn_mean_dist2((int)P, points.data_ptr<float>(), scratch.data_ptr(), bytes, out.data_ptr<float>(), current_stream(points.device())));
+    return out;
+}
+
+// == densification (extension, include/stp_raster.h: stp_densify_stats / _plan / _scan / _apply; densification_stats_, densify_plan,
+// densify_tensors and densify_and_prune in __init__.py).  Only densify_scan synchronises with the host (inside the library: the new row count).
+void densify_check_column(const char* who, const char* name, const torch::Tensor& t, const int64_t P)
+{
+    check_float(who, name, t);
+    check_column(who, name, t);
+    TORCH_CHECK(t.size(0) == P, who, ": ", name, " has ", t.size(0), " rows, expected ", P);
+}
+void densify_check_P(const char* who, const int64_t P) { TORCH_CHECK(3 * P < (1ll << 31), who, ": ", P, " rows: 3 P >= 2^31"); }
+
+// in place on the accumulators (which must be contiguous); max_radii2D may be None.  radii: the forward's int32 radii, or a bool / uint8 mask.
+int densify_stats(const torch::Tensor& grad_accum, const torch::Tensor& denom, const c10::optional<torch::Tensor>& max_radii2D, const torch::Tensor& grad2d,
+                  const torch::Tensor& radii)
+{
+    static const char* const who = "densification_stats_";
+    need_library();
+    require(g_api.densify_stats, "densify_stats");
+    check_float(who, "grad2d", grad2d);
+    TORCH_CHECK(grad2d.dim() == 2 && (grad2d.size(1) == 2 || grad2d.size(1) == 3), who, ": grad2d must be (P, 3) or (P, 2), got ", grad2d.sizes());
+    const int64_t P = grad2d.size(0);
+    densify_check_P(who, P);
+    densify_check_column(who, "xyz_gradient_accum", grad_accum, P);
+    densify_check_column(who, "denom", denom, P);
+    if (max_radii2D.has_value()) densify_check_column(who, "max_radii2D", *max_radii2D, P);
+    TORCH_CHECK(radii.defined(), who, ": radii must be a tensor");
+    const auto vt = radii.scalar_type();
+    TORCH_CHECK(vt == torch::kBool || vt == torch::kByte || vt == torch::kInt32, who, ": radii must be int32 (the forward's radii) or a bool / uint8 mask, got ", vt);
+    TORCH_CHECK(radii.numel() == P, who, ": radii has ", radii.numel(), " elements, expected ", P);
+    TORCH_CHECK(!max_radii2D.has_value() || vt == torch::kInt32, who, ": max_radii2D needs the forward's int32 radii, not a mask (pass max_radii2D=None)");
+    check_device(who, "xyz_gradient_accum", grad_accum, grad2d);
+    check_device(who, "denom", denom, grad2d);
+    if (max_radii2D.has_value()) check_device(who, "max_radii2D", *max_radii2D, grad2d);
+    check_device(who, "radii", radii, grad2d);
+    check_device(who, "grad2d", grad2d, grad2d);
+    TORCH_CHECK(grad_accum.is_contiguous() && denom.is_contiguous() && (!max_radii2D.has_value() || max_radii2D->is_contiguous()), who,
+                ": the accumulators must be contiguous (they are updated in place)");
+    if (P == 0) return 0;
+    const torch::Tensor g = grad2d.contiguous(), vis = radii.contiguous();
+    const c10::hip::HIPGuard guard(g.device().index());
+    return checked(g_api.densify_stats((int)P, grad_accum.data_ptr<float>(), denom.data_ptr<float>(), max_radii2D.has_value() ? max_radii2D->data_ptr<float>() : nullptr,
+                                       g.data_ptr<float>(), (int)g.size(1), vis.data_ptr(), vt == torch::kInt32 ? 1 : 0, current_stream(g.device())));
+}
+
+// -> the plan, uint8 (P,).  rule: (grad_threshold, split_size, min_opacity, max_screen_size, max_world_size, split_shrink), rounded to float32 here.
+torch::Tensor densify_plan(const torch::Tensor& grad_accum, const torch::Tensor& denom, const torch::Tensor& scaling, const torch::Tensor& opacity,
+                           const c10::optional<torch::Tensor>& max_radii2D, const std::vector<double>& rule_in, const bool raw, const bool prune_big)
+{
+    static const char* const who = "densify_plan";
+    need_library();
+    require(g_api.densify_plan, who);
+    TORCH_CHECK(rule_in.size() == 6, who, ": the rule has six numbers");
+    check_float(who, "scaling", scaling);
+    TORCH_CHECK(scaling.dim() == 2 && scaling.size(1) == 3, who, ": scaling must be (P, 3), got ", scaling.sizes());
+    const int64_t P = scaling.size(0);
+    densify_check_P(who, P);
+    densify_check_column(who, "xyz_gradient_accum", grad_accum, P);
+    densify_check_column(who, "denom", denom, P);
+    densify_check_column(who, "opacity", opacity, P);
+    if (max_radii2D.has_value()) densify_check_column(who, "max_radii2D", *max_radii2D, P);
+    check_device(who, "xyz_gradient_accum", grad_accum, scaling);
+    check_device(who, "denom", denom, scaling);
+    check_device(who, "opacity", opacity, scaling);
+    if (max_radii2D.has_value()) check_device(who, "max_radii2D", *max_radii2D, scaling);
+    check_device(who, "scaling", scaling, scaling);
+    const c10::hip::HIPGuard guard(scaling.device().index());
+    torch::Tensor plan = torch::empty({P}, scaling.options().dtype(torch::kByte));
+    if (P == 0) return plan;
+    const torch::Tensor ga = grad_accum.contiguous(), de = denom.contiguous(), sc = scaling.contiguous(), op = opacity.contiguous();
+    torch::Tensor mr;
+    if (max_radii2D.has_value()) mr = max_radii2D->contiguous();
+    const StpDensifyRule rule = {(float)rule_in[0], (float)rule_in[1], (float)rule_in[2], (float)rule_in[3], (float)rule_in[4], (float)rule_in[5], raw ? 1 : 0, prune_big ? 1 : 0};
+    checked(g_api.densify_plan((int)P, ga.data_ptr<float>(), de.data_ptr<float>(), sc.data_ptr<float>(), op.data_ptr<float>(), mr.defined() ? mr.data_ptr<float>() : nullptr,
+                               &rule, plan.data_ptr<uint8_t>(), current_stream(scaling.device())));
+    return plan;
+}
+
+// -> (offsets (3P,) int32, nK, nC, nS).  SYNCHRONISES the current stream (in the library): the caller needs the counts to allocate.
+std::tuple<torch::Tensor, int64_t, int64_t, int64_t> densify_scan(const torch::Tensor& plan_in)
+{
+    static const char* const who = "densify_scan";
+    need_library();
+    require(g_api.densify_scan, who);
+    require(g_api.densify_scratch_bytes, who);
+    TORCH_CHECK(plan_in.defined() && plan_in.scalar_type() == torch::kByte, who, ": plan: expected uint8 tensor, got ", plan_in.scalar_type());
+    TORCH_CHECK(plan_in.dim() == 1, who, ": plan must be (P,), got ", plan_in.sizes());
+    densify_check_P(who, plan_in.size(0));
+    check_on_gpu(who, "plan", plan_in);
+    const torch::Tensor plan = plan_in.contiguous();
+    const int64_t P = plan.size(0);
+    const c10::hip::HIPGuard guard(plan.device().index());
+    torch::Tensor offsets = torch::empty({3 * P}, plan.options().dtype(torch::kInt32));
+    int64_t counts[3] = {0, 0, 0};
+    if (P == 0) return {offsets, 0, 0, 0};
+    const size_t bytes = g_api.densify_scratch_bytes((int)P);
+    torch::Tensor scratch = torch::empty({(int64_t)bytes}, plan.options());
+    checked(g_api.densify_scan((int)P, plan.data_ptr<uint8_t>(), scratch.data_ptr(), bytes, reinterpret_cast<uint32_t*>(offsets.data_ptr<int32_t>()), counts,
+                               current_stream(plan.device())));
+    return {offsets, counts[0], counts[1], counts[2]};
+}
+
+// -> (new tensors, new exp_avgs, new exp_avg_sqs): lists as long as `tensors`, the moment lists holding None where none was given.  Tensor k
+// is (P, ...) of any trailing shape; the outputs are (nK + nC + 2 nS, ...).  No host synchronisation.
+std::tuple<std::vector<torch::Tensor>, std::vector<c10::optional<torch::Tensor>>, std::vector<c10::optional<torch::Tensor>>>
+densify_apply(const torch::Tensor& plan_in, const torch::Tensor& offsets, const std::vector<int64_t>& counts_in, const std::vector<torch::Tensor>& tensors,
+              const std::vector<int64_t>& roles, const std::vector<c10::optional<torch::Tensor>>& exp_avgs, const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs,
+              const c10::optional<torch::Tensor>& noise_in, const double split_shrink, const bool raw)
+{
+    static const char* const who = "densify_apply";
+    need_library();
+    require(g_api.densify_apply, who);
+    const size_t n = tensors.size();
+    TORCH_CHECK(roles.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n, who, ": tensors, roles, exp_avgs and exp_avg_sqs must have one entry per tensor");
+    TORCH_CHECK(n <= 64, who, ": ", n, " tensors, at most 64 in one call");
+    TORCH_CHECK(counts_in.size() == 3, who, ": counts must be (nK, nC, nS)");
+    TORCH_CHECK(plan_in.defined() && plan_in.scalar_type() == torch::kByte && plan_in.dim() == 1, who, ": plan: expected a uint8 (P,) tensor");
+    const int64_t P = plan_in.size(0);
+    densify_check_P(who, P);
+    const int64_t counts[3] = {counts_in[0], counts_in[1], counts_in[2]};
+    for (int j = 0; j < 3; j++) TORCH_CHECK(counts[j] >= 0 && counts[j] <= P, who, ": counts[", j, "] = ", counts[j], " outside [0, P]");
+    const int64_t nS = counts[2], M = counts[0] + counts[1] + 2 * nS;
+    TORCH_CHECK(offsets.defined() && offsets.scalar_type() == torch::kInt32 && offsets.dim() == 1 && offsets.size(0) == 3 * P, who, ": offsets: expected an int32 (3 P,) tensor");
+    for (size_t k = 0; k < n; k++) {
+        const torch::Tensor& t = tensors[k];
+        TORCH_CHECK(t.defined(), who, ": tensor ", k, " is undefined");
+        TORCH_CHECK(t.scalar_type() == torch::kFloat32, who, ": tensor ", k, ": expected float32 tensor, got ", t.scalar_type());
+        TORCH_CHECK(t.dim() >= 1 && t.size(0) == P, who, ": tensor ", k, " must have ", P, " rows (the plan's), got ", t.sizes());
+        TORCH_CHECK(P == 0 || t.numel() > 0, who, ": tensor ", k, ": rows without elements, ", t.sizes());
+        TORCH_CHECK(roles[k] >= 0 && roles[k] <= 3, who, ": tensor ", k, ": unknown role ", roles[k], " (0 plain, 1 xyz, 2 scaling, 3 rotation)");
+        TORCH_CHECK(exp_avgs[k].has_value() == exp_avg_sqs[k].has_value(), who, ": tensor ", k, ": exp_avg and exp_avg_sq must both be given or both be None");
+        if (exp_avgs[k].has_value())
+            for (const torch::Tensor* m : {&*exp_avgs[k], &*exp_avg_sqs[k]}) {
+                TORCH_CHECK(m->defined() && m->scalar_type() == torch::kFloat32, who, ": tensor ", k, ": moments: expected float32 tensors");
+                TORCH_CHECK(m->sizes() == t.sizes(), who, ": tensor ", k, ": a moment has shape ", m->sizes(), ", the parameter has ", t.sizes());
+            }
+    }
+    if (nS > 0) {
+        TORCH_CHECK(noise_in.has_value(), who, ": nS = ", nS, " needs noise");
+        check_float(who, "noise", *noise_in);
+        check_rows(who, "noise", *noise_in, 2 * nS, 3);
+    }
+    check_on_gpu(who, "plan", plan_in);
+    check_device(who, "offsets", offsets, plan_in);
+    for (size_t k = 0; k < n; k++) {
+        check_device(who, "a tensor", tensors[k], plan_in);
+        if (exp_avgs[k].has_value()) {
+            check_device(who, "an exp_avg", *exp_avgs[k], plan_in);
+            check_device(who, "an exp_avg_sq", *exp_avg_sqs[k], plan_in);
+        }
+    }
+    if (nS > 0) check_device(who, "noise", *noise_in, plan_in);
+    const torch::Tensor plan = plan_in.contiguous(), off = offsets.contiguous();
+    const c10::hip::HIPGuard guard(plan.device().index());
+    std::vector<torch::Tensor> held; // the contiguous inputs, alive until the launches are made
+    std::vector<torch::Tensor> out_p(n);
+    std::vector<c10::optional<torch::Tensor>> out_m(n), out_v(n);
+    std::vector<StpDensifyTensor> table(n);
+    for (size_t k = 0; k < n; k++) {
+        std::vector<int64_t> shape = tensors[k].sizes().vec();
+        int64_t row = 1;
+        for (size_t d = 1; d < shape.size(); d++) row *= shape[d];
+        TORCH_CHECK(row > 0 && P * row < (1ll << 31), who, ": tensor ", k, ": ", P, " rows of ", row, " floats: outside (0, 2^31)");
+        shape[0] = M;
+        held.push_back(tensors[k].contiguous());
+        out_p[k] = torch::empty(shape, held.back().options());
+        StpDensifyTensor& t = table[k];
+        t = StpDensifyTensor{held.back().data_ptr<float>(), nullptr, nullptr, out_p[k].data_ptr<float>(), nullptr, nullptr, (int32_t)row, (int32_t)roles[k]};
+        if (exp_avgs[k].has_value()) {
+            held.push_back(exp_avgs[k]->contiguous());
+            t.exp_avg = held.back().data_ptr<float>();
+            held.push_back(exp_avg_sqs[k]->contiguous());
+            t.exp_avg_sq = held.back().data_ptr<float>();
+            out_m[k] = torch::empty(shape, held.back().options());
+            out_v[k] = torch::empty(shape, held.back().options());
+            t.exp_avg_out = out_m[k]->data_ptr<float>();
+            t.exp_avg_sq_out = out_v[k]->data_ptr<float>();
+        }
+    }
+    torch::Tensor noise;
+    if (nS > 0) noise = noise_in->contiguous();
+    checked(g_api.densify_apply((int)P, plan.data_ptr<uint8_t>(), reinterpret_cast<const uint32_t*>(off.data_ptr<int32_t>()), counts, (int)n, table.data(),
+                                noise.defined() ? noise.data_ptr<float>() : nullptr, (float)split_shrink, raw ? 1 : 0, current_stream(plan.device())));
+    return {out_p, out_m, out_v};
+}
+
+// == the fused photometric loss (extension, include/stp_raster.h: stp_photometric_forward / _backward; photometric_loss and fused_ssim in
+// __init__.py).  image, target: float32 (C, H, W) or (B, C, H, W) on one GPU, made contiguous here.
+struct PhotometricShape { int planes, H, W; };
+PhotometricShape photometric_check(const char* who, const torch::Tensor& image, const torch::Tensor& target)
+{
+    require(g_api.photometric_forward, who);
+    require(g_api.photometric_backward, who);
+    require(g_api.photometric_workspace_floats, who);
+    TORCH_CHECK(image.defined() && target.defined(), who, ": image and target must be tensors");
+    TORCH_CHECK(image.scalar_type() == torch::kFloat32, "expected float32 tensor, got ", image.scalar_type());
+    TORCH_CHECK(target.scalar_type() == torch::kFloat32, "expected float32 tensor, got ", target.scalar_type());
+    TORCH_CHECK(image.dim() == 3 || image.dim() == 4, who, ": image must be (C, H, W) or (B, C, H, W), got ", image.dim(), " dimensions");
+    TORCH_CHECK(image.sizes() == target.sizes(), who, ": image has shape ", image.sizes(), ", target has ", target.sizes());
+    TORCH_CHECK(target.device() == image.device(), "expected all tensors on ", image.device(), ", got one on ", target.device());
+    TORCH_CHECK(image.is_cuda(), GPU_ONLY);
+    const int64_t H = image.size(-2), W = image.size(-1), planes = H * W > 0 ? image.numel() / (H * W) : 0;
+    TORCH_CHECK(image.numel() < (1ll << 31), who, ": ", image.numel(), " elements >= 2^31");
+    return PhotometricShape{(int)planes, (int)H, (int)W};
+}
+
+// -> (out2 = [mean |image - target|, mean SSIM], the three derivative maps (3, *image.shape) or an undefined tensor)
+std::tuple<torch::Tensor, torch::Tensor> photometric_forward(const torch::Tensor& image_in, const torch::Tensor& target_in, const bool want_maps)
+{
+    need_library();
+    const PhotometricShape s = photometric_check("photometric_forward", image_in, target_in);
+    const torch::Tensor image = image_in.contiguous(), target = target_in.contiguous();
+    const auto opt = image.options();
+    const c10::hip::HIPGuard guard(image.device().index());
+    torch::Tensor out2 = torch::empty({2}, opt), maps;
+    if (image.numel() == 0) { // the mean of nothing, as torch's
+        out2.fill_(std::numeric_limits<float>::quiet_NaN());
+        if (want_maps) maps = torch::empty({3, 0}, opt);
+        return {out2, maps};
+    }
+    if (want_maps) {
+        std::vector<int64_t> shape{3};
+        for (const int64_t d : image.sizes()) shape.push_back(d);
+        maps = torch::empty(shape, opt);
+    }
+    torch::Tensor workspace = torch::empty({(int64_t)g_api.photometric_workspace_floats(s.planes, s.H, s.W)}, opt);
+    checked(g_api.photometric_forward(s.planes, s.H, s.W, image.data_ptr<float>(), target.data_ptr<float>(), out2.data_ptr<float>(),
+                                      want_maps ? maps.data_ptr<float>() : nullptr, workspace.data_ptr<float>(), current_stream(image.device())));
+    return {out2, maps};
+}
+
+// -> dL/dimage (image's shape); grad_out2 = dL/dout2, two floats on the device (read there: no host synchronisation)
+torch::Tensor photometric_backward(const torch::Tensor& image_in, const torch::Tensor& target_in, const torch::Tensor& maps, const torch::Tensor& grad_out2_in)
+{
+    need_library();
+    const PhotometricShape s = photometric_check("photometric_backward", image_in, target_in);
+    const torch::Tensor image = image_in.contiguous(), target = target_in.contiguous();
+    TORCH_CHECK(maps.defined() && maps.is_cuda() && maps.device() == image.device() && maps.scalar_type() == torch::kFloat32 && maps.is_contiguous() &&
+                    maps.numel() == 3 * image.numel(),
+                "photometric_backward: maps must be the contiguous float32 tensor of 3 * image.numel() elements a forward with want_maps returned");
+    TORCH_CHECK(grad_out2_in.defined() && grad_out2_in.is_cuda() && grad_out2_in.device() == image.device() && grad_out2_in.numel() == 2,
+                "photometric_backward: grad_out2 must hold two elements on the device of image");
+    const torch::Tensor grad_out2 = grad_out2_in.to(torch::kFloat32).contiguous();
+    const c10::hip::HIPGuard guard(image.device().index());
+    torch::Tensor dL_dimage = torch::empty(image.sizes(), image.options());
+    if (image.numel() == 0) return dL_dimage;
+    checked(g_api.photometric_backward(s.planes, s.H, s.W, image.data_ptr<float>(), target.data_ptr<float>(), maps.data_ptr<float>(),
+                                       grad_out2.data_ptr<float>(), dL_dimage.data_ptr<float>(), current_stream(image.device())));
+    return dL_dimage;
+}
+} // namespace

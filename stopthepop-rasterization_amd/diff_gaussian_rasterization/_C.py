@@ -39,58 +39,44 @@ class StpSettings(ctypes.Structure):
 
 _lib_override = None
 
-# exports newer than ABI 7's first release: resolved when present (name -> (argtypes, restype))
+# exports newer than ABI 7's first release: resolved when present (name -> (argtypes, restype, the feature it came with: the rebuild message names it))
 _OPTIONAL_SYMBOLS = {
-    "stp_camera_grad_workspace_bytes": ([ctypes.c_int], ctypes.c_size_t),
-    "stp_set_backward_camera_grads": ([ctypes.c_void_p] * 4 + [ctypes.c_size_t], None),
-    "stp_set_backward_absgrad": ([ctypes.c_void_p], None),
-    "stp_set_backward_blend_stats": ([ctypes.c_void_p], None),
-    "stp_set_forward_background": ([ctypes.c_void_p] * 2, None),
-    "stp_set_backward_background": ([ctypes.c_void_p] * 3, None),
-    "stp_set_forward_invdepth": ([ctypes.c_void_p], None),
-    "stp_set_backward_invdepth": ([ctypes.c_void_p] * 2, None),
-    "stp_set_forward_split_sh": ([ctypes.c_void_p], None),
-    "stp_set_backward_split_sh": ([ctypes.c_void_p] * 2, None),
-    "stp_set_forward_sh_stash": ([ctypes.c_int], None),
-    "stp_geometry_buffer_size_stash": ([ctypes.c_int, ctypes.POINTER(StpSettings)], ctypes.c_size_t),
+    "stp_camera_grad_workspace_bytes": ([ctypes.c_int], ctypes.c_size_t, "camera gradients"),
+    "stp_set_backward_camera_grads": ([ctypes.c_void_p] * 4 + [ctypes.c_size_t], None, "camera gradients"),
+    "stp_set_backward_absgrad": ([ctypes.c_void_p], None, "absgrad"),
+    "stp_set_backward_blend_stats": ([ctypes.c_void_p], None, "blend statistics"),
+    "stp_set_forward_background": ([ctypes.c_void_p] * 2, None, "the alpha output and per-pixel background"),
+    "stp_set_backward_background": ([ctypes.c_void_p] * 3, None, "the alpha output and per-pixel background"),
+    "stp_set_forward_invdepth": ([ctypes.c_void_p], None, "the inverse-depth output"),
+    "stp_set_backward_invdepth": ([ctypes.c_void_p] * 2, None, "the inverse-depth output"),
+    "stp_set_forward_split_sh": ([ctypes.c_void_p], None, "split SH inputs"),
+    "stp_set_backward_split_sh": ([ctypes.c_void_p] * 2, None, "split SH inputs"),
+    "stp_set_forward_sh_stash": ([ctypes.c_int], None, "the SH stash"),
+    "stp_geometry_buffer_size_stash": ([ctypes.c_int, ctypes.POINTER(StpSettings)], ctypes.c_size_t, "the SH stash"),
     "stp_sparse_adam": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
-                        ctypes.c_int),
-    "stp_mcmc_relocation": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3, ctypes.c_int),
-    "stp_mcmc_add_noise": ([ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_float] * 3 + [ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
-    "stp_knn_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t),
-    "stp_knn_mean_dist2": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2, ctypes.c_int),
-    "stp_densify_stats": ([ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
-    "stp_densify_plan": ([ctypes.c_int] + [ctypes.c_void_p] * 8, ctypes.c_int),
-    "stp_densify_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t),
-    "stp_densify_scan": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3, ctypes.c_int),
+                        ctypes.c_int, "the sparse Adam step"),
+    "stp_mcmc_relocation": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3, ctypes.c_int, "the 3DGS-MCMC kernels"),
+    "stp_mcmc_add_noise": ([ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_float] * 3 + [ctypes.c_int, ctypes.c_void_p], ctypes.c_int, "the 3DGS-MCMC kernels"),
+    "stp_knn_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t, "the nearest-neighbour kernels"),
+    "stp_knn_mean_dist2": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2, ctypes.c_int, "the nearest-neighbour kernels"),
+    "stp_densify_stats": ([ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int, "the densification kernels"),
+    "stp_densify_plan": ([ctypes.c_int] + [ctypes.c_void_p] * 8, ctypes.c_int, "the densification kernels"),
+    "stp_densify_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t, "the densification kernels"),
+    "stp_densify_scan": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3, ctypes.c_int, "the densification kernels"),
     "stp_densify_apply": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p],
-                          ctypes.c_int),
-    "stp_photometric_workspace_floats": ([ctypes.c_int] * 3, ctypes.c_size_t),
-    "stp_photometric_forward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int),
-    "stp_photometric_backward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int),
+                          ctypes.c_int, "the densification kernels"),
+    "stp_photometric_workspace_floats": ([ctypes.c_int] * 3, ctypes.c_size_t, "the photometric loss"),
+    "stp_photometric_forward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int, "the photometric loss"),
+    "stp_photometric_backward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int, "the photometric loss"),
 }
-# the feature an optional export came with (the rebuild message names it)
-_SYMBOL_FEATURE = {"stp_set_backward_absgrad": "absgrad", "stp_set_backward_blend_stats": "blend statistics",
-                   "stp_set_forward_background": "the alpha output and per-pixel background",
-                   "stp_set_backward_background": "the alpha output and per-pixel background",
-                   "stp_set_forward_invdepth": "the inverse-depth output", "stp_set_backward_invdepth": "the inverse-depth output",
-                   "stp_set_forward_split_sh": "split SH inputs", "stp_set_backward_split_sh": "split SH inputs",
-                   "stp_set_forward_sh_stash": "the SH stash", "stp_geometry_buffer_size_stash": "the SH stash",
-                   "stp_sparse_adam": "the sparse Adam step",
-                   "stp_mcmc_relocation": "the 3DGS-MCMC kernels", "stp_mcmc_add_noise": "the 3DGS-MCMC kernels",
-                   "stp_knn_scratch_bytes": "the nearest-neighbour kernels", "stp_knn_mean_dist2": "the nearest-neighbour kernels",
-                   "stp_densify_stats": "the densification kernels", "stp_densify_plan": "the densification kernels",
-                   "stp_densify_scratch_bytes": "the densification kernels", "stp_densify_scan": "the densification kernels",
-                   "stp_densify_apply": "the densification kernels",
-                   "stp_photometric_workspace_floats": "the photometric loss", "stp_photometric_forward": "the photometric loss",
-                   "stp_photometric_backward": "the photometric loss"}
+_SYMBOL_FEATURE = {name: entry[2] for name, entry in _OPTIONAL_SYMBOLS.items()}   # (a view of the table above)
 
 
 def _require(name: str):
     """An optional export of the loaded library; RuntimeError naming it when the library predates it."""
     L = _load()
     if not hasattr(L, name):
-        raise RuntimeError(f"{library_path()} does not export {name} (a library built before {_SYMBOL_FEATURE.get(name, 'camera gradients')}): rebuild it")
+        raise RuntimeError(f"{library_path()} does not export {name} (a library built before {_OPTIONAL_SYMBOLS[name][2]}): rebuild it")
     return getattr(L, name)
 
 
@@ -158,7 +144,7 @@ def _load():
     for name in _OPTIONAL_SYMBOLS:   # (an older library without them still loads: camera_grad_workspace_bytes / camera_grads=True raise)
         if hasattr(L, name):
             fn = getattr(L, name)
-            fn.argtypes, fn.restype = _OPTIONAL_SYMBOLS[name]
+            fn.argtypes, fn.restype = _OPTIONAL_SYMBOLS[name][:2]
     if L.stp_abi_version() != 7:
         raise ImportError("libstp_raster.so ABI version mismatch")
     _lib = L
@@ -323,7 +309,7 @@ def _raise_last(rc: int):
     raise RuntimeError((msg.decode() if msg else "") or f"libstp_raster error {rc}")
 
 
-# ---- scratch pool (csrc/host/stp_torch_binding.cpp: buffers of >= 256 MiB -- tile lists with their entry records, image
+# ---- scratch pool (csrc/host/stp_scratch_pool.h: buffers of >= 256 MiB -- tile lists with their entry records, image
 # ---- state with the blend log -- are kept on a free list per device instead of cycling through torch's caching allocator)
 def clear_scratch_pool(device=None) -> int:
     """Drops the pooled scratch buffers (tile lists / blend logs waiting for reuse) of `device` (all devices when None) so
