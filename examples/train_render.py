@@ -3,12 +3,13 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--split-sh] [--init-scales scene|knn]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--split-sh] [--raw-params] [--init-scales scene|knn]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
   model  : get_xyz, get_opacity, get_scaling, get_rotation, get_features, active_sh_degree
-           (a model with `split_sh` set also has get_features_dc and get_features_rest, which are then passed as they are)
+           (a model with `split_sh` set also has get_features_dc and get_features_rest, which are then passed as they are;
+            a model with `raw_params` set hands over _scaling, _rotation and _opacity, its stored parameters, to GaussianRasterizer(..., raw=True))
 and returns the trainer's usual dict (render, viewspace_points, visibility_filter, radii; "alpha" and "invdepth" too when asked for).
 """
 from __future__ import annotations
@@ -37,7 +38,9 @@ def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, 
     (INTEGRATION.md section 3h); with `splat_args._invdepth = True` "invdepth", the blended inverse depth sum alpha T / z (1, H, W) that
     upstream's rasterizer returns as `invdepths`, differentiable too.
     A model with `split_sh` hands its two SH parameters over as they are -- dc=_features_dc, shs=_features_rest -- where a trainer
-    otherwise concatenates them every step."""
+    otherwise concatenates them every step.  A model with `raw_params` hands over its stored _opacity (logit),
+    _scaling (log) and _rotation (unnormalised) to a rasterizer made with raw=True: sigmoid, exp and normalize run inside the rasterizer's kernels, and the
+    gradients arrive on the three leaves without an activated copy in between."""
     screenspace_points = torch.zeros_like(model.get_xyz, requires_grad=True)
     raster_settings = GaussianRasterizationSettings(
         image_height=int(camera.image_height), image_width=int(camera.image_width),
@@ -45,12 +48,17 @@ def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, 
         scale_modifier=scaling_modifier, viewmatrix=camera.world_view_transform, projmatrix=camera.full_proj_transform,
         inv_viewprojmatrix=camera.full_proj_transform.inverse(), sh_degree=model.active_sh_degree,
         campos=camera.camera_center, prefiltered=False, settings=splat_args, render_depth=render_depth, debug=debug)
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
+    raw = bool(getattr(model, "raw_params", False))
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings, raw=raw)
     shs, colors, dc = (None, override_color, None) if override_color is not None else (model.get_features, None, None)
     if override_color is None and getattr(model, "split_sh", False):   # no torch.cat: the two leaves go in, their two .grad come out
         shs, dc = model.get_features_rest, model.get_features_dc
-    image, radii, *extra = rasterizer(means3D=model.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors,
-                                      opacities=model.get_opacity, scales=model.get_scaling, rotations=model.get_rotation, dc=dc)
+    if raw:
+        image, radii, *extra = rasterizer(means3D=model.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors,
+                                          opacities=model._opacity, scales=model._scaling, rotations=model._rotation, dc=dc)
+    else:
+        image, radii, *extra = rasterizer(means3D=model.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors,
+                                          opacities=model.get_opacity, scales=model.get_scaling, rotations=model.get_rotation, dc=dc)
     out = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
     if getattr(splat_args, "_alpha", False):      # (the extra outputs in their order: alpha, then the inverse depth)
         out["alpha"] = extra.pop(0)
@@ -75,9 +83,10 @@ def splat_config(name: str) -> ExtendedSettings:
 class ToyGaussians(torch.nn.Module):
     """The part of the trainer's GaussianModel that render() touches (activations included)."""
 
-    def __init__(self, sc: scenes.Scene, device, split_sh: bool = False):
+    def __init__(self, sc: scenes.Scene, device, split_sh: bool = False, raw_params: bool = False):
         super().__init__()
         self.split_sh = split_sh
+        self.raw_params = raw_params   # render() passes the stored parameters with raw=True (the regularisers keep using get_opacity / get_scaling)
         t = lambda a: torch.nn.Parameter(torch.tensor(a, device=device))
         self._xyz = t(sc.means3D)
         self._scaling = torch.nn.Parameter(torch.log(torch.tensor(sc.scales, device=device)))
@@ -176,6 +185,9 @@ def main(argv=None):
     ap.add_argument("--split-sh", action="store_true",
                     help="the model keeps _features_dc and _features_rest as two parameters (two optimizer groups, the rest at a twentieth of the "
                          "learning rate, as upstream) and renders with dc=: no torch.cat per step (INTEGRATION.md section 3n)")
+    ap.add_argument("--raw-params", action="store_true",
+                    help="render from the stored parameters: _opacity, _scaling and _rotation go in with raw=True and sigmoid / exp / normalize "
+                         "run inside the rasterizer's kernels (INTEGRATION.md section 3q)")
     ap.add_argument("--init-scales", default="scene", choices=["scene", "knn"],
                     help="knn: the model's initial _scaling comes from the points alone, as the trainers' GaussianModel.create_from_pcd sets it: "
                          "log(sqrt(clamp_min(distCUDA2(xyz), 1e-7))) on all three axes, with `from simple_knn._C import distCUDA2` "
@@ -197,7 +209,7 @@ def main(argv=None):
         target, target_alpha, target_invdepth = target_out["render"], target_out.get("alpha"), target_out.get("invdepth")
 
     # start from perturbed colours and opacities and fit them back
-    model = ToyGaussians(target_scene, dev, split_sh=args.split_sh)
+    model = ToyGaussians(target_scene, dev, split_sh=args.split_sh, raw_params=args.raw_params)
     with torch.no_grad():
         for f in model.feature_params():
             f.mul_(0.3)

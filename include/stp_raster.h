@@ -344,6 +344,36 @@ void stp_set_backward_split_sh(const float* dc /* P x 3 */, float* dL_ddc /* P x
    paths have the same error: tests/test_gpu_sh_stash.py).  The image, radii, colours and clamp flags of the forward do not change. */
 void stp_set_forward_sh_stash(int enable);
 
+/* Extension: raw parameter inputs.  A 3DGS-family trainer stores a Gaussian as _scaling (the logarithm of the scale), _rotation (an
+   unnormalised quaternion) and _opacity (a logit) and runs exp, normalize and sigmoid in front of every render.  With these requests the two
+   kernels that read `scales`, `rotations` and `opacities` apply the activation at the load and its chain rule at the store; no activated
+   copy exists anywhere.  `mask`: bit 0 = opacities, bit 1 = scales, bit 2 = rotations hold raw values.  In float32, every step but expf one
+   correctly rounded operation (csrc/stp_activations.h):
+       o = 1 / (1 + expf(-x))          s = expf(x), scale_modifier * s follows unchanged          q / max(|q|, 1e-12f)
+       |q| = sqrt(fma(q3, q3, fma(q2, q2, fma(q1, q1, q0 * q0))))    (torch.sigmoid, torch.exp, torch.nn.functional.normalize with its eps)
+   stp_set_forward_raw_params -- the NEXT stp_forward of the calling thread reads the arrays of the mask as raw.  Every output is that of the
+       plain call on stp_activate_params' copies, bit for bit.  With cov3D_precomp AND scales and rotations given the bits apply wherever
+       the library reads the two arrays (Sigma^-1 of the sorted modes).
+   stp_set_backward_raw_params -- the NEXT stp_backward / stp_backward_phases of the calling thread that runs the per-Gaussian half (phases
+       bit 1) reads them as raw and writes the gradients with respect to the RAW values -- what autograd gives for the activations composed
+       in front of the plain call, that call's conventions included (dL_dscale stays the derivative with respect to scale_modifier * s):
+           dL_dopacity_raw = dL_dopacity o (1 - o)      dL_dscale_raw = dL_dscale s      dL_drot_raw = (g - qh (qh . g)) / |q|, qh = q / |q|,
+       g the plain call's dL_drot; where |q| < 1e-12f the norm took no part: g / 1e-12f.  Rows with radii <= 0 get zeros.  Works with compact
+       and padded records and in every chunk of a chunked half (each chunk is a call and carries its own request).  Without
+       proper_ewa_scaling bit 0 makes the half read opacities (4 B per Gaussian), which it otherwise does not.
+   Both requests are consumed by the call they are meant for whatever its outcome; a render-only backward (phases = 1) leaves the backward
+   request pending, as it does the camera request.  Mask 0 clears a pending request: the call is the plain one, launch for launch and bit for
+   bit.  STP_ERR_INVALID_ARGUMENT, before anything is launched, with a message naming the bit: a mask outside 0..7, or a bit whose array is
+   NULL in that call.
+   stp_activate_params -- the activated copies themselves (logging, export, tests): scales[3 P] from scaling, rotations[4 P] from rotation,
+       opacities[P] from opacity, the values the raw path renders with to the bit.  Any of the three pairs may be NULL together.  One launch
+       per pair; 16-byte aligned pairs move 16 bytes per lane.  Returns the launches made (0 for P == 0 or no pair), or a negative StpStatus:
+       a negative P, P >= 2^29, or a pair with only one pointer. */
+void stp_set_forward_raw_params(int mask);
+void stp_set_backward_raw_params(int mask);
+int stp_activate_params(int P, const float* scaling, const float* rotation, const float* opacity, float* scales, float* rotations,
+                        float* opacities, void* stream);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:188-193, rasterizer_impl.cu:161-173).
    `present` is P bytes (bool). */
 int stp_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

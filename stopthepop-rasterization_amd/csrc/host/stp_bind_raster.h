@@ -74,15 +74,18 @@ int split_sh_total(const torch::Tensor& dc, const torch::Tensor& sh, const torch
 // invdepth (extension, include/stp_raster.h: stp_set_forward_invdepth): with invdepth = true one more element behind alpha's: sum alpha T / z,
 // (1,H,W); an undefined tensor otherwise.
 // dc (keyword, extension): see split_sh_total; `sh` is then the (P,M-1,3) rest.  Ignored with precomputed colours.
+// raw (keyword, extension, include/stp_raster.h: stp_set_forward_raw_params): bit 0 opacity, bit 1 scales, bit 2 rotations hold a trainer's raw
+// parameters; the library checks the mask against the arrays it is handed.
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors, const torch::Tensor& opacity,
                     const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier, const torch::Tensor& cov3D_precomp,
                     const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const torch::Tensor& inv_viewprojmatrix, const float tan_fovx,
                     const float tan_fovy, const int image_height, const int image_width, const torch::Tensor& sh, const int degree,
                     const torch::Tensor& campos, const bool prefiltered, const py::dict& settings, const bool render_depth, const bool debug,
-                    const bool record_log, const bool alpha, const bool invdepth, const c10::optional<torch::Tensor>& dc)
+                    const bool record_log, const bool alpha, const bool invdepth, const c10::optional<torch::Tensor>& dc, const int raw)
 {
     need_library();
+    if (raw != 0) require(g_api.set_forward_raw_params, "raw");
     TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must have dimensions (num_points, 3)");
     TORCH_CHECK(means3D.is_cuda(), GPU_ONLY);
     const bool split = dc.has_value() && dc->defined() && colors.numel() == 0; // (precomputed colours win)
@@ -135,6 +138,7 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
             if (invdepth) g_api.set_forward_invdepth(out_invdepth.data_ptr<float>());
             if (split) g_api.set_forward_split_sh(dc_.data_ptr<float>());
             if (sh_stash) g_api.set_forward_sh_stash(1);
+            if (raw != 0) g_api.set_forward_raw_params(raw);
             rc = g_api.forward(&Resizer::call, &geom, &Resizer::call, &binning, &Resizer::call, &img, P, degree, M, fptr(in.bg), W, H, &s, fptr(in.m3),
                                fptr(in.sh), fptr(in.col), fptr(in.op), fptr(in.sc), scale_modifier, fptr(in.ro), fptr(in.c3), fptr(in.vm), fptr(in.pm),
                                fptr(in.inv), fptr(in.cam), tan_fovx, tan_fovy, prefiltered ? 1 : 0, out_color.data_ptr<float>(), radii.data_ptr<int>(),
@@ -167,6 +171,8 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
 // dc (keyword, extension, include/stp_raster.h: stp_set_backward_split_sh): the first SH coefficient, (P,1,3) or (P,3); `sh` is then the (P,M-1,3)
 // rest.  dL_dsh, in its usual slot, is (P,M-1,3), and dL_ddc, (P,3), is the LAST tensor of the result.  The full order of the result is
 //   [the eight] [dL_dview, dL_dproj, dL_dcam] [absgrad] [blend_stats] [dL_dbackground] [dL_ddc]
+// raw (keyword, extension, include/stp_raster.h: stp_set_backward_raw_params): the forward's mask; dL_dopacity, dL_dscales and dL_drotations of the
+// mask's bits are then the gradients with respect to the raw values.  Calls with the per-Gaussian half (phases bit 1), every chunk of a chunked one.
 // each bracket present when asked for.  Calls with the per-Gaussian half (phases bit 1); with `outputs` (a later chunk) a ninth tensor in it is
 // the dL_ddc of the first chunk.  Ignored with precomputed colours.
 std::vector<torch::Tensor>
@@ -180,10 +186,12 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const c10::optional<std::vector<torch::Tensor>>& outputs, const bool camera_grads, const bool absgrad, const bool blend_stats,
                              const c10::optional<torch::Tensor>& dL_dalpha, const bool bg_grad,
                              const c10::optional<torch::Tensor>& dL_dinvdepth, const c10::optional<torch::Tensor>& invdepth,
-                             const c10::optional<torch::Tensor>& dc)
+                             const c10::optional<torch::Tensor>& dc, const int raw_mask)
 {
     need_library();
     TORCH_CHECK(means3D.is_cuda(), GPU_ONLY);
+    const int raw = (phases & 2) ? raw_mask : 0; // (the render half reads none of the three arrays)
+    if (raw != 0) require(g_api.set_backward_raw_params, "raw");
     const bool split = dc.has_value() && dc->defined() && colors.numel() == 0 && (phases & 2); // (precomputed colours win; the render half reads no SH)
     if (split) require(g_api.set_backward_split_sh, "dc");
     const int M_split = split ? split_sh_total(*dc, sh, means3D) : 0;
@@ -279,6 +287,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                                           bg_grad ? dL_dbg.data_ptr<float>() : nullptr);
         if (have_dinv && P != 0) g_api.set_backward_invdepth(inv_out_.data_ptr<float>(), dinv_.data_ptr<float>());
         if (split && P != 0) g_api.set_backward_split_sh(dc_.data_ptr<float>(), dL_ddc.data_ptr<float>());
+        if (raw != 0 && P != 0) g_api.set_backward_raw_params(raw);
         if (blend_stats && P != 0) g_api.set_backward_blend_stats(stats.data_ptr<float>());
         if (absgrad && P != 0) g_api.set_backward_absgrad(dL_dmeans2D_abs.data_ptr<float>());
         if (camera_grads) g_api.set_backward_camera_grads(dL_dview.data_ptr<float>(), dL_dproj.data_ptr<float>(), dL_dcam.data_ptr<float>(), cam_ws.data_ptr(), (size_t)cam_ws.numel());

@@ -113,6 +113,41 @@ int mcmc_add_noise(const torch::Tensor& xyz, const torch::Tensor& scales, const 
                                         (float)noise_scale, (float)k, (float)x0, raw ? 1 : 0, current_stream(xyz.device())));
 }
 
+// == the activated copies of a trainer's raw parameters (extension, include/stp_raster.h: stp_activate_params; activate_params in __init__.py): the
+// values the rasterizer's raw path renders with, to the bit.  -> (scales, rotations, opacities), fresh contiguous float32 tensors in the inputs' shapes,
+// an undefined tensor (None) for an absent input.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> activate_params(const c10::optional<torch::Tensor>& scaling, const c10::optional<torch::Tensor>& rotation,
+                                                                        const c10::optional<torch::Tensor>& opacity)
+{
+    static const char* const who = "activate_params";
+    need_library();
+    require(g_api.activate_params, who);
+    const c10::optional<torch::Tensor>* all[3] = {&scaling, &rotation, &opacity};
+    static const char* const names[3] = {"scaling", "rotation", "opacity"};
+    const torch::Tensor* first = nullptr;
+    for (int j = 0; j < 3; j++)
+        if (all[j]->has_value()) { check_float(who, names[j], **all[j]); if (!first) first = &**all[j]; }
+    if (!first) return {torch::Tensor(), torch::Tensor(), torch::Tensor()};
+    const int64_t P = first->dim() > 0 ? first->size(0) : -1;
+    if (scaling.has_value()) check_rows(who, "scaling", *scaling, P, 3);
+    if (rotation.has_value()) check_rows(who, "rotation", *rotation, P, 4);
+    if (opacity.has_value()) {
+        check_column(who, "opacity", *opacity);
+        TORCH_CHECK(opacity->size(0) == P, who, ": opacity has ", opacity->size(0), " rows, ", P, " expected");
+    }
+    TORCH_CHECK(P < (1ll << 29), who, ": ", P, " rows >= 2^29");
+    for (int j = 0; j < 3; j++)
+        if (all[j]->has_value()) check_device(who, names[j], **all[j], *first);
+    torch::Tensor in[3], out[3];
+    for (int j = 0; j < 3; j++)
+        if (all[j]->has_value()) { in[j] = (*all[j])->detach().contiguous(); out[j] = torch::empty(in[j].sizes(), in[j].options()); }
+    if (P == 0) return {out[0], out[1], out[2]};
+    auto ptr = [](const torch::Tensor& t) -> float* { return t.defined() ? t.data_ptr<float>() : nullptr; };
+    const c10::hip::HIPGuard guard(first->device().index());
+    checked(g_api.activate_params((int)P, ptr(in[0]), ptr(in[1]), ptr(in[2]), ptr(out[0]), ptr(out[1]), ptr(out[2]), current_stream(first->device())));
+    return {out[0], out[1], out[2]};
+}
+
 // == simple_knn's distCUDA2 (extension, include/stp_raster.h: stp_knn_mean_dist2; knn_mean_dist2 in __init__.py and simple_knn._C.distCUDA2), on the
 // caller's current stream: -> (P,) float32, the mean of the three smallest squared distances to the other points, in input order.  The scratch is
 // a torch tensor of the caching allocator, returned to it when this function leaves (the allocator keeps it for the stream until the kernels

@@ -35,6 +35,9 @@
     X(set_backward_invdepth, false, "the inverse-depth output")                            \
     X(set_forward_split_sh, false, "split SH inputs")                                      \
     X(set_backward_split_sh, false, "split SH inputs")                                     \
+    X(set_forward_raw_params, false, "raw parameter inputs")                               \
+    X(set_backward_raw_params, false, "raw parameter inputs")                              \
+    X(activate_params, false, "raw parameter inputs")                                      \
     X(set_forward_sh_stash, false, "the SH stash") /* (a library with it also takes NULL for dL_dcolor / dL_dcov3D) */ \
     X(sparse_adam, false, "the sparse Adam step")                                          \
     X(mcmc_relocation, false, "the 3DGS-MCMC kernels")                                     \

@@ -24,6 +24,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("sparse_adam", &sparse_adam);
     m.def("compute_relocation", &compute_relocation);
     m.def("mcmc_add_noise", &mcmc_add_noise);
+    m.def("activate_params", &activate_params);
     m.def("knn_mean_dist2", &knn_mean_dist2);
     m.def("densify_stats", &densify_stats);
     m.def("densify_plan", &densify_plan);

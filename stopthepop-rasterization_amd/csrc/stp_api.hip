@@ -52,12 +52,22 @@ void fill_frame(FrameParams& f, int P, int D, int M, const float* background, in
     f.log_depth = 0; f.log_need = nullptr; f.log_tag = 0;
 }
 
+// stp_set_forward_raw_params / stp_set_backward_raw_params: the mask against the arrays of the call that took it
+int check_raw_params(int mask, const float* opacities, const float* scales, const float* rotations)
+{
+    if (mask < 0 || mask > 7) return fail(STP_ERR_INVALID_ARGUMENT, "raw parameters: mask " + std::to_string(mask) + " is outside 0..7 (bit 0 opacities, bit 1 scales, bit 2 rotations)");
+    if ((mask & 1) && !opacities) return fail(STP_ERR_INVALID_ARGUMENT, "raw parameters: bit 0 (opacities) is set but opacities is NULL");
+    if ((mask & 2) && !scales) return fail(STP_ERR_INVALID_ARGUMENT, "raw parameters: bit 1 (scales) is set but scales is NULL");
+    if ((mask & 4) && !rotations) return fail(STP_ERR_INVALID_ARGUMENT, "raw parameters: bit 2 (rotations) is set but rotations is NULL");
+    return 0;
+}
+
 // ---- the one-shot requests of the calling thread: set by the stp_set_* calls below, each taken by the next call it is meant for.  ALL of
 // ---- them live in this one struct, and the two functions below are the only ones that take them.
 struct BackwardBackground { const float* bg_image = nullptr; const float* dL_dalpha = nullptr; float* dL_dbackground = nullptr; }; // stp_set_backward_background
 struct BackwardInvdepth { const float* invdepth = nullptr; const float* dL_dinvdepth = nullptr; }; // stp_set_backward_invdepth
 struct BackwardSplitSh { const float* dc = nullptr; float* dL_ddc = nullptr; }; // stp_set_backward_split_sh
-struct BackwardRequests { CameraGradRequest cam; float* absgrad = nullptr; float* blend_stats = nullptr; BackwardBackground background; BackwardInvdepth invdepth; BackwardSplitSh split_sh; };
+struct BackwardRequests { CameraGradRequest cam; float* absgrad = nullptr; float* blend_stats = nullptr; BackwardBackground background; BackwardInvdepth invdepth; BackwardSplitSh split_sh; int raw_params = 0; /* stp_set_backward_raw_params */ };
 struct PendingRequests { ForwardRequests forward; BackwardRequests backward; };
 static thread_local PendingRequests t_pending;
 
@@ -65,7 +75,7 @@ static thread_local PendingRequests t_pending;
 // outcome.  stp_forward calls this in front of its very first check, so a call refused there has consumed them too.
 ForwardRequests take_forward_requests() { return std::exchange(t_pending.forward, ForwardRequests{}); }
 // What a backward with these `phases` takes; what it does not take stays pending.
-//   camera gradients and split SH: consumed by the next backward that runs the per-Gaussian half (phases bit 1), whatever its outcome.  A call without
+//   camera gradients, split SH and raw parameters: consumed by the next backward that runs the per-Gaussian half (phases bit 1), whatever its outcome.  A call without
 //       bit 1 leaves them pending.
 //   backward background: consumed by the next backward that runs the render half (phases bit 0), whatever its outcome.  A call without
 //       bit 0 leaves it pending (nothing of it lives in the gradient records).
@@ -77,7 +87,7 @@ static BackwardRequests take_backward_requests(int phases)
 {
     BackwardRequests& p = t_pending.backward;
     BackwardRequests r;
-    if (phases & 2) { r.cam = std::exchange(p.cam, CameraGradRequest{}); r.split_sh = std::exchange(p.split_sh, BackwardSplitSh{}); }
+    if (phases & 2) { r.cam = std::exchange(p.cam, CameraGradRequest{}); r.split_sh = std::exchange(p.split_sh, BackwardSplitSh{}); r.raw_params = std::exchange(p.raw_params, 0); }
     r.absgrad = std::exchange(p.absgrad, nullptr); r.blend_stats = std::exchange(p.blend_stats, nullptr);
     r.invdepth = std::exchange(p.invdepth, BackwardInvdepth{});
     if (phases & 1) r.background = std::exchange(p.background, BackwardBackground{});
@@ -115,6 +125,8 @@ void stp_set_backward_invdepth(const float* invdepth, const float* dL_dinvdepth)
 void stp_set_forward_split_sh(const float* dc) { t_pending.forward.sh_dc = dc; }
 void stp_set_forward_sh_stash(int enable) { t_pending.forward.sh_stash = enable != 0; }
 void stp_set_backward_split_sh(const float* dc, float* dL_ddc) { t_pending.backward.split_sh = dc ? BackwardSplitSh{dc, dL_ddc} : BackwardSplitSh{}; }
+void stp_set_forward_raw_params(int mask) { t_pending.forward.raw_params = mask; }
+void stp_set_backward_raw_params(int mask) { t_pending.backward.raw_params = mask; }
 
 namespace {
 // Scratch of the uniform background gradient's two-stage sum (stp_background.hip): a small ring of partial-row buffers per device, made at the
@@ -196,6 +208,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
         if (((phases >> 8) & 0xFF) > 1)
             return fail(STP_ERR_INVALID_ARGUMENT, "camera gradients are not available from a chunked per-Gaussian half (phases bits 8-23)");
     }
+    if (int rc = check_raw_params(req.raw_params, opacities, scales, rotations)) return rc;
     if (!settings) return fail(STP_ERR_INVALID_ARGUMENT, "null settings");
     if (P == 0) { // reference rasterize_points.cu:191 (a camera request still gets its outputs: zeros; so does a background gradient -- the forward left the caller's image alone)
         if (cam.dL_dview) STP_TRY(launch_camera_grad_finalize(0, cam, st), "camera gradient launch");
@@ -236,6 +249,7 @@ int stp_backward_phases(int phases, int P, int D, int M, int R, const float* bac
     bw.invdepth = binv.invdepth; bw.dL_dinvdepth = binv.dL_dinvdepth;
     bw.sh_stash = sh_stash;
     if (bsh.dc && !colors_precomp) { f.sh_dc = bsh.dc; bw.dL_ddc = bsh.dL_ddc; }
+    f.raw_params = req.raw_params;
     bw.pixel_colors = pixel_colors; bw.dL_dpix = dL_dpix; bw.dL_dmean2D = dL_dmean2D; bw.grad_rec = grad_records;
     bw.grad_stride = (phases & 4) ? STP_GRAD_RECORD_USED : STP_GRAD_RECORD_FLOATS;
     bw.clear_rec = (phases & 8) ? 1 : 0;
@@ -294,6 +308,20 @@ int stp_backward(int P, int D, int M, int R, const float* background, int width,
                                scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, cam_pos, tan_fovx,
                                tan_fovy, pixel_colors, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dmean2D, grad_records,
                                dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream);
+}
+
+int stp_activate_params(int P, const float* scaling, const float* rotation, const float* opacity, float* scales, float* rotations, float* opacities,
+                        void* stream)
+{
+    if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_activate_params: negative P");
+    if (P >= (1 << 29)) return fail(STP_ERR_INVALID_ARGUMENT, "stp_activate_params: P must be below 2^29");
+    if (!scaling != !scales || !rotation != !rotations || !opacity != !opacities)
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_activate_params: an input and its output must be given, or be NULL, together");
+    if (P == 0) return 0;
+    hipError_t e = hipSuccess;
+    const int launches = launch_activate_params(P, scaling, rotation, opacity, scales, rotations, opacities, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "activate_params launch");
+    return launches;
 }
 
 int stp_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present, void* stream)

@@ -12,6 +12,7 @@
 #include "stp_internal.h"
 #include "stp_device.h"
 #include "stp_sh_dir.h"
+#include "stp_activations.h"
 
 namespace stp {
 
@@ -47,7 +48,21 @@ struct BwdPreArgs {
     const float* dc;       // SPLIT only: the (P, 3) first SH coefficient; `shs` is then the (P, M-1, 3) rest (not read for M == 1, never nullptr)
     float* dL_ddc;         // SPLIT only: P x 3; dL_dsh is then P x (M-1) x 3
     const float* sh_stash; // STASH only: the forward's nine planes of P floats (stp_sh_dir.h; stp_set_forward_sh_stash)
+    int raw;               // stp_set_backward_raw_params: which of opacities / scales / rotations hold raw parameters (stp_activations.h: RAW_*); wave-uniform
 };
+
+// The chain rule of the three activations (stp_activations.h) behind the gradient the kernel has for the activated value: what autograd gives for
+// torch.sigmoid / torch.exp / F.normalize in front of the call, every step one correctly rounded operation (no contraction can reach into them).
+__device__ __forceinline__ float raw_opacity_grad(float g, float o) { return __fmul_rn(g, __fmul_rn(o, __fsub_rn(1.0f, o))); }
+__device__ __forceinline__ float raw_scale_grad(float g, float s) { return __fmul_rn(g, s); }
+// qh: the normalised quaternion, norm: |q| before the clamp.  (g - qh (qh . g)) / |q|; where the clamp was active the norm took no part: g / eps
+__device__ __forceinline__ float4 raw_rotation_grad(float4 g, float4 qh, float norm)
+{
+    if (norm < kRawQuatEps) return make_float4(__fdiv_rn(g.x, kRawQuatEps), __fdiv_rn(g.y, kRawQuatEps), __fdiv_rn(g.z, kRawQuatEps), __fdiv_rn(g.w, kRawQuatEps));
+    const float d = __fmaf_rn(qh.w, g.w, __fmaf_rn(qh.z, g.z, __fmaf_rn(qh.y, g.y, __fmul_rn(qh.x, g.x))));
+    return make_float4(__fdiv_rn(__fmaf_rn(-qh.x, d, g.x), norm), __fdiv_rn(__fmaf_rn(-qh.y, d, g.y), norm), __fdiv_rn(__fmaf_rn(-qh.z, d, g.z), norm),
+                       __fdiv_rn(__fmaf_rn(-qh.w, d, g.w), norm));
+}
 
 // Camera-gradient contributions of one Gaussian (CAM instantiation), in the order of a workspace row:
 //   [0..11]  dL/dviewmatrix[i][j], i = 0..3 (world axis; 3 = translation), j = 0..2 (view axis) at 3*i + j  (column 3 is never read)
@@ -174,8 +189,14 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
             const float det_plus = c_xx * c_yy - c_xy * c_xy;
             const float h_scal = sqrtf(fmaxf(0.000025f, det_cov_orig / det_plus));
             const float dL_dop_v = rec_op;
-            const float d_h_scal = dL_dop_v * (TERMS ? opaque(a.opacities[idx]) : a.opacities[idx]);
-            if constexpr (!TERMS) a.dL_dopacity[idx] = dL_dop_v * h_scal;
+            float op_v = a.opacities[idx];
+            if (a.raw & RAW_OPACITY) op_v = activate_opacity(op_v); // (recomputed from the raw value: no activated copy exists)
+            const float d_h_scal = dL_dop_v * (TERMS ? opaque(op_v) : op_v);
+            if constexpr (!TERMS) {
+                float g_op = dL_dop_v * h_scal;
+                if (a.raw & RAW_OPACITY) g_op = raw_opacity_grad(g_op, op_v);
+                a.dL_dopacity[idx] = g_op;
+            }
             const float d_inside_root = (det_cov_orig / det_plus) <= 0.000025f ? 0.f : d_h_scal / (2 * h_scal);
             const float x = c_xx, y = c_yy, z = c_xy, w = h_var;
             const float qd = w * w + w * (x + y) + x * y - z * z;
@@ -184,7 +205,9 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
             dL_dc_yy = w * (w * x + x * x + z * z) * denom_f;
             dL_dc_xy = -2.f * w * z * (w + x + y) * denom_f;
         } else if constexpr (!TERMS) {
-            a.dL_dopacity[idx] = rec_op;
+            float g_op = rec_op;
+            if (a.raw & RAW_OPACITY) g_op = raw_opacity_grad(g_op, activate_opacity(a.opacities[idx])); // (the one read the mask adds: 4 B per Gaussian)
+            a.dL_dopacity[idx] = g_op;
         }
         const float denom = c_xx * c_yy - c_xy * c_xy;
         const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
@@ -348,11 +371,16 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
 
     // ---- covariance -> scale / rotation ----
     if (a.scales != nullptr) {
-        const float4 qv = reinterpret_cast<const float4*>(a.rotations)[idx];
+        float4 qv = reinterpret_cast<const float4*>(a.rotations)[idx];
+        float s0 = a.scales[3 * (size_t)idx], s1 = a.scales[3 * (size_t)idx + 1], s2 = a.scales[3 * (size_t)idx + 2];
+        float q_norm = 0.0f;
+        if (a.raw != 0) { // raw parameters: the activations recomputed at the load, their chain rule at the stores below
+            if (a.raw & RAW_ROTATION) qv = activate_rotation(qv, &q_norm);
+            if (a.raw & RAW_SCALE) { s0 = activate_scale(s0); s1 = activate_scale(s1); s2 = activate_scale(s2); }
+        }
         const float r = qv.x, x = qv.y, y = qv.z, z = qv.w;
         const Mat3 R = quat_to_mat(qv);
-        const float sx = a.scale_modifier * a.scales[3 * (size_t)idx], sy = a.scale_modifier * a.scales[3 * (size_t)idx + 1],
-                    sz = a.scale_modifier * a.scales[3 * (size_t)idx + 2];
+        const float sx = a.scale_modifier * s0, sy = a.scale_modifier * s1, sz = a.scale_modifier * s2;
         const Mat3 Mm = mat_mul(mat_diag(sx, sy, sz), R);
         const float* d = dcov;
         Mat3 dSig;
@@ -367,9 +395,13 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         const Mat3 dL_dM = mat_mul(M2, dSig);
         const Mat3 Rt = mat_transpose(R);
         Mat3 dMt = mat_transpose(dL_dM);
-        a.dL_dscale[3 * (size_t)idx + 0] = Rt.m[0][0] * dMt.m[0][0] + Rt.m[0][1] * dMt.m[0][1] + Rt.m[0][2] * dMt.m[0][2];
-        a.dL_dscale[3 * (size_t)idx + 1] = Rt.m[1][0] * dMt.m[1][0] + Rt.m[1][1] * dMt.m[1][1] + Rt.m[1][2] * dMt.m[1][2];
-        a.dL_dscale[3 * (size_t)idx + 2] = Rt.m[2][0] * dMt.m[2][0] + Rt.m[2][1] * dMt.m[2][1] + Rt.m[2][2] * dMt.m[2][2];
+        float gs0 = Rt.m[0][0] * dMt.m[0][0] + Rt.m[0][1] * dMt.m[0][1] + Rt.m[0][2] * dMt.m[0][2];
+        float gs1 = Rt.m[1][0] * dMt.m[1][0] + Rt.m[1][1] * dMt.m[1][1] + Rt.m[1][2] * dMt.m[1][2];
+        float gs2 = Rt.m[2][0] * dMt.m[2][0] + Rt.m[2][1] * dMt.m[2][1] + Rt.m[2][2] * dMt.m[2][2];
+        if (a.raw & RAW_SCALE) { gs0 = raw_scale_grad(gs0, s0); gs1 = raw_scale_grad(gs1, s1); gs2 = raw_scale_grad(gs2, s2); }
+        a.dL_dscale[3 * (size_t)idx + 0] = gs0;
+        a.dL_dscale[3 * (size_t)idx + 1] = gs1;
+        a.dL_dscale[3 * (size_t)idx + 2] = gs2;
 #pragma unroll
         for (int j = 0; j < 3; j++) { dMt.m[0][j] *= sx; dMt.m[1][j] *= sy; dMt.m[2][j] *= sz; }
         float4 dq;
@@ -377,7 +409,8 @@ __device__ __forceinline__ void gaussian_backward(const BwdPreArgs& a, int idx, 
         dq.y = 2 * y * (dMt.m[1][0] + dMt.m[0][1]) + 2 * z * (dMt.m[2][0] + dMt.m[0][2]) + 2 * r * (dMt.m[1][2] - dMt.m[2][1]) - 4 * x * (dMt.m[2][2] + dMt.m[1][1]);
         dq.z = 2 * x * (dMt.m[1][0] + dMt.m[0][1]) + 2 * r * (dMt.m[2][0] - dMt.m[0][2]) + 2 * z * (dMt.m[1][2] + dMt.m[2][1]) - 4 * y * (dMt.m[2][2] + dMt.m[0][0]);
         dq.w = 2 * r * (dMt.m[0][1] - dMt.m[1][0]) + 2 * x * (dMt.m[2][0] + dMt.m[0][2]) + 2 * y * (dMt.m[1][2] + dMt.m[2][1]) - 4 * z * (dMt.m[1][1] + dMt.m[0][0]);
-        reinterpret_cast<float4*>(a.dL_drot)[idx] = dq; // gradient w.r.t. the quaternion as given (not re-normalised)
+        if (a.raw & RAW_ROTATION) dq = raw_rotation_grad(dq, qv, q_norm);
+        reinterpret_cast<float4*>(a.dL_drot)[idx] = dq; // gradient w.r.t. the quaternion as given (not re-normalised; raw: through the normalisation)
     }
 }
 
@@ -677,6 +710,7 @@ hipError_t launch_preprocess_backward(const FrameParams& f, const GeometryState&
     // the forward's stash (carve_geometry; stp_api.hip has asked the buffer whether one was written): only where there are SH rows to spare
     const bool stash = bw.sh_stash != nullptr && a.shs != nullptr && a.M > 0;
     a.sh_stash = stash ? bw.sh_stash : nullptr;
+    a.raw = f.raw_params; // stp_set_backward_raw_params (every chunk of a chunked half: the request is the call's)
     using Kernel = void (*)(const BwdPreArgs);
     static const Kernel kernels[16] = {
         preprocess_backward_kernel<false, false, false, false>, preprocess_backward_kernel<false, false, true, false>,

@@ -424,6 +424,7 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
         return fail(STP_ERR_INVALID_ARGUMENT, "alpha output / per-pixel background (stp_set_forward_background) are not available with the debug depth visualisation: its image is not C + T * background");
     if (req.out_invdepth && settings->debug_visualization == STP_DEBUG_DEPTH)
         return fail(STP_ERR_INVALID_ARGUMENT, "the inverse-depth output (stp_set_forward_invdepth) is not available with the debug depth visualisation");
+    if (int rc = check_raw_params(req.raw_params, opacities, scales, rotations)) return rc; // stp_set_forward_raw_params
     const float* const sh_dc = colors_precomp ? nullptr : req.sh_dc; // stp_set_forward_split_sh (precomputed colours win)
     if (sh_dc && M > 1 && !shs) return fail(STP_ERR_INVALID_ARGUMENT, "split SH (stp_set_forward_split_sh): M > 1 needs the rest of the coefficients in shs");
     if (!colors_precomp && !shs && !sh_dc) return fail(STP_ERR_INVALID_ARGUMENT, "neither SHs nor precomputed colours given");
@@ -436,6 +437,7 @@ int stp_forward(stp_alloc_fn geometry_alloc, void* geometry_user, stp_alloc_fn b
                rotations, cov3D_precomp, viewmatrix, projmatrix, inv_viewprojmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered);
     f.out_invdepth = req.out_invdepth;
     f.sh_dc = sh_dc;
+    f.raw_params = req.raw_params;
     f.bg_image = fbg.bg_image; f.out_alpha = fbg.out_alpha; // (every render launch of the call: both halves of a split forward, a redone run-ahead frame)
     // stp_set_forward_sh_stash: only a forward that runs the SH colour kernel has anything to stash (launch_sh_color's own test)
     const bool with_stash = req.sh_stash && !colors_precomp && (shs || sh_dc) && M > 0;

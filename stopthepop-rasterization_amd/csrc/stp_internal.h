@@ -188,6 +188,7 @@ struct FrameParams {
     float* out_alpha = nullptr;      // ... and where the render kernels also write alpha = 1 - final_T (H x W)
     float* out_invdepth = nullptr;   // forward, stp_set_forward_invdepth: the render kernels' INVD variants also write sum(alpha T / z) (H x W); preprocess keeps 1 / z
     const float* sh_dc = nullptr;    // stp_set_forward_split_sh / stp_set_backward_split_sh: the (P, 3) first SH coefficient; `shs` is then the (P, M-1, 3) rest (nullptr allowed for M == 1)
+    int raw_params = 0; // stp_set_forward_raw_params / stp_set_backward_raw_params: bit 0 opacities, bit 1 scales, bit 2 rotations hold a trainer's raw parameters (stp_activations.h)
     int wild_cov; // forward, after the status read-back: some visible Gaussian has a Sigma^-1 entry >= 1e36 or not finite (depth keys then take the reciprocal with its domain check)
 };
 
@@ -243,8 +244,9 @@ void fill_frame(FrameParams& f, int P, int D, int M, const float* background, in
 // ---- the one-shot per-thread requests (stp_api.hip: the stp_set_* setters, and the rules by which a call takes them) ----
 struct ForwardSplit { int row = 0; hipEvent_t event = nullptr; bool armed = false; };      // stp_set_forward_split
 struct ForwardBackground { const float* bg_image = nullptr; float* out_alpha = nullptr; }; // stp_set_forward_background
-struct ForwardRequests { ForwardSplit split; ForwardBackground background; float* out_invdepth = nullptr; /* stp_set_forward_invdepth */ const float* sh_dc = nullptr; /* stp_set_forward_split_sh */ bool sh_stash = false; /* stp_set_forward_sh_stash */ };
+struct ForwardRequests { ForwardSplit split; ForwardBackground background; float* out_invdepth = nullptr; /* stp_set_forward_invdepth */ const float* sh_dc = nullptr; /* stp_set_forward_split_sh */ bool sh_stash = false; /* stp_set_forward_sh_stash */ int raw_params = 0; /* stp_set_forward_raw_params */ };
 ForwardRequests take_forward_requests();
+int check_raw_params(int mask, const float* opacities, const float* scales, const float* rotations); // 0, or fail(STP_ERR_INVALID_ARGUMENT) naming the bit
 
 // ---- launchers (one per stage; each returns hipSuccess or the launch error) ----
 hipError_t launch_preprocess(const FrameParams& f, const GeometryState& g, int* radii, uint32_t* tile_counts, hipStream_t st); // tile_counts: nullptr = do not count per tile
@@ -288,6 +290,10 @@ hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmat
 // the launches made, *err = the launch error that ended them early (or hipSuccess)
 int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind, float beta1, float beta2,
                        hipStream_t st, hipError_t* err);
+// the activated copies of a trainer's raw parameters (stp_activate.hip) over arguments stp_activate_params has validated (P in [1, 2^31 / 4)); any
+// of the three pairs may be nullptr together: one launch per pair given; returns the launches made, *err = the launch error (or hipSuccess)
+int launch_activate_params(int P, const float* scaling, const float* rotation, const float* opacity, float* scales, float* rotations, float* opacities,
+                           hipStream_t st, hipError_t* err);
 // the 3DGS-MCMC kernels (stp_mcmc.hip) over arguments stp_mcmc_relocation / stp_mcmc_add_noise have validated (n, P in [1, 2^31)): one launch
 // each; both return the launches made, *err = the launch error (or hipSuccess)
 int launch_mcmc_relocation(int n, const float* opacity_old, const float* scale_old, const void* N, int n_kind, int n_max, float* opacity_new,

@@ -14,6 +14,7 @@
 #include "stp_internal.h"
 #include "stp_device.h"
 #include "stp_sh_dir.h"
+#include "stp_activations.h"
 
 namespace stp {
 
@@ -24,6 +25,7 @@ struct PreArgs {
     int P, D, M, W, H, gx, gy, ty0, ty1;
     float focal_x, focal_y, tan_fovx, tan_fovy, scale_modifier;
     int sort_order, rect_bounding, tight_opacity_bounding, tile_based_culling, proper_ewa_scaling, prefiltered;
+    int raw; // stp_set_forward_raw_params: which of opacities / scales / rotations hold raw parameters (stp_activations.h: RAW_*); wave-uniform
     const float* means3D;
     const float* scales;
     const float* rotations;
@@ -108,7 +110,7 @@ __device__ __forceinline__ bool preprocess_stage_a(const PreArgs& a, int idx, Pr
     // every per-Gaussian input up front, before the first test can branch: the loads are in flight together (one memory
     // latency) instead of one after each early-out
     const float3 mean = make_float3(a.means3D[3 * (size_t)idx], a.means3D[3 * (size_t)idx + 1], a.means3D[3 * (size_t)idx + 2]);
-    const float opacity = a.opacities[idx];
+    float opacity = a.opacities[idx];
     float3 sc_in = make_float3(0.0f, 0.0f, 0.0f);
     float4 q_in = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float c3_in[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -119,6 +121,13 @@ __device__ __forceinline__ bool preprocess_stage_a(const PreArgs& a, int idx, Pr
     if (a.scales != nullptr && a.rotations != nullptr) { // (also WITH a precomputed covariance: Sigma^-1 is always built from these, forward.cu:208-220)
         sc_in = make_float3(a.scales[3 * (size_t)idx], a.scales[3 * (size_t)idx + 1], a.scales[3 * (size_t)idx + 2]);
         q_in = reinterpret_cast<const float4*>(a.rotations)[idx];
+    }
+    if (a.raw != 0) { // raw parameters: activated at the load, and everything below is what it is for activated inputs (mask 0: one scalar test)
+        if (a.raw & RAW_OPACITY) opacity = activate_opacity(opacity);
+        if (a.scales != nullptr && a.rotations != nullptr) {
+            if (a.raw & RAW_SCALE) sc_in = make_float3(activate_scale(sc_in.x), activate_scale(sc_in.y), activate_scale(sc_in.z));
+            if (a.raw & RAW_ROTATION) q_in = activate_rotation(q_in, nullptr);
+        }
     }
     const float* __restrict__ view = a.view;
     // view-space position; near culling at z <= 0.2 (reference auxiliary.h:211-236)
@@ -715,6 +724,7 @@ hipError_t launch_preprocess(const FrameParams& f, const GeometryState& g, int* 
     a.focal_x = f.focal_x; a.focal_y = f.focal_y; a.tan_fovx = f.tan_fovx; a.tan_fovy = f.tan_fovy; a.scale_modifier = f.scale_modifier;
     a.sort_order = f.s.sort_order; a.rect_bounding = f.s.rect_bounding; a.tight_opacity_bounding = f.s.tight_opacity_bounding;
     a.tile_based_culling = f.s.tile_based_culling; a.proper_ewa_scaling = f.s.proper_ewa_scaling; a.prefiltered = f.prefiltered;
+    a.raw = f.raw_params;
     a.means3D = f.means3D; a.scales = f.scales; a.rotations = f.rotations; a.opacities = f.opacities; a.shs = f.shs;
     a.cov3D_precomp = f.cov3D_precomp; a.colors_precomp = f.colors_precomp; a.view = f.viewmatrix; a.proj = f.projmatrix; a.cam = f.cam_pos;
     a.radii = radii; a.g = g; a.tile_counts = tile_counts;

@@ -52,6 +52,9 @@ _OPTIONAL_SYMBOLS = {
     "stp_set_forward_split_sh": ([ctypes.c_void_p], None, "split SH inputs"),
     "stp_set_backward_split_sh": ([ctypes.c_void_p] * 2, None, "split SH inputs"),
     "stp_set_forward_sh_stash": ([ctypes.c_int], None, "the SH stash"),
+    "stp_set_forward_raw_params": ([ctypes.c_int], None, "raw parameter inputs"),
+    "stp_set_backward_raw_params": ([ctypes.c_int], None, "raw parameter inputs"),
+    "stp_activate_params": ([ctypes.c_int] + [ctypes.c_void_p] * 7, ctypes.c_int, "raw parameter inputs"),
     "stp_geometry_buffer_size_stash": ([ctypes.c_int, ctypes.POINTER(StpSettings)], ctypes.c_size_t, "the SH stash"),
     "stp_sparse_adam": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
                         ctypes.c_int, "the sparse Adam step"),
@@ -355,7 +358,7 @@ def _records_log(d: dict) -> bool:
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, inv_viewprojmatrix, tan_fovx, tan_fovy, image_height, image_width,
                         sh, degree, campos, prefiltered, settings_dict, render_depth, debug, alpha=False, invdepth=False,
-                        dc=None) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                        raw=0, dc=None) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """== RasterizeGaussiansCUDA (reference rasterize_points.cu:43-138).
     Returns (num_rendered, out_color (3,H,W), radii (P,) int32, geomBuffer, binningBuffer, imgBuffer).
 
@@ -369,7 +372,11 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 
     dc=(P,1,3) or (P,3) tensor (keyword; extension, include/stp_raster.h: stp_set_forward_split_sh): the first SH coefficient as a tensor of
     its own (a trainer's _features_dc); `sh` is then the rest, (P,M-1,3) (_features_rest; empty for a degree-0 model).  No concatenated copy
-    is made, and every output equals that of the call on torch.cat((dc, rest), 1) bit for bit.  Ignored with precomputed colours."""
+    is made, and every output equals that of the call on torch.cat((dc, rest), 1) bit for bit.  Ignored with precomputed colours.
+
+    raw=mask (keyword; extension, include/stp_raster.h: stp_set_forward_raw_params): bit 0 `opacity`, bit 1 `scales`, bit 2 `rotations` hold a
+    trainer's raw parameters (logit, log, unnormalised quaternion); the kernel activates them at its load and every output equals that of the
+    call on activate_params' copies bit for bit.  A mask outside 0..7 or a bit whose tensor is empty raises, naming the bit."""
     if means3D.dim() != 2 or means3D.size(1) != 3:   # (the reference's first check, rasterize_points.cu:69-71)
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if alpha or _per_pixel_background(background, image_height, image_width):
@@ -380,10 +387,12 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
             raise RuntimeError("the inverse-depth output (_invdepth) is not available with render_depth (the debug depth visualisation)")
     if dc is not None:
         _require("stp_set_forward_split_sh")
+    if raw:
+        _require("stp_set_forward_raw_params")
     out = (_host or _native()).rasterize_gaussians(
         background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         inv_viewprojmatrix, tan_fovx, tan_fovy, int(image_height), int(image_width), sh, int(degree), campos, bool(prefiltered),
-        settings_dict, bool(render_depth), bool(debug), _records_log(settings_dict), bool(alpha), bool(invdepth), dc)
+        settings_dict, bool(render_depth), bool(debug), _records_log(settings_dict), bool(alpha), bool(invdepth), dc, int(raw))
     return tuple(out[:6]) + ((out[6],) if alpha else ()) + ((out[7],) if invdepth else ())
 
 
@@ -397,7 +406,7 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
                                  pixel_colors, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                                  imageBuffer, settings_dict, debug, phases=3, partial=None, chunk=None, outputs=None,
                                  camera_grads=False, absgrad=False, blend_stats=False, dL_dalpha=None, bg_grad=False,
-                                 dL_dinvdepth=None, invdepth=None, dc=None):
+                                 dL_dinvdepth=None, invdepth=None, raw=0, dc=None):
     """== RasterizeGaussiansBackwardCUDA (reference rasterize_points.cu:140-232).
     Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
 
@@ -428,6 +437,10 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
     extra above: (the eight) (the camera's three) (absgrad) (blend_stats) (dL_dbackground) (dL_ddc).  Both equal the two slices of the
     concatenated call's dL_dsh bit for bit.  Per-Gaussian half (phases bit 1); works chunked, `outputs` then carries nine tensors.
 
+    raw=mask (keyword; extension, include/stp_raster.h: stp_set_backward_raw_params): the forward's mask.  dL_dopacity / dL_dscales /
+    dL_drotations of its bits are then the gradients with respect to the RAW values (the chain rule of sigmoid / exp / normalize applied at the
+    kernel's stores).  Per-Gaussian half (phases bit 1; ignored by a render-only call); works chunked and with compact records.
+
     Extension for tile-row sharding (not in the reference): phases=1 runs only the render half and
     returns its per-Gaussian partial sums as the library's (P,16) gradient records (stp_raster.h);
     phases=2 takes the records (after the caller's all-reduce) as `partial` and runs the preprocess half.
@@ -449,13 +462,15 @@ def rasterize_gaussians_backward(background, means3D, radii, opacities, colors, 
         _require("stp_set_backward_invdepth")
     if dc is not None:
         _require("stp_set_backward_split_sh")
+    if raw:
+        _require("stp_set_backward_raw_params")
     if dL_dalpha is not None or bg_grad or _per_pixel_background(background, dL_dout_color.shape[-2], dL_dout_color.shape[-1]):
         _require("stp_set_backward_background")
     out = (_host or _native()).rasterize_gaussians_backward(
         background, means3D, radii, opacities, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         inv_viewprojmatrix, tan_fovx, tan_fovy, pixel_colors, dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer,
         imageBuffer, settings_dict, bool(debug), _records_log(settings_dict), int(phases), partial, None if outputs is None else list(outputs),
-        bool(camera_grads), bool(absgrad), bool(blend_stats), dL_dalpha, bool(bg_grad), dL_dinvdepth, invdepth, dc)
+        bool(camera_grads), bool(absgrad), bool(blend_stats), dL_dalpha, bool(bg_grad), dL_dinvdepth, invdepth, dc, int(raw))
     return out[0] if (int(phases) & 3) == 1 and not bg_grad else tuple(out)
 
 
@@ -503,6 +518,18 @@ def mcmc_add_noise(xyz, scales, rotations, opacities, noise, noise_scale, k, x0,
     (P, 1), noise (P, 3), all float32 on one GPU.  Returns the kernel launches made (1; 0 for P == 0)."""
     _require("stp_mcmc_add_noise")
     return int((_host or _native()).mcmc_add_noise(xyz, scales, rotations, opacities, noise, float(noise_scale), float(k), float(x0), bool(raw)))
+
+
+def activate_params(scaling=None, rotation=None, opacity=None):
+    """The activated copies of a trainer's raw parameters (extension, include/stp_raster.h: stp_activate_params), on the current stream:
+    -> (scales, rotations, opacities) = (exp(scaling), rotation / max(|rotation|, 1e-12), sigmoid(opacity)), fresh contiguous float32 tensors in
+    the inputs' shapes, None for an absent input -- the values the rasterizer's raw= path renders with, to the bit.  scaling (P, 3),
+    rotation (P, 4), opacity (P,) or (P, 1), float32 on one GPU.  One launch per tensor given."""
+    if scaling is None and rotation is None and opacity is None:
+        return None, None, None
+    _require("stp_activate_params")
+    out = (_host or _native()).activate_params(scaling, rotation, opacity)
+    return tuple(o if given is not None else None for o, given in zip(out, (scaling, rotation, opacity)))
 
 
 KNN_BOX = 256   # == STP_KNN_BOX (include/stp_raster.h): points per box of the search, and lanes per workgroup

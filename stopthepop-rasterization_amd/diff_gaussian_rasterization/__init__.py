@@ -27,7 +27,7 @@ from . import _C
 __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes", "SortSettings", "CullingSettings",
            "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam",
            "photometric_terms", "fused_ssim", "photometric_loss", "compute_relocation", "mcmc_add_noise_",
-           "knn_mean_dist2", "distCUDA2", "dist_cuda2",
+           "knn_mean_dist2", "distCUDA2", "dist_cuda2", "activate_params",
            "densification_stats_", "densify_plan", "densify_tensors", "densify_and_prune"]
 
 
@@ -41,9 +41,14 @@ def cpu_deep_copy_tuple(input_tuple):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, dc=None):
+                        raster_settings, dc=None, raw=0):
     """dc (extension, include/stp_raster.h: stp_set_forward_split_sh): the first SH coefficient, (P, 1, 3) or (P, 3), as a tensor of its own;
-    `sh` is then the rest, (P, M-1, 3).  It rides behind raster_settings in every Function, so that the inputs in front keep their places."""
+    `sh` is then the rest, (P, M-1, 3).  It rides behind raster_settings in every Function, so that the inputs in front keep their places.
+    raw (extension, include/stp_raster.h: stp_set_forward_raw_params): the mask of the raw parameter inputs (bit 0 opacities, bit 1 scales,
+    bit 2 rotations).  It is no input of the Functions -- dc stays their last --: it rides on the settings tuple (_with_raw_mask); with a
+    mask of 0 the tuple is the caller's own and the call is the one it always was."""
+    if raw:
+        raster_settings = _with_raw_mask(raster_settings, int(raw))
     rs = raster_settings
     if torch.is_grad_enabled() and isinstance(rs.bg, torch.Tensor) and rs.bg.requires_grad:
         # a learnable background: bg -- and the camera tensors, which get their gradients here too where they require them -- become explicit
@@ -62,7 +67,8 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
                   save_camera=False, bg=None, dc=None):
     """The forward the autograd Functions share (the camera tensors are rs's own, or the camera Function's explicit inputs, which
     save_camera=True saves for the backward behind the twelve tensors every Function saves; bg: the background Function's explicit input,
-    saved behind them; dc: the split SH input, saved behind those -- sh is then the rest --; the inverse-depth output stays LAST)."""
+    saved behind them; dc: the split SH input, saved behind those -- sh is then the rest --; the inverse-depth output stays LAST; a raw
+    mask on rs (_with_raw_mask): opacities / scales / rotations are then saved as they came in, raw, and the backward recomputes the activations)."""
     sdict = rs.settings.to_dict()
     save_bg = bg is not None
     if bg is None:
@@ -137,8 +143,12 @@ def _forward_body(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, 
     if dc is not None and colors_precomp.numel() == 0:
         kw["dc"] = dc
         ctx.dc_index = 12 + (3 if save_camera else 0) + (1 if save_bg else 0)
+    # raw parameter inputs (extension; include/stp_raster.h: stp_set_forward_raw_params): the mask rides to the kernel, no activated copy is made
+    ctx.raw = int(getattr(rs, "raw_mask", 0))
+    if ctx.raw:
+        kw["raw"] = ctx.raw
     if rs.debug:
-        cpu_args = cpu_deep_copy_tuple(args + ((dc,) if "dc" in kw else ()))  # snapshot before anything can corrupt them (dc: behind the 22)
+        cpu_args = cpu_deep_copy_tuple(args + ((dc,) if "dc" in kw else ()) + ((ctx.raw,) if ctx.raw else ()))  # snapshot before anything can corrupt them (dc, then the raw mask: behind the 22)
         try:
             num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, *extra = _C.rasterize_gaussians(*args, **kw)
         except Exception as ex:
@@ -211,8 +221,10 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
     dc = ctx.saved_tensors[ctx.dc_index] if ctx.dc_index is not None else None
     if dc is not None:
         kw["dc"] = dc
+    if ctx.raw:
+        kw["raw"] = ctx.raw
     if rs.debug:
-        cpu_args = cpu_deep_copy_tuple(args + ((dc,) if dc is not None else ()))
+        cpu_args = cpu_deep_copy_tuple(args + ((dc,) if dc is not None else ()) + ((ctx.raw,) if ctx.raw else ()))
         try:
             out = _C.rasterize_gaussians_backward(*args, **kw)
         except Exception as ex:
@@ -244,6 +256,12 @@ def _backward_body(ctx, grad_out_color, viewmatrix, projmatrix, campos, camera_g
     if ctx.absgrad_target is not None:
         ctx.absgrad_target.absgrad = out[-1]
         out = out[:-1]
+    if ctx.raw:   # (the gradients of the raw leaves in the leaves' own shapes: an opacity of (P,) gets (P,), not the library's (P, 1))
+        out = list(out)
+        for i, t in ((2, opacities), (6, scales), (7, rotations)):
+            if out[i] is not None and t.numel() != 0:
+                out[i] = out[i].view(t.shape)
+        out = tuple(out)
     return out + (grad_bg,) if bg_grad else out
 
 
@@ -474,10 +492,63 @@ def _check_split_sh(dc, shs, means3D):
                                f"means3D, got {tuple(shs.shape)} {shs.dtype} on {shs.device}")
 
 
+class _RawRasterizationSettings(GaussianRasterizationSettings):
+    """The settings tuple of one call with raw parameter inputs: the caller's fields, and the mask as the attribute raw_mask."""
+
+
+def _with_raw_mask(rs, mask):
+    out = _RawRasterizationSettings(*rs)
+    out.raw_mask = int(mask)
+    return out
+
+
+RAW_PARAM_BITS = {"opacities": 1, "scales": 2, "rotations": 4}   # == the mask of include/stp_raster.h: stp_set_forward_raw_params
+
+
+def _raw_mask(raw, opacities, scales, rotations) -> int:
+    """GaussianRasterizer's raw= argument -> the library's mask, before any device work.  True: every one of the three inputs that
+    is given; False / None: none; otherwise an iterable of their names.  RuntimeError naming what is wrong."""
+    given = {"opacities": opacities is not None, "scales": scales is not None, "rotations": rotations is not None}
+    if raw is None or raw is False:
+        return 0
+    if raw is True:
+        return sum(bit for name, bit in RAW_PARAM_BITS.items() if given[name])
+    if isinstance(raw, str):
+        raw = (raw,)
+    try:
+        names = list(raw)
+    except TypeError:
+        raise RuntimeError(f"raw must be True, False or an iterable of names out of {sorted(RAW_PARAM_BITS)}, got {type(raw).__name__}") from None
+    mask = 0
+    for name in names:
+        if name not in RAW_PARAM_BITS:
+            raise RuntimeError(f"raw: unknown name {name!r}: expected names out of {sorted(RAW_PARAM_BITS)}")
+        if not given[name]:
+            raise RuntimeError(f"raw: {name!r} is named but no {name} are given (with cov3D_precomp there are no scales and rotations to activate)")
+        mask |= RAW_PARAM_BITS[name]
+    return mask
+
+
+def activate_params(scaling=None, rotation=None, opacity=None):
+    """The activated copies of a trainer's raw parameters (extension; include/stp_raster.h: stp_activate_params) -> (scales, rotations,
+    opacities) = (exp(scaling), rotation / max(|rotation|, 1e-12), sigmoid(opacity)): fresh float32 tensors in the inputs' shapes that never
+    require grad, None for an absent input.  These are the values GaussianRasterizer(..., raw=) renders with, to the bit -- for logging,
+    export and tests; the render itself needs no such copy.  scaling (P, 3), rotation (P, 4), opacity (P,) or (P, 1), float32 on one GPU."""
+    return _C.activate_params(*(None if t is None else t.detach() for t in (scaling, rotation, opacity)))
+
+
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings):
+    """raw (extension, a keyword of the constructor; include/stp_raster.h: stp_set_forward_raw_params): the opacities / scales / rotations this
+    rasterizer is called with are a trainer's _opacity (logit), _scaling (log) and _rotation (unnormalised quaternion) as they are stored.
+    True = every one of the three that a call gives, False = none, otherwise an iterable of the names "opacities", "scales", "rotations"
+    (the others are taken as activated).  sigmoid, exp and F.normalize run inside the kernels that read the arrays, the raw tensors are
+    what the backward keeps, and .grad arrives on the raw leaves.  Results equal those of the plain call on activate_params(...) bit for
+    bit in the forward, and autograd's chain rule in the backward.  forward()'s own signature is the reference's plus dc."""
+
+    def __init__(self, raster_settings, raw=False):
         super().__init__()
         self.raster_settings = raster_settings
+        self.raw = raw
 
     def markVisible(self, positions):
         """Boolean mask of the points that pass the camera's near-plane test."""
@@ -489,19 +560,21 @@ class GaussianRasterizer(nn.Module):
                 cov3D_precomp=None, dc=None):
         """dc (extension; include/stp_raster.h: stp_set_forward_split_sh): a trainer's _features_dc, (P, 1, 3) or (P, 3), with shs = its
         _features_rest, (P, M-1, 3) (None or (P, 0, 3) for a degree-0 model) -- no torch.cat going in, and dc.grad / shs.grad come back as
-        two fresh contiguous tensors in the inputs' shapes.  Results equal those of shs = torch.cat((dc, rest), dim=1)."""
+        two fresh contiguous tensors in the inputs' shapes.  Results equal those of shs = torch.cat((dc, rest), dim=1).
+        A rasterizer made with raw= (see the class) reads opacities / scales / rotations as a trainer's stored parameters."""
         rs = self.raster_settings
         have_sh = shs is not None or dc is not None
         if (not have_sh and colors_precomp is None) or (have_sh and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if dc is not None:
             _check_split_sh(dc, shs, means3D)
+        mask = _raw_mask(self.raw, opacities, scales, rotations)
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         empty = lambda t: torch.Tensor([]) if t is None else t  # absent optional input == empty CPU tensor
         return rasterize_gaussians(means3D, means2D, empty(shs), empty(colors_precomp), opacities, empty(scales),
-                                   empty(rotations), empty(cov3D_precomp), rs, dc)
+                                   empty(rotations), empty(cov3D_precomp), rs, dc, *((mask,) if mask else ()))
 
 
 class SparseGaussianAdam(torch.optim.Adam):

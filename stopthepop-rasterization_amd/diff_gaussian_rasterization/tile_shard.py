@@ -370,10 +370,14 @@ class TileRowShardedRasterizer(torch.nn.Module):
     The loss must be evaluated so that each rank back-propagates the gradient of ITS rows (e.g. a per-pixel
     loss evaluated redundantly, or dL/dimage scattered from rank 0)."""
 
-    def __init__(self, raster_settings, dist, rank: int, world: int, to_all: bool = False, rebalance: bool = False):
+    def __init__(self, raster_settings, dist, rank: int, world: int, to_all: bool = False, rebalance: bool = False, raw=False):
         """rebalance: re-partition the tile rows before every frame by the PREVIOUS frame's per-row tile-list lengths (one
         all-reduce of n_rows integers per frame) so that ranks get equal work, not equal height -- for scenes whose
         content is not uniform over the image.  Off by default: the partition is then the fixed ceil(Ty/G) blocks."""
+        if not (raw is None or raw is False or (not isinstance(raw, bool) and hasattr(raw, "__len__") and len(raw) == 0)):
+            # (GaussianRasterizer's raw parameter inputs: left out on purpose, like forward's split SH input)
+            raise RuntimeError("raw= (raw parameter inputs) is not wired through the tile-row shard: pass torch.sigmoid / torch.exp / "
+                               "F.normalize of the raw tensors, or render on one GPU")
         super().__init__()
         self.raster_settings = raster_settings
         self.n_rows = tile_rows(raster_settings.image_height)
