@@ -3,7 +3,7 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--split-sh] [--raw-params] [--init-scales scene|knn]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--relocate torch|fused] [--cap-max N] [--split-sh] [--raw-params] [--init-scales scene|knn]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
@@ -25,7 +25,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "stopthepop-rasterization_amd"))
 from diff_gaussian_rasterization import (CullingSettings, ExtendedSettings, GaussianRasterizationSettings,  # noqa: E402
                                          GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, SparseGaussianAdam, compute_relocation,
-                                         densification_stats_, densify_and_prune, densify_plan, mcmc_add_noise_, photometric_loss, scenes)
+                                         densification_stats_, densify_and_prune, densify_plan, mcmc_add_new, mcmc_add_noise_, mcmc_relocate_, photometric_loss, scenes)
 
 
 def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, scaling_modifier: float = 1.0,
@@ -182,6 +182,11 @@ def main(argv=None):
                          "compute_relocation, and the opacity / scale L1 regularisers (INTEGRATION.md section 3l).  adc: 3DGS adaptive density control "
                          "-- the fused densification statistics after every backward, densify_plan + densify_and_prune every 10 iterations "
                          "(INTEGRATION.md section 3m)")
+    ap.add_argument("--relocate", default="torch", choices=["torch", "fused"],
+                    help="under --strategy mcmc, fused: mcmc_relocate_ in place of the torch composition relocate_dead() -- the draw and the rewrite of every "
+                         "tensor and both Adam moments without host synchronisation -- and mcmc_add_new (upstream's add_new_gs) every 10 iterations, "
+                         "growing towards --cap-max (INTEGRATION.md section 3r)")
+    ap.add_argument("--cap-max", type=int, default=None, metavar="N", help="the most Gaussians --relocate fused grows to (default: 1.15 x --points)")
     ap.add_argument("--split-sh", action="store_true",
                     help="the model keeps _features_dc and _features_rest as two parameters (two optimizer groups, the rest at a twentieth of the "
                          "learning rate, as upstream) and renders with dc=: no torch.cat per step (INTEGRATION.md section 3n)")
@@ -220,7 +225,9 @@ def main(argv=None):
             model._scaling.copy_(torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3))
             print(f"initial scales from distCUDA2 over {dist2.numel()} points: mean 3-NN distance {float(torch.sqrt(dist2).mean()):.4f}")
     adc = args.strategy == "adc"
-    if adc and args.optimizer != "sparse_adam":   # densify_and_prune wants the trainers' layout: one named group per tensor
+    fused_mcmc = args.strategy == "mcmc" and args.relocate == "fused"
+    cap_max = args.cap_max if args.cap_max is not None else (115 * args.points) // 100
+    if (adc or fused_mcmc) and args.optimizer != "sparse_adam":   # densify_and_prune and mcmc_relocate_ want the trainers' layout: one named group per tensor
         opt = torch.optim.Adam([*model.feature_groups(2e-2), {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
                                 {"params": [model._xyz], "lr": 0.0, "name": "xyz"}, {"params": [model._scaling], "lr": 0.0, "name": "scaling"},
                                 {"params": [model._rotation], "lr": 0.0, "name": "rotation"}], lr=0.0, eps=1e-15)
@@ -247,7 +254,8 @@ def main(argv=None):
     label = "L1" if args.loss == "l1" else "0.8 L1 + 0.2 (1 - SSIM)"
     mcmc = args.strategy == "mcmc"
     noise_scale = 5e5 * 1.6e-4   # upstream's noise_lr times its initial position learning rate (the positions themselves are not fitted here)
-    relocated = relocations = 0
+    relocated = relocations = 0   # (--relocate fused: `relocated` is a device scalar until the end: counting must not synchronise either)
+    added = 0
     if mcmc:
         torch.manual_seed(0)   # (the noise and the sampling are torch's: a run is reproducible)
         with torch.no_grad():  # every fiftieth Gaussian starts dead (opacity 0.002), so that the first relocation has work whatever the fit does
@@ -277,11 +285,32 @@ def main(argv=None):
             if args.absgrad:   # assigned by every backward, never accumulated: the running sum is the trainer's
                 stat_abs[vis] += out["viewspace_points"].absgrad[vis, :2].norm(dim=-1)
         if args.optimizer == "sparse_adam":   # the forward's radii are the visibility: no mask tensor on the way
+            if not args.split_sh:
+                # SparseGaussianAdam has no bias correction (as upstream's): its step t is (1 - b1^t) / sqrt(1 - b2^t) times Adam's, 3.2 at t = 1 and 6.5
+                # at t = 10.  Upstream's groups bear that -- the higher-order SH coefficients step at a twentieth of the dc rate there -- but
+                # this model's single SH tensor steps them all at the dc rate, and the fit's loss tripled within two steps (0.035 -> 0.123;
+                # profiles/EXPERIMENTS.md).  The class reads group["lr"] at every step, so the correction goes in there, as a trainer's schedule would.
+                group = next(g for g in opt.param_groups if g.get("name") == "f")
+                b1, b2 = group["betas"]
+                group["lr"] = 2e-2 * math.sqrt(1.0 - b2 ** (it + 1)) / (1.0 - b1 ** (it + 1))
             opt.step(out["radii"], model.get_xyz.shape[0])
         else:
             opt.step()
         if mcmc:
-            if it > 0 and it % 10 == 0:
+            if it > 0 and it % 10 == 0 and fused_mcmc:
+                # upstream's relocate_gs and add_new_gs on the optimizer's named groups, without a host synchronisation: the Parameters keep their
+                # identity through the relocation; the growth hands new ones back, as densify_and_prune does
+                plan = mcmc_relocate_(opt, raw=True, reset_dead_moments=True)   # (relocate_dead() below zeroes the dead rows' moments too)
+                relocated = relocated + (plan[0] >= 0).sum()
+                relocations += 1
+                new = mcmc_add_new(opt, cap_max, raw=True)
+                if new:
+                    before = model.get_xyz.shape[0]
+                    model.take_features(new)
+                    model._opacity, model._xyz, model._scaling, model._rotation = (new[n] for n in ("opacity", "xyz", "scaling", "rotation"))
+                    added += model.get_xyz.shape[0] - before
+                    stat_signed, stat_abs = (torch.zeros(model.get_xyz.shape[0], device=dev) for _ in range(2))
+            elif it > 0 and it % 10 == 0:
                 relocated += relocate_dead(model, opt)
                 relocations += 1
             # xyz += Sigma (randn * op_sigmoid(1 - opacity) * noise_lr * xyz_lr) in one kernel, from the raw parameters the step just moved
@@ -308,7 +337,9 @@ def main(argv=None):
     if adc:
         print(f"adc: {grown} rows appended and {pruned} originals removed over the run, {model.get_xyz.shape[0]} Gaussians at the end")
     if mcmc:
-        print(f"mcmc: relocated {relocated} Gaussians in {relocations} relocation steps (opacity <= 0.005), position noise after each of {args.iters} steps")
+        print(f"mcmc: relocated {int(relocated)} Gaussians in {relocations} relocation steps (opacity <= 0.005), position noise after each of {args.iters} steps")
+        if fused_mcmc:
+            print(f"mcmc: {added} Gaussians added towards cap_max = {cap_max}, {model.get_xyz.shape[0]} at the end")
     if args.absgrad:
         print(f"densification statistic, mean over Gaussians: signed {float(stat_signed.mean()):.3e}, absolute {float(stat_abs.mean()):.3e} "
               f"(absolute >= signed for {float((stat_abs >= stat_signed * (1 - 1e-5)).float().mean()) * 100:.1f} % of them)")

@@ -419,6 +419,58 @@ int stp_mcmc_relocation(int n, const float* opacity_old, const float* scale_old,
 int stp_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise,
                        float noise_scale, float k, float x0, int raw, void* stream);
 
+/* Extension (not in the reference): the rest of a 3DGS-MCMC trainer's relocate_gs and add_new_gs around stp_mcmc_relocation -- the multinomial
+   draw of the sources and the rewrite of every parameter and both Adam moments -- in three calls.  All tensors are float32, all pointers are
+   device pointers to contiguous data, every call runs on the caller's stream, allocates nothing and NEVER synchronises with the host; no float
+   atomics: equal inputs (the uniforms included) give equal bits.  o below is the opacity: opacity[i] itself, or 1 / (1 + expf(-opacity[i]))
+   where raw (the evaluation of stp_mcmc_add_noise).
+   stp_mcmc_sample draws sources with probability proportional to opacity by an inverse CDF over INTEGER weights:
+       w_i = rint(min(max(o_i, 0), 1) * 2^24) for a candidate row (round to nearest even), 0 for any other      S_i = w_0 + ... + w_i  (64-bit: exact)
+       u clamped into [0, 1) (NaN, negatives: 0; >= 1: the largest float32 below 1)         t = min(total - 1, (uint64) ((double) u * (double) total))
+       the source of a draw = the smallest k with S_k > t  (never a row of weight 0)         count[k] = the number of draws that chose k
+     rule 0 (relocation): the candidates are the rows with o > min_opacity; n_draws must be P, draw i is row i's (it reads uniforms[i]) and is
+       made only where o_i <= min_opacity (a dead row); src[i] = -1 for every other row.  A NaN opacity is neither dead nor a candidate.
+     rule 1 (growth): every row whose opacity is a number is a candidate; draw j < n_draws reads uniforms[j] and writes src[j]; min_opacity
+       is not read.
+     A total weight of 0 (or no dead row) leaves every src -1 and every count 0: decided on the device.  The quantisation of the weights
+     moves w_i by at most half a unit, that is 2^-25 of the largest weight: a probability o_i / sum(o) moves by at most 2^-25 / o_i relative
+     (opacities of 0.5 and above are exact; one of 2^-25 or below has weight 0 and is never drawn).
+     weights (P uint32) may be null; src: n_draws int32; count: P int32 (cleared by the call).  The uniforms are the caller's (torch.rand).
+   stp_mcmc_relocate_apply, IN PLACE, by a (src, count) pair of rule 0: with (o', s') = stp_mcmc_relocation's results for (o_k, s_k,
+       N = min(count[k] + 1, 50)), o' = min(max(o', min_opacity), 1 - 2^-23), stored as they are or, where raw, as logf(o' / (1 - o')) and logf(s')
+       (s_k = expf(scaling[k]) then):
+     a row k with count[k] > 0 takes (o', s') in the tensors of role 1 (opacity, row 1) and 2 (scaling, row 3), keeps every other parameter
+       and gets +0.0 in both moments of every tensor;
+     a row i with count[i] <= 0 and src[i] in [0, P) takes row src[i] of every tensor, with that row's (o', s') in the role-1 and role-2
+       tensors; its moments keep their bits, or are +0.0 where reset_dead_moments;
+     every other row, and every other float, keeps its bits.  The new (o', s') are computed per source into the scratch before anything is
+     written, so the result does not depend on the order in which rows are rewritten.  The pair must come from stp_mcmc_sample
+     (count == the histogram of src, no src on a row that draws); a src outside [0, P) is treated as -1.
+   stp_mcmc_add_apply, OUT OF PLACE, by a (src, count) pair of rule 1 with n_new draws, into P + n_new output rows: row r < P is row r with its
+     moments, except that a row with count[r] > 0 takes (o', s') and +0.0 moments; row P + j is row src[j] with that row's (o', s') and +0.0
+     moments (a src outside [0, P) -- a model without any weight -- gives a row of +0.0).  Inputs are not modified; outputs must not overlap
+     inputs.  n_new is a host number (a trainer knows it from P and its cap): no read-back.
+   Each entry: row = floats per Gaussian, exp_avg and exp_avg_sq both given or both null (then nothing is done for moments); the *_out
+   pointers are read by stp_mcmc_add_apply only.  A tensor whose rows are multiples of 16 bytes and whose pointers are all 16-byte aligned
+   moves 16 bytes per lane, others one float at a time, with equal bits.  Up to eight entries go in one launch.
+   scratch: stp_mcmc_relocate_scratch_bytes(P) bytes (a function of P alone: max(8 (P + tiles + 4), 16 P) rounded up to 256, with tiles =
+   ceil(P / STP_MCMC_SAMPLE_TILE); 0 for a P the calls refuse), 16-byte aligned; one buffer serves a sample and the apply that follows it.
+   The three calls return the number of kernel launches made (0 for P == 0: nothing is touched), or a negative StpStatus with the reason in
+   the last-error text.  Refused BEFORE anything is launched (STP_ERR_INVALID_ARGUMENT): a negative count, P > 2^28 (the total weight must
+   stay below 2^53), a raw outside {0, 1}, an unknown rule, n_draws != P under rule 0, null pointers (of anything that would be read or
+   written), a scratch that is too small or not 16-byte aligned; and by the applies: more than 64 entries, row <= 0 or (written rows) * row >=
+   2^31, an unknown role, one moment pointer without the other, a role-1 tensor whose row is not 1 or a role-2 tensor whose row is not 3,
+   and anything but exactly one entry of each of the roles 1 and 2. */
+#define STP_MCMC_SAMPLE_TILE 2048
+typedef struct { float *param, *exp_avg, *exp_avg_sq; float *param_out, *exp_avg_out, *exp_avg_sq_out; int32_t row; int32_t role; } StpMcmcTensor;
+size_t stp_mcmc_relocate_scratch_bytes(int P);
+int stp_mcmc_sample(int P, const float* opacity, int rule /* 0: relocation, 1: growth */, float min_opacity, int raw, int n_draws, const float* uniforms,
+                    void* scratch, size_t scratch_bytes, uint32_t* weights /* may be null */, int32_t* src, int32_t* count, void* stream);
+int stp_mcmc_relocate_apply(int P, const int32_t* src, const int32_t* count, int n_tensors, const StpMcmcTensor* tensors, float min_opacity, int raw,
+                            int reset_dead_moments, void* scratch, size_t scratch_bytes, void* stream);
+int stp_mcmc_add_apply(int P, int n_new, const int32_t* src, const int32_t* count, int n_tensors, const StpMcmcTensor* tensors, float min_opacity, int raw,
+                       void* scratch, size_t scratch_bytes, void* stream);
+
 /* Extension (not in the reference): adaptive density control of a 3DGS / StopThePop trainer -- the per-step statistics and densify_and_prune --
    in four calls.  All data is float32, all pointers are device pointers to contiguous data (stp_densify_scan's `counts` excepted), every call
    runs on the caller's stream and allocates nothing; no atomics: equal inputs give equal bits.

@@ -113,6 +113,171 @@ int mcmc_add_noise(const torch::Tensor& xyz, const torch::Tensor& scales, const 
                                         (float)noise_scale, (float)k, (float)x0, raw ? 1 : 0, current_stream(xyz.device())));
 }
 
+// == the 3DGS-MCMC relocation and growth (extension, include/stp_raster.h: stp_mcmc_sample / stp_mcmc_relocate_apply / stp_mcmc_add_apply;
+// mcmc_relocation_plan, mcmc_relocate_tensors_, mcmc_add_plan and mcmc_add_tensors in __init__.py).  No host synchronisation anywhere; the scratch is
+// a torch tensor of the caching allocator, returned to it when a function leaves (the allocator keeps it for the stream until the kernels have run).
+constexpr int64_t MCMC_RELOCATE_MAX_P = 1ll << 28;
+
+// rule 0 (who = mcmc_relocation_plan): uniforms (P,), one per row; rule 1 (who = mcmc_add_plan): uniforms (n,), one per new row.
+// -> (src int32 (uniforms' length), count int32 (P,), weights int32 (P,) or an undefined tensor)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> mcmc_sample(const torch::Tensor& opacity_in, const torch::Tensor& uniforms_in, const int64_t rule,
+                                                                    const double min_opacity, const bool raw, const bool want_weights)
+{
+    const char* const who = rule == 0 ? "mcmc_relocation_plan" : "mcmc_add_plan";
+    need_library();
+    require(g_api.mcmc_sample, who);
+    require(g_api.mcmc_relocate_scratch_bytes, who);
+    TORCH_CHECK(rule == 0 || rule == 1, "mcmc_sample: unknown rule ", rule);
+    check_float(who, "opacity", opacity_in);
+    check_float(who, "uniforms", uniforms_in);
+    check_column(who, "opacity", opacity_in);
+    const int64_t P = opacity_in.size(0);
+    TORCH_CHECK(P <= MCMC_RELOCATE_MAX_P, who, ": opacity: ", P, " rows > 2^28");
+    TORCH_CHECK(uniforms_in.dim() == 1, who, ": uniforms must be (n,), got ", uniforms_in.sizes());
+    const int64_t n = uniforms_in.size(0);
+    TORCH_CHECK(rule != 0 || n == P, who, ": uniforms has ", n, " rows, opacity has ", P);
+    TORCH_CHECK(n < (1ll << 31), who, ": uniforms: ", n, " rows >= 2^31");
+    TORCH_CHECK(P > 0 || n == 0, who, ": ", n, " draws from a model without rows");
+    check_device(who, "uniforms", uniforms_in, opacity_in);
+    check_device(who, "opacity", opacity_in, opacity_in);
+    const torch::Tensor opacity = opacity_in.contiguous(), uniforms = uniforms_in.contiguous();
+    const c10::hip::HIPGuard guard(opacity.device().index());
+    const auto ints = opacity.options().dtype(torch::kInt32);
+    torch::Tensor src = torch::empty({n}, ints), count = torch::empty({P}, ints), weights;
+    if (want_weights) weights = torch::empty({P}, ints);
+    if (P == 0) return {src, count, weights};
+    const size_t bytes = g_api.mcmc_relocate_scratch_bytes((int)P);
+    torch::Tensor scratch = torch::empty({(int64_t)bytes}, opacity.options().dtype(torch::kByte));
+    checked(g_api.mcmc_sample((int)P, opacity.data_ptr<float>(), (int)rule, (float)min_opacity, raw ? 1 : 0, (int)n, uniforms.data_ptr<float>(), scratch.data_ptr(), bytes,
+                              want_weights ? reinterpret_cast<uint32_t*>(weights.data_ptr<int32_t>()) : nullptr, src.data_ptr<int32_t>(), count.data_ptr<int32_t>(),
+                              current_stream(opacity.device())));
+    return {src, count, weights};
+}
+
+// what the two applies ask of their lists; -> P (count's length)
+int64_t mcmc_check_apply(const char* who, const torch::Tensor& src, const torch::Tensor& count, const std::vector<torch::Tensor>& tensors, const std::vector<int64_t>& roles,
+                         const std::vector<c10::optional<torch::Tensor>>& exp_avgs, const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs, const bool in_place)
+{
+    const size_t n = tensors.size();
+    TORCH_CHECK(roles.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n, who, ": tensors, roles, exp_avgs and exp_avg_sqs must have one entry per tensor");
+    TORCH_CHECK(n <= 64, who, ": ", n, " tensors, at most 64 in one call");
+    TORCH_CHECK(src.defined() && src.scalar_type() == torch::kInt32 && src.dim() == 1, who, ": plan: src: expected an int32 (n,) tensor");
+    TORCH_CHECK(count.defined() && count.scalar_type() == torch::kInt32 && count.dim() == 1, who, ": plan: count: expected an int32 (P,) tensor");
+    const int64_t P = count.size(0);
+    TORCH_CHECK(P <= MCMC_RELOCATE_MAX_P, who, ": ", P, " rows > 2^28");
+    TORCH_CHECK(!in_place || src.size(0) == P, who, ": plan: src has ", src.size(0), " rows, count has ", P);
+    int of_role[3] = {0, 0, 0};
+    for (size_t k = 0; k < n; k++) {
+        const torch::Tensor& t = tensors[k];
+        TORCH_CHECK(t.defined(), who, ": tensor ", k, " is undefined");
+        TORCH_CHECK(t.scalar_type() == torch::kFloat32, who, ": tensor ", k, ": expected float32 tensor, got ", t.scalar_type());
+        TORCH_CHECK(t.dim() >= 1 && t.size(0) == P, who, ": tensor ", k, " must have ", P, " rows (the plan's), got ", t.sizes());
+        TORCH_CHECK(P == 0 || t.numel() > 0, who, ": tensor ", k, ": rows without elements, ", t.sizes());
+        TORCH_CHECK(roles[k] >= 0 && roles[k] <= 2, who, ": tensor ", k, ": unknown role ", roles[k], " (0 plain, 1 opacity, 2 scaling)");
+        const int64_t row = P > 0 ? t.numel() / P : 1;
+        TORCH_CHECK(P == 0 || roles[k] == 0 || row == (roles[k] == 1 ? 1 : 3), who, ": tensor ", k, ": the ", roles[k] == 1 ? "opacity must have 1 float" : "scaling must have 3 floats",
+                    " per row, got ", t.sizes());
+        of_role[roles[k]]++;
+        TORCH_CHECK(exp_avgs[k].has_value() == exp_avg_sqs[k].has_value(), who, ": tensor ", k, ": exp_avg and exp_avg_sq must both be given or both be None");
+        TORCH_CHECK(!in_place || t.is_contiguous(), who, ": tensor ", k, " must be contiguous (it is updated in place)");
+        if (exp_avgs[k].has_value())
+            for (const torch::Tensor* m : {&*exp_avgs[k], &*exp_avg_sqs[k]}) {
+                TORCH_CHECK(m->defined() && m->scalar_type() == torch::kFloat32, who, ": tensor ", k, ": moments: expected float32 tensors");
+                TORCH_CHECK(m->sizes() == t.sizes(), who, ": tensor ", k, ": a moment has shape ", m->sizes(), ", the parameter has ", t.sizes());
+                TORCH_CHECK(!in_place || m->is_contiguous(), who, ": tensor ", k, ": the moments must be contiguous (they are updated in place)");
+            }
+    }
+    TORCH_CHECK(of_role[1] == 1 && of_role[2] == 1, who, ": exactly one tensor must have the role opacity and exactly one the role scaling, got ", of_role[1], " and ", of_role[2]);
+    check_on_gpu(who, "plan", count);
+    check_device(who, "plan", src, count);
+    for (size_t k = 0; k < n; k++) {
+        check_device(who, "a tensor", tensors[k], count);
+        if (exp_avgs[k].has_value()) {
+            check_device(who, "an exp_avg", *exp_avgs[k], count);
+            check_device(who, "an exp_avg_sq", *exp_avg_sqs[k], count);
+        }
+    }
+    return P;
+}
+
+// IN PLACE on every tensor and moment (all contiguous).  Returns the launches made.
+int mcmc_relocate_apply(const torch::Tensor& src_in, const torch::Tensor& count_in, const std::vector<torch::Tensor>& tensors, const std::vector<int64_t>& roles,
+                        const std::vector<c10::optional<torch::Tensor>>& exp_avgs, const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs, const double min_opacity,
+                        const bool raw, const bool reset_dead_moments)
+{
+    static const char* const who = "mcmc_relocate_tensors_";
+    need_library();
+    require(g_api.mcmc_relocate_apply, who);
+    require(g_api.mcmc_relocate_scratch_bytes, who);
+    const int64_t P = mcmc_check_apply(who, src_in, count_in, tensors, roles, exp_avgs, exp_avg_sqs, true);
+    if (P == 0) return 0;
+    const size_t n = tensors.size();
+    const torch::Tensor src = src_in.contiguous(), count = count_in.contiguous();
+    const c10::hip::HIPGuard guard(count.device().index());
+    std::vector<StpMcmcTensor> table(n);
+    for (size_t k = 0; k < n; k++) {
+        const int64_t row = tensors[k].numel() / P;
+        TORCH_CHECK(tensors[k].numel() < (1ll << 31), who, ": tensor ", k, ": ", P, " rows of ", row, " floats: outside (0, 2^31)");
+        table[k] = StpMcmcTensor{tensors[k].data_ptr<float>(), nullptr, nullptr, nullptr, nullptr, nullptr, (int32_t)row, (int32_t)roles[k]};
+        if (exp_avgs[k].has_value()) {
+            table[k].exp_avg = exp_avgs[k]->data_ptr<float>();
+            table[k].exp_avg_sq = exp_avg_sqs[k]->data_ptr<float>();
+        }
+    }
+    const size_t bytes = g_api.mcmc_relocate_scratch_bytes((int)P);
+    torch::Tensor scratch = torch::empty({(int64_t)bytes}, count.options().dtype(torch::kByte));
+    return checked(g_api.mcmc_relocate_apply((int)P, src.data_ptr<int32_t>(), count.data_ptr<int32_t>(), (int)n, table.data(), (float)min_opacity, raw ? 1 : 0,
+                                             reset_dead_moments ? 1 : 0, scratch.data_ptr(), bytes, current_stream(count.device())));
+}
+
+// -> (new tensors, new exp_avgs, new exp_avg_sqs) of P + src.size(0) rows: lists as long as `tensors`, the moment lists holding None where none was given
+std::tuple<std::vector<torch::Tensor>, std::vector<c10::optional<torch::Tensor>>, std::vector<c10::optional<torch::Tensor>>>
+mcmc_add_apply(const torch::Tensor& src_in, const torch::Tensor& count_in, const std::vector<torch::Tensor>& tensors, const std::vector<int64_t>& roles,
+               const std::vector<c10::optional<torch::Tensor>>& exp_avgs, const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs, const double min_opacity, const bool raw)
+{
+    static const char* const who = "mcmc_add_tensors";
+    need_library();
+    require(g_api.mcmc_add_apply, who);
+    require(g_api.mcmc_relocate_scratch_bytes, who);
+    const int64_t P = mcmc_check_apply(who, src_in, count_in, tensors, roles, exp_avgs, exp_avg_sqs, false);
+    const int64_t n_new = src_in.size(0), M = P + n_new;
+    TORCH_CHECK(P > 0 || n_new == 0, who, ": ", n_new, " new rows from a model without rows");
+    const size_t n = tensors.size();
+    const torch::Tensor src = src_in.contiguous(), count = count_in.contiguous();
+    const c10::hip::HIPGuard guard(count.device().index());
+    std::vector<torch::Tensor> held; // the contiguous inputs, alive until the launches are made
+    std::vector<torch::Tensor> out_p(n);
+    std::vector<c10::optional<torch::Tensor>> out_m(n), out_v(n);
+    std::vector<StpMcmcTensor> table(n);
+    for (size_t k = 0; k < n; k++) {
+        std::vector<int64_t> shape = tensors[k].sizes().vec();
+        int64_t row = 1;
+        for (size_t d = 1; d < shape.size(); d++) row *= shape[d];
+        TORCH_CHECK(row > 0 && M * row < (1ll << 31), who, ": tensor ", k, ": ", M, " rows of ", row, " floats: outside (0, 2^31)");
+        shape[0] = M;
+        held.push_back(tensors[k].contiguous());
+        out_p[k] = torch::empty(shape, held.back().options());
+        StpMcmcTensor& t = table[k];
+        t = StpMcmcTensor{held.back().data_ptr<float>(), nullptr, nullptr, out_p[k].data_ptr<float>(), nullptr, nullptr, (int32_t)row, (int32_t)roles[k]};
+        if (exp_avgs[k].has_value()) {
+            held.push_back(exp_avgs[k]->contiguous());
+            t.exp_avg = held.back().data_ptr<float>();
+            held.push_back(exp_avg_sqs[k]->contiguous());
+            t.exp_avg_sq = held.back().data_ptr<float>();
+            out_m[k] = torch::empty(shape, held.back().options());
+            out_v[k] = torch::empty(shape, held.back().options());
+            t.exp_avg_out = out_m[k]->data_ptr<float>();
+            t.exp_avg_sq_out = out_v[k]->data_ptr<float>();
+        }
+    }
+    if (P == 0) return {out_p, out_m, out_v};
+    const size_t bytes = g_api.mcmc_relocate_scratch_bytes((int)P);
+    torch::Tensor scratch = torch::empty({(int64_t)bytes}, count.options().dtype(torch::kByte));
+    checked(g_api.mcmc_add_apply((int)P, (int)n_new, src.data_ptr<int32_t>(), count.data_ptr<int32_t>(), (int)n, table.data(), (float)min_opacity, raw ? 1 : 0,
+                                 scratch.data_ptr(), bytes, current_stream(count.device())));
+    return {out_p, out_m, out_v};
+}
+
 // == the activated copies of a trainer's raw parameters (extension, include/stp_raster.h: stp_activate_params; activate_params in __init__.py): the
 // values the rasterizer's raw path renders with, to the bit.  -> (scales, rotations, opacities), fresh contiguous float32 tensors in the inputs' shapes,
 // an undefined tensor (None) for an absent input.

@@ -42,6 +42,10 @@
     X(sparse_adam, false, "the sparse Adam step")                                          \
     X(mcmc_relocation, false, "the 3DGS-MCMC kernels")                                     \
     X(mcmc_add_noise, false, "the 3DGS-MCMC kernels")                                      \
+    X(mcmc_relocate_scratch_bytes, false, "the 3DGS-MCMC relocation kernels")              \
+    X(mcmc_sample, false, "the 3DGS-MCMC relocation kernels")                              \
+    X(mcmc_relocate_apply, false, "the 3DGS-MCMC relocation kernels")                      \
+    X(mcmc_add_apply, false, "the 3DGS-MCMC relocation kernels")                           \
     X(knn_scratch_bytes, false, "the nearest-neighbour kernels")                           \
     X(knn_mean_dist2, false, "the nearest-neighbour kernels")                              \
     X(densify_stats, false, "the densification kernels")                                   \

@@ -24,6 +24,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("sparse_adam", &sparse_adam);
     m.def("compute_relocation", &compute_relocation);
     m.def("mcmc_add_noise", &mcmc_add_noise);
+    m.def("mcmc_sample", &mcmc_sample);
+    m.def("mcmc_relocate_apply", &mcmc_relocate_apply);
+    m.def("mcmc_add_apply", &mcmc_add_apply);
     m.def("activate_params", &activate_params);
     m.def("knn_mean_dist2", &knn_mean_dist2);
     m.def("densify_stats", &densify_stats);

@@ -390,6 +390,113 @@ int stp_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rota
     return launches;
 }
 
+// ---- the 3DGS-MCMC relocation and growth (stp_mcmc_relocate.hip): everything is checked before the first launch
+static constexpr int MCMC_RELOCATE_MAX_P = 1 << 28;
+
+// P, raw and the scratch of the three calls: 0 = fine, negative = refused
+static int check_mcmc_relocate(const char* who, int P, int raw, const void* scratch, size_t scratch_bytes)
+{
+    if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative P");
+    if (P > MCMC_RELOCATE_MAX_P) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": P = " + std::to_string(P) + " > 2^28");
+    if (raw != 0 && raw != 1) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": raw must be 0 or 1, got " + std::to_string(raw));
+    if (P == 0) return 0;
+    if (!scratch) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer (scratch)");
+    const size_t need = mcmc_relocate_scratch_bytes(P);
+    if (scratch_bytes < need)
+        return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": scratch of " + std::to_string(scratch_bytes) + " bytes, stp_mcmc_relocate_scratch_bytes(P) = " + std::to_string(need));
+    if (reinterpret_cast<uintptr_t>(scratch) & 15u) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": scratch is not 16-byte aligned");
+    return 0;
+}
+
+// the entry table of an apply that writes out_rows rows (in place: the *_out pointers are not looked at)
+static int check_mcmc_tensors(const char* who, int n_tensors, const StpMcmcTensor* tensors, long long out_rows, bool in_place, bool work)
+{
+    if (n_tensors < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative n_tensors");
+    if (n_tensors > 64) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(n_tensors) + " tensors, at most 64 in one call");
+    if (n_tensors > 0 && !tensors) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null tensor table");
+    int of_role[3] = {0, 0, 0};
+    for (int k = 0; k < n_tensors; k++) {
+        const StpMcmcTensor& t = tensors[k];
+        const std::string which = std::string(who) + ": tensor " + std::to_string(k);
+        if (t.row <= 0) return fail(STP_ERR_INVALID_ARGUMENT, which + ": row " + std::to_string(t.row) + " <= 0");
+        if (out_rows * t.row >= (1ll << 31)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": rows * row = " + std::to_string(out_rows * t.row) + " >= 2^31");
+        if (t.role < 0 || t.role > 2) return fail(STP_ERR_INVALID_ARGUMENT, which + ": unknown role " + std::to_string(t.role) + " (0 plain, 1 opacity, 2 scaling)");
+        if (t.role != 0 && t.row != (t.role == 1 ? 1 : 3))
+            return fail(STP_ERR_INVALID_ARGUMENT, which + ": role " + std::to_string(t.role) + " needs row " + (t.role == 1 ? "1" : "3") + ", got " + std::to_string(t.row));
+        if ((t.exp_avg == nullptr) != (t.exp_avg_sq == nullptr)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": exp_avg and exp_avg_sq must both be given or both be null");
+        of_role[t.role]++;
+        if (work) {
+            if (!t.param || (!in_place && !t.param_out)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer");
+            if (!in_place && t.exp_avg && (!t.exp_avg_out || !t.exp_avg_sq_out)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer (moment output)");
+        }
+    }
+    for (int role = 1; role <= 2; role++) {
+        const char* const name = role == 1 ? "1 (opacity, row 1)" : "2 (scaling, row 3)";
+        if (of_role[role] == 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": missing role " + name + ": exactly one tensor must have it");
+        if (of_role[role] > 1) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": duplicated role " + name + ": exactly one tensor must have it");
+    }
+    return 0;
+}
+
+size_t stp_mcmc_relocate_scratch_bytes(int P)
+{
+    if (P < 0 || P > MCMC_RELOCATE_MAX_P) return 0;
+    return mcmc_relocate_scratch_bytes(P);
+}
+
+int stp_mcmc_sample(int P, const float* opacity, int rule, float min_opacity, int raw, int n_draws, const float* uniforms, void* scratch, size_t scratch_bytes,
+                    uint32_t* weights, int32_t* src, int32_t* count, void* stream)
+{
+    static const char* const who = "stp_mcmc_sample";
+    if (n_draws < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative n_draws");
+    if (rule != 0 && rule != 1) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown rule " + std::to_string(rule) + " (0: relocation, 1: growth)");
+    if (const int rc = check_mcmc_relocate(who, P, raw, scratch, scratch_bytes)) return rc;
+    if (rule == 0 && n_draws != P)
+        return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": rule 0 draws once per row: n_draws = " + std::to_string(n_draws) + ", P = " + std::to_string(P));
+    if (n_draws > 0 && (!uniforms || !src)) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    if (P == 0) {
+        if (n_draws > 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(n_draws) + " draws from P = 0 rows");
+        return 0;
+    }
+    if (!opacity || !count) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    hipError_t e;
+    const int launches = launch_mcmc_sample(P, opacity, rule, min_opacity, raw, n_draws, uniforms, scratch, weights, src, count, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "mcmc_sample launch");
+    return launches;
+}
+
+int stp_mcmc_relocate_apply(int P, const int32_t* src, const int32_t* count, int n_tensors, const StpMcmcTensor* tensors, float min_opacity, int raw,
+                            int reset_dead_moments, void* scratch, size_t scratch_bytes, void* stream)
+{
+    static const char* const who = "stp_mcmc_relocate_apply";
+    if (const int rc = check_mcmc_relocate(who, P, raw, scratch, scratch_bytes)) return rc;
+    if (const int rc = check_mcmc_tensors(who, n_tensors, tensors, P, true, P > 0)) return rc;
+    if (P == 0) return 0;
+    if (!src || !count) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    hipError_t e;
+    const int launches = launch_mcmc_relocate_apply(P, src, count, n_tensors, tensors, min_opacity, raw, reset_dead_moments ? 1 : 0, scratch, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "mcmc_relocate_apply launch");
+    return launches;
+}
+
+int stp_mcmc_add_apply(int P, int n_new, const int32_t* src, const int32_t* count, int n_tensors, const StpMcmcTensor* tensors, float min_opacity, int raw,
+                       void* scratch, size_t scratch_bytes, void* stream)
+{
+    static const char* const who = "stp_mcmc_add_apply";
+    if (n_new < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative n_new");
+    if (const int rc = check_mcmc_relocate(who, P, raw, scratch, scratch_bytes)) return rc;
+    if (const int rc = check_mcmc_tensors(who, n_tensors, tensors, (long long)P + n_new, false, P > 0)) return rc;
+    if (P == 0) {
+        if (n_new > 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(n_new) + " new rows from P = 0 rows");
+        return 0;
+    }
+    if (!count || (n_new > 0 && !src)) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    hipError_t e;
+    const int launches = launch_mcmc_add_apply(P, n_new, src, count, n_tensors, tensors, min_opacity, raw, scratch, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "mcmc_add_apply launch");
+    return launches;
+}
+
 size_t stp_knn_scratch_bytes(int P) { return knn_scratch_bytes(P); }
 
 int stp_knn_mean_dist2(int P, const float* points, void* scratch, size_t scratch_bytes, float* mean_dist2, void* stream)

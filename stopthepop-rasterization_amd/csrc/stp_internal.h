@@ -300,6 +300,17 @@ int launch_mcmc_relocation(int n, const float* opacity_old, const float* scale_o
                            float* scale_new, hipStream_t st, hipError_t* err);
 int launch_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise, float noise_scale,
                           float k, float x0, int raw, hipStream_t st, hipError_t* err);
+// the 3DGS-MCMC relocation and growth (stp_mcmc_relocate.hip) over arguments stp_mcmc_sample / stp_mcmc_relocate_apply / stp_mcmc_add_apply have
+// validated (P in [1, 2^28], every written row count times row < 2^31, exactly one tensor of each of the roles 1 and 2, a scratch of
+// mcmc_relocate_scratch_bytes(P) bytes, 16-byte aligned): each returns the launches made, *err = the launch error that ended it early (or
+// hipSuccess).  No host synchronisation.
+size_t mcmc_relocate_scratch_bytes(int P);
+int launch_mcmc_sample(int P, const float* opacity, int rule, float min_opacity, int raw, int n_draws, const float* uniforms, void* scratch, uint32_t* weights,
+                       int32_t* src, int32_t* count, hipStream_t st, hipError_t* err);
+int launch_mcmc_relocate_apply(int P, const int32_t* src, const int32_t* count, int n_tensors, const StpMcmcTensor* tensors, float min_opacity, int raw,
+                               int reset_dead_moments, void* scratch, hipStream_t st, hipError_t* err);
+int launch_mcmc_add_apply(int P, int n_new, const int32_t* src, const int32_t* count, int n_tensors, const StpMcmcTensor* tensors, float min_opacity, int raw,
+                          void* scratch, hipStream_t st, hipError_t* err);
 // densification (stp_densify.hip) over arguments stp_densify_* have validated (P in [1, 2^31 / 3), every P * row < 2^31): each returns the
 // launches made, *err = the error that ended it early (or hipSuccess).  launch_densify_scan copies the three counts to the host and
 // SYNCHRONISES the stream; its scratch holds densify_scratch_bytes(P) bytes, 4-byte aligned.

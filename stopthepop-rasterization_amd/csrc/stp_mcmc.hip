@@ -25,6 +25,7 @@
 // whole group, one float per access.  With an unaligned pointer a lane owns one Gaussian, one float per access.  The arithmetic of a
 // Gaussian is the same function on every path.
 #include "stp_internal.h"
+#include "stp_mcmc_relocation.h"
 
 namespace stp {
 
@@ -43,15 +44,8 @@ __global__ void __launch_bounds__(MCMC_BLOCK) mcmc_relocation_kernel(const uint3
     if (i >= n) return;
     const long long asked = (long long)N[i];
     const int copies = asked < 1 ? 1 : asked > n_cap ? n_cap : (int)asked;
-    const double o = (double)opacity_old[i];
-    const double x = -expm1(__ddiv_rn(log1p(-o), (double)copies));
-    double c = (double)copies, p = x, sum = 0.0;
-    for (int k = 0; k < copies; k++) {
-        sum = __dadd_rn(sum, __ddiv_rn(__dmul_rn(c, p), __dsqrt_rn((double)(k + 1))));
-        c = __ddiv_rn(__dmul_rn(c, (double)(copies - k - 1)), (double)(k + 2));
-        p = __dmul_rn(p, -x);
-    }
-    const double coef = __ddiv_rn(o, sum);
+    double x, coef;
+    mcmc_relocation_row(opacity_old[i], copies, x, coef);
     opacity_new[i] = (float)x;
     const size_t e = 3 * (size_t)i;
 #pragma unroll

@@ -60,6 +60,13 @@ _OPTIONAL_SYMBOLS = {
                         ctypes.c_int, "the sparse Adam step"),
     "stp_mcmc_relocation": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3, ctypes.c_int, "the 3DGS-MCMC kernels"),
     "stp_mcmc_add_noise": ([ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_float] * 3 + [ctypes.c_int, ctypes.c_void_p], ctypes.c_int, "the 3DGS-MCMC kernels"),
+    "stp_mcmc_relocate_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t, "the 3DGS-MCMC relocation kernels"),
+    "stp_mcmc_sample": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4,
+                        ctypes.c_int, "the 3DGS-MCMC relocation kernels"),
+    "stp_mcmc_relocate_apply": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                 ctypes.c_void_p], ctypes.c_int, "the 3DGS-MCMC relocation kernels"),
+    "stp_mcmc_add_apply": ([ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
+                           ctypes.c_int, "the 3DGS-MCMC relocation kernels"),
     "stp_knn_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t, "the nearest-neighbour kernels"),
     "stp_knn_mean_dist2": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2, ctypes.c_int, "the nearest-neighbour kernels"),
     "stp_densify_stats": ([ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int, "the densification kernels"),
@@ -518,6 +525,49 @@ def mcmc_add_noise(xyz, scales, rotations, opacities, noise, noise_scale, k, x0,
     (P, 1), noise (P, 3), all float32 on one GPU.  Returns the kernel launches made (1; 0 for P == 0)."""
     _require("stp_mcmc_add_noise")
     return int((_host or _native()).mcmc_add_noise(xyz, scales, rotations, opacities, noise, float(noise_scale), float(k), float(x0), bool(raw)))
+
+
+class StpMcmcTensor(ctypes.Structure):
+    """include/stp_raster.h: StpMcmcTensor (for callers of the C ABI through ctypes; the native module builds its own)"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("param", "exp_avg", "exp_avg_sq", "param_out", "exp_avg_out", "exp_avg_sq_out")] + \
+               [("row", ctypes.c_int32), ("role", ctypes.c_int32)]
+
+
+MCMC_ROLES = {"plain": 0, "opacity": 1, "scaling": 2}
+MCMC_SAMPLE_TILE = 2048   # == STP_MCMC_SAMPLE_TILE (include/stp_raster.h): rows of a workgroup of the sampling's scan
+MCMC_RELOCATE_MAX_P = 1 << 28
+
+
+def mcmc_relocate_scratch_bytes(P: int) -> int:
+    """Bytes of device scratch stp_mcmc_sample and the two applies need for P Gaussians (include/stp_raster.h): a function of P alone, 0 for a
+    P the calls refuse (negative, above 2^28)."""
+    return int(_require("stp_mcmc_relocate_scratch_bytes")(int(P)))
+
+
+def mcmc_sample(opacity, uniforms, rule, min_opacity, raw, want_weights):
+    """The draw of a relocation (rule 0: uniforms (P,), one per row, read on the dead rows) or of a growth (rule 1: uniforms (n,)) (extension,
+    include/stp_raster.h: stp_mcmc_sample) -> (src int32, count int32 (P,), weights int32 (P,) or None), on the current stream, without host
+    synchronisation."""
+    _require("stp_mcmc_sample")
+    src, count, weights = (_host or _native()).mcmc_sample(opacity, uniforms, int(rule), float(min_opacity), bool(raw), bool(want_weights))
+    return src, count, (weights if want_weights else None)
+
+
+def mcmc_relocate_apply(src, count, tensors, roles, exp_avgs, exp_avg_sqs, min_opacity, raw, reset_dead_moments) -> int:
+    """The relocation by a plan, IN PLACE on every tensor and moment (extension, include/stp_raster.h: stp_mcmc_relocate_apply).  roles: 0 plain,
+    1 opacity, 2 scaling; exp_avgs / exp_avg_sqs hold None where a tensor has no moments.  Returns the kernel launches made.  No host
+    synchronisation."""
+    _require("stp_mcmc_relocate_apply")
+    return int((_host or _native()).mcmc_relocate_apply(src, count, list(tensors), [int(r) for r in roles], list(exp_avgs), list(exp_avg_sqs), float(min_opacity),
+                                                        bool(raw), bool(reset_dead_moments)))
+
+
+def mcmc_add_apply(src, count, tensors, roles, exp_avgs, exp_avg_sqs, min_opacity, raw):
+    """The growth by a plan (extension, include/stp_raster.h: stp_mcmc_add_apply) -> (new_tensors, new_exp_avgs, new_exp_avg_sqs) of
+    P + len(src) rows, lists as long as `tensors`.  No host synchronisation."""
+    _require("stp_mcmc_add_apply")
+    out = (_host or _native()).mcmc_add_apply(src, count, list(tensors), [int(r) for r in roles], list(exp_avgs), list(exp_avg_sqs), float(min_opacity), bool(raw))
+    return list(out[0]), list(out[1]), list(out[2])
 
 
 def activate_params(scaling=None, rotation=None, opacity=None):

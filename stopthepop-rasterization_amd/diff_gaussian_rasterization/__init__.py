@@ -28,7 +28,8 @@ __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes
            "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam",
            "photometric_terms", "fused_ssim", "photometric_loss", "compute_relocation", "mcmc_add_noise_",
            "knn_mean_dist2", "distCUDA2", "dist_cuda2", "activate_params",
-           "densification_stats_", "densify_plan", "densify_tensors", "densify_and_prune"]
+           "densification_stats_", "densify_plan", "densify_tensors", "densify_and_prune",
+           "mcmc_relocation_plan", "mcmc_relocate_tensors_", "mcmc_relocate_", "mcmc_add_plan", "mcmc_add_tensors", "mcmc_add_new"]
 
 
 def enum_dict_factory(data):
@@ -804,6 +805,22 @@ def densify_tensors(plan: torch.Tensor, tensors, roles=None, exp_avgs=None, exp_
     return new_t, new_m, new_v, counts
 
 
+def _replace_group_tensors(optimizer, groups, params, new_t, new_m, new_v):
+    """Every group gets a new nn.Parameter of its new tensor, optimizer.state moves onto it with the new moments (a group whose state is still empty
+    stays empty; other entries, "step", are kept) -> {name: new Parameter}, upstream's optimizable_tensors."""
+    out = {}
+    for group, old, t, m, v in zip(groups, params, new_t, new_m, new_v):
+        new = torch.nn.Parameter(t.requires_grad_(old.requires_grad))
+        state = optimizer.state.pop(old, None)
+        if state is not None and len(state) > 0:
+            if m is not None:
+                state["exp_avg"], state["exp_avg_sq"] = m, v
+            optimizer.state[new] = state
+        group["params"][0] = new
+        out[group["name"]] = new
+    return out
+
+
 def densify_and_prune(optimizer, plan: torch.Tensor, *, noise: Optional[torch.Tensor] = None, split_shrink: float = 1.6, raw: bool = True,
                       names=("xyz", "scaling", "rotation")):
     """upstream's densify_and_prune on an optimizer, by a plan (extension): every group of `optimizer` (a torch.optim.Adam or a
@@ -824,14 +841,119 @@ def densify_and_prune(optimizer, plan: torch.Tensor, *, noise: Optional[torch.Te
         ms.append(state.get("exp_avg"))
         vs.append(state.get("exp_avg_sq"))
     new_t, new_m, new_v, _ = densify_tensors(plan, params, roles, ms, vs, noise, split_shrink=split_shrink, raw=raw)
-    out = {}
-    for group, old, t, m, v in zip(groups, params, new_t, new_m, new_v):
-        new = torch.nn.Parameter(t.requires_grad_(old.requires_grad))
-        state = optimizer.state.pop(old, None)
-        if state is not None and len(state) > 0:
-            if m is not None:
-                state["exp_avg"], state["exp_avg_sq"] = m, v
-            optimizer.state[new] = state
-        group["params"][0] = new
-        out[group["name"]] = new
-    return out
+    return _replace_group_tensors(optimizer, groups, params, new_t, new_m, new_v)
+
+
+def _mcmc_lists(tensors, roles, exp_avgs, exp_avg_sqs):
+    tensors = [t.detach() for t in tensors]
+    n = len(tensors)
+    roles = [0] * n if roles is None else [_C.MCMC_ROLES[r] if isinstance(r, str) else int(r) for r in roles]
+    exp_avgs = [None] * n if exp_avgs is None else [None if m is None else m.detach() for m in exp_avgs]
+    exp_avg_sqs = [None] * n if exp_avg_sqs is None else [None if v is None else v.detach() for v in exp_avg_sqs]
+    return tensors, roles, exp_avgs, exp_avg_sqs
+
+
+def mcmc_relocation_plan(opacity: torch.Tensor, uniforms: torch.Tensor, *, min_opacity: float = 0.005, raw: bool = True, return_weights: bool = False):
+    """The draw of 3DGS-MCMC's relocate_gs in four small kernels without host synchronisation (extension; include/stp_raster.h: stp_mcmc_sample)
+    -> (src int32 (P,), count int32 (P,)) and, with return_weights, the int32 (P,) weights.  With o the opacity (its sigmoid where raw, the model's
+    stored _opacity): a row with o <= min_opacity is dead and draws a source among the rows with o > min_opacity, with replacement, with
+    probability proportional to o; src[i] is the source of dead row i and -1 on every other row, count[k] the number of dead rows that drew k.
+    uniforms: (P,) float32 in [0, 1), torch.rand(P) -- the random numbers stay torch's, and only the dead rows' entries are read.  The draw is an
+    inverse CDF over the integer weights rint(o * 2^24) in exact 64-bit sums: equal inputs give equal bits, and a test can restate it with
+    cumsum and searchsorted.  No dead row, or no live one: src is all -1 and count all 0 (decided on the device).  A NaN opacity is neither
+    dead nor drawn.  min_opacity is rounded to float32 once."""
+    return _mcmc_plan(opacity, uniforms, 0, min_opacity, raw, return_weights)
+
+
+def _mcmc_plan(opacity, uniforms, rule, min_opacity, raw, return_weights):
+    src, count, weights = _C.mcmc_sample(opacity.detach(), uniforms.detach(), rule, _f32(min_opacity), raw, return_weights)
+    return (src, count, weights) if return_weights else (src, count)
+
+
+def mcmc_relocate_tensors_(plan, tensors, roles, exp_avgs=None, exp_avg_sqs=None, *, min_opacity: float = 0.005, raw: bool = True,
+                           reset_dead_moments: bool = False) -> None:
+    """3DGS-MCMC's relocate_gs by a plan of mcmc_relocation_plan, IN PLACE on every tensor and both Adam moments, in one pass per eight tensors and
+    without host synchronisation (extension; include/stp_raster.h: stp_mcmc_relocate_apply).  tensors: float32 (P, ...) of any trailing shape,
+    contiguous; roles: per tensor "plain" / "opacity" / "scaling" (or 0..2) with exactly one opacity, (P,) or (P, 1), and one scaling, (P, 3);
+    exp_avgs / exp_avg_sqs: the moments per tensor, None where there are none.  A drawn row k (count[k] > 0) gets the opacity and scaling
+    compute_relocation gives for N = count[k] + 1 (clamped to 50), the opacity clamped to [min_opacity, 1 - eps] -- stored through logit and log
+    where raw -- and zero moments in every tensor; a dead row i takes every parameter of row src[i], with that row's new opacity and scaling, and
+    keeps its moments (upstream) unless reset_dead_moments.  Every other float keeps its bits.  The new values are computed per source before
+    anything is written: the result does not depend on scheduling.  Works on the tensors' storage like an optimizer step (nothing is recorded
+    in autograd).  Returns None."""
+    src, count = plan[0], plan[1]
+    tensors, roles, exp_avgs, exp_avg_sqs = _mcmc_lists(tensors, roles, exp_avgs, exp_avg_sqs)
+    _C.mcmc_relocate_apply(src, count, tensors, roles, exp_avgs, exp_avg_sqs, _f32(min_opacity), raw, reset_dead_moments)
+
+
+def _mcmc_groups(who, optimizer, names):
+    role_of = dict(zip(names, ("opacity", "scaling")))
+    groups = list(optimizer.param_groups)
+    params, roles, ms, vs = [], [], [], []
+    for group in groups:
+        if len(group["params"]) != 1 or "name" not in group:
+            raise ValueError(f"{who}: every group must hold one tensor and carry a \"name\"")
+        p = group["params"][0]
+        state = optimizer.state.get(p, {})
+        params.append(p)
+        roles.append(role_of.get(group["name"], "plain"))
+        ms.append(state.get("exp_avg"))
+        vs.append(state.get("exp_avg_sq"))
+    if roles.count("opacity") != 1 or roles.count("scaling") != 1:
+        raise ValueError(f"{who}: the optimizer needs exactly one group named {names[0]!r} and one named {names[1]!r}")
+    return groups, params, roles, ms, vs
+
+
+def mcmc_relocate_(optimizer, uniforms: Optional[torch.Tensor] = None, *, min_opacity: float = 0.005, raw: bool = True, reset_dead_moments: bool = False,
+                   names=("opacity", "scaling")):
+    """3DGS-MCMC's relocate_gs on an optimizer (extension): the draw and the in-place rewrite of every group's tensor and moments, without host
+    synchronisation -> the plan (src, count).  `optimizer`: a torch.optim.Adam or a SparseGaussianAdam whose groups hold one tensor each and carry
+    "name"; the groups named names = (opacity, scaling) play those roles.  uniforms: (P,) float32 in [0, 1); None draws torch.rand(P) on the
+    model's device.  The Parameters keep their identity and optimizer.state is untouched apart from the contents of exp_avg and exp_avg_sq.
+    int((plan[0] >= 0).sum()) is the number of Gaussians relocated (a host synchronisation of the caller's choosing)."""
+    groups, params, roles, ms, vs = _mcmc_groups("mcmc_relocate_", optimizer, names)
+    opacity = params[roles.index("opacity")]
+    if uniforms is None:
+        uniforms = torch.rand(opacity.shape[0], device=opacity.device, dtype=torch.float32)
+    plan = mcmc_relocation_plan(opacity, uniforms, min_opacity=min_opacity, raw=raw)
+    mcmc_relocate_tensors_(plan, params, roles, ms, vs, min_opacity=min_opacity, raw=raw, reset_dead_moments=reset_dead_moments)
+    return plan
+
+
+def mcmc_add_plan(opacity: torch.Tensor, uniforms: torch.Tensor, *, raw: bool = True):
+    """The draw of 3DGS-MCMC's add_new_gs (extension; include/stp_raster.h: stp_mcmc_sample, rule 1) -> (src int32 (n,), count int32 (P,)):
+    one source per entry of uniforms ((n,) float32 in [0, 1), torch.rand(n)) among ALL rows, with probability proportional to the opacity (its
+    sigmoid where raw), by the inverse CDF of mcmc_relocation_plan.  A model whose opacities are all 0 gives src = -1.  No host synchronisation."""
+    return _mcmc_plan(opacity, uniforms, 1, 0.0, raw, False)
+
+
+def mcmc_add_tensors(plan, tensors, roles, exp_avgs=None, exp_avg_sqs=None, *, min_opacity: float = 0.005, raw: bool = True):
+    """3DGS-MCMC's add_new_gs by a plan of mcmc_add_plan, out of place, without host synchronisation (extension; include/stp_raster.h:
+    stp_mcmc_add_apply) -> (new_tensors, new_exp_avgs, new_exp_avg_sqs) of P + n rows.  Rows [0, P) are the model's, bit for bit with their
+    moments, except that a drawn row (count > 0) gets compute_relocation's opacity and scaling for N = count + 1 (as mcmc_relocate_tensors_
+    stores them) and zero moments; row P + j is a copy of row src[j] with that row's new opacity and scaling and zero moments.  tensors, roles
+    and moments as for mcmc_relocate_tensors_ (non-contiguous inputs are made contiguous); the inputs are not modified."""
+    src, count = plan[0], plan[1]
+    tensors, roles, exp_avgs, exp_avg_sqs = _mcmc_lists(tensors, roles, exp_avgs, exp_avg_sqs)
+    return _C.mcmc_add_apply(src, count, tensors, roles, exp_avgs, exp_avg_sqs, _f32(min_opacity), raw)
+
+
+def mcmc_add_new(optimizer, cap_max: int, uniforms: Optional[torch.Tensor] = None, *, min_opacity: float = 0.005, raw: bool = True, names=("opacity", "scaling")):
+    """3DGS-MCMC's add_new_gs on an optimizer (extension): the model of P Gaussians grows by n_new = max(0, min(cap_max, int(1.05 * P)) - P)
+    rows -- a host number: no read-back -- drawn with probability proportional to opacity.  Groups as for mcmc_relocate_; uniforms: (n_new,)
+    float32 in [0, 1), None draws torch.rand(n_new).  Each group gets a new nn.Parameter in group["params"][0], optimizer.state moves onto it
+    with the new exp_avg and exp_avg_sq exactly as densify_and_prune moves it (a group whose state is still empty stays empty; "step" is
+    kept), and {name: new Parameter} is returned for the model to take -- an empty dict, and nothing changed, when n_new == 0."""
+    groups, params, roles, ms, vs = _mcmc_groups("mcmc_add_new", optimizer, names)
+    opacity = params[roles.index("opacity")]
+    P = opacity.shape[0]
+    n_new = max(0, min(int(cap_max), int(1.05 * P)) - P)
+    if uniforms is not None and uniforms.shape[0] != n_new:
+        raise ValueError(f"mcmc_add_new: uniforms has {uniforms.shape[0]} rows, n_new = max(0, min(cap_max, int(1.05 * P)) - P) = {n_new}")
+    if n_new == 0:
+        return {}
+    if uniforms is None:
+        uniforms = torch.rand(n_new, device=opacity.device, dtype=torch.float32)
+    plan = mcmc_add_plan(opacity, uniforms, raw=raw)
+    new_t, new_m, new_v = mcmc_add_tensors(plan, params, roles, ms, vs, min_opacity=min_opacity, raw=raw)
+    return _replace_group_tensors(optimizer, groups, params, new_t, new_m, new_v)
