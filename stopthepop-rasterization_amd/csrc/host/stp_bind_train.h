@@ -2,6 +2,7 @@
 // All run on the caller's current stream.  What is wrong with the tensors themselves is refused first, where they live last (stp_tensor_checks.h).
 #pragma once
 
+#include <algorithm>
 #include <limits>
 #include <tuple>
 
@@ -154,30 +155,29 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> mcmc_sample(const torch:
     return {src, count, weights};
 }
 
-// what the two applies ask of their lists; -> P (count's length)
-int64_t mcmc_check_apply(const char* who, const torch::Tensor& src, const torch::Tensor& count, const std::vector<torch::Tensor>& tensors, const std::vector<int64_t>& roles,
-                         const std::vector<c10::optional<torch::Tensor>>& exp_avgs, const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs, const bool in_place)
+// == what the calls over lists of row tensors share (the two 3DGS-MCMC applies and densify_apply).
+// The roles of such a call: 0 (plain) .. last, `known` the list behind "unknown role"; width[r] the floats per row of role r and width_text[r] what
+// the refusal says (both nullptr: no width is asked for here -- the library asks, under a split).
+struct RowRoleRules { int64_t last; const char* known; const int64_t* width; const char* const* width_text; };
+
+// what is wrong with the lists themselves: one entry per tensor, tensors of P rows, known roles, moments both-or-neither in the tensor's shape (in
+// place: all contiguous)
+void check_row_lists(const char* who, const int64_t P, const std::vector<torch::Tensor>& tensors, const std::vector<int64_t>& roles,
+                     const std::vector<c10::optional<torch::Tensor>>& exp_avgs, const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs, const RowRoleRules& rules,
+                     const bool in_place)
 {
     const size_t n = tensors.size();
     TORCH_CHECK(roles.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n, who, ": tensors, roles, exp_avgs and exp_avg_sqs must have one entry per tensor");
     TORCH_CHECK(n <= 64, who, ": ", n, " tensors, at most 64 in one call");
-    TORCH_CHECK(src.defined() && src.scalar_type() == torch::kInt32 && src.dim() == 1, who, ": plan: src: expected an int32 (n,) tensor");
-    TORCH_CHECK(count.defined() && count.scalar_type() == torch::kInt32 && count.dim() == 1, who, ": plan: count: expected an int32 (P,) tensor");
-    const int64_t P = count.size(0);
-    TORCH_CHECK(P <= MCMC_RELOCATE_MAX_P, who, ": ", P, " rows > 2^28");
-    TORCH_CHECK(!in_place || src.size(0) == P, who, ": plan: src has ", src.size(0), " rows, count has ", P);
-    int of_role[3] = {0, 0, 0};
     for (size_t k = 0; k < n; k++) {
         const torch::Tensor& t = tensors[k];
         TORCH_CHECK(t.defined(), who, ": tensor ", k, " is undefined");
         TORCH_CHECK(t.scalar_type() == torch::kFloat32, who, ": tensor ", k, ": expected float32 tensor, got ", t.scalar_type());
         TORCH_CHECK(t.dim() >= 1 && t.size(0) == P, who, ": tensor ", k, " must have ", P, " rows (the plan's), got ", t.sizes());
         TORCH_CHECK(P == 0 || t.numel() > 0, who, ": tensor ", k, ": rows without elements, ", t.sizes());
-        TORCH_CHECK(roles[k] >= 0 && roles[k] <= 2, who, ": tensor ", k, ": unknown role ", roles[k], " (0 plain, 1 opacity, 2 scaling)");
-        const int64_t row = P > 0 ? t.numel() / P : 1;
-        TORCH_CHECK(P == 0 || roles[k] == 0 || row == (roles[k] == 1 ? 1 : 3), who, ": tensor ", k, ": the ", roles[k] == 1 ? "opacity must have 1 float" : "scaling must have 3 floats",
-                    " per row, got ", t.sizes());
-        of_role[roles[k]]++;
+        TORCH_CHECK(roles[k] >= 0 && roles[k] <= rules.last, who, ": tensor ", k, ": unknown role ", roles[k], " ", rules.known);
+        TORCH_CHECK(!rules.width || P == 0 || roles[k] == 0 || t.numel() / P == rules.width[roles[k]], who, ": tensor ", k, ": the ", rules.width_text[roles[k]], " per row, got ",
+                    t.sizes());
         TORCH_CHECK(exp_avgs[k].has_value() == exp_avg_sqs[k].has_value(), who, ": tensor ", k, ": exp_avg and exp_avg_sq must both be given or both be None");
         TORCH_CHECK(!in_place || t.is_contiguous(), who, ": tensor ", k, " must be contiguous (it is updated in place)");
         if (exp_avgs[k].has_value())
@@ -187,16 +187,80 @@ int64_t mcmc_check_apply(const char* who, const torch::Tensor& src, const torch:
                 TORCH_CHECK(!in_place || m->is_contiguous(), who, ": tensor ", k, ": the moments must be contiguous (they are updated in place)");
             }
     }
-    TORCH_CHECK(of_role[1] == 1 && of_role[2] == 1, who, ": exactly one tensor must have the role opacity and exactly one the role scaling, got ", of_role[1], " and ", of_role[2]);
-    check_on_gpu(who, "plan", count);
-    check_device(who, "plan", src, count);
-    for (size_t k = 0; k < n; k++) {
-        check_device(who, "a tensor", tensors[k], count);
+}
+
+// where the lists live: on the device of `plan`
+void check_row_devices(const char* who, const std::vector<torch::Tensor>& tensors, const std::vector<c10::optional<torch::Tensor>>& exp_avgs,
+                       const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs, const torch::Tensor& plan)
+{
+    for (size_t k = 0; k < tensors.size(); k++) {
+        check_device(who, "a tensor", tensors[k], plan);
         if (exp_avgs[k].has_value()) {
-            check_device(who, "an exp_avg", *exp_avgs[k], count);
-            check_device(who, "an exp_avg_sq", *exp_avg_sqs[k], count);
+            check_device(who, "an exp_avg", *exp_avgs[k], plan);
+            check_device(who, "an exp_avg_sq", *exp_avg_sqs[k], plan);
         }
     }
+}
+
+// The entry table (StpMcmcTensor or StpDensifyTensor) of an out-of-place call and its outputs of M rows: lists as long as `tensors`, the moment lists
+// holding None where none was given.  bound_rows: the rows the library flattens its work over (bound_rows * row < 2^31).
+template <class Entry> struct RowOutputs {
+    std::vector<torch::Tensor> held; // the contiguous inputs, alive until the launches are made
+    std::vector<torch::Tensor> out_p;
+    std::vector<c10::optional<torch::Tensor>> out_m, out_v;
+    std::vector<Entry> table;
+};
+template <class Entry>
+RowOutputs<Entry> row_outputs(const char* who, const std::vector<torch::Tensor>& tensors, const std::vector<int64_t>& roles, const std::vector<c10::optional<torch::Tensor>>& exp_avgs,
+                              const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs, const int64_t M, const int64_t bound_rows)
+{
+    const size_t n = tensors.size();
+    RowOutputs<Entry> r;
+    r.out_p.resize(n); r.out_m.resize(n); r.out_v.resize(n); r.table.resize(n);
+    std::vector<torch::Tensor> &held = r.held, &out_p = r.out_p; // (by their own types: r's are dependent names here)
+    std::vector<c10::optional<torch::Tensor>> &out_m = r.out_m, &out_v = r.out_v;
+    for (size_t k = 0; k < n; k++) {
+        std::vector<int64_t> shape = tensors[k].sizes().vec();
+        int64_t row = 1;
+        for (size_t d = 1; d < shape.size(); d++) row *= shape[d];
+        TORCH_CHECK(row > 0 && bound_rows * row < (1ll << 31), who, ": tensor ", k, ": ", bound_rows, " rows of ", row, " floats: outside (0, 2^31)");
+        shape[0] = M;
+        held.push_back(tensors[k].contiguous());
+        out_p[k] = torch::empty(shape, held.back().options());
+        Entry& t = r.table[k];
+        t = Entry{held.back().data_ptr<float>(), nullptr, nullptr, out_p[k].data_ptr<float>(), nullptr, nullptr, (int32_t)row, (int32_t)roles[k]};
+        if (exp_avgs[k].has_value()) {
+            held.push_back(exp_avgs[k]->contiguous());
+            t.exp_avg = held.back().data_ptr<float>();
+            held.push_back(exp_avg_sqs[k]->contiguous());
+            t.exp_avg_sq = held.back().data_ptr<float>();
+            out_m[k] = torch::empty(shape, held.back().options());
+            out_v[k] = torch::empty(shape, held.back().options());
+            t.exp_avg_out = out_m[k]->data_ptr<float>();
+            t.exp_avg_sq_out = out_v[k]->data_ptr<float>();
+        }
+    }
+    return r;
+}
+
+// what the two 3DGS-MCMC applies ask of their plan and lists; -> P (count's length)
+int64_t mcmc_check_apply(const char* who, const torch::Tensor& src, const torch::Tensor& count, const std::vector<torch::Tensor>& tensors, const std::vector<int64_t>& roles,
+                         const std::vector<c10::optional<torch::Tensor>>& exp_avgs, const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs, const bool in_place)
+{
+    static const int64_t width[3] = {0, 1, 3};
+    static const char* const width_text[3] = {"", "opacity must have 1 float", "scaling must have 3 floats"};
+    static const RowRoleRules rules = {2, "(0 plain, 1 opacity, 2 scaling)", width, width_text};
+    TORCH_CHECK(src.defined() && src.scalar_type() == torch::kInt32 && src.dim() == 1, who, ": plan: src: expected an int32 (n,) tensor");
+    TORCH_CHECK(count.defined() && count.scalar_type() == torch::kInt32 && count.dim() == 1, who, ": plan: count: expected an int32 (P,) tensor");
+    const int64_t P = count.size(0);
+    TORCH_CHECK(P <= MCMC_RELOCATE_MAX_P, who, ": ", P, " rows > 2^28");
+    TORCH_CHECK(!in_place || src.size(0) == P, who, ": plan: src has ", src.size(0), " rows, count has ", P);
+    check_row_lists(who, P, tensors, roles, exp_avgs, exp_avg_sqs, rules, in_place);
+    const auto n_opacity = std::count(roles.begin(), roles.end(), 1), n_scaling = std::count(roles.begin(), roles.end(), 2);
+    TORCH_CHECK(n_opacity == 1 && n_scaling == 1, who, ": exactly one tensor must have the role opacity and exactly one the role scaling, got ", n_opacity, " and ", n_scaling);
+    check_on_gpu(who, "plan", count);
+    check_device(who, "plan", src, count);
+    check_row_devices(who, tensors, exp_avgs, exp_avg_sqs, count);
     return P;
 }
 
@@ -242,40 +306,15 @@ mcmc_add_apply(const torch::Tensor& src_in, const torch::Tensor& count_in, const
     const int64_t P = mcmc_check_apply(who, src_in, count_in, tensors, roles, exp_avgs, exp_avg_sqs, false);
     const int64_t n_new = src_in.size(0), M = P + n_new;
     TORCH_CHECK(P > 0 || n_new == 0, who, ": ", n_new, " new rows from a model without rows");
-    const size_t n = tensors.size();
     const torch::Tensor src = src_in.contiguous(), count = count_in.contiguous();
     const c10::hip::HIPGuard guard(count.device().index());
-    std::vector<torch::Tensor> held; // the contiguous inputs, alive until the launches are made
-    std::vector<torch::Tensor> out_p(n);
-    std::vector<c10::optional<torch::Tensor>> out_m(n), out_v(n);
-    std::vector<StpMcmcTensor> table(n);
-    for (size_t k = 0; k < n; k++) {
-        std::vector<int64_t> shape = tensors[k].sizes().vec();
-        int64_t row = 1;
-        for (size_t d = 1; d < shape.size(); d++) row *= shape[d];
-        TORCH_CHECK(row > 0 && M * row < (1ll << 31), who, ": tensor ", k, ": ", M, " rows of ", row, " floats: outside (0, 2^31)");
-        shape[0] = M;
-        held.push_back(tensors[k].contiguous());
-        out_p[k] = torch::empty(shape, held.back().options());
-        StpMcmcTensor& t = table[k];
-        t = StpMcmcTensor{held.back().data_ptr<float>(), nullptr, nullptr, out_p[k].data_ptr<float>(), nullptr, nullptr, (int32_t)row, (int32_t)roles[k]};
-        if (exp_avgs[k].has_value()) {
-            held.push_back(exp_avgs[k]->contiguous());
-            t.exp_avg = held.back().data_ptr<float>();
-            held.push_back(exp_avg_sqs[k]->contiguous());
-            t.exp_avg_sq = held.back().data_ptr<float>();
-            out_m[k] = torch::empty(shape, held.back().options());
-            out_v[k] = torch::empty(shape, held.back().options());
-            t.exp_avg_out = out_m[k]->data_ptr<float>();
-            t.exp_avg_sq_out = out_v[k]->data_ptr<float>();
-        }
-    }
-    if (P == 0) return {out_p, out_m, out_v};
+    RowOutputs<StpMcmcTensor> r = row_outputs<StpMcmcTensor>(who, tensors, roles, exp_avgs, exp_avg_sqs, M, M);
+    if (P == 0) return {r.out_p, r.out_m, r.out_v};
     const size_t bytes = g_api.mcmc_relocate_scratch_bytes((int)P);
     torch::Tensor scratch = torch::empty({(int64_t)bytes}, count.options().dtype(torch::kByte));
-    checked(g_api.mcmc_add_apply((int)P, (int)n_new, src.data_ptr<int32_t>(), count.data_ptr<int32_t>(), (int)n, table.data(), (float)min_opacity, raw ? 1 : 0,
+    checked(g_api.mcmc_add_apply((int)P, (int)n_new, src.data_ptr<int32_t>(), count.data_ptr<int32_t>(), (int)r.table.size(), r.table.data(), (float)min_opacity, raw ? 1 : 0,
                                  scratch.data_ptr(), bytes, current_stream(count.device())));
-    return {out_p, out_m, out_v};
+    return {r.out_p, r.out_m, r.out_v};
 }
 
 // == the activated copies of a trainer's raw parameters (extension, include/stp_raster.h: stp_activate_params; activate_params in __init__.py): the
@@ -449,9 +488,7 @@ densify_apply(const torch::Tensor& plan_in, const torch::Tensor& offsets, const 
     static const char* const who = "densify_apply";
     need_library();
     require(g_api.densify_apply, who);
-    const size_t n = tensors.size();
-    TORCH_CHECK(roles.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n, who, ": tensors, roles, exp_avgs and exp_avg_sqs must have one entry per tensor");
-    TORCH_CHECK(n <= 64, who, ": ", n, " tensors, at most 64 in one call");
+    static const RowRoleRules rules = {3, "(0 plain, 1 xyz, 2 scaling, 3 rotation)", nullptr, nullptr};
     TORCH_CHECK(counts_in.size() == 3, who, ": counts must be (nK, nC, nS)");
     TORCH_CHECK(plan_in.defined() && plan_in.scalar_type() == torch::kByte && plan_in.dim() == 1, who, ": plan: expected a uint8 (P,) tensor");
     const int64_t P = plan_in.size(0);
@@ -460,20 +497,7 @@ densify_apply(const torch::Tensor& plan_in, const torch::Tensor& offsets, const 
     for (int j = 0; j < 3; j++) TORCH_CHECK(counts[j] >= 0 && counts[j] <= P, who, ": counts[", j, "] = ", counts[j], " outside [0, P]");
     const int64_t nS = counts[2], M = counts[0] + counts[1] + 2 * nS;
     TORCH_CHECK(offsets.defined() && offsets.scalar_type() == torch::kInt32 && offsets.dim() == 1 && offsets.size(0) == 3 * P, who, ": offsets: expected an int32 (3 P,) tensor");
-    for (size_t k = 0; k < n; k++) {
-        const torch::Tensor& t = tensors[k];
-        TORCH_CHECK(t.defined(), who, ": tensor ", k, " is undefined");
-        TORCH_CHECK(t.scalar_type() == torch::kFloat32, who, ": tensor ", k, ": expected float32 tensor, got ", t.scalar_type());
-        TORCH_CHECK(t.dim() >= 1 && t.size(0) == P, who, ": tensor ", k, " must have ", P, " rows (the plan's), got ", t.sizes());
-        TORCH_CHECK(P == 0 || t.numel() > 0, who, ": tensor ", k, ": rows without elements, ", t.sizes());
-        TORCH_CHECK(roles[k] >= 0 && roles[k] <= 3, who, ": tensor ", k, ": unknown role ", roles[k], " (0 plain, 1 xyz, 2 scaling, 3 rotation)");
-        TORCH_CHECK(exp_avgs[k].has_value() == exp_avg_sqs[k].has_value(), who, ": tensor ", k, ": exp_avg and exp_avg_sq must both be given or both be None");
-        if (exp_avgs[k].has_value())
-            for (const torch::Tensor* m : {&*exp_avgs[k], &*exp_avg_sqs[k]}) {
-                TORCH_CHECK(m->defined() && m->scalar_type() == torch::kFloat32, who, ": tensor ", k, ": moments: expected float32 tensors");
-                TORCH_CHECK(m->sizes() == t.sizes(), who, ": tensor ", k, ": a moment has shape ", m->sizes(), ", the parameter has ", t.sizes());
-            }
-    }
+    check_row_lists(who, P, tensors, roles, exp_avgs, exp_avg_sqs, rules, false);
     if (nS > 0) {
         TORCH_CHECK(noise_in.has_value(), who, ": nS = ", nS, " needs noise");
         check_float(who, "noise", *noise_in);
@@ -481,46 +505,16 @@ densify_apply(const torch::Tensor& plan_in, const torch::Tensor& offsets, const 
     }
     check_on_gpu(who, "plan", plan_in);
     check_device(who, "offsets", offsets, plan_in);
-    for (size_t k = 0; k < n; k++) {
-        check_device(who, "a tensor", tensors[k], plan_in);
-        if (exp_avgs[k].has_value()) {
-            check_device(who, "an exp_avg", *exp_avgs[k], plan_in);
-            check_device(who, "an exp_avg_sq", *exp_avg_sqs[k], plan_in);
-        }
-    }
+    check_row_devices(who, tensors, exp_avgs, exp_avg_sqs, plan_in);
     if (nS > 0) check_device(who, "noise", *noise_in, plan_in);
     const torch::Tensor plan = plan_in.contiguous(), off = offsets.contiguous();
     const c10::hip::HIPGuard guard(plan.device().index());
-    std::vector<torch::Tensor> held; // the contiguous inputs, alive until the launches are made
-    std::vector<torch::Tensor> out_p(n);
-    std::vector<c10::optional<torch::Tensor>> out_m(n), out_v(n);
-    std::vector<StpDensifyTensor> table(n);
-    for (size_t k = 0; k < n; k++) {
-        std::vector<int64_t> shape = tensors[k].sizes().vec();
-        int64_t row = 1;
-        for (size_t d = 1; d < shape.size(); d++) row *= shape[d];
-        TORCH_CHECK(row > 0 && P * row < (1ll << 31), who, ": tensor ", k, ": ", P, " rows of ", row, " floats: outside (0, 2^31)");
-        shape[0] = M;
-        held.push_back(tensors[k].contiguous());
-        out_p[k] = torch::empty(shape, held.back().options());
-        StpDensifyTensor& t = table[k];
-        t = StpDensifyTensor{held.back().data_ptr<float>(), nullptr, nullptr, out_p[k].data_ptr<float>(), nullptr, nullptr, (int32_t)row, (int32_t)roles[k]};
-        if (exp_avgs[k].has_value()) {
-            held.push_back(exp_avgs[k]->contiguous());
-            t.exp_avg = held.back().data_ptr<float>();
-            held.push_back(exp_avg_sqs[k]->contiguous());
-            t.exp_avg_sq = held.back().data_ptr<float>();
-            out_m[k] = torch::empty(shape, held.back().options());
-            out_v[k] = torch::empty(shape, held.back().options());
-            t.exp_avg_out = out_m[k]->data_ptr<float>();
-            t.exp_avg_sq_out = out_v[k]->data_ptr<float>();
-        }
-    }
+    RowOutputs<StpDensifyTensor> r = row_outputs<StpDensifyTensor>(who, tensors, roles, exp_avgs, exp_avg_sqs, M, P); // (the library's work is over the P source rows)
     torch::Tensor noise;
     if (nS > 0) noise = noise_in->contiguous();
-    checked(g_api.densify_apply((int)P, plan.data_ptr<uint8_t>(), reinterpret_cast<const uint32_t*>(off.data_ptr<int32_t>()), counts, (int)n, table.data(),
+    checked(g_api.densify_apply((int)P, plan.data_ptr<uint8_t>(), reinterpret_cast<const uint32_t*>(off.data_ptr<int32_t>()), counts, (int)r.table.size(), r.table.data(),
                                 noise.defined() ? noise.data_ptr<float>() : nullptr, (float)split_shrink, raw ? 1 : 0, current_stream(plan.device())));
-    return {out_p, out_m, out_v};
+    return {r.out_p, r.out_m, r.out_v};
 }
 
 // == the fused photometric loss (extension, include/stp_raster.h: stp_photometric_forward / _backward; photometric_loss and fused_ssim in

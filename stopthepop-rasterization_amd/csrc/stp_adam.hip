@@ -3,9 +3,10 @@
 //     m <- b1 * m + (1 - b1) * g      v <- b2 * v + (1 - b2) * g * g      p <- p - lr * m / (sqrt(v) + eps)
 // in float32, without bias correction; the elements of invisible rows are neither read nor written.
 //
-// One launch serves up to ADAM_MAX_TENSORS tensors.  The kernel arguments carry a table of descriptors by value; a tensor of numel
-// elements owns ceil(numel / ADAM_UNIT) consecutive work units, a workgroup is one unit and finds its tensor by a wave-uniform search
-// for the last descriptor whose first unit is not behind its own (blockIdx.x is in SGPRs: the search is scalar code).
+// One launch serves up to ROW_TABLE_ENTRIES tensors.  The kernel arguments carry a table of descriptors by value; a tensor of numel
+// elements owns ceil(numel / ADAM_UNIT) consecutive work units, a workgroup is one unit and finds its tensor by the wave-uniform search
+// of stp_row_table.h (row_table_entry).  The descriptor and the packing loop are this file's own: four streams, a learning rate, units
+// counted in elements with a tail, tensors without elements skipped.
 //
 // Streaming shape.  p, g, m and v of a unit are read and p, m, v written with 16 bytes per lane where all four pointers are 16-byte
 // aligned (every tensor torch allocates); a thread owns the 16-byte pieces t, t + 256, t + 512 and t + 768 of its unit, so that a wave's
@@ -25,21 +26,20 @@
 // Visibility is read where the trainer has it: N bytes (bool / uint8, non-zero = visible) or the N int32 radii of the forward (> 0 =
 // visible).  A lane reads the entry of its piece's first row and again only where the row changes inside the piece.
 //
-// sqrt and the division are the correctly rounded ones (the kernel has about 180 VALU slots per element at the HBM rate and uses a
-// fraction): a denormal v or denominator is handled like any other value.
+// The division is the correctly rounded one (v_div_scale / v_rcp / refinement / v_div_fmas / v_div_fixup).  The root is NOT: __fsqrt_rn
+// compiles in this toolchain to the hardware's approximate v_sqrt_f32 between two v_ldexp_f32 (a denormal v is scaled up first) without a
+// refinement step, as stp_densify.hip's comment says of it.  The step's bits are pinned as they are (the kernel has about 180 VALU slots per element at
+// the HBM rate and uses a fraction); a denormal v or denominator is handled like any other value.
 #include "stp_internal.h"
-#include "stp_adam_div.h"
+#include "stp_row_table.h"
 
 namespace stp {
 
 namespace {
 
-constexpr int ADAM_BLOCK = 256;
+constexpr int ADAM_BLOCK = ROW_BLOCK;
 constexpr int ADAM_PIECES = 4;                              // 16-byte pieces a thread owns in its unit
 constexpr uint32_t ADAM_UNIT = ADAM_BLOCK * ADAM_PIECES * 4; // elements of a work unit (4096: 16 KiB of each stream)
-constexpr int ADAM_MAX_TENSORS = 8;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct AdamDesc {
     float* p;
@@ -53,7 +53,7 @@ struct AdamDesc {
     AdamDivisor div;     // e / M
 };
 struct AdamTable {
-    AdamDesc t[ADAM_MAX_TENSORS];
+    AdamDesc t[ROW_TABLE_ENTRIES];
 };
 
 template <int KIND> __device__ __forceinline__ bool row_visible(const void* __restrict__ visible, uint32_t row)
@@ -76,13 +76,8 @@ template <int KIND>
 __global__ void __launch_bounds__(ADAM_BLOCK) sparse_adam_kernel(const AdamTable table, const int n_tensors, const void* __restrict__ visible,
                                                                  const float b1, const float b2)
 {
-    // wave-uniform search: the last tensor whose first unit is <= this workgroup's
     const uint32_t unit = blockIdx.x;
-    int ti = 0;
-#pragma unroll
-    for (int i = 1; i < ADAM_MAX_TENSORS; i++)
-        if (i < n_tensors && unit >= table.t[i].first_unit) ti = i;
-    const AdamDesc& d = table.t[ti];
+    const AdamDesc& d = row_table_entry(table, n_tensors, unit);
     const uint32_t M = d.M, numel = d.numel;
     const AdamDivisor div = d.div;
     const AdamCoef c = {b1, 1.0f - b1, b2, 1.0f - b2, d.lr, d.eps};
@@ -153,8 +148,6 @@ __global__ void __launch_bounds__(ADAM_BLOCK) sparse_adam_kernel(const AdamTable
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 } // namespace
 
 int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind, float beta1, float beta2,
@@ -166,7 +159,7 @@ int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const
         AdamTable table{};
         int n = 0;
         uint32_t units = 0;
-        for (; next < n_tensors && n < ADAM_MAX_TENSORS; next++) {
+        for (; next < n_tensors && n < ROW_TABLE_ENTRIES; next++) {
             const StpAdamTensor& t = tensors[next];
             if (t.numel == 0) continue;
             AdamDesc& d = table.t[n++];
@@ -175,7 +168,7 @@ int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const
             d.M = (uint32_t)(t.numel / N);
             d.lr = t.lr; d.eps = t.eps;
             d.first_unit = units;
-            d.wide = aligned16(t.param) && aligned16(t.grad) && aligned16(t.exp_avg) && aligned16(t.exp_avg_sq);
+            d.wide = aligned16(t.param, t.grad, t.exp_avg, t.exp_avg_sq);
             d.div = adam_divisor(d.M);
             units += (d.numel + ADAM_UNIT - 1) / ADAM_UNIT; // <= 2^19 per tensor
         }

@@ -98,6 +98,69 @@ static void keep_for_per_gaussian_call(const BackwardRequests& r)
     t_pending.backward.absgrad = r.absgrad; t_pending.backward.blend_stats = r.blend_stats; t_pending.backward.invdepth = r.invdepth;
 }
 
+// ---- what the calls with a caller's scratch and the calls with a table of row tensors (StpMcmcTensor, StpDensifyTensor) share: 0 = fine,
+// ---- negative = refused
+// a scratch (not null: the caller's check) of `bytes` bytes against what size_fn(P) returned and the alignment the kernels read it with
+static int check_scratch(const char* who, const void* scratch, size_t bytes, size_t need, unsigned align, const char* size_fn)
+{
+    if (bytes < need)
+        return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": scratch of " + std::to_string(bytes) + " bytes, " + size_fn + "(P) = " + std::to_string(need));
+    if (reinterpret_cast<uintptr_t>(scratch) & (align - 1u)) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": scratch is not " + std::to_string(align) + "-byte aligned");
+    return 0;
+}
+
+// The roles of a table's entries: role 0 is a plain tensor of any width, role r in [1, n] is named name[r] in the messages and has row[r]
+// floats per row.  together == nullptr (3DGS-MCMC): a wrong width is refused at its tensor, and a role that is not there exactly once by its
+// name; otherwise (densification) `together` is the one sentence that refuses either, and only where the roles are required.
+struct RowRoles {
+    int n;
+    const char* const* name;
+    const int* row;
+    const char* known;    // the list behind "unknown role"
+    const char* rows;     // what the bound rows * row < 2^31 calls its rows
+    const char* together;
+};
+
+// The entry table of an apply that is flattened over `rows` rows.  in_place: the *_out pointers are not looked at; work: the call will launch
+// (pointers must be there); required: exactly one entry of each of the roles 1 .. n.
+template <class Entry>
+static int check_row_tensors(const char* who, int n_tensors, const Entry* tensors, long long rows, const RowRoles& roles, bool in_place, bool work, bool required)
+{
+    if (n_tensors < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative n_tensors");
+    if (n_tensors > 64) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(n_tensors) + " tensors, at most 64 in one call");
+    if (n_tensors > 0 && !tensors) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null tensor table");
+    int of_role[4] = {0, 0, 0, 0}; // (n <= 3)
+    bool rows_fit = true;
+    for (int k = 0; k < n_tensors; k++) {
+        const Entry& t = tensors[k];
+        const std::string which = std::string(who) + ": tensor " + std::to_string(k);
+        if (t.row <= 0) return fail(STP_ERR_INVALID_ARGUMENT, which + ": row " + std::to_string(t.row) + " <= 0");
+        if (rows * t.row >= (1ll << 31)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": " + roles.rows + " * row = " + std::to_string(rows * t.row) + " >= 2^31");
+        if (t.role < 0 || t.role > roles.n) return fail(STP_ERR_INVALID_ARGUMENT, which + ": unknown role " + std::to_string(t.role) + " " + roles.known);
+        if (t.role != 0 && t.row != roles.row[t.role]) {
+            if (!roles.together)
+                return fail(STP_ERR_INVALID_ARGUMENT, which + ": role " + std::to_string(t.role) + " needs row " + std::to_string(roles.row[t.role]) + ", got " + std::to_string(t.row));
+            rows_fit = false;
+        }
+        if ((t.exp_avg == nullptr) != (t.exp_avg_sq == nullptr)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": exp_avg and exp_avg_sq must both be given or both be null");
+        of_role[t.role]++;
+        if (work) {
+            if (!t.param || (!in_place && !t.param_out)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer");
+            if (!in_place && t.exp_avg && (!t.exp_avg_out || !t.exp_avg_sq_out)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer (moment output)");
+        }
+    }
+    if (!required) return 0;
+    for (int role = 1; role <= roles.n; role++) {
+        if (roles.together) {
+            if (of_role[role] != 1 || !rows_fit) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": " + roles.together);
+            continue;
+        }
+        if (of_role[role] == 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": missing role " + roles.name[role] + ": exactly one tensor must have it");
+        if (of_role[role] > 1) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": duplicated role " + roles.name[role] + ": exactly one tensor must have it");
+    }
+    return 0;
+}
+
 } // namespace stp
 
 using namespace stp;
@@ -392,6 +455,9 @@ int stp_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rota
 
 // ---- the 3DGS-MCMC relocation and growth (stp_mcmc_relocate.hip): everything is checked before the first launch
 static constexpr int MCMC_RELOCATE_MAX_P = 1 << 28;
+static const char* const MCMC_ROLE_NAMES[3] = {"", "1 (opacity, row 1)", "2 (scaling, row 3)"};
+static const int MCMC_ROLE_ROWS[3] = {0, 1, 3};
+static const RowRoles MCMC_ROLES = {2, MCMC_ROLE_NAMES, MCMC_ROLE_ROWS, "(0 plain, 1 opacity, 2 scaling)", "rows", nullptr};
 
 // P, raw and the scratch of the three calls: 0 = fine, negative = refused
 static int check_mcmc_relocate(const char* who, int P, int raw, const void* scratch, size_t scratch_bytes)
@@ -401,41 +467,7 @@ static int check_mcmc_relocate(const char* who, int P, int raw, const void* scra
     if (raw != 0 && raw != 1) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": raw must be 0 or 1, got " + std::to_string(raw));
     if (P == 0) return 0;
     if (!scratch) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer (scratch)");
-    const size_t need = mcmc_relocate_scratch_bytes(P);
-    if (scratch_bytes < need)
-        return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": scratch of " + std::to_string(scratch_bytes) + " bytes, stp_mcmc_relocate_scratch_bytes(P) = " + std::to_string(need));
-    if (reinterpret_cast<uintptr_t>(scratch) & 15u) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": scratch is not 16-byte aligned");
-    return 0;
-}
-
-// the entry table of an apply that writes out_rows rows (in place: the *_out pointers are not looked at)
-static int check_mcmc_tensors(const char* who, int n_tensors, const StpMcmcTensor* tensors, long long out_rows, bool in_place, bool work)
-{
-    if (n_tensors < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative n_tensors");
-    if (n_tensors > 64) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(n_tensors) + " tensors, at most 64 in one call");
-    if (n_tensors > 0 && !tensors) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null tensor table");
-    int of_role[3] = {0, 0, 0};
-    for (int k = 0; k < n_tensors; k++) {
-        const StpMcmcTensor& t = tensors[k];
-        const std::string which = std::string(who) + ": tensor " + std::to_string(k);
-        if (t.row <= 0) return fail(STP_ERR_INVALID_ARGUMENT, which + ": row " + std::to_string(t.row) + " <= 0");
-        if (out_rows * t.row >= (1ll << 31)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": rows * row = " + std::to_string(out_rows * t.row) + " >= 2^31");
-        if (t.role < 0 || t.role > 2) return fail(STP_ERR_INVALID_ARGUMENT, which + ": unknown role " + std::to_string(t.role) + " (0 plain, 1 opacity, 2 scaling)");
-        if (t.role != 0 && t.row != (t.role == 1 ? 1 : 3))
-            return fail(STP_ERR_INVALID_ARGUMENT, which + ": role " + std::to_string(t.role) + " needs row " + (t.role == 1 ? "1" : "3") + ", got " + std::to_string(t.row));
-        if ((t.exp_avg == nullptr) != (t.exp_avg_sq == nullptr)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": exp_avg and exp_avg_sq must both be given or both be null");
-        of_role[t.role]++;
-        if (work) {
-            if (!t.param || (!in_place && !t.param_out)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer");
-            if (!in_place && t.exp_avg && (!t.exp_avg_out || !t.exp_avg_sq_out)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer (moment output)");
-        }
-    }
-    for (int role = 1; role <= 2; role++) {
-        const char* const name = role == 1 ? "1 (opacity, row 1)" : "2 (scaling, row 3)";
-        if (of_role[role] == 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": missing role " + name + ": exactly one tensor must have it");
-        if (of_role[role] > 1) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": duplicated role " + name + ": exactly one tensor must have it");
-    }
-    return 0;
+    return check_scratch(who, scratch, scratch_bytes, mcmc_relocate_scratch_bytes(P), 16, "stp_mcmc_relocate_scratch_bytes");
 }
 
 size_t stp_mcmc_relocate_scratch_bytes(int P)
@@ -470,7 +502,7 @@ int stp_mcmc_relocate_apply(int P, const int32_t* src, const int32_t* count, int
 {
     static const char* const who = "stp_mcmc_relocate_apply";
     if (const int rc = check_mcmc_relocate(who, P, raw, scratch, scratch_bytes)) return rc;
-    if (const int rc = check_mcmc_tensors(who, n_tensors, tensors, P, true, P > 0)) return rc;
+    if (const int rc = check_row_tensors(who, n_tensors, tensors, P, MCMC_ROLES, true, P > 0, true)) return rc;
     if (P == 0) return 0;
     if (!src || !count) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
     hipError_t e;
@@ -485,7 +517,7 @@ int stp_mcmc_add_apply(int P, int n_new, const int32_t* src, const int32_t* coun
     static const char* const who = "stp_mcmc_add_apply";
     if (n_new < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative n_new");
     if (const int rc = check_mcmc_relocate(who, P, raw, scratch, scratch_bytes)) return rc;
-    if (const int rc = check_mcmc_tensors(who, n_tensors, tensors, (long long)P + n_new, false, P > 0)) return rc;
+    if (const int rc = check_row_tensors(who, n_tensors, tensors, (long long)P + n_new, MCMC_ROLES, false, P > 0, true)) return rc;
     if (P == 0) {
         if (n_new > 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(n_new) + " new rows from P = 0 rows");
         return 0;
@@ -507,10 +539,7 @@ int stp_knn_mean_dist2(int P, const float* points, void* scratch, size_t scratch
     if (P < 4)
         return fail(STP_ERR_INVALID_ARGUMENT, "stp_knn_mean_dist2: P = " + std::to_string(P) + ": the mean over three neighbours needs at least 4 points");
     if (!points || !scratch || !mean_dist2) return fail(STP_ERR_INVALID_ARGUMENT, "stp_knn_mean_dist2: null pointer");
-    const size_t need = knn_scratch_bytes(P);
-    if (scratch_bytes < need)
-        return fail(STP_ERR_INVALID_ARGUMENT, "stp_knn_mean_dist2: scratch of " + std::to_string(scratch_bytes) + " bytes, stp_knn_scratch_bytes(P) = " + std::to_string(need));
-    if (reinterpret_cast<uintptr_t>(scratch) & 15u) return fail(STP_ERR_INVALID_ARGUMENT, "stp_knn_mean_dist2: scratch is not 16-byte aligned");
+    if (const int rc = check_scratch("stp_knn_mean_dist2", scratch, scratch_bytes, knn_scratch_bytes(P), 16, "stp_knn_scratch_bytes")) return rc;
     hipError_t e;
     const int launches = launch_knn_mean_dist2(P, points, scratch, mean_dist2, (hipStream_t)stream, &e);
     if (e != hipSuccess) return fail_hip(e, "knn_mean_dist2");
@@ -518,6 +547,9 @@ int stp_knn_mean_dist2(int P, const float* points, void* scratch, size_t scratch
 }
 
 // ---- densification (stp_densify.hip): everything is checked before the first launch
+static const int DENSIFY_ROLE_ROWS[4] = {0, 3, 3, 4};
+static const RowRoles DENSIFY_ROLES = {3, nullptr, DENSIFY_ROLE_ROWS, "(0 plain, 1 xyz, 2 scaling, 3 rotation)", "P",
+                                       "a split needs exactly one tensor of each of the roles 1 (xyz, row 3), 2 (scaling, row 3) and 3 (rotation, row 4)"};
 static int check_densify_P(const char* who, int P)
 {
     if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative P");
@@ -571,10 +603,7 @@ int stp_densify_scan(int P, const uint8_t* plan, void* scratch, size_t scratch_b
         return 0;
     }
     if (!plan || !scratch || !offsets) return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_scan: null pointer");
-    if (scratch_bytes < densify_scratch_bytes(P))
-        return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_scan: scratch of " + std::to_string(scratch_bytes) + " bytes, stp_densify_scratch_bytes(P) = " +
-                                                  std::to_string(densify_scratch_bytes(P)));
-    if (reinterpret_cast<uintptr_t>(scratch) & 3u) return fail(STP_ERR_INVALID_ARGUMENT, "stp_densify_scan: scratch is not 4-byte aligned");
+    if (const int rc = check_scratch("stp_densify_scan", scratch, scratch_bytes, densify_scratch_bytes(P), 4, "stp_densify_scratch_bytes")) return rc;
     hipError_t e;
     const int launches = launch_densify_scan(P, plan, scratch, offsets, counts, (hipStream_t)stream, &e);
     if (e != hipSuccess) return fail_hip(e, "densify_scan");
@@ -586,34 +615,15 @@ int stp_densify_apply(int P, const uint8_t* plan, const uint32_t* offsets, const
 {
     static const char* const who = "stp_densify_apply";
     if (const int rc = check_densify_P(who, P)) return rc;
-    if (n_tensors < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative n_tensors");
-    if (n_tensors > 64) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(n_tensors) + " tensors, at most 64 in one call");
     if (raw != 0 && raw != 1) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": raw must be 0 or 1, got " + std::to_string(raw));
     if (!counts) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null counts");
     for (int j = 0; j < 3; j++)
         if (counts[j] < 0 || counts[j] > P)
             return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": counts[" + std::to_string(j) + "] = " + std::to_string((long long)counts[j]) + " outside [0, P]");
-    if (n_tensors > 0 && !tensors) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null tensor table");
     const int64_t nS = counts[2], M = counts[0] + counts[1] + 2 * nS;
-    int of_role[4] = {0, 0, 0, 0};
-    bool rows_fit = true;
-    for (int k = 0; k < n_tensors; k++) {
-        const StpDensifyTensor& t = tensors[k];
-        const std::string which = std::string(who) + ": tensor " + std::to_string(k);
-        if (t.row <= 0) return fail(STP_ERR_INVALID_ARGUMENT, which + ": row " + std::to_string(t.row) + " <= 0");
-        if ((long long)P * t.row >= (1ll << 31)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": P * row = " + std::to_string((long long)P * t.row) + " >= 2^31");
-        if (t.role < 0 || t.role > 3) return fail(STP_ERR_INVALID_ARGUMENT, which + ": unknown role " + std::to_string(t.role) + " (0 plain, 1 xyz, 2 scaling, 3 rotation)");
-        if ((t.exp_avg == nullptr) != (t.exp_avg_sq == nullptr)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": exp_avg and exp_avg_sq must both be given or both be null");
-        of_role[t.role]++;
-        if (t.role != 0 && t.row != (t.role == 3 ? 4 : 3)) rows_fit = false;
-        if (M > 0) {
-            if (!t.param || !t.param_out) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer");
-            if (t.exp_avg && (!t.exp_avg_out || !t.exp_avg_sq_out)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer (moment output)");
-        }
-    }
+    // (the work is flattened over the P source rows; without a split any role may be absent and have any width)
+    if (const int rc = check_row_tensors(who, n_tensors, tensors, P, DENSIFY_ROLES, false, M > 0, nS > 0)) return rc;
     if (nS > 0) {
-        if (of_role[1] != 1 || of_role[2] != 1 || of_role[3] != 1 || !rows_fit)
-            return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": a split needs exactly one tensor of each of the roles 1 (xyz, row 3), 2 (scaling, row 3) and 3 (rotation, row 4)");
         if (!noise) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null noise with nS = " + std::to_string((long long)nS));
     }
     if (P == 0 || M == 0 || n_tensors == 0) return 0;

@@ -13,12 +13,12 @@
 //
 // Scan.  The 3P flags [K bits | C bits | S bits] are never materialised: flag j is bit j / P of plan[j % P].  A thread owns SCAN_ITEMS
 // consecutive flags, a workgroup SCAN_TILE; (1) every workgroup sums its tile, (2) one workgroup turns the tile sums into their exclusive
-// prefix in place, (3) every workgroup scans its tile again from that prefix and writes the offsets.  The thread that passes flag P, flag 2P
+// prefix in place (tile_prefix_kernel of stp_row_table.h), (3) every workgroup scans its tile again from that prefix and writes the offsets.  The thread that passes flag P, flag 2P
 // and the last flag leaves the running sum there in three words, from which the host forms (nK, nC, nS).  The scratch is the tile sums and
 // those words: its size depends on P alone.
 //
-// Apply.  The work is flattened over (source row, element) like the Adam step's: a tensor of P rows of `row` floats owns ceil(items /
-// APPLY_UNIT) consecutive work units, an item being 16 bytes of a row where the row stream is 16-byte aligned (row % 4 == 0 and all the
+// Apply.  The work is flattened over (source row, element) by the row table of stp_row_table.h: a tensor of P rows of `row` floats owns ceil(items /
+// ROW_UNIT) consecutive work units, an item being 16 bytes of a row where the row stream is 16-byte aligned (row % 4 == 0 and all the
 // tensor's pointers aligned) and one float otherwise; the arithmetic does not depend on the path.  A lane reads its Gaussian's plan byte;
 // a row that goes nowhere is skipped before its loads.  K: parameter and moments are copied to row offsets[i]; C: the parameter is copied to
 // row offsets[P + i] with zero moments; S: rows offsets[2P + i] and offsets[2P + i] + nS get the parameter -- or, in the xyz and scaling
@@ -27,7 +27,7 @@
 // sqrtf(fma(q3, q3, fma(q2, q2, fma(q1, q1, q0 * q0)))), q / n by division; R as in stp_mcmc.hip; t = s * noise; xyz'_c = xyz_c + fma(R_c2, t_2,
 // fma(R_c1, t_1, R_c0 * t_0)); scaling' = raw ? logf(s / split_shrink) : s / split_shrink.
 #include "stp_internal.h"
-#include "stp_adam_div.h"
+#include "stp_row_table.h"
 
 // Nothing in this file is contracted: __fmul_rn / __fadd_rn are plain operators to the compiler, which would otherwise fuse gx * gx + gy * gy
 // into a multiply-add.  The fused multiply-adds that are wanted are written as __fmaf_rn.
@@ -37,9 +37,7 @@ namespace stp {
 
 namespace {
 
-constexpr int DENSIFY_BLOCK = 256;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int DENSIFY_BLOCK = ROW_BLOCK;
 
 template <int KIND> __device__ __forceinline__ bool densify_visible(const void* __restrict__ visible, uint32_t i)
 {
@@ -105,30 +103,6 @@ __device__ __forceinline__ uint32_t plan_flag(const uint8_t* __restrict__ plan, 
     return ((uint32_t)plan[j - seg * P] >> seg) & 1u;
 }
 
-// the exclusive prefix of v over the workgroup's threads and (total) the workgroup's sum; lds: DENSIFY_BLOCK / 64 words
-__device__ __forceinline__ uint32_t block_exclusive(const uint32_t v, uint32_t* lds, uint32_t& total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(inc, d, 64);
-        if (lane >= (uint32_t)d) inc += up;
-    }
-    __syncthreads(); // (lds may still be read from an earlier call)
-    if (lane == 63u) lds[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < DENSIFY_BLOCK / 64; w++) {
-        const uint32_t t = lds[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    return before + inc - v;
-}
-
 __device__ __forceinline__ uint32_t thread_flags(const uint8_t* __restrict__ plan, const uint32_t P, const uint32_t n, const uint32_t j0)
 {
     uint32_t sum = 0;
@@ -147,22 +121,6 @@ __global__ void __launch_bounds__(DENSIFY_BLOCK) densify_tile_sums_kernel(const 
     uint32_t total;
     (void)block_exclusive(thread_flags(plan, P, n, j0), lds, total);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-// one workgroup: tile_sums[0 .. tiles) -> their exclusive prefix, in place; a thread owns `chunk` consecutive entries
-__global__ void __launch_bounds__(DENSIFY_BLOCK) densify_tile_prefix_kernel(const uint32_t tiles, const uint32_t chunk, uint32_t* __restrict__ tile_sums)
-{
-    __shared__ uint32_t lds[DENSIFY_BLOCK / 64];
-    const uint32_t first = threadIdx.x * chunk;
-    uint32_t sum = 0;
-    for (uint32_t k = first; k < first + chunk && k < tiles; k++) sum += tile_sums[k];
-    uint32_t total;
-    uint32_t run = block_exclusive(sum, lds, total);
-    for (uint32_t k = first; k < first + chunk && k < tiles; k++) {
-        const uint32_t t = tile_sums[k];
-        tile_sums[k] = run;
-        run += t;
-    }
 }
 
 __global__ void __launch_bounds__(DENSIFY_BLOCK) densify_offsets_kernel(const uint32_t P, const uint8_t* __restrict__ plan, const uint32_t* __restrict__ tile_sums,
@@ -187,21 +145,6 @@ __global__ void __launch_bounds__(DENSIFY_BLOCK) densify_offsets_kernel(const ui
 
 // ---- the apply -----------------------------------------------------------------------------------------------------------------------------
 
-constexpr int APPLY_MAX_TENSORS = 8;
-constexpr int APPLY_PIECES = 4;                                     // items a thread owns in its unit
-constexpr uint32_t APPLY_UNIT = DENSIFY_BLOCK * APPLY_PIECES;       // items of a work unit
-
-struct ApplyDesc {
-    const float *p, *m, *v; // (m, v: both or neither)
-    float *po, *mo, *vo;
-    uint32_t row, items;    // floats per Gaussian; items of the tensor (floats, or 16-byte pieces where wide)
-    uint32_t first_unit, wide;
-    int32_t role;
-    AdamDivisor div;        // e / row
-};
-struct ApplyTable {
-    ApplyDesc t[APPLY_MAX_TENSORS];
-};
 // what the children of a split need beside their own tensor
 struct ApplySplit {
     const float *scaling, *rotation, *noise; // the INPUT scaling (P, 3) and rotation (P, 4), noise (2 nS, 3)
@@ -240,25 +183,20 @@ __device__ __forceinline__ float child_xyz(const float x, const uint32_t i, cons
     return __fadd_rn(x, __fmaf_rn(R2, t[2], __fmaf_rn(R1, t[1], __fmul_rn(R0, t[0]))));
 }
 
-__global__ void __launch_bounds__(DENSIFY_BLOCK) densify_apply_kernel(const ApplyTable table, const int n_tensors, const uint32_t P,
+__global__ void __launch_bounds__(DENSIFY_BLOCK) densify_apply_kernel(const RowTable table, const int n_tensors, const uint32_t P,
                                                                        const uint8_t* __restrict__ plan, const uint32_t* __restrict__ offsets,
                                                                        const ApplySplit sp)
 {
-    // wave-uniform search: the last tensor whose first unit is <= this workgroup's
     const uint32_t unit = blockIdx.x;
-    int ti = 0;
-#pragma unroll
-    for (int i = 1; i < APPLY_MAX_TENSORS; i++)
-        if (i < n_tensors && unit >= table.t[i].first_unit) ti = i;
-    const ApplyDesc& d = table.t[ti];
+    const RowDesc& d = row_table_entry(table, n_tensors, unit);
     const uint32_t row = d.row, items = d.items;
     const AdamDivisor div = d.div;
     const bool moments = d.m != nullptr;
-    const uint32_t base = (unit - d.first_unit) * APPLY_UNIT;
+    const uint32_t base = (unit - d.first_unit) * ROW_UNIT;
     const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
 
 #pragma unroll
-    for (int k = 0; k < APPLY_PIECES; k++) {
+    for (int k = 0; k < ROW_PIECES; k++) {
         const uint32_t item = base + threadIdx.x + (uint32_t)k * DENSIFY_BLOCK;
         if (item >= items) break;
         const uint32_t e = d.wide ? item << 2 : item;   // the item's first float (< P * row < 2^31)
@@ -331,8 +269,6 @@ __global__ void __launch_bounds__(DENSIFY_BLOCK) densify_apply_kernel(const Appl
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 uint32_t scan_tiles(int P) { return (uint32_t)((3ull * (uint32_t)P + SCAN_TILE - 1) / SCAN_TILE); }
 
 } // namespace
@@ -374,7 +310,7 @@ int launch_densify_scan(int P, const uint8_t* plan, void* scratch, uint32_t* off
     hipLaunchKernelGGL(densify_tile_sums_kernel, dim3(tiles), block, 0, st, (uint32_t)P, plan, tile_sums);
     if ((*err = hipGetLastError()) != hipSuccess) return launches;
     launches++;
-    hipLaunchKernelGGL(densify_tile_prefix_kernel, dim3(1), block, 0, st, tiles, (tiles + DENSIFY_BLOCK - 1) / DENSIFY_BLOCK, tile_sums);
+    hipLaunchKernelGGL(tile_prefix_kernel<uint32_t>, dim3(1), block, 0, st, tiles, (tiles + DENSIFY_BLOCK - 1) / DENSIFY_BLOCK, tile_sums, (uint32_t*)nullptr);
     if ((*err = hipGetLastError()) != hipSuccess) return launches;
     launches++;
     hipLaunchKernelGGL(densify_offsets_kernel, dim3(tiles), block, 0, st, (uint32_t)P, plan, tile_sums, marks, offsets);
@@ -392,7 +328,6 @@ int launch_densify_scan(int P, const uint8_t* plan, void* scratch, uint32_t* off
 int launch_densify_apply(int P, const uint8_t* plan, const uint32_t* offsets, const int64_t counts[3], int n_tensors, const StpDensifyTensor* tensors,
                          const float* noise, float split_shrink, int raw, hipStream_t st, hipError_t* err)
 {
-    *err = hipSuccess;
     ApplySplit sp{};
     sp.noise = noise;
     sp.first_row = (uint32_t)(counts[0] + counts[1]);
@@ -403,31 +338,10 @@ int launch_densify_apply(int P, const uint8_t* plan, const uint32_t* offsets, co
         if (tensors[k].role == 2) sp.scaling = tensors[k].param;
         if (tensors[k].role == 3) sp.rotation = tensors[k].param;
     }
-    int launches = 0;
-    for (int next = 0; next < n_tensors;) {
-        ApplyTable table{};
-        int n = 0;
-        uint32_t units = 0;
-        for (; next < n_tensors && n < APPLY_MAX_TENSORS; next++) {
-            const StpDensifyTensor& t = tensors[next];
-            ApplyDesc& d = table.t[n++];
-            d.p = t.param; d.m = t.exp_avg; d.v = t.exp_avg_sq;
-            d.po = t.param_out; d.mo = t.exp_avg_out; d.vo = t.exp_avg_sq_out;
-            d.row = (uint32_t)t.row;
-            d.role = t.role;
-            d.wide = t.row % 4 == 0 && aligned16(t.param) && aligned16(t.exp_avg) && aligned16(t.exp_avg_sq) && aligned16(t.param_out) &&
-                     aligned16(t.exp_avg_out) && aligned16(t.exp_avg_sq_out);
-            const uint32_t numel = (uint32_t)P * d.row; // (< 2^31: checked by the caller)
-            d.items = d.wide ? numel >> 2 : numel;
-            d.first_unit = units;
-            d.div = adam_divisor(d.row);
-            units += (d.items + APPLY_UNIT - 1) / APPLY_UNIT;
-        }
+    // (the work is flattened over the P SOURCE rows)
+    return launch_row_tables(n_tensors, tensors, (uint32_t)P, false, err, [&](const RowTable& table, int n, uint32_t units) {
         hipLaunchKernelGGL(densify_apply_kernel, dim3(units), dim3(DENSIFY_BLOCK), 0, st, table, n, (uint32_t)P, plan, offsets, sp);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return launches; }
-        launches++;
-    }
-    return launches;
+    });
 }
 
 } // namespace stp

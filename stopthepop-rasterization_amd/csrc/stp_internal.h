@@ -286,7 +286,8 @@ size_t camera_grad_workspace_bytes(int P);
 // sums the per-workgroup rows the CAM kernel wrote (none for P == 0) into the three outputs; launch_preprocess_backward calls it itself
 hipError_t launch_camera_grad_finalize(int P, const CameraGradRequest& cam, hipStream_t st);
 hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t st);
-// the fused sparse Adam step (stp_adam.hip) over tensors stp_sparse_adam has validated: one launch per eight tensors with elements; returns
+// the fused sparse Adam step (stp_adam.hip) over tensors stp_sparse_adam has validated: one launch per eight tensors with elements (the
+// descriptor table's size and its search: stp_row_table.h, which stp_adam.hip, stp_densify.hip and stp_mcmc_relocate.hip include); returns
 // the launches made, *err = the launch error that ended them early (or hipSuccess)
 int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind, float beta1, float beta2,
                        hipStream_t st, hipError_t* err);
@@ -303,7 +304,8 @@ int launch_mcmc_add_noise(int P, float* xyz, const float* scales, const float* r
 // the 3DGS-MCMC relocation and growth (stp_mcmc_relocate.hip) over arguments stp_mcmc_sample / stp_mcmc_relocate_apply / stp_mcmc_add_apply have
 // validated (P in [1, 2^28], every written row count times row < 2^31, exactly one tensor of each of the roles 1 and 2, a scratch of
 // mcmc_relocate_scratch_bytes(P) bytes, 16-byte aligned): each returns the launches made, *err = the launch error that ended it early (or
-// hipSuccess).  No host synchronisation.
+// hipSuccess).  No host synchronisation.  The applies pack their tensors with launch_row_tables and the sampling scans with block_exclusive /
+// tile_prefix_kernel of stp_row_table.h, as the densification below does.
 size_t mcmc_relocate_scratch_bytes(int P);
 int launch_mcmc_sample(int P, const float* opacity, int rule, float min_opacity, int raw, int n_draws, const float* uniforms, void* scratch, uint32_t* weights,
                        int32_t* src, int32_t* count, hipStream_t st, hipError_t* err);

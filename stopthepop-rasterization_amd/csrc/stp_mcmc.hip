@@ -18,7 +18,9 @@
 //
 // Noise.  xyz[i] += R diag(s^2) R^T (noise[i] * g * noise_scale), g = 1 / (1 + exp(-k ((1 - o) - x0))), R the rotation of the normalised
 // quaternion (w, x, y, z), in float32 with every multiply-add written out: v = (noise * g) * noise_scale, u = R^T v, u *= s * s, d = R u,
-// xyz += d -- Sigma itself is never formed.  raw: o = 1 / (1 + exp(-opacity)) and s = exp(scale) first.
+// xyz += d -- Sigma itself is never formed.  raw: o = 1 / (1 + exp(-opacity)) and s = exp(scale) first.  The quaternion's norm is __fsqrt_rn,
+// which in this toolchain is the hardware's approximate v_sqrt_f32 between two v_ldexp_f32 (denormal pre-scaling), without a refinement step -- not
+// the correctly rounded root; the divisions by it are correctly rounded.  The kernel's bits stay as they are.
 // Streaming shape.  Where all five pointers are 16-byte aligned a lane owns FOUR consecutive Gaussians: their 48 bytes of xyz, of scales
 // and of noise are three 16-byte pieces each, their quaternions four and their opacities one -- 14 loads and 3 stores of 16 bytes, every
 // one aligned, and a wave covers 3 KiB contiguous of each (P, 3) stream.  The last P % 4 Gaussians belong to the lane after the last
@@ -26,14 +28,13 @@
 // Gaussian is the same function on every path.
 #include "stp_internal.h"
 #include "stp_mcmc_relocation.h"
+#include "stp_row_table.h"
 
 namespace stp {
 
 namespace {
 
 constexpr int MCMC_BLOCK = 256;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <typename NT>
 __global__ void __launch_bounds__(MCMC_BLOCK) mcmc_relocation_kernel(const uint32_t n, const float* __restrict__ opacity_old, const float* __restrict__ scale_old,
@@ -147,8 +148,6 @@ __global__ void __launch_bounds__(MCMC_BLOCK) mcmc_noise_kernel(const uint32_t P
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 } // namespace
 
 int launch_mcmc_relocation(int n, const float* opacity_old, const float* scale_old, const void* N, int n_kind, int n_max, float* opacity_new,
@@ -169,7 +168,7 @@ int launch_mcmc_add_noise(int P, float* xyz, const float* scales, const float* r
                           float k, float x0, int raw, hipStream_t st, hipError_t* err)
 {
     const NoiseCoef c = {noise_scale, k, x0};
-    const bool wide = aligned16(xyz) && aligned16(scales) && aligned16(rotations) && aligned16(opacities) && aligned16(noise);
+    const bool wide = aligned16(xyz, scales, rotations, opacities, noise);
     const uint32_t threads = wide ? ((uint32_t)P + 3) / 4 : (uint32_t)P; // (wide: P / 4 groups and, where P % 4, the thread of the tail)
     const dim3 grid((threads + MCMC_BLOCK - 1) / MCMC_BLOCK), block(MCMC_BLOCK);
     if (wide) {

@@ -5,7 +5,7 @@
 //
 // Sampling.  An inverse CDF over INTEGER weights: w_i = rint(clamp(o_i, 0, 1) * 2^24) (round to nearest even; exact, the scaling is a power of
 // two) for a candidate row and 0 for any other, o the opacity (raw: 1 / (1 + expf(-logit)), as mcmc_noise_kernel evaluates it).  The inclusive
-// prefix S_i = w_0 + ... + w_i is a 64-bit integer sum -- exact whatever the scan order -- by the tile-sum pattern of stp_densify.hip: a thread
+// prefix S_i = w_0 + ... + w_i is a 64-bit integer sum -- exact whatever the scan order -- by the tile-sum pattern of stp_row_table.h: a thread
 // owns SAMPLE_ITEMS consecutive rows, a workgroup SAMPLE_TILE; (1) every workgroup sums its tile (and clears its rows of `count`), (2) one
 // workgroup turns the tile sums into their exclusive prefix and leaves the total, (3) every workgroup scans its tile again from that prefix
 // and writes S.  (4) A lane per draw: u is clamped into [0, 1) (NaN and negatives: 0), t = min(total - 1, (uint64)(double(u) * double(total)))
@@ -20,11 +20,11 @@
 // only.  The other tensors need nothing: a row that is read (a source: count > 0) is never a row that is written (count == 0 and src >= 0).
 // o' and s' are mcmc_relocation_row's (stp_mcmc_relocation.h: the bits of stp_mcmc_relocation) with N = min(count + 1, 50); then
 // o' = min(max(o', min_opacity), 1 - 2^-23); raw: the stored values are logf(o' / (1 - o')) and logf(s'), the inputs expf(scaling) and the sigmoid above.
-// The work is flattened over (row, element) as in stp_densify.hip: 16 bytes per lane where a tensor's rows are multiples of 16 bytes and its
+// The work is flattened over (row, element) by the row table of stp_row_table.h: 16 bytes per lane where a tensor's rows are multiples of 16 bytes and its
 // pointers aligned, one float otherwise, with equal bits.  src values outside [0, P) are treated as -1: no plan can make a lane leave its arrays.
 #include "stp_internal.h"
-#include "stp_adam_div.h"
 #include "stp_mcmc_relocation.h"
+#include "stp_row_table.h"
 
 // Nothing in this file is contracted (the reason is stp_densify.hip's).
 #pragma clang fp contract(off)
@@ -33,9 +33,7 @@ namespace stp {
 
 namespace {
 
-constexpr int RELOCATE_BLOCK = 256;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int RELOCATE_BLOCK = ROW_BLOCK;
 
 constexpr uint32_t SAMPLE_ITEMS = 8;                            // consecutive rows of a thread
 constexpr uint32_t SAMPLE_TILE = RELOCATE_BLOCK * SAMPLE_ITEMS; // rows of a workgroup
@@ -48,36 +46,6 @@ __device__ __forceinline__ uint32_t sample_weight(const float o, const int rule,
 {
     const bool candidate = rule == 0 ? o > min_opacity : o == o;
     return candidate ? (uint32_t)rintf(fminf(fmaxf(o, 0.0f), 1.0f) * 16777216.0f) : 0u;
-}
-
-__device__ __forceinline__ uint64_t shfl_up64(const uint64_t v, const int d)
-{
-    const uint32_t lo = __shfl_up((uint32_t)v, d, 64), hi = __shfl_up((uint32_t)(v >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// the exclusive prefix of v over the workgroup's threads and (total) the workgroup's sum; lds: RELOCATE_BLOCK / 64 words
-__device__ __forceinline__ uint64_t block_exclusive64(const uint64_t v, uint64_t* lds, uint64_t& total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t up = shfl_up64(inc, d);
-        if (lane >= (uint32_t)d) inc += up;
-    }
-    __syncthreads(); // (lds may still be read from an earlier call)
-    if (lane == 63u) lds[wave] = inc;
-    __syncthreads();
-    uint64_t before = 0;
-    total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < RELOCATE_BLOCK / 64; w++) {
-        const uint64_t t = lds[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    return before + inc - v;
 }
 
 __global__ void __launch_bounds__(RELOCATE_BLOCK) sample_tile_sums_kernel(const uint32_t P, const float* __restrict__ opacity, const int rule,
@@ -94,26 +62,8 @@ __global__ void __launch_bounds__(RELOCATE_BLOCK) sample_tile_sums_kernel(const 
         count[i] = 0;
     }
     uint64_t total;
-    (void)block_exclusive64(sum, lds, total);
+    (void)block_exclusive(sum, lds, total);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-// one workgroup: tile_sums[0 .. tiles) -> their exclusive prefix, in place, and head[0] = their sum; a thread owns `chunk` consecutive entries
-__global__ void __launch_bounds__(RELOCATE_BLOCK) sample_tile_prefix_kernel(const uint32_t tiles, const uint32_t chunk, uint64_t* __restrict__ tile_sums,
-                                                                             uint64_t* __restrict__ head)
-{
-    __shared__ uint64_t lds[RELOCATE_BLOCK / 64];
-    const uint32_t first = threadIdx.x * chunk;
-    uint64_t sum = 0;
-    for (uint32_t k = first; k < first + chunk && k < tiles; k++) sum += tile_sums[k];
-    uint64_t total;
-    uint64_t run = block_exclusive64(sum, lds, total);
-    for (uint32_t k = first; k < first + chunk && k < tiles; k++) {
-        const uint64_t t = tile_sums[k];
-        tile_sums[k] = run;
-        run += t;
-    }
-    if (threadIdx.x == 0) head[0] = total;
 }
 
 __global__ void __launch_bounds__(RELOCATE_BLOCK) sample_prefix_kernel(const uint32_t P, const float* __restrict__ opacity, const int rule,
@@ -131,7 +81,7 @@ __global__ void __launch_bounds__(RELOCATE_BLOCK) sample_prefix_kernel(const uin
         sum += w[k];
     }
     uint64_t total;
-    uint64_t run = tile_sums[blockIdx.x] + block_exclusive64(sum, lds, total);
+    uint64_t run = tile_sums[blockIdx.x] + block_exclusive(sum, lds, total);
 #pragma unroll
     for (uint32_t k = 0; k < SAMPLE_ITEMS; k++) {
         const uint32_t i = i0 + k;
@@ -175,23 +125,10 @@ __global__ void __launch_bounds__(RELOCATE_BLOCK) sample_draw_kernel(const uint3
 
 // ---- the applies ---------------------------------------------------------------------------------------------------------------------------
 
-constexpr int APPLY_MAX_TENSORS = 8;
-constexpr int APPLY_PIECES = 4;                                 // items a thread owns in its unit
-constexpr uint32_t APPLY_UNIT = RELOCATE_BLOCK * APPLY_PIECES;  // items of a work unit
 constexpr int MAX_COPIES = 50;                                  // compute_relocation's clamp of N
 constexpr float ONE_MINUS_EPS = 0x1.fffffcp-1f;                 // 1 - float32 eps (2^-23)
 
-struct ApplyDesc {
-    const float *p, *m, *v; // the rows that are read (in place: the same arrays as po, mo, vo, hence no __restrict__ anywhere below)
-    float *po, *mo, *vo;    // (mo, vo: both or neither)
-    uint32_t row, items;    // floats per Gaussian; items of the tensor's WRITTEN rows (floats, or 16-byte pieces where wide)
-    uint32_t first_unit, wide;
-    int32_t role;           // 0 plain, 1 opacity, 2 scaling
-    AdamDivisor div;        // e / row
-};
-struct ApplyTable {
-    ApplyDesc t[APPLY_MAX_TENSORS];
-};
+// (RowDesc of stp_row_table.h: the items are those of the tensor's WRITTEN rows; role 0 plain, 1 opacity, 2 scaling)
 
 // the stored (o', s') of every row that was drawn, 16 bytes per row; rows with count <= 0 are not written (and never read)
 __global__ void __launch_bounds__(RELOCATE_BLOCK) fresh_kernel(const uint32_t P, const int32_t* __restrict__ count, const float* __restrict__ opacity,
@@ -219,16 +156,6 @@ __global__ void __launch_bounds__(RELOCATE_BLOCK) fresh_kernel(const uint32_t P,
     fresh[i] = out;
 }
 
-__device__ __forceinline__ const ApplyDesc& apply_tensor(const ApplyTable& table, const int n_tensors, const uint32_t unit)
-{
-    // wave-uniform search: the last tensor whose first unit is <= this workgroup's
-    int ti = 0;
-#pragma unroll
-    for (int i = 1; i < APPLY_MAX_TENSORS; i++)
-        if (i < n_tensors && unit >= table.t[i].first_unit) ti = i;
-    return table.t[ti];
-}
-
 // element `col` of a row of role 1 (opacity: the row is one float) or 2 (scaling: three)
 __device__ __forceinline__ float fresh_value(const f32x4* __restrict__ fresh, const uint32_t k, const int32_t role, const uint32_t col)
 {
@@ -238,18 +165,18 @@ __device__ __forceinline__ float fresh_value(const f32x4* __restrict__ fresh, co
 
 // in place: rows with count > 0 take (o', s') and zero moments; rows with count <= 0 and a src in [0, P) take row src (with its (o', s')), and
 // zero moments where reset_dead
-__global__ void __launch_bounds__(RELOCATE_BLOCK) relocate_apply_kernel(const ApplyTable table, const int n_tensors, const uint32_t P, const int32_t* __restrict__ src,
+__global__ void __launch_bounds__(RELOCATE_BLOCK) relocate_apply_kernel(const RowTable table, const int n_tensors, const uint32_t P, const int32_t* __restrict__ src,
                                                                          const int32_t* __restrict__ count, const f32x4* __restrict__ fresh, const int reset_dead)
 {
-    const ApplyDesc& d = apply_tensor(table, n_tensors, blockIdx.x);
+    const RowDesc& d = row_table_entry(table, n_tensors, blockIdx.x);
     const uint32_t row = d.row, items = d.items;
     const AdamDivisor div = d.div;
     const bool moments = d.mo != nullptr;
-    const uint32_t base = (blockIdx.x - d.first_unit) * APPLY_UNIT;
+    const uint32_t base = (blockIdx.x - d.first_unit) * ROW_UNIT;
     const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
 
 #pragma unroll
-    for (int k = 0; k < APPLY_PIECES; k++) {
+    for (int k = 0; k < ROW_PIECES; k++) {
         const uint32_t item = base + threadIdx.x + (uint32_t)k * RELOCATE_BLOCK;
         if (item >= items) break;
         const uint32_t e = d.wide ? item << 2 : item;   // the item's first float (< P * row < 2^31)
@@ -289,18 +216,18 @@ __global__ void __launch_bounds__(RELOCATE_BLOCK) relocate_apply_kernel(const Ap
 
 // out of place, over the P + n_new OUTPUT rows: row r < P is row r (with (o', s') and zero moments where count[r] > 0), row P + j is row src[j]
 // with its (o', s') and zero moments -- or, where src[j] is outside [0, P) (a model without any weight), +0.0 everywhere
-__global__ void __launch_bounds__(RELOCATE_BLOCK) add_apply_kernel(const ApplyTable table, const int n_tensors, const uint32_t P, const int32_t* __restrict__ src,
+__global__ void __launch_bounds__(RELOCATE_BLOCK) add_apply_kernel(const RowTable table, const int n_tensors, const uint32_t P, const int32_t* __restrict__ src,
                                                                     const int32_t* __restrict__ count, const f32x4* __restrict__ fresh)
 {
-    const ApplyDesc& d = apply_tensor(table, n_tensors, blockIdx.x);
+    const RowDesc& d = row_table_entry(table, n_tensors, blockIdx.x);
     const uint32_t row = d.row, items = d.items;
     const AdamDivisor div = d.div;
     const bool moments = d.mo != nullptr;
-    const uint32_t base = (blockIdx.x - d.first_unit) * APPLY_UNIT;
+    const uint32_t base = (blockIdx.x - d.first_unit) * ROW_UNIT;
     const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
 
 #pragma unroll
-    for (int k = 0; k < APPLY_PIECES; k++) {
+    for (int k = 0; k < ROW_PIECES; k++) {
         const uint32_t item = base + threadIdx.x + (uint32_t)k * RELOCATE_BLOCK;
         if (item >= items) break;
         const uint32_t e = d.wide ? item << 2 : item;   // the item's first float in the OUTPUT (< (P + n_new) * row < 2^31)
@@ -327,41 +254,7 @@ __global__ void __launch_bounds__(RELOCATE_BLOCK) add_apply_kernel(const ApplyTa
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 uint32_t sample_tiles(int P) { return ((uint32_t)P + SAMPLE_TILE - 1) / SAMPLE_TILE; }
-
-// the launches of an apply over all tensors, eight per launch; out_rows: the rows that are written
-template <class Launch>
-int launch_apply_tables(int n_tensors, const StpMcmcTensor* tensors, uint32_t out_rows, bool in_place, hipError_t* err, Launch launch)
-{
-    int launches = 0;
-    for (int next = 0; next < n_tensors;) {
-        ApplyTable table{};
-        int n = 0;
-        uint32_t units = 0;
-        for (; next < n_tensors && n < APPLY_MAX_TENSORS; next++) {
-            const StpMcmcTensor& t = tensors[next];
-            ApplyDesc& d = table.t[n++];
-            d.p = t.param; d.m = t.exp_avg; d.v = t.exp_avg_sq;
-            d.po = in_place ? t.param : t.param_out;
-            d.mo = in_place ? t.exp_avg : t.exp_avg_out;
-            d.vo = in_place ? t.exp_avg_sq : t.exp_avg_sq_out;
-            d.row = (uint32_t)t.row;
-            d.role = t.role;
-            d.wide = t.row % 4 == 0 && aligned16(d.p) && aligned16(d.m) && aligned16(d.v) && aligned16(d.po) && aligned16(d.mo) && aligned16(d.vo);
-            const uint32_t numel = out_rows * d.row; // (< 2^31: checked by the caller)
-            d.items = d.wide ? numel >> 2 : numel;
-            d.first_unit = units;
-            d.div = adam_divisor(d.row);
-            units += (d.items + APPLY_UNIT - 1) / APPLY_UNIT;
-        }
-        launch(table, n, units);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return launches; }
-        launches++;
-    }
-    return launches;
-}
 
 const float* role_param(int n_tensors, const StpMcmcTensor* tensors, int role)
 {
@@ -392,7 +285,7 @@ int launch_mcmc_sample(int P, const float* opacity, int rule, float min_opacity,
     hipLaunchKernelGGL(sample_tile_sums_kernel, dim3(tiles), block, 0, st, (uint32_t)P, opacity, rule, min_opacity, raw, tile_sums, count);
     if ((*err = hipGetLastError()) != hipSuccess) return launches;
     launches++;
-    hipLaunchKernelGGL(sample_tile_prefix_kernel, dim3(1), block, 0, st, tiles, (tiles + RELOCATE_BLOCK - 1) / RELOCATE_BLOCK, tile_sums, head);
+    hipLaunchKernelGGL(tile_prefix_kernel<uint64_t>, dim3(1), block, 0, st, tiles, (tiles + RELOCATE_BLOCK - 1) / RELOCATE_BLOCK, tile_sums, head);
     if ((*err = hipGetLastError()) != hipSuccess) return launches;
     launches++;
     hipLaunchKernelGGL(sample_prefix_kernel, dim3(tiles), block, 0, st, (uint32_t)P, opacity, rule, min_opacity, raw, tile_sums, prefix, weights);
@@ -421,7 +314,7 @@ int launch_mcmc_relocate_apply(int P, const int32_t* src, const int32_t* count, 
     int launches = launch_fresh(P, count, n_tensors, tensors, min_opacity, raw, scratch, st, err);
     if (*err != hipSuccess) return launches;
     const f32x4* const fresh = static_cast<const f32x4*>(scratch);
-    launches += launch_apply_tables(n_tensors, tensors, (uint32_t)P, true, err, [&](const ApplyTable& table, int n, uint32_t units) {
+    launches += launch_row_tables(n_tensors, tensors, (uint32_t)P, true, err, [&](const RowTable& table, int n, uint32_t units) {
         hipLaunchKernelGGL(relocate_apply_kernel, dim3(units), dim3(RELOCATE_BLOCK), 0, st, table, n, (uint32_t)P, src, count, fresh, reset_dead_moments);
     });
     return launches;
@@ -433,7 +326,7 @@ int launch_mcmc_add_apply(int P, int n_new, const int32_t* src, const int32_t* c
     int launches = launch_fresh(P, count, n_tensors, tensors, min_opacity, raw, scratch, st, err);
     if (*err != hipSuccess) return launches;
     const f32x4* const fresh = static_cast<const f32x4*>(scratch);
-    launches += launch_apply_tables(n_tensors, tensors, (uint32_t)P + (uint32_t)n_new, false, err, [&](const ApplyTable& table, int n, uint32_t units) {
+    launches += launch_row_tables(n_tensors, tensors, (uint32_t)P + (uint32_t)n_new, false, err, [&](const RowTable& table, int n, uint32_t units) {
         hipLaunchKernelGGL(add_apply_kernel, dim3(units), dim3(RELOCATE_BLOCK), 0, st, table, n, (uint32_t)P, src, count, fresh);
     });
     return launches;

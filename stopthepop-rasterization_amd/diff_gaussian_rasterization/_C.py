@@ -528,10 +528,12 @@ def mcmc_add_noise(xyz, scales, rotations, opacities, noise, noise_scale, k, x0,
 
 
 class StpMcmcTensor(ctypes.Structure):
-    """include/stp_raster.h: StpMcmcTensor (for callers of the C ABI through ctypes; the native module builds its own)"""
+    """include/stp_raster.h: StpMcmcTensor and StpDensifyTensor, one layout (for callers of the C ABI through ctypes; the native module builds its own)"""
     _fields_ = [(name, ctypes.c_void_p) for name in ("param", "exp_avg", "exp_avg_sq", "param_out", "exp_avg_out", "exp_avg_sq_out")] + \
                [("row", ctypes.c_int32), ("role", ctypes.c_int32)]
 
+
+StpDensifyTensor = StpMcmcTensor
 
 MCMC_ROLES = {"plain": 0, "opacity": 1, "scaling": 2}
 MCMC_SAMPLE_TILE = 2048   # == STP_MCMC_SAMPLE_TILE (include/stp_raster.h): rows of a workgroup of the sampling's scan
@@ -603,12 +605,6 @@ class StpDensifyRule(ctypes.Structure):
     """include/stp_raster.h: StpDensifyRule (for callers of the C ABI through ctypes; the native module builds its own)"""
     _fields_ = [(name, ctypes.c_float) for name in ("grad_threshold", "split_size", "min_opacity", "max_screen_size", "max_world_size", "split_shrink")] + \
                [("raw", ctypes.c_int32), ("prune_big", ctypes.c_int32)]
-
-
-class StpDensifyTensor(ctypes.Structure):
-    """include/stp_raster.h: StpDensifyTensor"""
-    _fields_ = [(name, ctypes.c_void_p) for name in ("param", "exp_avg", "exp_avg_sq", "param_out", "exp_avg_out", "exp_avg_sq_out")] + \
-               [("row", ctypes.c_int32), ("role", ctypes.c_int32)]
 
 
 DENSIFY_ROLES = {"plain": 0, "xyz": 1, "scaling": 2, "rotation": 3}

@@ -781,6 +781,34 @@ def densify_plan(xyz_gradient_accum: torch.Tensor, denom: torch.Tensor, scaling:
                            None if max_radii2D is None else max_radii2D.detach(), rule, raw, big)
 
 
+def _row_lists(tensors, roles, role_ids, exp_avgs, exp_avg_sqs):
+    """The lists the native row-tensor calls take: detached tensors, roles as numbers (names through role_ids; None: all plain), one moment or None
+    per tensor (None: no moments at all)."""
+    tensors = [t.detach() for t in tensors]
+    n = len(tensors)
+    roles = [0] * n if roles is None else [role_ids[r] if isinstance(r, str) else int(r) for r in roles]
+    exp_avgs = [None] * n if exp_avgs is None else [None if m is None else m.detach() for m in exp_avgs]
+    exp_avg_sqs = [None] * n if exp_avg_sqs is None else [None if v is None else v.detach() for v in exp_avg_sqs]
+    return tensors, roles, exp_avgs, exp_avg_sqs
+
+
+def _named_groups(who, optimizer, role_of):
+    """-> (groups, params, roles, exp_avgs, exp_avg_sqs) of an optimizer whose groups hold one tensor each and carry "name"; role_of: {group name: role},
+    every other group is plain; the moments are None where the state has none."""
+    groups = list(optimizer.param_groups)
+    params, roles, ms, vs = [], [], [], []
+    for group in groups:
+        if len(group["params"]) != 1 or "name" not in group:
+            raise ValueError(f"{who}: every group must hold one tensor and carry a \"name\"")
+        p = group["params"][0]
+        state = optimizer.state.get(p, {})
+        params.append(p)
+        roles.append(role_of.get(group["name"], "plain"))
+        ms.append(state.get("exp_avg"))
+        vs.append(state.get("exp_avg_sq"))
+    return groups, params, roles, ms, vs
+
+
 def densify_tensors(plan: torch.Tensor, tensors, roles=None, exp_avgs=None, exp_avg_sqs=None, noise: Optional[torch.Tensor] = None, *,
                     split_shrink: float = 1.6, raw: bool = True):
     """Clone, split and prune a model by a plan (densify_plan's, or one written with torch) in one scan and one apply (extension;
@@ -793,11 +821,7 @@ def densify_tensors(plan: torch.Tensor, tensors, roles=None, exp_avgs=None, exp_
     where raw is False), s = exp(scaling) where raw.  noise: (2 nS, 3) standard normal (random numbers stay torch's); None draws
     torch.randn.  A split needs exactly one tensor of each of the roles xyz (P, 3), scaling (P, 3), rotation (P, 4).
     ONE host synchronisation, in the scan: the counts have to be known to allocate.  Inputs are not modified."""
-    tensors = [t.detach() for t in tensors]
-    n = len(tensors)
-    roles = [0] * n if roles is None else [_C.DENSIFY_ROLES[r] if isinstance(r, str) else int(r) for r in roles]
-    exp_avgs = [None] * n if exp_avgs is None else [None if m is None else m.detach() for m in exp_avgs]
-    exp_avg_sqs = [None] * n if exp_avg_sqs is None else [None if v is None else v.detach() for v in exp_avg_sqs]
+    tensors, roles, exp_avgs, exp_avg_sqs = _row_lists(tensors, roles, _C.DENSIFY_ROLES, exp_avgs, exp_avg_sqs)
     offsets, counts = _C.densify_scan(plan)
     if noise is None and counts[2] > 0:
         noise = torch.randn(2 * counts[2], 3, device=plan.device, dtype=torch.float32)
@@ -828,29 +852,9 @@ def densify_and_prune(optimizer, plan: torch.Tensor, *, noise: Optional[torch.Te
     names = (xyz, scaling, rotation) play those roles.  Each group gets a new nn.Parameter in group["params"][0], optimizer.state moves onto
     it with the new exp_avg and exp_avg_sq (a group whose state is still empty stays empty; other entries, "step", are kept), and
     {name: new Parameter} -- upstream's optimizable_tensors -- is returned for the model to take.  One host synchronisation."""
-    role_of = dict(zip(names, ("xyz", "scaling", "rotation")))
-    groups = list(optimizer.param_groups)
-    params, roles, ms, vs = [], [], [], []
-    for group in groups:
-        if len(group["params"]) != 1 or "name" not in group:
-            raise ValueError("densify_and_prune: every group must hold one tensor and carry a \"name\"")
-        p = group["params"][0]
-        state = optimizer.state.get(p, {})
-        params.append(p)
-        roles.append(role_of.get(group["name"], "plain"))
-        ms.append(state.get("exp_avg"))
-        vs.append(state.get("exp_avg_sq"))
+    groups, params, roles, ms, vs = _named_groups("densify_and_prune", optimizer, dict(zip(names, ("xyz", "scaling", "rotation"))))
     new_t, new_m, new_v, _ = densify_tensors(plan, params, roles, ms, vs, noise, split_shrink=split_shrink, raw=raw)
     return _replace_group_tensors(optimizer, groups, params, new_t, new_m, new_v)
-
-
-def _mcmc_lists(tensors, roles, exp_avgs, exp_avg_sqs):
-    tensors = [t.detach() for t in tensors]
-    n = len(tensors)
-    roles = [0] * n if roles is None else [_C.MCMC_ROLES[r] if isinstance(r, str) else int(r) for r in roles]
-    exp_avgs = [None] * n if exp_avgs is None else [None if m is None else m.detach() for m in exp_avgs]
-    exp_avg_sqs = [None] * n if exp_avg_sqs is None else [None if v is None else v.detach() for v in exp_avg_sqs]
-    return tensors, roles, exp_avgs, exp_avg_sqs
 
 
 def mcmc_relocation_plan(opacity: torch.Tensor, uniforms: torch.Tensor, *, min_opacity: float = 0.005, raw: bool = True, return_weights: bool = False):
@@ -882,23 +886,12 @@ def mcmc_relocate_tensors_(plan, tensors, roles, exp_avgs=None, exp_avg_sqs=None
     anything is written: the result does not depend on scheduling.  Works on the tensors' storage like an optimizer step (nothing is recorded
     in autograd).  Returns None."""
     src, count = plan[0], plan[1]
-    tensors, roles, exp_avgs, exp_avg_sqs = _mcmc_lists(tensors, roles, exp_avgs, exp_avg_sqs)
+    tensors, roles, exp_avgs, exp_avg_sqs = _row_lists(tensors, roles, _C.MCMC_ROLES, exp_avgs, exp_avg_sqs)
     _C.mcmc_relocate_apply(src, count, tensors, roles, exp_avgs, exp_avg_sqs, _f32(min_opacity), raw, reset_dead_moments)
 
 
 def _mcmc_groups(who, optimizer, names):
-    role_of = dict(zip(names, ("opacity", "scaling")))
-    groups = list(optimizer.param_groups)
-    params, roles, ms, vs = [], [], [], []
-    for group in groups:
-        if len(group["params"]) != 1 or "name" not in group:
-            raise ValueError(f"{who}: every group must hold one tensor and carry a \"name\"")
-        p = group["params"][0]
-        state = optimizer.state.get(p, {})
-        params.append(p)
-        roles.append(role_of.get(group["name"], "plain"))
-        ms.append(state.get("exp_avg"))
-        vs.append(state.get("exp_avg_sq"))
+    groups, params, roles, ms, vs = _named_groups(who, optimizer, dict(zip(names, ("opacity", "scaling"))))
     if roles.count("opacity") != 1 or roles.count("scaling") != 1:
         raise ValueError(f"{who}: the optimizer needs exactly one group named {names[0]!r} and one named {names[1]!r}")
     return groups, params, roles, ms, vs
@@ -934,7 +927,7 @@ def mcmc_add_tensors(plan, tensors, roles, exp_avgs=None, exp_avg_sqs=None, *, m
     stores them) and zero moments; row P + j is a copy of row src[j] with that row's new opacity and scaling and zero moments.  tensors, roles
     and moments as for mcmc_relocate_tensors_ (non-contiguous inputs are made contiguous); the inputs are not modified."""
     src, count = plan[0], plan[1]
-    tensors, roles, exp_avgs, exp_avg_sqs = _mcmc_lists(tensors, roles, exp_avgs, exp_avg_sqs)
+    tensors, roles, exp_avgs, exp_avg_sqs = _row_lists(tensors, roles, _C.MCMC_ROLES, exp_avgs, exp_avg_sqs)
     return _C.mcmc_add_apply(src, count, tensors, roles, exp_avgs, exp_avg_sqs, _f32(min_opacity), raw)
 
 

@@ -267,8 +267,30 @@ def test_apply_hand_written_plans_and_the_output_order(P, which):
         assert all(torch.equal(a, b) for a, b in zip(got[0], got2[0]))
 
 
-def test_scan_offsets_and_counts():
-    P = 4097
+def test_apply_more_than_eight_tensors():
+    """Nine tensors: the packing loop's second launch.  The five of the hand-written plans and four more plain ones of 1, 2, 4 and 5 floats per
+    row (one 16-byte path among them), two of them with moments and two without."""
+    P = 257
+    d = model(P)[0]
+    plan = HAND_PLANS["every-value"](P).astype(np.uint8)
+    S = trd.plan_rows(plan)[2]
+    noise = d["noise"][:2 * S.size]
+    index = np.arange(P, dtype=np.float32)[:, None]
+    rng = np.random.default_rng(9)
+    more = [rng.standard_normal((P, w)).astype(np.float32) for w in (1, 2, 4, 5)]
+    more_m = [rng.standard_normal(t.shape).astype(np.float32) if k % 2 == 0 else None for k, t in enumerate(more)]
+    more_v = [None if m is None else rng.uniform(0.5, 1.5, m.shape).astype(np.float32) for m in more_m]
+    tensors, roles = [d["xyz"], d["scaling"], d["rotation"], index, d["f_rest"]] + more, [1, 2, 3, 0, 0, 0, 0, 0, 0]
+    ms = [d["m_xyz"], None, d["m_rotation"], index + 0.5, d["m_f_rest"]] + more_m
+    vs = [d["v_xyz"], None, d["v_rotation"], index + 0.25, d["v_f_rest"]] + more_v
+    up = lambda arrays: [None if a is None else dev(a) for a in arrays]
+    got = dgr().densify_tensors(torch.from_numpy(plan).cuda(), up(tensors), roles, up(ms), up(vs), dev(noise))
+    assert len(got[0]) == 9
+    check_apply(plan, tensors, roles, ms, vs, noise, got)
+
+
+@pytest.mark.parametrize("P", [4097, 349_526])   # 349 526: the smallest P with ceil(3 P / 4096) = 257 tiles, a thread of the tile prefix owns two
+def test_scan_offsets_and_counts(P):
     plan = ((np.arange(P) * 5 + 3) % 8).astype(np.uint8)
     offsets, counts = _C().densify_scan(torch.from_numpy(plan).cuda())
     K, C, S = trd.plan_rows(plan)

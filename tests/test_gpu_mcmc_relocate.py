@@ -52,7 +52,7 @@ _inputs = {}
 def inputs(P, raw):
     """the yardstick's inputs of a size, generated once and never modified (the tests work on clones on the device)"""
     if (P, raw) not in _inputs:
-        _inputs[(P, raw)] = trr.model_inputs(P, raw)
+        _inputs[(P, raw)] = trr.model_inputs(P, raw, names=trr.NAMES if P <= max(trr.SIZES) else ("opacity", "scaling"))   # (MANY_TILES: sampling only)
     return _inputs[(P, raw)]
 
 
@@ -64,8 +64,10 @@ def on_gpu(inp):
 
 # ---- 1. sampling ---------------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("raw", [False, True])
-@pytest.mark.parametrize("P", trr.SIZES)
+MANY_TILES = 524_289   # 257 tiles of 2048 rows: a thread of the tile prefix owns two tile sums
+
+
+@pytest.mark.parametrize("P,raw", [(P, raw) for P in trr.SIZES for raw in (False, True)] + [(MANY_TILES, False)])
 def test_sampling_is_exact(P, raw):
     inp = inputs(P, raw)
     o, u = inp["opacity"].cuda(), inp["uniforms"].cuda()

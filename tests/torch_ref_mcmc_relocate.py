@@ -251,10 +251,11 @@ def check_opacities(opacity, raw, min_opacity=MIN_OPACITY, sources_below=MAX_SOU
         assert bool((o[o > f32(min_opacity)] <= sources_below).all()), "a source opacity above the tolerance tests' limit"
 
 
-def model_inputs(P, raw, seed=40, dead_every=9):
+def model_inputs(P, raw, seed=40, dead_every=9, names=NAMES):
     """dict name -> float32 tensor (P, *TRAILING[name]) of a model in its stored form (raw: logits and log-scales), with about one row in
     dead_every dead (opacity in [0, 0.004], an exact 0 among them) and the live opacities in [0.01, 0.99]; plus "uniforms" (P,) in [0, 1) and,
-    per name, the moments "m_" + name and "v_" + name (non-zero everywhere).  A smaller P is not a prefix of a larger one."""
+    per name, the moments "m_" + name and "v_" + name (non-zero everywhere).  A smaller P is not a prefix of a larger one.  names: the tensors
+    to make (a test of the sampling alone at a large P needs the opacity only)."""
     rng = np.random.default_rng(seed + 7 * P + int(raw))
     o = rng.uniform(0.01, 0.99, P)
     dead = rng.integers(0, dead_every, P) == 0
@@ -267,12 +268,16 @@ def model_inputs(P, raw, seed=40, dead_every=9):
     s = np.exp(rng.uniform(-6.0, 1.0, (P, 3))).astype(np.float32)
     out = {}
     for name, shape in TRAILING.items():
+        if name not in names:
+            continue
         out[name] = torch.from_numpy(rng.standard_normal((P,) + shape).astype(np.float32))
     with np.errstate(all="ignore"):
         logit = (np.log(o.astype(np.float64)) - np.log1p(-o.astype(np.float64))).astype(np.float32)
     out["opacity"] = torch.from_numpy(logit if raw else o).reshape(P, 1)
     out["scaling"] = torch.from_numpy(np.log(s.astype(np.float64)).astype(np.float32) if raw else s)
     for name, shape in TRAILING.items():
+        if name not in names:
+            continue
         out["m_" + name] = torch.from_numpy(rng.uniform(0.5, 1.5, (P,) + shape).astype(np.float32) * np.where(rng.integers(0, 2, (P,) + shape) == 0, -1, 1).astype(np.float32))
         out["v_" + name] = torch.from_numpy(rng.uniform(0.5, 1.5, (P,) + shape).astype(np.float32))
     out["uniforms"] = torch.from_numpy(rng.uniform(0.0, 1.0, P).astype(np.float32)).clamp(max=float(np.nextafter(np.float32(1), np.float32(0))))
