@@ -25,7 +25,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "stopthepop-rasterization_amd"))
 from diff_gaussian_rasterization import (CullingSettings, ExtendedSettings, GaussianRasterizationSettings,  # noqa: E402
                                          GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, SparseGaussianAdam, compute_relocation,
-                                         densification_stats_, densify_and_prune, densify_plan, mcmc_add_new, mcmc_add_noise_, mcmc_relocate_, photometric_loss, scenes)
+                                         densification_stats_, densify_and_prune, densify_plan, mcmc_add_new, mcmc_add_noise_, mcmc_relocate_, scenes, training_loss, training_terms)
 
 
 def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, scaling_modifier: float = 1.0,
@@ -172,11 +172,15 @@ def main(argv=None):
                     help="add W * mean |alpha - target alpha| to the loss: mask supervision on the rasterizer's alpha output")
     ap.add_argument("--depth-weight", type=float, default=0.0, metavar="W",
                     help="add W * mean |invdepth - target invdepth| to the loss: depth regularisation on the rasterizer's inverse-depth output "
-                         "(upstream's `-d` monocular depth priors; INTEGRATION.md section 3k)")
+                         "(upstream's `-d` monocular depth priors; INTEGRATION.md section 3k), as the third term of the fused training_loss "
+                         "(INTEGRATION.md section 3s)")
+    ap.add_argument("--exposure", action="store_true",
+                    help="learn a (3, 4) exposure, initialised to the identity, with its own Adam: the render goes through it inside the fused "
+                         "training_loss, the only route by which it gets a gradient without a torch matmul (INTEGRATION.md section 3s)")
     ap.add_argument("--optimizer", default="adam", choices=["adam", "sparse_adam"],
                     help="sparse_adam: SparseGaussianAdam, one fused launch that steps only the Gaussians visible in the frame (INTEGRATION.md section 3i)")
     ap.add_argument("--loss", default="l1", choices=["l1", "l1_ssim"],
-                    help="l1_ssim: the trainers' 0.8 * L1 + 0.2 * (1 - SSIM) from the fused photometric_loss (INTEGRATION.md section 3j)")
+                    help="l1_ssim: the trainers' 0.8 * L1 + 0.2 * (1 - SSIM) from the fused training_loss (INTEGRATION.md sections 3j, 3s)")
     ap.add_argument("--strategy", default="none", choices=["none", "mcmc", "adc"],
                     help="mcmc: 3DGS-MCMC -- the fused position noise after every optimizer step, dead Gaussians relocated every 10 iterations with "
                          "compute_relocation, and the opacity / scale L1 regularisers (INTEGRATION.md section 3l).  adc: 3DGS adaptive density control "
@@ -238,6 +242,10 @@ def main(argv=None):
     else:
         opt = torch.optim.Adam([*model.feature_groups(2e-2), {"params": [model._opacity], "lr": 5e-2},
                                 {"params": [model._xyz, model._scaling, model._rotation], "lr": 0.0}])
+    exposure = exposure_opt = None
+    if args.exposure:   # upstream's per-image exposure (one image here), with its own optimizer as there
+        exposure = torch.eye(3, 4, device=dev).requires_grad_(True)
+        exposure_opt = torch.optim.Adam([exposure], lr=1e-3)
     train_cfg = splat_config(args.config)
     train_cfg._alpha = masked
     train_cfg._invdepth = with_depth
@@ -262,18 +270,28 @@ def main(argv=None):
             model._opacity[::50] = math.log(0.002 / 0.998)
     for it in range(args.iters):
         out = render(cam, model, bg, train_cfg)
-        if args.loss == "l1_ssim":   # both terms from one fused kernel pair; the printed figure is this loss then
-            loss = photometric_loss(out["render"], target, lambda_dssim=0.2)
+        extras = {}   # what the fused loss takes beside image and target: the exposure and the depth term ride in its kernels
+        if exposure is not None:
+            extras["exposure"] = exposure
+        if with_depth:   # (the inverse depth is an output of the same autograd node: no second render)
+            extras.update(invdepth=out["invdepth"], mono_invdepth=target_invdepth)
+        if args.loss == "l1_ssim":   # all terms from one fused kernel pair; the printed figure is this loss then
+            loss = training_loss(out["render"], target, lambda_dssim=0.2, depth_weight=args.depth_weight, **extras)
+        elif extras:
+            terms = training_terms(out["render"], target, **extras)
+            loss = terms[0] + args.depth_weight * terms[2]
         else:
             loss = (out["render"] - target).abs().mean()
         if masked:   # alpha is an output of the same autograd node: one backward serves both terms
             loss = loss + args.mask_weight * (out["alpha"] - target_alpha).abs().mean()
-        if with_depth:   # (and so is the inverse depth: no second render)
-            loss = loss + args.depth_weight * (out["invdepth"] - target_invdepth).abs().mean()
         if mcmc:   # upstream's opacity_reg and scale_reg: L1 pressure that lets unneeded Gaussians die, to be relocated
             loss = loss + 0.01 * model.get_opacity.mean() + 0.01 * model.get_scaling.mean()
         opt.zero_grad(set_to_none=True)
+        if exposure_opt is not None:
+            exposure_opt.zero_grad(set_to_none=True)
         loss.backward()
+        if exposure_opt is not None:
+            exposure_opt.step()
         grad2d = out["viewspace_points"].grad  # what densification accumulates
         vis = out["visibility_filter"]
         if adc:   # one kernel, no mask indexing and no synchronisation: the forward's radii are the visibility
@@ -340,6 +358,8 @@ def main(argv=None):
         print(f"mcmc: relocated {int(relocated)} Gaussians in {relocations} relocation steps (opacity <= 0.005), position noise after each of {args.iters} steps")
         if fused_mcmc:
             print(f"mcmc: {added} Gaussians added towards cap_max = {cap_max}, {model.get_xyz.shape[0]} at the end")
+    if exposure is not None:
+        print(f"exposure: largest deviation from the identity {float((exposure.detach() - torch.eye(3, 4, device=dev)).abs().max()):.5f} after {args.iters} steps of its Adam")
     if args.absgrad:
         print(f"densification statistic, mean over Gaussians: signed {float(stat_signed.mean()):.3e}, absolute {float(stat_abs.mean()):.3e} "
               f"(absolute >= signed for {float((stat_abs >= stat_signed * (1 - 1e-5)).float().mean()) * 100:.1f} % of them)")

@@ -563,6 +563,50 @@ int stp_photometric_forward(int planes, int H, int W, const float* image, const 
 int stp_photometric_backward(int planes, int H, int W, const float* image, const float* target, const float* maps,
                              const float* dL_dout2 /* device, 2 floats */, float* dL_dimage, void* stream);
 
+/* Extension (not in the reference): the loss a 3DGS trainer's step really runs, in the kernels above -- the photometric terms of the
+   EXPOSED, CLAMPED and MASKED render plus the inverse-depth regulariser:
+       v_j = sum_i x_i E[i][j] + E[j][3]   (the row index is the INPUT channel: upstream's matmul(image.permute(1, 2, 0), E[:3, :3]) + E[:3, 3]),
+             evaluated as ONE float32 chain  fma(E[2][j], x_2, fma(E[1][j], x_1, fma(E[0][j], x_0, E[j][3])))
+       v_j clamped to [0, 1] when `clamp` (the gradient passes where 0 <= v_j <= 1),   x''_j = v_j * alpha_mask
+       out3[0] = mean |x'' - y|,  out3[1] = mean SSIM(x'', y)  as above; the window's zero padding applies to x'' (a pixel outside the
+                 image is 0, not E[j][3])
+       out3[2] = mean |(invdepth - mono_invdepth) * depth_mask| over the depth_planes * H * W depth elements (exactly 0.0 without them)
+   Every member of StpTrainingLoss is optional (NULL / 0) and may be given alone; invdepth and mono_invdepth come together.  `exposure`
+   is 3 x 4 floats (exposure_batched = 0) or one 3 x 4 per image of the batch (1: planes / 3 of them) and needs planes % 3 == 0, the
+   planes being the (B, 3, H, W) channels; alpha_mask is one H x W plane (alpha_mask_batched = 0) or one per image (1: planes / channels
+   of them, `channels` = planes per image, 0 = 3).  The backward gives
+       dL/dx_i = sum_j E[i][j] g'_j,   g'_j = g''_j * alpha_mask * [clamp passes],  g''_j = the photometric dL/dx''_j above
+       dL/dE[i][j] = sum_p x_i g'_j,  dL/dE[j][3] = sum_p g'_j   (dL_dexposure, laid out like exposure; NULL = not wanted)
+       dL/dinvdepth = (g2 / n_d) sign((d - m) mask) mask          (dL_dinvdepth; NULL = not wanted)
+   with (g0, g1, g2) = dL_dout3 read from device memory.  All sums in a fixed order without atomics.  With `extras` NULL (or all of
+   its members 0) the calls run the kernels of stp_photometric_forward / _backward on out3[0 .. 1] and write out3[2] = 0.
+   `workspace`: stp_training_loss_workspace_floats floats, used by the forward and (with dL_dexposure) by the backward.
+   Each call returns the kernel launches made (forward 2; backward 1, or 2 with dL_dexposure; 0 when planes, H or W is 0: nothing is
+   touched), or a negative StpStatus.  Refused BEFORE anything is launched (STP_ERR_INVALID_ARGUMENT): a negative size or count,
+   planes * H * W or depth_planes * H * W >= 2^31, a null required pointer, exposure with planes % 3 != 0 or channels != 3, planes not a
+   multiple of channels, invdepth without mono_invdepth or the reverse, a depth_mask or depth_planes > 0 without them, depth_planes == 0
+   with them, clamp or a _batched flag that is not 0 or 1, null maps in the backward, dL_dexposure without exposure, dL_dinvdepth without
+   invdepth, dL_dexposure without workspace. */
+typedef struct StpTrainingLoss {
+    const float* exposure;       /* 3 x 4, or (planes / 3) x 3 x 4 */
+    const float* alpha_mask;     /* H x W, or (planes / channels) x H x W */
+    const float* invdepth;       /* depth_planes x H x W */
+    const float* mono_invdepth;  /* depth_planes x H x W */
+    const float* depth_mask;     /* depth_planes x H x W, or NULL */
+    int32_t clamp;
+    int32_t exposure_batched;
+    int32_t alpha_mask_batched;
+    int32_t channels;            /* planes per image (0 = 3) */
+    int32_t depth_planes;
+} StpTrainingLoss;
+size_t stp_training_loss_workspace_floats(int planes, int H, int W, int depth_planes);
+int stp_training_loss_forward(int planes, int H, int W, const float* image, const float* target, const StpTrainingLoss* extras,
+                              float* out3 /* device: L1, SSIM, depth L1 */, float* maps /* 3*planes*H*W floats, or NULL */,
+                              float* workspace, void* stream);
+int stp_training_loss_backward(int planes, int H, int W, const float* image, const float* target, const StpTrainingLoss* extras,
+                               const float* maps, const float* dL_dout3 /* device, 3 floats */, float* dL_dimage,
+                               float* dL_dexposure /* or NULL */, float* dL_dinvdepth /* or NULL */, float* workspace, void* stream);
+
 /* Sizes of the three scratch buffers (the reference's `required<State>()`, rasterizer_impl.h:68-75). */
 size_t stp_geometry_buffer_size(int P, const StpSettings* settings);
 size_t stp_geometry_buffer_size_stash(int P, const StpSettings* settings); /* of a forward with stp_set_forward_sh_stash: the above + the nine planes of P floats */

@@ -1,4 +1,4 @@
-// stp_bind_train.h -- the training kernels beside the rasterizer: sparse Adam, 3DGS-MCMC, nearest neighbours, densification, the photometric loss.
+// stp_bind_train.h -- the training kernels beside the rasterizer: sparse Adam, 3DGS-MCMC, nearest neighbours, densification, the photometric and the training loss.
 // All run on the caller's current stream.  What is wrong with the tensors themselves is refused first, where they live last (stp_tensor_checks.h).
 #pragma once
 
@@ -520,21 +520,30 @@ densify_apply(const torch::Tensor& plan_in, const torch::Tensor& offsets, const 
 // == the fused photometric loss (extension, include/stp_raster.h: stp_photometric_forward / _backward; photometric_loss and fused_ssim in
 // __init__.py).  image, target: float32 (C, H, W) or (B, C, H, W) on one GPU, made contiguous here.
 struct PhotometricShape { int planes, H, W; };
-PhotometricShape photometric_check(const char* who, const torch::Tensor& image, const torch::Tensor& target)
+// what is wrong with image and target themselves, before where they live
+void photometric_tensor_check(const char* who, const torch::Tensor& image, const torch::Tensor& target)
 {
-    require(g_api.photometric_forward, who);
-    require(g_api.photometric_backward, who);
-    require(g_api.photometric_workspace_floats, who);
     TORCH_CHECK(image.defined() && target.defined(), who, ": image and target must be tensors");
     TORCH_CHECK(image.scalar_type() == torch::kFloat32, "expected float32 tensor, got ", image.scalar_type());
     TORCH_CHECK(target.scalar_type() == torch::kFloat32, "expected float32 tensor, got ", target.scalar_type());
     TORCH_CHECK(image.dim() == 3 || image.dim() == 4, who, ": image must be (C, H, W) or (B, C, H, W), got ", image.dim(), " dimensions");
     TORCH_CHECK(image.sizes() == target.sizes(), who, ": image has shape ", image.sizes(), ", target has ", target.sizes());
     TORCH_CHECK(target.device() == image.device(), "expected all tensors on ", image.device(), ", got one on ", target.device());
+}
+PhotometricShape photometric_shape(const char* who, const torch::Tensor& image)
+{
     TORCH_CHECK(image.is_cuda(), GPU_ONLY);
     const int64_t H = image.size(-2), W = image.size(-1), planes = H * W > 0 ? image.numel() / (H * W) : 0;
     TORCH_CHECK(image.numel() < (1ll << 31), who, ": ", image.numel(), " elements >= 2^31");
     return PhotometricShape{(int)planes, (int)H, (int)W};
+}
+PhotometricShape photometric_check(const char* who, const torch::Tensor& image, const torch::Tensor& target)
+{
+    require(g_api.photometric_forward, who);
+    require(g_api.photometric_backward, who);
+    require(g_api.photometric_workspace_floats, who);
+    photometric_tensor_check(who, image, target);
+    return photometric_shape(who, image);
 }
 
 // -> (out2 = [mean |image - target|, mean SSIM], the three derivative maps (3, *image.shape) or an undefined tensor)
@@ -580,5 +589,144 @@ torch::Tensor photometric_backward(const torch::Tensor& image_in, const torch::T
     checked(g_api.photometric_backward(s.planes, s.H, s.W, image.data_ptr<float>(), target.data_ptr<float>(), maps.data_ptr<float>(),
                                        grad_out2.data_ptr<float>(), dL_dimage.data_ptr<float>(), current_stream(image.device())));
     return dL_dimage;
+}
+
+// == the training loss (extension, include/stp_raster.h: stp_training_loss_forward / _backward; training_terms and training_loss in
+// __init__.py): the photometric terms of the exposed, clamped and masked image plus the inverse-depth term.  Every extra is optional.
+using OptTensor = c10::optional<torch::Tensor>;
+struct TrainingExtras {
+    PhotometricShape s;
+    StpTrainingLoss pod{};
+    torch::Tensor exposure, alpha_mask, invdepth, mono_invdepth, depth_mask; // contiguous; undefined = not given
+};
+// an (H, W), (1, H, W) or (B, 1, H, W) plane set beside the image: its contiguous form and the number of planes
+int64_t check_planes(const char* who, const char* name, const torch::Tensor& t, const torch::Tensor& image, const bool allow_2d)
+{
+    check_float(who, name, t);
+    const int64_t H = image.size(-2), W = image.size(-1);
+    const bool dims = (allow_2d && t.dim() == 2) || (t.dim() == 3 && t.size(0) == 1) || (t.dim() == 4 && t.size(1) == 1);
+    TORCH_CHECK(dims && t.size(-2) == H && t.size(-1) == W, who, ": ", name, " must be ", allow_2d ? "(H, W), " : "", "(1, H, W) or (B, 1, H, W) with the image's H = ", H,
+                ", W = ", W, ", got ", t.sizes());
+    return t.dim() == 4 ? t.size(0) : 1;
+}
+TrainingExtras training_check(const char* who, const torch::Tensor& image, const torch::Tensor& target, const OptTensor& exposure, const bool clamp,
+                              const OptTensor& alpha_mask, const OptTensor& invdepth, const OptTensor& mono_invdepth, const OptTensor& depth_mask)
+{
+    require(g_api.training_loss_forward, who);
+    require(g_api.training_loss_backward, who);
+    require(g_api.training_loss_workspace_floats, who);
+    TrainingExtras x;
+    photometric_tensor_check(who, image, target); // (3j's refusals, in 3j's words)
+    const int64_t C = image.size(-3), B = image.dim() == 4 ? image.size(0) : 1;
+    x.pod.clamp = clamp ? 1 : 0;
+    x.pod.channels = (int32_t)std::max<int64_t>(C, 1);
+    if (exposure.has_value()) {
+        check_float(who, "exposure", *exposure);
+        TORCH_CHECK(C == 3, who, ": exposure needs an image of three channels, got C = ", C);
+        const bool one = exposure->dim() == 2 && exposure->size(0) == 3 && exposure->size(1) == 4;
+        const bool per_image = exposure->dim() == 3 && image.dim() == 4 && exposure->size(0) == B && exposure->size(1) == 3 && exposure->size(2) == 4;
+        TORCH_CHECK(one || per_image, who, ": exposure must be (3, 4) or, with a (B, 3, H, W) image, (B, 3, 4), got ", exposure->sizes());
+        x.exposure = exposure->contiguous();
+        x.pod.exposure = x.exposure.data_ptr<float>();
+        x.pod.exposure_batched = per_image ? 1 : 0;
+    }
+    if (alpha_mask.has_value()) {
+        const int64_t planes = check_planes(who, "alpha_mask", *alpha_mask, image, true);
+        TORCH_CHECK(alpha_mask->dim() != 4 || (image.dim() == 4 && planes == B), who, ": alpha_mask of ", planes, " images beside an image batch of ", B);
+        x.alpha_mask = alpha_mask->contiguous();
+        x.pod.alpha_mask = x.alpha_mask.data_ptr<float>();
+        x.pod.alpha_mask_batched = alpha_mask->dim() == 4 ? 1 : 0;
+    }
+    TORCH_CHECK(invdepth.has_value() == mono_invdepth.has_value(), who, ": invdepth and mono_invdepth come together or not at all");
+    TORCH_CHECK(invdepth.has_value() || !depth_mask.has_value(), who, ": depth_mask without invdepth");
+    if (invdepth.has_value()) {
+        const int64_t planes = check_planes(who, "invdepth", *invdepth, image, false);
+        check_planes(who, "mono_invdepth", *mono_invdepth, image, false);
+        TORCH_CHECK(mono_invdepth->sizes() == invdepth->sizes(), who, ": invdepth has shape ", invdepth->sizes(), ", mono_invdepth has ", mono_invdepth->sizes());
+        x.invdepth = invdepth->contiguous();
+        x.mono_invdepth = mono_invdepth->contiguous();
+        x.pod.depth_planes = (int32_t)planes;
+        if (depth_mask.has_value()) {
+            check_planes(who, "depth_mask", *depth_mask, image, false);
+            TORCH_CHECK(depth_mask->sizes() == invdepth->sizes(), who, ": invdepth has shape ", invdepth->sizes(), ", depth_mask has ", depth_mask->sizes());
+                x.depth_mask = depth_mask->contiguous();
+        }
+        if (x.invdepth.numel() > 0) {
+            x.pod.invdepth = x.invdepth.data_ptr<float>();
+            x.pod.mono_invdepth = x.mono_invdepth.data_ptr<float>();
+            if (x.depth_mask.defined()) x.pod.depth_mask = x.depth_mask.data_ptr<float>();
+        } else {
+            x.pod.depth_planes = 0;
+        }
+    }
+    // where they live, last
+    x.s = photometric_shape(who, image);
+    const OptTensor* extras[5] = {&exposure, &alpha_mask, &invdepth, &mono_invdepth, &depth_mask};
+    static const char* const names[5] = {"exposure", "alpha_mask", "invdepth", "mono_invdepth", "depth_mask"};
+    for (int k = 0; k < 5; k++)
+        if (extras[k]->has_value()) check_device(who, names[k], **extras[k], image);
+    return x;
+}
+
+// -> (out3 = [mean |x'' - target|, mean SSIM(x'', target), mean |(invdepth - mono_invdepth) depth_mask|], the maps (3, *image.shape) or undefined)
+std::tuple<torch::Tensor, torch::Tensor> training_loss_forward(const torch::Tensor& image_in, const torch::Tensor& target_in, const OptTensor& exposure, const bool clamp,
+                                                               const OptTensor& alpha_mask, const OptTensor& invdepth, const OptTensor& mono_invdepth,
+                                                               const OptTensor& depth_mask, const bool want_maps)
+{
+    need_library();
+    static const char* const who = "training_loss_forward";
+    const TrainingExtras x = training_check(who, image_in, target_in, exposure, clamp, alpha_mask, invdepth, mono_invdepth, depth_mask);
+    const torch::Tensor image = image_in.contiguous(), target = target_in.contiguous();
+    const auto opt = image.options();
+    const c10::hip::HIPGuard guard(image.device().index());
+    torch::Tensor out3 = torch::empty({3}, opt), maps;
+    if (image.numel() == 0) { // the means of nothing, as torch's
+        out3.fill_(std::numeric_limits<float>::quiet_NaN());
+        if (want_maps) maps = torch::empty({3, 0}, opt);
+        return {out3, maps};
+    }
+    if (want_maps) {
+        std::vector<int64_t> shape{3};
+        for (const int64_t d : image.sizes()) shape.push_back(d);
+        maps = torch::empty(shape, opt);
+    }
+    torch::Tensor workspace = torch::empty({(int64_t)g_api.training_loss_workspace_floats(x.s.planes, x.s.H, x.s.W, x.pod.depth_planes)}, opt);
+    checked(g_api.training_loss_forward(x.s.planes, x.s.H, x.s.W, image.data_ptr<float>(), target.data_ptr<float>(), &x.pod, out3.data_ptr<float>(),
+                                        want_maps ? maps.data_ptr<float>() : nullptr, workspace.data_ptr<float>(), current_stream(image.device())));
+    return {out3, maps};
+}
+
+// -> (dL/dimage, dL/dexposure (exposure's shape) or undefined, dL/dinvdepth (invdepth's shape) or undefined); grad_out3: three floats on the device
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> training_loss_backward(const torch::Tensor& image_in, const torch::Tensor& target_in, const OptTensor& exposure,
+                                                                               const bool clamp, const OptTensor& alpha_mask, const OptTensor& invdepth,
+                                                                               const OptTensor& mono_invdepth, const OptTensor& depth_mask, const torch::Tensor& maps,
+                                                                               const torch::Tensor& grad_out3_in, const bool want_exposure, const bool want_invdepth)
+{
+    need_library();
+    static const char* const who = "training_loss_backward";
+    const TrainingExtras x = training_check(who, image_in, target_in, exposure, clamp, alpha_mask, invdepth, mono_invdepth, depth_mask);
+    const torch::Tensor image = image_in.contiguous(), target = target_in.contiguous();
+    TORCH_CHECK(maps.defined() && maps.is_cuda() && maps.device() == image.device() && maps.scalar_type() == torch::kFloat32 && maps.is_contiguous() &&
+                    maps.numel() == 3 * image.numel(),
+                who, ": maps must be the contiguous float32 tensor of 3 * image.numel() elements a forward with want_maps returned");
+    TORCH_CHECK(grad_out3_in.defined() && grad_out3_in.is_cuda() && grad_out3_in.device() == image.device() && grad_out3_in.numel() == 3,
+                who, ": grad_out3 must hold three elements on the device of image");
+    TORCH_CHECK(!want_exposure || x.exposure.defined(), who, ": a gradient for an exposure that was not given");
+    TORCH_CHECK(!want_invdepth || x.invdepth.defined(), who, ": a gradient for an invdepth that was not given");
+    const torch::Tensor grad_out3 = grad_out3_in.to(torch::kFloat32).contiguous();
+    const c10::hip::HIPGuard guard(image.device().index());
+    torch::Tensor dL_dimage = torch::empty(image.sizes(), image.options()), dL_dexposure, dL_dinvdepth, workspace;
+    if (want_exposure) dL_dexposure = torch::empty(x.exposure.sizes(), image.options());
+    if (want_invdepth) dL_dinvdepth = torch::empty(x.invdepth.sizes(), image.options());
+    if (image.numel() == 0) {
+        if (want_exposure) dL_dexposure.zero_();
+        return {dL_dimage, dL_dexposure, dL_dinvdepth};
+    }
+    if (want_exposure) workspace = torch::empty({(int64_t)g_api.training_loss_workspace_floats(x.s.planes, x.s.H, x.s.W, x.pod.depth_planes)}, image.options());
+    checked(g_api.training_loss_backward(x.s.planes, x.s.H, x.s.W, image.data_ptr<float>(), target.data_ptr<float>(), &x.pod, maps.data_ptr<float>(),
+                                         grad_out3.data_ptr<float>(), dL_dimage.data_ptr<float>(), want_exposure ? dL_dexposure.data_ptr<float>() : nullptr,
+                                         want_invdepth && x.pod.invdepth ? dL_dinvdepth.data_ptr<float>() : nullptr,
+                                         want_exposure ? workspace.data_ptr<float>() : nullptr, current_stream(image.device())));
+    return {dL_dimage, dL_dexposure, dL_dinvdepth};
 }
 } // namespace

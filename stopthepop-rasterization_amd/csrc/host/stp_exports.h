@@ -55,7 +55,10 @@
     X(densify_apply, false, "the densification kernels")                                   \
     X(photometric_workspace_floats, false, "the photometric loss")                         \
     X(photometric_forward, false, "the photometric loss")                                  \
-    X(photometric_backward, false, "the photometric loss")
+    X(photometric_backward, false, "the photometric loss")                                 \
+    X(training_loss_workspace_floats, false, "the training loss")                          \
+    X(training_loss_forward, false, "the training loss")                                   \
+    X(training_loss_backward, false, "the training loss")
 
 namespace {
 struct Api {

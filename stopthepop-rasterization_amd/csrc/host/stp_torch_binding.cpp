@@ -35,6 +35,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("densify_apply", &densify_apply);
     m.def("photometric_forward", &photometric_forward);
     m.def("photometric_backward", &photometric_backward);
+    m.def("training_loss_forward", &training_loss_forward);
+    m.def("training_loss_backward", &training_loss_backward);
     m.def("scratch_generation", &scratch_generation);
     m.def("check_scratch", &check_scratch);
     m.def("release_scratch", &release_scratch);

@@ -678,4 +678,68 @@ int stp_photometric_backward(int planes, int H, int W, const float* image, const
     return launches;
 }
 
+// the extras of a training-loss call in their final form (*x): 0 = fine, negative = refused.  Looks at sizes and pointers only
+static int check_training_extras(const char* who, int planes, int H, int W, const StpTrainingLoss* extras, StpTrainingLoss* x)
+{
+    *x = extras ? *extras : StpTrainingLoss{};
+    const std::string w = std::string(who) + ": ";
+    for (const int32_t flag : {x->clamp, x->exposure_batched, x->alpha_mask_batched})
+        if (flag != 0 && flag != 1) return fail(STP_ERR_INVALID_ARGUMENT, w + "clamp, exposure_batched and alpha_mask_batched must be 0 or 1");
+    if (x->channels < 0 || x->depth_planes < 0) return fail(STP_ERR_INVALID_ARGUMENT, w + "negative size");
+    if (x->channels == 0) x->channels = 3;
+    if (x->exposure && (x->channels != 3 || planes % 3 != 0))
+        return fail(STP_ERR_INVALID_ARGUMENT, w + "exposure needs three channels per image, got planes = " + std::to_string(planes) + ", channels = " + std::to_string(x->channels));
+    if (x->alpha_mask && planes % x->channels != 0)
+        return fail(STP_ERR_INVALID_ARGUMENT, w + "planes = " + std::to_string(planes) + " is no multiple of channels = " + std::to_string(x->channels));
+    if (planes % x->channels != 0) x->channels = 1; // (no per-image input: every plane is its own image)
+    if (!x->invdepth != !x->mono_invdepth) return fail(STP_ERR_INVALID_ARGUMENT, w + "invdepth and mono_invdepth come together or not at all");
+    if (!x->invdepth && (x->depth_mask || x->depth_planes > 0)) return fail(STP_ERR_INVALID_ARGUMENT, w + "depth_mask or depth_planes without invdepth");
+    if (x->invdepth && x->depth_planes == 0) return fail(STP_ERR_INVALID_ARGUMENT, w + "invdepth with depth_planes = 0");
+    if (x->invdepth && check_photometric_sizes(who, x->depth_planes, H, W) < 0) return STP_ERR_INVALID_ARGUMENT;
+    return 0;
+}
+
+size_t stp_training_loss_workspace_floats(int planes, int H, int W, int depth_planes)
+{
+    if (stp_photometric_workspace_floats(planes, H, W) == 0) return 0;
+    if (depth_planes < 0 || (depth_planes > 0 && stp_photometric_workspace_floats(depth_planes, H, W) == 0)) return 0; // (sizes the calls refuse)
+    return training_loss_workspace_floats(planes, H, W, depth_planes);
+}
+
+int stp_training_loss_forward(int planes, int H, int W, const float* image, const float* target, const StpTrainingLoss* extras, float* out3, float* maps,
+                              float* workspace, void* stream)
+{
+    static const char* const who = "stp_training_loss_forward";
+    const int work = check_photometric_sizes(who, planes, H, W);
+    if (work < 0) return work;
+    StpTrainingLoss x;
+    if (const int rc = check_training_extras(who, planes, H, W, extras, &x)) return rc;
+    if (work == 0) return 0;
+    if (!image || !target || !out3 || !workspace) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    hipError_t e;
+    const int launches = launch_training_loss_forward(planes, H, W, image, target, x, out3, maps, workspace, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "training loss forward launch");
+    return launches;
+}
+
+int stp_training_loss_backward(int planes, int H, int W, const float* image, const float* target, const StpTrainingLoss* extras, const float* maps,
+                               const float* dL_dout3, float* dL_dimage, float* dL_dexposure, float* dL_dinvdepth, float* workspace, void* stream)
+{
+    static const char* const who = "stp_training_loss_backward";
+    const int work = check_photometric_sizes(who, planes, H, W);
+    if (work < 0) return work;
+    StpTrainingLoss x;
+    if (const int rc = check_training_extras(who, planes, H, W, extras, &x)) return rc;
+    if (dL_dexposure && !x.exposure) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": dL_dexposure without exposure");
+    if (dL_dinvdepth && !x.invdepth) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": dL_dinvdepth without invdepth");
+    if (work == 0) return 0;
+    if (!maps) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null maps (a forward without maps cannot be differentiated)");
+    if (!image || !target || !dL_dout3 || !dL_dimage || (dL_dexposure && !workspace)) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    hipError_t e;
+    const int launches = launch_training_loss_backward(planes, H, W, image, target, x, maps, dL_dout3, dL_dimage, dL_dexposure, dL_dinvdepth, workspace,
+                                                       (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "training loss backward launch");
+    return launches;
+}
+
 } // extern "C"

@@ -332,6 +332,15 @@ int launch_photometric_forward(int planes, int H, int W, const float* image, con
                                hipStream_t st, hipError_t* err);
 int launch_photometric_backward(int planes, int H, int W, const float* image, const float* target, const float* maps, const float* dL_dout2,
                                 float* dL_dimage, hipStream_t st, hipError_t* err);
+// the training loss (stp_loss.hip) over arguments stp_training_loss_* have validated; `x` has every member in its final form (channels set,
+// depth_planes = 0 without invdepth).  Without any extra the forward is the photometric tile kernel itself.  The workspace: two partial
+// sums per colour workgroup, one per depth workgroup behind them (forward); 12 per (image, tile) workgroup (backward with dL_dexposure)
+size_t training_loss_workspace_floats(int planes, int H, int W, int depth_planes);
+int launch_training_loss_forward(int planes, int H, int W, const float* image, const float* target, const StpTrainingLoss& x, float* out3, float* maps,
+                                 float* workspace, hipStream_t st, hipError_t* err);
+int launch_training_loss_backward(int planes, int H, int W, const float* image, const float* target, const StpTrainingLoss& x, const float* maps,
+                                  const float* dL_dout3, float* dL_dimage, float* dL_dexposure, float* dL_dinvdepth, float* workspace, hipStream_t st,
+                                  hipError_t* err);
 
 // the 3-nearest-neighbour mean squared distance (stp_knn.hip) over arguments stp_knn_mean_dist2 has validated (P in [4, 2^31), a scratch of
 // knn_scratch_bytes(P) bytes, 16-byte aligned): returns the launches made (the library's sort counting as one), *err = the error that ended

@@ -28,6 +28,11 @@
 // Sums in a FIXED order, no atomics: a thread adds its four pixels, a butterfly adds inside each wave, the four waves are added in order
 // -> two floats per workgroup; ONE workgroup (photometric_sum_kernel) adds those rows, thread t the rows t, t + 256, ... in order, the
 // same tree after that, and divides by n.  Equal inputs give equal bits.
+//
+// The training loss (stp_training_loss_forward / _backward) is the same pair with the trainer's exposure, clamp, alpha mask and depth term:
+// variants of these kernels further down, under a comment of their own that states the colour transform's fixed chain
+//     v_j = fma(E[2][j], x_2, fma(E[1][j], x_1, fma(E[0][j], x_0, E[j][3])))
+// The three kernels of the plain call are not touched by them.
 #include "stp_internal.h"
 
 namespace stp {
@@ -230,6 +235,321 @@ __global__ void __launch_bounds__(LOSS_BLOCK) photometric_backward_kernel(const 
     }
 }
 
+// ---- the training loss: the same tiles with the colour transform, the clamp and the alpha mask in the staging, the depth term in the same
+// launch.  The kernels above are not touched (their registers, LDS and code are those of the plain photometric call); these are their
+// variants, and everything they add to the arithmetic is written with explicit fused multiply-adds and is never contracted.
+//     v_j = fma(E[2][j], x_2, fma(E[1][j], x_1, fma(E[0][j], x_0, E[j][3])))       (E row-major 3 x 4; the row index is the INPUT channel)
+//     clamp: v < 0 ? 0 : v > 1 ? 1 : v (a NaN stays)        x''_j = v_j * alpha_mask       a halo pixel outside the image: 0
+// Backward: a workgroup owns an (image, tile) and loops over the image's channels j with the same LDS; g''_j is the expression of
+// photometric_backward_kernel on (x''_j, y_j), g'_j = g''_j * alpha_mask where the clamp passes (0 <= v_j <= 1), else 0;
+//     dL/dx_i = fma(E[i][2], g'_2, fma(E[i][1], g'_1, fma(E[i][0], g'_0, 0)))
+// and, for dL/dE, four workgroup sums per channel (a thread: fma(x_i, g'_j, .) over its four pixels from 0, then block_sum) into 12 floats per
+// workgroup, which ONE workgroup (exposure_sum_kernel) adds in order per image.  The depth planes' tiles are extra workgroups behind the
+// colour ones: forward sum |(d - m) mask|, backward (g2 / n_d) sign((d - m) mask) mask.
+struct LossColour {
+    const float* exposure;   // 3 x 4 per image (stride exposure_stride floats: 0 or 12), or null
+    const float* alpha_mask; // H x W per image (stride mask_stride floats: 0 or H * W), or null
+    int exposure_stride, clamp, channels;
+    size_t mask_stride;
+};
+struct LossDepth { const float *invdepth, *mono, *mask; };
+
+__device__ __forceinline__ LossTile loss_tile_at(const uint32_t idx, const int tiles_x, const int tiles_y)
+{
+    const uint32_t per_plane = (uint32_t)tiles_x * (uint32_t)tiles_y;
+    const uint32_t plane = idx / per_plane, t = idx - plane * per_plane;
+    const uint32_t ty = t / (uint32_t)tiles_x, tx = t - ty * (uint32_t)tiles_x;
+    return LossTile{(int)plane, (int)tx * LOSS_TW, (int)ty * LOSS_TH};
+}
+
+__device__ __forceinline__ float clamp01(const float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
+
+// x''_j at pixel `pix` of the image whose first channel plane starts at `img` (E: that image's exposure or null, mk: its mask plane or null)
+__device__ __forceinline__ float exposed(const float* __restrict__ img, const size_t hw, const size_t pix, const int j, const float* __restrict__ E,
+                                         const int clamp, float* v_out)
+{
+    float v;
+    if (E) v = __fmaf_rn(E[8 + j], img[2 * hw + pix], __fmaf_rn(E[4 + j], img[hw + pix], __fmaf_rn(E[j], img[pix], E[4 * j + 3])));
+    else v = img[(size_t)j * hw + pix];
+    *v_out = v;
+    return clamp ? clamp01(v) : v;
+}
+
+// the depth term's part of a tile: sum |(d - m) mask| of the thread's four pixels
+__device__ __forceinline__ float depth_tile_sum(const LossDepth d, const LossTile t, const int H, const int W)
+{
+#pragma clang fp contract(off)
+    const int col = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * LOSS_ROWS;
+    const size_t plane_off = (size_t)t.plane * H * W;
+    const int gx = t.x0 + col;
+    float sum = 0.0f;
+#pragma unroll
+    for (int o = 0; o < LOSS_ROWS; o++) {
+        const int gy = t.y0 + r0 + o;
+        if (gx < W && gy < H) {
+            const size_t e = plane_off + (size_t)gy * W + gx;
+            float v = d.invdepth[e] - d.mono[e];
+            if (d.mask) v = v * d.mask[e];
+            sum += fabsf(v);
+        }
+    }
+    return sum;
+}
+
+// grid: the colour_groups (plane, tile) workgroups of photometric_forward_kernel, then the depth planes' tiles.  partials: two per colour
+// workgroup, then one per depth workgroup
+template <bool MAPS>
+__global__ void __launch_bounds__(LOSS_BLOCK) training_forward_kernel(const float* __restrict__ image, const float* __restrict__ target, const LossColour c, const LossDepth d,
+                                                                      const int H, const int W, const int tiles_x, const int tiles_y, const uint32_t colour_groups,
+                                                                      const size_t n, float* __restrict__ maps, float* __restrict__ partials)
+{
+    __shared__ float s_x[LOSS_HH][LOSS_HW], s_y[LOSS_HH][LOSS_HW];
+    __shared__ float s_h[5][LOSS_HH][LOSS_TW];
+    __shared__ float s_wave[LOSS_BLOCK / 64];
+    if (blockIdx.x >= colour_groups) { // (workgroup-uniform)
+        const float bd = block_sum(depth_tile_sum(d, loss_tile_at(blockIdx.x - colour_groups, tiles_x, tiles_y), H, W), s_wave);
+        if (threadIdx.x == 0) partials[2 * (size_t)colour_groups + (blockIdx.x - colour_groups)] = bd;
+        return;
+    }
+    const LossTile t = loss_tile(tiles_x, tiles_y);
+    const size_t hw = (size_t)H * W, plane_off = (size_t)t.plane * hw;
+    {
+        const int b = t.plane / c.channels, j = t.plane - b * c.channels;
+        const float* img = image + (size_t)b * c.channels * hw;
+        const float* E = c.exposure ? c.exposure + (size_t)b * c.exposure_stride : nullptr;
+        const float* mk = c.alpha_mask ? c.alpha_mask + (size_t)b * c.mask_stride : nullptr;
+        for (int i = (int)threadIdx.x; i < LOSS_HH * LOSS_HW; i += LOSS_BLOCK) {
+            const int r = i / LOSS_HW, cc = i - r * LOSS_HW;
+            const int gy = t.y0 - LOSS_R + r, gx = t.x0 - LOSS_R + cc;
+            float v = 0.0f;
+            if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+                const size_t pix = (size_t)gy * W + gx;
+                float raw;
+                v = exposed(img, hw, pix, j, E, c.clamp, &raw);
+                if (mk) v = v * mk[pix];
+            }
+            s_x[r][cc] = v;
+        }
+    }
+    stage_halo(s_y, target + plane_off, t.x0, t.y0, H, W, 1.0f);
+    __syncthreads();
+
+    // from here on: photometric_forward_kernel on s_x = x''
+    const int col = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = wave; r < LOSS_HH; r += LOSS_BLOCK / 64) {
+        float x[11], y[11], xx[11], yy[11], xy[11];
+#pragma unroll
+        for (int j = 0; j < 11; j++) {
+            x[j] = s_x[r][col + j];
+            y[j] = s_y[r][col + j];
+            xx[j] = x[j] * x[j];
+            yy[j] = y[j] * y[j];
+            xy[j] = x[j] * y[j];
+        }
+        s_h[0][r][col] = window11(x);
+        s_h[1][r][col] = window11(y);
+        s_h[2][r][col] = window11(xx);
+        s_h[3][r][col] = window11(yy);
+        s_h[4][r][col] = window11(xy);
+    }
+    __syncthreads();
+
+    float st[5][LOSS_ROWS];
+    const int r0 = wave * LOSS_ROWS;
+#pragma unroll
+    for (int q = 0; q < 5; q++) {
+        float v[LOSS_ROWS + 10];
+#pragma unroll
+        for (int j = 0; j < LOSS_ROWS + 10; j++) v[j] = s_h[q][r0 + j][col];
+#pragma unroll
+        for (int o = 0; o < LOSS_ROWS; o++) st[q][o] = window11(v + o);
+    }
+
+    float sum_l1 = 0.0f, sum_m = 0.0f;
+    const int gx = t.x0 + col;
+#pragma unroll
+    for (int o = 0; o < LOSS_ROWS; o++) {
+        const int gy = t.y0 + r0 + o;
+        if (gx < W && gy < H) {
+            const float mu1 = st[0][o], mu2 = st[1][o];
+            const float s1 = __fmaf_rn(-mu1, mu1, st[2][o]), s2 = __fmaf_rn(-mu2, mu2, st[3][o]), s12 = __fmaf_rn(-mu1, mu2, st[4][o]);
+            const float A = __fmaf_rn(2.0f * mu1, mu2, LOSS_C1), B = __fmaf_rn(2.0f, s12, LOSS_C2);
+            const float Cc = __fmaf_rn(mu1, mu1, __fmaf_rn(mu2, mu2, LOSS_C1)), D = (s1 + s2) + LOSS_C2;
+            const float rcd = 1.0f / (Cc * D);
+            const float m = (A * B) * rcd;
+            sum_m += m;
+            sum_l1 += fabsf(s_x[r0 + o + LOSS_R][col + LOSS_R] - s_y[r0 + o + LOSS_R][col + LOSS_R]);
+            if constexpr (MAPS) {
+                const size_t e = plane_off + (size_t)gy * W + gx;
+                maps[e] = 2.0f * __fmaf_rn(mu2, B - A, (mu1 * m) * (Cc - D)) * rcd;
+                maps[n + e] = -m / D;
+                maps[2 * n + e] = (2.0f * A) * rcd;
+            }
+        }
+    }
+    const float bl1 = block_sum(sum_l1, s_wave);
+    const float bm = block_sum(sum_m, s_wave);
+    if (threadIdx.x == 0) {
+        partials[2 * (size_t)blockIdx.x] = bl1;
+        partials[2 * (size_t)blockIdx.x + 1] = bm;
+    }
+}
+
+// photometric_sum_kernel with the depth term's column: out3[0 .. 1] by the same additions, out3[2] = the depth rows' sum / n_d (0 without rows)
+__global__ void __launch_bounds__(LOSS_BLOCK) training_sum_kernel(const float* __restrict__ partials, const uint32_t groups, const float n, const uint32_t depth_groups,
+                                                                  const float n_d, float* __restrict__ out3)
+{
+    __shared__ float s_wave[LOSS_BLOCK / 64];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        float acc = 0.0f;
+        for (uint32_t r = threadIdx.x; r < groups; r += LOSS_BLOCK) acc += partials[2 * (size_t)r + k];
+        const float s = block_sum(acc, s_wave);
+        if (threadIdx.x == 0) out3[k] = s / n;
+    }
+    float acc = 0.0f;
+    for (uint32_t r = threadIdx.x; r < depth_groups; r += LOSS_BLOCK) acc += partials[2 * (size_t)groups + r];
+    const float s = block_sum(acc, s_wave);
+    if (threadIdx.x == 0) out3[2] = depth_groups ? s / n_d : 0.0f;
+}
+
+// grid: image_groups (image, tile) workgroups, then (with dL_dinvdepth) the depth planes' tiles
+__global__ void __launch_bounds__(LOSS_BLOCK) training_backward_kernel(const float* __restrict__ image, const float* __restrict__ target, const float* __restrict__ maps,
+                                                                       const float* __restrict__ dL_dout3, const LossColour c, const LossDepth d, const int H, const int W,
+                                                                       const int tiles_x, const int tiles_y, const uint32_t image_groups, const size_t n, const float nf,
+                                                                       const float ndf, float* __restrict__ dL_dimage, float* __restrict__ dL_dinvdepth,
+                                                                       float* __restrict__ exposure_partials)
+{
+#pragma clang fp contract(off)
+    __shared__ float s_d[3][LOSS_HH][LOSS_HW];
+    __shared__ float s_h[3][LOSS_HH][LOSS_TW];
+    __shared__ float s_wave[LOSS_BLOCK / 64];
+    const int col = threadIdx.x & 63, wave = threadIdx.x >> 6, r0 = wave * LOSS_ROWS;
+    const size_t hw = (size_t)H * W;
+    if (blockIdx.x >= image_groups) { // (workgroup-uniform) a depth tile
+        const LossTile t = loss_tile_at(blockIdx.x - image_groups, tiles_x, tiles_y);
+        const float w = dL_dout3[2] / ndf;
+        const int gx = t.x0 + col;
+#pragma unroll
+        for (int o = 0; o < LOSS_ROWS; o++) {
+            const int gy = t.y0 + r0 + o;
+            if (gx < W && gy < H) {
+                const size_t e = (size_t)t.plane * hw + (size_t)gy * W + gx;
+                float v = d.invdepth[e] - d.mono[e], mk = 1.0f;
+                if (d.mask) {
+                    mk = d.mask[e];
+                    v = v * mk;
+                }
+                const float sg = v > 0.0f ? mk : (v < 0.0f ? -mk : 0.0f); // sign((d - m) mask) mask: exact
+                dL_dinvdepth[e] = sg * w;
+            }
+        }
+        return;
+    }
+    const LossTile t = loss_tile(tiles_x, tiles_y); // .plane: the image
+    const float* img = image + (size_t)t.plane * c.channels * hw;
+    const float* E = c.exposure ? c.exposure + (size_t)t.plane * c.exposure_stride : nullptr;
+    const float* mk_plane = c.alpha_mask ? c.alpha_mask + (size_t)t.plane * c.mask_stride : nullptr;
+    const float l1w = dL_dout3[0] / nf, s = dL_dout3[1] / nf;
+    const int gx = t.x0 + col;
+    float acc[3][LOSS_ROWS]; // dL/dx_i of the thread's four pixels (with exposure)
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int o = 0; o < LOSS_ROWS; o++) acc[i][o] = 0.0f;
+
+    for (int j = 0; j < c.channels; j++) {
+        const size_t plane_off = ((size_t)t.plane * c.channels + j) * hw;
+#pragma unroll
+        for (int k = 0; k < 3; k++) stage_halo(s_d[k], maps + (size_t)k * n + plane_off, t.x0, t.y0, H, W, s);
+        __syncthreads();
+        for (int r = wave; r < LOSS_HH; r += LOSS_BLOCK / 64) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                float v[11];
+#pragma unroll
+                for (int q = 0; q < 11; q++) v[q] = s_d[k][r][col + q];
+                s_h[k][r][col] = window11(v);
+            }
+        }
+        __syncthreads();
+        float b[3][LOSS_ROWS];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            float v[LOSS_ROWS + 10];
+#pragma unroll
+            for (int q = 0; q < LOSS_ROWS + 10; q++) v[q] = s_h[k][r0 + q][col];
+#pragma unroll
+            for (int o = 0; o < LOSS_ROWS; o++) b[k][o] = window11(v + o);
+        }
+        float pe[4] = {0.0f, 0.0f, 0.0f, 0.0f}; // the thread's sums of x_0 g', x_1 g', x_2 g', g' of channel j
+#pragma unroll
+        for (int o = 0; o < LOSS_ROWS; o++) {
+            const int gy = t.y0 + r0 + o;
+            if (gx < W && gy < H) {
+                const size_t pix = (size_t)gy * W + gx;
+                float v;
+                float x = exposed(img, hw, pix, j, E, c.clamp, &v);
+                const bool pass = !c.clamp || (v >= 0.0f && v <= 1.0f);
+                float mk = 1.0f;
+                if (mk_plane) {
+                    mk = mk_plane[pix];
+                    x = x * mk;
+                }
+                const float y = target[plane_off + pix];
+                const float sgn = x > y ? l1w : (x < y ? -l1w : 0.0f); // (a NaN pixel: 0)
+                float g = __fmaf_rn(y, b[2][o], __fmaf_rn(2.0f * x, b[1][o], b[0][o])) + sgn; // g'': photometric_backward_kernel's expression
+                if (mk_plane) g = g * mk;
+                if (!pass) g = 0.0f;
+                if (E) {
+#pragma unroll
+                    for (int i = 0; i < 3; i++) {
+                        acc[i][o] = __fmaf_rn(E[4 * i + j], g, acc[i][o]);
+                        pe[i] = __fmaf_rn(img[(size_t)i * hw + pix], g, pe[i]);
+                    }
+                    pe[3] += g;
+                } else {
+                    dL_dimage[plane_off + pix] = g;
+                }
+            }
+        }
+        if (exposure_partials) { // (uniform; only with E)
+            float* row = exposure_partials + 12 * (size_t)blockIdx.x;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const float bs = block_sum(pe[i], s_wave);
+                if (threadIdx.x == 0) row[i < 3 ? 4 * i + j : 4 * j + 3] = bs;
+            }
+        }
+        // (the next channel's staging overwrites s_d, which nobody reads after the horizontal pass's barrier; s_h is written again only behind the next barrier)
+    }
+    if (E) {
+#pragma unroll
+        for (int o = 0; o < LOSS_ROWS; o++) {
+            const int gy = t.y0 + r0 + o;
+            if (gx < W && gy < H) {
+                const size_t pix = (size_t)gy * W + gx;
+#pragma unroll
+                for (int i = 0; i < 3; i++) dL_dimage[((size_t)t.plane * 3 + i) * hw + pix] = acc[i][o];
+            }
+        }
+    }
+}
+
+// one workgroup: out[e][k] = the sum of the rows e * rows_per .. (e + 1) * rows_per - 1 of 12 partials, thread t the rows t, t + 256, ... in order
+__global__ void __launch_bounds__(LOSS_BLOCK) exposure_sum_kernel(const float* __restrict__ partials, const uint32_t rows_per, const uint32_t n_out, float* __restrict__ out)
+{
+    __shared__ float s_wave[LOSS_BLOCK / 64];
+    for (uint32_t e = 0; e < n_out; e++) {
+        for (int k = 0; k < 12; k++) {
+            float acc = 0.0f;
+            for (uint32_t r = threadIdx.x; r < rows_per; r += LOSS_BLOCK) acc += partials[12 * ((size_t)e * rows_per + r) + k];
+            const float s = block_sum(acc, s_wave);
+            if (threadIdx.x == 0) out[12 * (size_t)e + k] = s;
+        }
+    }
+}
+
 } // namespace
 
 uint32_t photometric_groups(int planes, int H, int W)
@@ -263,6 +583,65 @@ int launch_photometric_backward(int planes, int H, int W, const float* image, co
                        tiles_x, tiles_y, n, (float)n, dL_dimage);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 0; }
     return 1;
+}
+
+static uint32_t image_groups(int planes, int channels, int H, int W) { return photometric_groups(planes / channels, H, W); }
+static bool has_colour_extras(const StpTrainingLoss& x) { return x.exposure || x.alpha_mask || x.clamp; }
+
+size_t training_loss_workspace_floats(int planes, int H, int W, int depth_planes)
+{
+    const size_t forward = 2 * (size_t)photometric_groups(planes, H, W) + (depth_planes > 0 ? photometric_groups(depth_planes, H, W) : 0);
+    const size_t backward = 12 * (size_t)photometric_groups(planes, H, W); // (>= 12 per (image, tile) workgroup whatever the channel count)
+    return forward > backward ? forward : backward;
+}
+
+static LossColour loss_colour(const StpTrainingLoss& x, int H, int W)
+{
+    return LossColour{x.exposure, x.alpha_mask, x.exposure_batched ? 12 : 0, x.clamp, x.channels, x.alpha_mask_batched ? (size_t)H * W : 0};
+}
+
+int launch_training_loss_forward(int planes, int H, int W, const float* image, const float* target, const StpTrainingLoss& x, float* out3, float* maps,
+                                 float* workspace, hipStream_t st, hipError_t* err)
+{
+    const int tiles_x = (W + LOSS_TW - 1) / LOSS_TW, tiles_y = (H + LOSS_TH - 1) / LOSS_TH;
+    const uint32_t groups = photometric_groups(planes, H, W), depth_groups = x.invdepth ? photometric_groups(x.depth_planes, H, W) : 0;
+    const size_t n = (size_t)planes * H * W, n_d = (size_t)x.depth_planes * H * W;
+    *err = hipSuccess;
+    if (!has_colour_extras(x) && !depth_groups) { // the plain call's tile kernel, instantiation for instantiation
+        if (maps) hipLaunchKernelGGL(photometric_forward_kernel<true>, dim3(groups), dim3(LOSS_BLOCK), 0, st, image, target, H, W, tiles_x, tiles_y, n, maps, workspace);
+        else hipLaunchKernelGGL(photometric_forward_kernel<false>, dim3(groups), dim3(LOSS_BLOCK), 0, st, image, target, H, W, tiles_x, tiles_y, n, maps, workspace);
+    } else {
+        const LossColour c = loss_colour(x, H, W);
+        const LossDepth d{x.invdepth, x.mono_invdepth, x.depth_mask};
+        if (maps) hipLaunchKernelGGL(training_forward_kernel<true>, dim3(groups + depth_groups), dim3(LOSS_BLOCK), 0, st, image, target, c, d, H, W, tiles_x, tiles_y, groups, n, maps, workspace);
+        else hipLaunchKernelGGL(training_forward_kernel<false>, dim3(groups + depth_groups), dim3(LOSS_BLOCK), 0, st, image, target, c, d, H, W, tiles_x, tiles_y, groups, n, maps, workspace);
+    }
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 0; }
+    hipLaunchKernelGGL(training_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, groups, (float)n, depth_groups, (float)n_d, out3);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 1; }
+    return 2;
+}
+
+int launch_training_loss_backward(int planes, int H, int W, const float* image, const float* target, const StpTrainingLoss& x, const float* maps,
+                                  const float* dL_dout3, float* dL_dimage, float* dL_dexposure, float* dL_dinvdepth, float* workspace, hipStream_t st,
+                                  hipError_t* err)
+{
+    const int tiles_x = (W + LOSS_TW - 1) / LOSS_TW, tiles_y = (H + LOSS_TH - 1) / LOSS_TH;
+    const size_t n = (size_t)planes * H * W, n_d = (size_t)x.depth_planes * H * W;
+    *err = hipSuccess;
+    if (!has_colour_extras(x) && !dL_dinvdepth) // (dL_dout3[0 .. 1] are the plain call's two)
+        return launch_photometric_backward(planes, H, W, image, target, maps, dL_dout3, dL_dimage, st, err);
+    const uint32_t groups = image_groups(planes, x.channels, H, W), depth_groups = dL_dinvdepth ? photometric_groups(x.depth_planes, H, W) : 0;
+    const uint32_t tiles = (uint32_t)tiles_x * (uint32_t)tiles_y;
+    hipLaunchKernelGGL(training_backward_kernel, dim3(groups + depth_groups), dim3(LOSS_BLOCK), 0, st, image, target, maps, dL_dout3, loss_colour(x, H, W),
+                       LossDepth{x.invdepth, x.mono_invdepth, x.depth_mask}, H, W, tiles_x, tiles_y, groups, n, (float)n, (float)n_d, dL_dimage, dL_dinvdepth,
+                       dL_dexposure ? workspace : nullptr);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 0; }
+    if (!dL_dexposure) return 1;
+    if (x.exposure_batched) hipLaunchKernelGGL(exposure_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, tiles, groups / tiles, dL_dexposure);
+    else hipLaunchKernelGGL(exposure_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, groups, 1u, dL_dexposure);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 1; }
+    return 2;
 }
 
 } // namespace stp

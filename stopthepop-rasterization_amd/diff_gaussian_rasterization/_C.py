@@ -78,6 +78,9 @@ _OPTIONAL_SYMBOLS = {
     "stp_photometric_workspace_floats": ([ctypes.c_int] * 3, ctypes.c_size_t, "the photometric loss"),
     "stp_photometric_forward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int, "the photometric loss"),
     "stp_photometric_backward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 6, ctypes.c_int, "the photometric loss"),
+    "stp_training_loss_workspace_floats": ([ctypes.c_int] * 4, ctypes.c_size_t, "the training loss"),
+    "stp_training_loss_forward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 7, ctypes.c_int, "the training loss"),
+    "stp_training_loss_backward": ([ctypes.c_int] * 3 + [ctypes.c_void_p] * 10, ctypes.c_int, "the training loss"),
 }
 _SYMBOL_FEATURE = {name: entry[2] for name, entry in _OPTIONAL_SYMBOLS.items()}   # (a view of the table above)
 
@@ -659,6 +662,35 @@ def photometric_backward(image, target, maps, grad_out2):
     two floats ON THE DEVICE (the kernel reads them there).  One kernel launch, no host synchronisation.  There is no gradient for target."""
     _require("stp_photometric_backward")
     return (_host or _native()).photometric_backward(image, target, maps, grad_out2)
+
+
+class StpTrainingLoss(ctypes.Structure):
+    """POD mirror of StpTrainingLoss (include/stp_raster.h): the optional inputs of stp_training_loss_forward / _backward."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("exposure", "alpha_mask", "invdepth", "mono_invdepth", "depth_mask")] + \
+               [(n, ctypes.c_int32) for n in ("clamp", "exposure_batched", "alpha_mask_batched", "channels", "depth_planes")]
+
+
+_TRAINING_LOSS_SYMBOLS = ("stp_training_loss_workspace_floats", "stp_training_loss_forward", "stp_training_loss_backward")
+
+
+def training_loss_forward(image, target, exposure, clamp, alpha_mask, invdepth, mono_invdepth, depth_mask, want_maps):
+    """The forward of the training loss (extension, include/stp_raster.h: stp_training_loss_forward) on the current stream: (out3, maps) with
+    out3 = [mean |x'' - target|, mean SSIM(x'', target), mean |(invdepth - mono_invdepth) * depth_mask|] for x'' = the exposed, clamped and
+    masked image, and maps = the three derivative maps (3, *image.shape) or None.  Every extra may be None.  Two kernel launches, no host
+    synchronisation."""
+    for name in _TRAINING_LOSS_SYMBOLS:
+        _require(name)
+    out3, maps = (_host or _native()).training_loss_forward(image, target, exposure, bool(clamp), alpha_mask, invdepth, mono_invdepth, depth_mask, bool(want_maps))
+    return out3, (maps if want_maps else None)
+
+
+def training_loss_backward(image, target, exposure, clamp, alpha_mask, invdepth, mono_invdepth, depth_mask, maps, grad_out3, want_exposure, want_invdepth):
+    """(dL/dimage, dL/dexposure | None, dL/dinvdepth | None) of the training loss (stp_training_loss_backward) from the maps of a forward with
+    want_maps and grad_out3 = dL/dout3, three floats ON THE DEVICE.  One kernel launch, two with dL/dexposure; no host synchronisation."""
+    _require("stp_training_loss_backward")
+    g_image, g_exposure, g_invdepth = (_host or _native()).training_loss_backward(image, target, exposure, bool(clamp), alpha_mask, invdepth, mono_invdepth, depth_mask,
+                                                                                  maps, grad_out3, bool(want_exposure), bool(want_invdepth))
+    return g_image, (g_exposure if want_exposure else None), (g_invdepth if want_invdepth else None)
 
 
 # ---- introspection helpers (tests / bench; not part of the reference surface) -----------------------

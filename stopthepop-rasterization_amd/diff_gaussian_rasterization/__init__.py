@@ -26,7 +26,7 @@ from . import _C
 
 __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes", "SortSettings", "CullingSettings",
            "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam",
-           "photometric_terms", "fused_ssim", "photometric_loss", "compute_relocation", "mcmc_add_noise_",
+           "photometric_terms", "fused_ssim", "photometric_loss", "training_terms", "training_loss", "compute_relocation", "mcmc_add_noise_",
            "knn_mean_dist2", "distCUDA2", "dist_cuda2", "activate_params",
            "densification_stats_", "densify_plan", "densify_tensors", "densify_and_prune",
            "mcmc_relocation_plan", "mcmc_relocate_tensors_", "mcmc_relocate_", "mcmc_add_plan", "mcmc_add_tensors", "mcmc_add_new"]
@@ -699,6 +699,56 @@ def photometric_loss(image: torch.Tensor, target: torch.Tensor, lambda_dssim: fl
     composed on the two device scalars of photometric_terms (which see for shapes, refusals and the gradient rules)."""
     terms = _photometric(image, target)
     return (1.0 - lambda_dssim) * terms[0] + lambda_dssim * (1.0 - terms[1])
+
+
+class _TrainingTerms(torch.autograd.Function):
+    """(image, target, exposure, alpha_mask, invdepth, mono_invdepth, depth_mask, clamp, want_maps) -> the (3,) tensor of training_terms.
+    Gradients for image, exposure and invdepth; none for target, the masks and mono_invdepth."""
+
+    @staticmethod
+    def forward(ctx, image, target, exposure, alpha_mask, invdepth, mono_invdepth, depth_mask, clamp, want_maps):
+        out3, maps = _C.training_loss_forward(image, target, exposure, clamp, alpha_mask, invdepth, mono_invdepth, depth_mask, want_maps)
+        ctx.has_maps, ctx.clamp = maps is not None, clamp
+        ctx.given = [t is not None for t in (exposure, alpha_mask, invdepth, mono_invdepth, depth_mask)]
+        if ctx.has_maps:
+            ctx.save_for_backward(image, target, maps, *[t for t in (exposure, alpha_mask, invdepth, mono_invdepth, depth_mask) if t is not None])
+        return out3
+
+    @staticmethod
+    def backward(ctx, grad_out3):
+        if not ctx.has_maps:
+            raise RuntimeError("training_terms: this forward stored no derivative maps: it cannot be differentiated")
+        image, target, maps, *rest = ctx.saved_tensors
+        rest = iter(rest)
+        exposure, alpha_mask, invdepth, mono_invdepth, depth_mask = [next(rest) if g else None for g in ctx.given]
+        want_exposure = exposure is not None and ctx.needs_input_grad[2]
+        want_invdepth = invdepth is not None and ctx.needs_input_grad[4]
+        g_image, g_exposure, g_invdepth = _C.training_loss_backward(image, target, exposure, ctx.clamp, alpha_mask, invdepth, mono_invdepth, depth_mask, maps, grad_out3,
+                                                                    want_exposure, want_invdepth)
+        return g_image, None, g_exposure, None, g_invdepth, None, None, None, None
+
+
+def training_terms(image: torch.Tensor, target: torch.Tensor, *, exposure=None, clamp: bool = False, alpha_mask=None, invdepth=None, mono_invdepth=None,
+                   depth_mask=None) -> torch.Tensor:
+    """The three terms of the loss a 3DGS trainer's step runs, from the fused kernels of photometric_terms (extension; include/stp_raster.h:
+    stp_training_loss_forward): the (3,) float32 tensor
+        [mean |x'' - target|, mean SSIM(x'', target), mean |(invdepth - mono_invdepth) * depth_mask|]        (the last exactly 0.0 without invdepth)
+    with  v_j = sum_i image_i * exposure[i][j] + exposure[j][3]  (upstream's matmul(image.permute(1, 2, 0), exposure[:3, :3]) + exposure[:3, 3];
+    one float32 fma chain), v clamped to [0, 1] when clamp (the gradient passes where 0 <= v <= 1), x'' = v * alpha_mask; the window's zero
+    padding applies to x''.  image, target: as photometric_terms; exposure: (3, 4) or (B, 3, 4), needs C == 3; alpha_mask: (H, W), (1, H, W)
+    or (B, 1, H, W); invdepth, mono_invdepth, depth_mask: (1, H, W) or (B, 1, H, W); all float32 on the image's GPU, each optional, invdepth
+    and mono_invdepth together.  Differentiable in image, exposure and invdepth; target, the masks and mono_invdepth get NO gradient (None).
+    Deterministic, and no host synchronisation anywhere.  With no extra given this is photometric_terms, bit for bit, and a zero."""
+    tensors = (image, exposure, invdepth)
+    want_maps = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+    return _TrainingTerms.apply(image, target, exposure, alpha_mask, invdepth, mono_invdepth, depth_mask, bool(clamp), want_maps)
+
+
+def training_loss(image: torch.Tensor, target: torch.Tensor, lambda_dssim: float = 0.2, depth_weight: float = 0.0, **extras) -> torch.Tensor:
+    """(1 - lambda_dssim) * t[0] + lambda_dssim * (1 - t[1]) + depth_weight * t[2]  of t = training_terms(image, target, **extras), a scalar
+    tensor composed on the three device scalars."""
+    t = training_terms(image, target, **extras)
+    return (1.0 - lambda_dssim) * t[0] + lambda_dssim * (1.0 - t[1]) + depth_weight * t[2]
 
 
 def compute_relocation(opacity_old: torch.Tensor, scale_old: torch.Tensor, N: torch.Tensor):

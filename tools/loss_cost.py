@@ -12,7 +12,13 @@ times and the median per case is printed with its spread.  Cases:
   raster_step      the plain forward + backward of the same workload, for proportion
 and whether fused_loss was faster than torch_loss in EVERY round, beside the copy rate of stp_hbm_probe in the same run and the bytes
 the fused pair has to move at least (forward: x, y read, three maps written; backward: x, y and the maps read, dL/dx written: 44 bytes
-per element)."""
+per element).
+With --training two more cases, the full loss of upstream's step (per-image exposure, clamp, alpha mask, depth term; forward + backward down
+to dL/dimage, dL/dexposure and dL/dinvdepth), alternating like the others:
+  around_fused     today's way: the torch lines (permute / matmul, clamp, mask, the depth L1) around photometric_loss
+  training_loss    training_loss: the same in the fused kernels
+With --ab-lib PATH one more pair: photometric_loss alone on the default library and on the library at PATH, alternating (has the plain
+call moved?)."""
 import argparse
 import os
 import statistics
@@ -33,6 +39,8 @@ ap.add_argument("workloads", nargs="*", default=["C2", "C5"])
 ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--variant", default="full")
+ap.add_argument("--training", action="store_true", help="also time the extended loss: torch lines around photometric_loss against training_loss")
+ap.add_argument("--ab-lib", default=None, help="also time photometric_loss alone on the default library and on this one, alternating")
 ap.add_argument("--no-raster", action="store_true", help="do not build the workload's scene: synthetic images, no raster_step")
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -147,7 +155,71 @@ def workload(name):
     faster = all(f < t for f, t in zip(ms["fused_loss"], ms["torch_loss"]))
     print(f"  torch_loss / fused_loss = {med['torch_loss'] / med['fused_loss']:.2f} (per round: {', '.join('%.2f' % (t / f) for f, t in zip(ms['fused_loss'], ms['torch_loss']))}); "
           f"fused_loss faster in every round: {faster}")
+    if args.training:
+        training_cases(name, image, target, gen)
+    if args.ab_lib:
+        library_cases(name, image, target)
     return moved / (med["fused_loss"] * 1e-3) / 1e12
+
+
+def report(name, cases, a, b):
+    ms = {n: [] for n in cases}
+    for _ in range(args.rounds):
+        for n, step in cases.items():
+            ms[n].append(timed(step, args.steps))
+    for n in cases:
+        print(f"  {n:13s} {statistics.median(ms[n]):.4f} [{min(ms[n]):.4f} .. {max(ms[n]):.4f}]  {args.steps} steps per round")
+    print(f"  {a} / {b} = {statistics.median(ms[a]) / statistics.median(ms[b]):.2f} (per round: {', '.join('%.2f' % (t / f) for f, t in zip(ms[b], ms[a]))}); "
+          f"{b} faster in every round: {all(f < t for f, t in zip(ms[b], ms[a]))}")
+
+
+def training_cases(name, image, target, gen):
+    """the full loss of upstream's step: (a) torch ops around photometric_loss, (b) training_loss"""
+    H, W = image.shape[-2:]
+    exposure = (torch.eye(3, 4, device=dev) + 0.05 * torch.randn(3, 4, device=dev, generator=gen)).requires_grad_(True)
+    alpha_mask = (torch.rand(1, H, W, device=dev, generator=gen) > 0.1).float()
+    invdepth = torch.rand(1, H, W, device=dev, generator=gen).requires_grad_(True)
+    mono = torch.rand(1, H, W, device=dev, generator=gen)
+    depth_mask = (torch.rand(1, H, W, device=dev, generator=gen) > 0.2).float()
+
+    def around():
+        x = torch.matmul(image.permute(1, 2, 0), exposure[:3, :3]).permute(2, 0, 1) + exposure[:3, 3, None, None]
+        x = x.clamp(0, 1) * alpha_mask
+        return dgr.photometric_loss(x, target) + 0.5 * ((invdepth - mono) * depth_mask).abs().mean()
+
+    def fused():
+        return dgr.training_loss(image, target, 0.2, 0.5, exposure=exposure, clamp=True, alpha_mask=alpha_mask, invdepth=invdepth, mono_invdepth=mono, depth_mask=depth_mask)
+
+    def step_of(loss_fn):
+        def step():
+            loss_fn().backward()
+            image.grad = exposure.grad = invdepth.grad = None
+        return step
+
+    leaves = (image, exposure, invdepth)
+    a, b = around(), fused()
+    ga, gb = torch.autograd.grad(a, leaves), torch.autograd.grad(b, leaves)
+    diffs = ", ".join("%.3g of %.3g" % (float((x - y).abs().max()), float(x.abs().max())) for x, y in zip(ga, gb))
+    print(f"{name} extended loss (exposure, clamp, alpha mask, depth term): loss {float(a.detach()):.7f} / {float(b.detach()):.7f}, "
+          f"largest gradient differences (image, exposure, invdepth) {diffs}")
+    report(name, {"around_fused": step_of(around), "training_loss": step_of(fused)}, "around_fused", "training_loss")
+
+
+def library_cases(name, image, target):
+    """photometric_loss alone, the default library against args.ab_lib, alternating"""
+    def step():
+        dgr.photometric_loss(image, target).backward()
+        image.grad = None
+
+    ms = {"default_lib": [], "other_lib": []}
+    for _ in range(args.rounds):
+        for n, path in (("default_lib", None), ("other_lib", args.ab_lib)):
+            _C.use_library(path)   # (the next call loads it)
+            ms[n].append(timed(step, args.steps))
+    _C.use_library(None)
+    print(f"{name} photometric_loss alone, the default library against {args.ab_lib}:")
+    for n, v in ms.items():
+        print(f"  {n:13s} {statistics.median(v):.4f} [{min(v):.4f} .. {max(v):.4f}]  {args.steps} steps per round")
 
 
 print(f"stp_hbm_probe copy, 1 GiB, this box, this run: {(rate := copy_rate()):.2f} TB/s")
