@@ -3,7 +3,7 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--relocate torch|fused] [--cap-max N] [--split-sh] [--raw-params] [--init-scales scene|knn]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam|gaussian_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--relocate torch|fused] [--cap-max N] [--split-sh] [--raw-params] [--init-scales scene|knn]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
@@ -24,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "stopthepop-rasterization_amd"))
 from diff_gaussian_rasterization import (CullingSettings, ExtendedSettings, GaussianRasterizationSettings,  # noqa: E402
-                                         GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, SparseGaussianAdam, compute_relocation,
+                                         GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, GaussianAdam, SparseGaussianAdam, compute_relocation,
                                          densification_stats_, densify_and_prune, densify_plan, mcmc_add_new, mcmc_add_noise_, mcmc_relocate_, scenes, training_loss, training_terms)
 
 
@@ -177,8 +177,10 @@ def main(argv=None):
     ap.add_argument("--exposure", action="store_true",
                     help="learn a (3, 4) exposure, initialised to the identity, with its own Adam: the render goes through it inside the fused "
                          "training_loss, the only route by which it gets a gradient without a torch matmul (INTEGRATION.md section 3s)")
-    ap.add_argument("--optimizer", default="adam", choices=["adam", "sparse_adam"],
-                    help="sparse_adam: SparseGaussianAdam, one fused launch that steps only the Gaussians visible in the frame (INTEGRATION.md section 3i)")
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "sparse_adam", "gaussian_adam"],
+                    help="sparse_adam: SparseGaussianAdam, one fused launch that steps only the Gaussians visible in the frame (INTEGRATION.md section 3i).  "
+                         "gaussian_adam: GaussianAdam, torch.optim.Adam's own dense bias-corrected step in one fused launch; under --strategy mcmc the "
+                         "opacity and scale regularisers leave the loss and ride in that launch (INTEGRATION.md section 3t)")
     ap.add_argument("--loss", default="l1", choices=["l1", "l1_ssim"],
                     help="l1_ssim: the trainers' 0.8 * L1 + 0.2 * (1 - SSIM) from the fused training_loss (INTEGRATION.md sections 3j, 3s)")
     ap.add_argument("--strategy", default="none", choices=["none", "mcmc", "adc"],
@@ -231,7 +233,11 @@ def main(argv=None):
     adc = args.strategy == "adc"
     fused_mcmc = args.strategy == "mcmc" and args.relocate == "fused"
     cap_max = args.cap_max if args.cap_max is not None else (115 * args.points) // 100
-    if (adc or fused_mcmc) and args.optimizer != "sparse_adam":   # densify_and_prune and mcmc_relocate_ want the trainers' layout: one named group per tensor
+    if args.optimizer == "gaussian_adam":   # the class name is all that changes against the torch.optim.Adam below
+        opt = GaussianAdam([*model.feature_groups(2e-2), {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
+                            {"params": [model._xyz], "lr": 0.0, "name": "xyz"}, {"params": [model._scaling], "lr": 0.0, "name": "scaling"},
+                            {"params": [model._rotation], "lr": 0.0, "name": "rotation"}], lr=0.0, eps=1e-15)
+    elif (adc or fused_mcmc) and args.optimizer != "sparse_adam":   # densify_and_prune and mcmc_relocate_ want the trainers' layout: one named group per tensor
         opt = torch.optim.Adam([*model.feature_groups(2e-2), {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
                                 {"params": [model._xyz], "lr": 0.0, "name": "xyz"}, {"params": [model._scaling], "lr": 0.0, "name": "scaling"},
                                 {"params": [model._rotation], "lr": 0.0, "name": "rotation"}], lr=0.0, eps=1e-15)
@@ -264,6 +270,11 @@ def main(argv=None):
     noise_scale = 5e5 * 1.6e-4   # upstream's noise_lr times its initial position learning rate (the positions themselves are not fitted here)
     relocated = relocations = 0   # (--relocate fused: `relocated` is a device scalar until the end: counting must not synchronise either)
     added = 0
+    fused_reg = mcmc and args.optimizer == "gaussian_adam"
+    reg_value = 0.0
+    if fused_reg:   # opacity_reg * |sigmoid(_opacity)|.mean() and scale_reg * |exp(_scaling)|.mean(), as gradients inside the step
+        opt.set_regularizer("opacity", "sigmoid", 0.01)
+        opt.set_regularizer("scaling", "exp", 0.01)
     if mcmc:
         torch.manual_seed(0)   # (the noise and the sampling are torch's: a run is reproducible)
         with torch.no_grad():  # every fiftieth Gaussian starts dead (opacity 0.002), so that the first relocation has work whatever the fit does
@@ -284,7 +295,11 @@ def main(argv=None):
             loss = (out["render"] - target).abs().mean()
         if masked:   # alpha is an output of the same autograd node: one backward serves both terms
             loss = loss + args.mask_weight * (out["alpha"] - target_alpha).abs().mean()
-        if mcmc:   # upstream's opacity_reg and scale_reg: L1 pressure that lets unneeded Gaussians die, to be relocated
+        if mcmc and fused_reg:   # the two terms' gradients are added inside the optimizer's kernel; their value is computed for the printed figure only
+            if it % 10 == 0 or it == args.iters - 1:   # (the optimizer does not compute it: a trainer that logs it computes it itself, when it logs)
+                with torch.no_grad():
+                    reg_value = float(0.01 * torch.sigmoid(model._opacity).mean() + 0.01 * torch.exp(model._scaling).mean())
+        elif mcmc:   # upstream's opacity_reg and scale_reg: L1 pressure that lets unneeded Gaussians die, to be relocated
             loss = loss + 0.01 * model.get_opacity.mean() + 0.01 * model.get_scaling.mean()
         opt.zero_grad(set_to_none=True)
         if exposure_opt is not None:
@@ -346,7 +361,7 @@ def main(argv=None):
             grown, pruned = grown + cloned + 2 * split, pruned + before - kept
             print(f"iter {it:3d}  adc: {before} rows -> {after} (kept {kept}, cloned {cloned}, split {split} into {2 * split})")
             stat_signed, stat_abs, stat_denom, stat_radii, abs_denom = (torch.zeros(after, device=dev) for _ in range(5))   # (upstream's densification_postfix)
-        last = float(loss.detach())
+        last = float(loss.detach()) + reg_value
         first = last if first is None else first
         if it % 10 == 0 or it == args.iters - 1:
             print(f"iter {it:3d}  {label} {last:.5f}  visible {int(out['visibility_filter'].sum())}  |grad2D| max {float(grad2d.norm(dim=1).max()):.3e}")

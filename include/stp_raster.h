@@ -398,6 +398,29 @@ typedef struct { float* param; const float* grad; float* exp_avg; float* exp_avg
 int stp_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind /* 0: N bytes, non-zero = visible; 1: N int32, > 0 = visible */,
                     float beta1, float beta2, void* stream);
 
+/* Extension (not in the reference): the fused DENSE Adam step -- the bias-corrected torch.optim.Adam(lr, betas, eps) that the 3DGS trainer
+   (optimizer_type "default") and every 3DGS-MCMC trainer construct -- with the two 3DGS-MCMC regularisers' gradients folded in.  For every
+   tensor and every one of its numel elements, in float32:
+       g' = g + r      r = 0 (reg_kind 0),   reg_coef * (s * (1 - s)) with s = 1 / (1 + exp(-p)) (reg_kind 1, "sigmoid"),
+                       reg_coef * exp(p) (reg_kind 2, "exp")
+       m <- beta1 * m + one_minus_beta1 * g'      v <- beta2 * v + one_minus_beta2 * g' * g'
+       p <- p - (step_size * m) / (sqrt(v) / bias2_sqrt + eps)
+   p in r is the value BEFORE the step.  reg_kind 1 with reg_coef = w / numel is the gradient of w * mean(sigmoid(p)), reg_kind 2 that of
+   w * mean(exp(p)): a 3DGS-MCMC trainer's opacity_reg and scale_reg terms.  The CALLER forms every coefficient, as torch does: in float64
+   from the unrounded hyper-parameters -- one_minus_beta = 1 - beta, step_size = lr / (1 - beta1^t), bias2_sqrt = sqrt(1 - beta2^t) with t the
+   step count after this step -- rounded to float32 once; they travel per tensor, so tensors may disagree in all of them.  No weight decay, no
+   amsgrad, no maximize; the regulariser's VALUE is not computed.  grad is only read.  All pointers are device pointers to contiguous float32
+   data; 16-byte aligned ones are streamed 16 bytes per lane, others one float at a time, with equal bits.  One kernel launch updates up to
+   eight tensors (more tensors: further launches), without atomics: equal inputs give equal bits.
+   Returns the number of kernel launches made (>= 0; 0 for n_tensors == 0 or all numel == 0), or a negative StpStatus with the reason in the
+   last-error text.  Refused BEFORE anything is launched, so that nothing is half updated (STP_ERR_INVALID_ARGUMENT): a negative count, a null
+   table, a negative numel, numel >= 2^31, a reg_kind outside {0, 1, 2}, a bias2_sqrt that is not finite and positive, a null pointer of a
+   tensor with elements.  A plain call: no host synchronisation, no allocation, no per-thread request state.  The coefficients travel in the
+   kernel arguments: a step captured in a graph replays the step count it was captured with. */
+typedef struct { float* param; const float* grad; float* exp_avg; float* exp_avg_sq; long long numel;
+                 float beta1, one_minus_beta1, beta2, one_minus_beta2, step_size, bias2_sqrt, eps; int32_t reg_kind; float reg_coef; } StpDenseAdamTensor;
+int stp_dense_adam(int n_tensors, const StpDenseAdamTensor* tensors, void* stream);
+
 /* Extension (not in the reference): the two kernels of a 3DGS-MCMC trainer ("3D Gaussian Splatting as Markov Chain Monte Carlo").
    stp_mcmc_relocation is that project's compute_relocation: Gaussian i of opacity o and scales s, to be replaced by N_i copies of itself, gets
        o_new = 1 - (1 - o)^(1/N)     denom = sum_{j=1..N} sum_{k=0..j-1} C(j-1, k) (-1)^k o_new^(k+1) / sqrt(k+1)     s_new = (o / denom) s

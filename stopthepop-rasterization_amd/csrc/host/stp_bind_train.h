@@ -49,6 +49,43 @@ int sparse_adam(const std::vector<torch::Tensor>& params, const std::vector<torc
     return checked(g_api.sparse_adam((int)n, table.data(), (int)N, visible.data_ptr(), vt == torch::kInt32 ? 1 : 0, (float)beta1, (float)beta2, current_stream(dev)));
 }
 
+// == the fused dense Adam step (extension, include/stp_raster.h: stp_dense_adam; the step of GaussianAdam in __init__.py): one library call for all
+// quadruples (param, grad, exp_avg, exp_avg_sq), on the caller's current stream.  coefs: eight float64 values per tensor, in the order of
+// StpDenseAdamTensor -- beta1, 1 - beta1, beta2, 1 - beta2, step_size, bias2_sqrt, eps, reg_coef -- rounded to float32 HERE, once; reg_kinds: 0, 1
+// (sigmoid) or 2 (exp) per tensor.  Returns the kernel launches the library made.
+int dense_adam(const std::vector<torch::Tensor>& params, const std::vector<torch::Tensor>& grads, const std::vector<torch::Tensor>& exp_avgs,
+               const std::vector<torch::Tensor>& exp_avg_sqs, const std::vector<double>& coefs, const std::vector<int64_t>& reg_kinds)
+{
+    need_library();
+    require(g_api.dense_adam, "dense_adam");
+    const size_t n = params.size();
+    TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n && reg_kinds.size() == n && coefs.size() == 8 * n,
+                "dense_adam: params, grads, exp_avgs, exp_avg_sqs and reg_kinds must have one entry per tensor, coefs eight");
+    if (n == 0) return 0;
+    std::vector<StpDenseAdamTensor> table(n);
+    for (size_t k = 0; k < n; k++) {
+        const torch::Tensor* quad[4] = {&params[k], &grads[k], &exp_avgs[k], &exp_avg_sqs[k]};
+        static const char* const names[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
+        for (int j = 0; j < 4; j++) {
+            const torch::Tensor& t = *quad[j];
+            TORCH_CHECK(t.defined(), "dense_adam: tensor ", k, ": ", names[j], " is undefined");
+            TORCH_CHECK(t.layout() == torch::kStrided, "dense_adam: tensor ", k, ": ", names[j], " must be dense, got layout ", t.layout());
+            TORCH_CHECK(t.is_cuda(), GPU_ONLY);
+            TORCH_CHECK(t.device() == params[0].device(), "expected all tensors on ", params[0].device(), ", got one on ", t.device());
+            TORCH_CHECK(t.scalar_type() == torch::kFloat32, "expected float32 tensor, got ", t.scalar_type());
+            TORCH_CHECK(t.is_contiguous(), "dense_adam: tensor ", k, ": ", names[j], " must be contiguous (it is updated in place)");
+            TORCH_CHECK(t.sizes() == params[k].sizes(), "dense_adam: tensor ", k, ": ", names[j], " has shape ", t.sizes(), ", param has ", params[k].sizes());
+        }
+        const double* c = &coefs[8 * k];
+        table[k] = StpDenseAdamTensor{params[k].data_ptr<float>(), grads[k].data_ptr<float>(), exp_avgs[k].data_ptr<float>(), exp_avg_sqs[k].data_ptr<float>(),
+                                      (long long)params[k].numel(), (float)c[0], (float)c[1], (float)c[2], (float)c[3], (float)c[4], (float)c[5], (float)c[6],
+                                      (int32_t)reg_kinds[k], (float)c[7]};
+    }
+    const torch::Device dev = params[0].device();
+    const c10::hip::HIPGuard guard(dev.index());
+    return checked(g_api.dense_adam((int)n, table.data(), current_stream(dev)));
+}
+
 // == the 3DGS-MCMC kernels (extension, include/stp_raster.h: stp_mcmc_relocation / stp_mcmc_add_noise; compute_relocation and mcmc_add_noise_ in
 // __init__.py).
 // -> (opacity_new of opacity_old's shape, scale_new (n, 3)); upstream's name and argument order.  binoms: checked for its shape only -- the kernel

@@ -40,6 +40,7 @@
     X(activate_params, false, "raw parameter inputs")                                      \
     X(set_forward_sh_stash, false, "the SH stash") /* (a library with it also takes NULL for dL_dcolor / dL_dcov3D) */ \
     X(sparse_adam, false, "the sparse Adam step")                                          \
+    X(dense_adam, false, "the dense Adam step")                                            \
     X(mcmc_relocation, false, "the 3DGS-MCMC kernels")                                     \
     X(mcmc_add_noise, false, "the 3DGS-MCMC kernels")                                      \
     X(mcmc_relocate_scratch_bytes, false, "the 3DGS-MCMC relocation kernels")              \

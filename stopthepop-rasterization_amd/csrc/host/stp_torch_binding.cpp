@@ -22,6 +22,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward);
     m.def("mark_visible", &mark_visible);
     m.def("sparse_adam", &sparse_adam);
+    m.def("dense_adam", &dense_adam);
     m.def("compute_relocation", &compute_relocation);
     m.def("mcmc_add_noise", &mcmc_add_noise);
     m.def("mcmc_sample", &mcmc_sample);

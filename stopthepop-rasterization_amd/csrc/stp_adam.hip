@@ -30,6 +30,18 @@
 // compiles in this toolchain to the hardware's approximate v_sqrt_f32 between two v_ldexp_f32 (a denormal v is scaled up first) without a
 // refinement step, as stp_densify.hip's comment says of it.  The step's bits are pinned as they are (the kernel has about 180 VALU slots per element at
 // the HBM rate and uses a fraction); a denormal v or denominator is handled like any other value.
+//
+// The DENSE step of stp_dense_adam (dense_adam_kernel, below the sparse one; the step of GaussianAdam, a drop-in for the bias-corrected
+// torch.optim.Adam a 3DGS or 3DGS-MCMC trainer constructs) has the same unit geometry -- ROW_BLOCK threads, four 16-byte pieces per thread
+// and stream, 4096 elements per unit, the tail numel % 4 with the first threads of the last unit, one float per access where a pointer is
+// not 16-byte aligned -- and needs no visibility, no row index and no adam_div.  Per element
+//     g' = g + r      m <- b1 m + omb1 g'      v <- b2 v + omb2 g' g'      p <- p - (step_size m) / (sqrt(v) / bias2_sqrt + eps)
+// with r = 0, c s (1 - s) (s = the sigmoid of stp_activations.h: the gradient of c * sum sigmoid(p)) or c exp(p) (of c * sum exp(p)): the two
+// 3DGS-MCMC regularisers, folded in.  Every coefficient comes from the host, formed in float64 and rounded once (omb = 1 - beta from the
+// unrounded beta: torch's convention, which the sparse kernel's in-kernel 1.0f - b is not), per tensor.  The g stream is only read.  Both
+// divisions are the correctly rounded one; the root is the same __fsqrt_rn as above, the approximate v_sqrt_f32 between two v_ldexp_f32,
+// and the step's bits are pinned as they are.  No atomics, no LDS, no scratch; equal inputs give equal bits, on either path.
+#include "stp_activations.h"
 #include "stp_internal.h"
 #include "stp_row_table.h"
 
@@ -148,7 +160,128 @@ __global__ void __launch_bounds__(ADAM_BLOCK) sparse_adam_kernel(const AdamTable
     }
 }
 
+// ---- the dense, bias-corrected step (stp_dense_adam) ----
+struct DenseAdamCoef { float b1, omb1, b2, omb2, step_size, bias2_sqrt, eps, reg_coef; };
+struct DenseAdamDesc {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    uint32_t numel;
+    uint32_t first_unit; // of this tensor among the launch's units
+    uint32_t wide;       // 16-byte accesses (all four pointers aligned)
+    int32_t reg_kind;    // 0: none, 1: sigmoid, 2: exp
+    DenseAdamCoef c;
+};
+struct DenseAdamTable {
+    DenseAdamDesc t[ROW_TABLE_ENTRIES];
+};
+
+// one element's step, the one both paths call (every operation a correctly rounded one that no contraction setting can merge, expf and
+// the root excepted); reg_kind is uniform over the workgroup
+__device__ __forceinline__ void dense_adam_element(float& p, const float g, float& m, float& v, const DenseAdamCoef& c, const int reg_kind)
+{
+    float r = 0.0f;
+    if (reg_kind == 1) {
+        const float s = activate_opacity(p);
+        r = __fmul_rn(c.reg_coef, __fmul_rn(s, __fsub_rn(1.0f, s)));
+    } else if (reg_kind == 2) {
+        r = __fmul_rn(c.reg_coef, activate_scale(p));
+    }
+    const float gr = __fadd_rn(g, r);
+    m = __fmaf_rn(c.b1, m, __fmul_rn(c.omb1, gr));
+    v = __fmaf_rn(__fmul_rn(c.omb2, gr), gr, __fmul_rn(c.b2, v));
+    const float den = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), c.bias2_sqrt), c.eps);
+    p = __fsub_rn(p, __fdiv_rn(__fmul_rn(c.step_size, m), den));
+}
+
+__global__ void __launch_bounds__(ADAM_BLOCK) dense_adam_kernel(const DenseAdamTable table, const int n_tensors)
+{
+    const uint32_t unit = blockIdx.x;
+    const DenseAdamDesc& d = row_table_entry(table, n_tensors, unit);
+    const uint32_t numel = d.numel;
+    const DenseAdamCoef c = d.c;
+    const int kind = d.reg_kind;
+    float* __restrict__ const P = d.p;
+    const float* __restrict__ const G = d.g;
+    float* __restrict__ const Mo = d.m;
+    float* __restrict__ const V = d.v;
+    const uint32_t base = (unit - d.first_unit) * ADAM_UNIT; // < numel < 2^31
+    const uint32_t tid = threadIdx.x;
+
+    if (d.wide) {
+        const uint32_t numel4 = numel & ~3u;
+#pragma unroll
+        for (int k = 0; k < ADAM_PIECES; k++) {
+            const uint32_t e0 = base + 4u * (tid + (uint32_t)k * ADAM_BLOCK);
+            if (e0 >= numel4) break; // (e0 + 3 < numel4 <= numel: whole pieces only)
+            const uint32_t q = e0 >> 2;
+            f32x4 p = reinterpret_cast<f32x4*>(P)[q], m = reinterpret_cast<f32x4*>(Mo)[q], v = reinterpret_cast<f32x4*>(V)[q];
+            const f32x4 g = reinterpret_cast<const f32x4*>(G)[q];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                float pj = p[j], mj = m[j], vj = v[j];
+                dense_adam_element(pj, g[j], mj, vj, c, kind);
+                p[j] = pj;
+                m[j] = mj;
+                v[j] = vj;
+            }
+            reinterpret_cast<f32x4*>(P)[q] = p;
+            reinterpret_cast<f32x4*>(Mo)[q] = m;
+            reinterpret_cast<f32x4*>(V)[q] = v;
+        }
+        // the tensor's last numel % 4 elements: threads 0 .. 2 of its last unit
+        const uint32_t e = numel4 + tid;
+        if (e < numel && numel - base <= ADAM_UNIT) {
+            float pj = P[e], mj = Mo[e], vj = V[e];
+            dense_adam_element(pj, G[e], mj, vj, c, kind);
+            P[e] = pj;
+            Mo[e] = mj;
+            V[e] = vj;
+        }
+    } else {
+#pragma unroll 4
+        for (int k = 0; k < ADAM_PIECES * 4; k++) {
+            const uint32_t e = base + tid + (uint32_t)k * ADAM_BLOCK;
+            if (e >= numel) break;
+            float pj = P[e], mj = Mo[e], vj = V[e];
+            dense_adam_element(pj, G[e], mj, vj, c, kind);
+            P[e] = pj;
+            Mo[e] = mj;
+            V[e] = vj;
+        }
+    }
+}
+
 } // namespace
+
+int launch_dense_adam(int n_tensors, const StpDenseAdamTensor* tensors, hipStream_t st, hipError_t* err)
+{
+    *err = hipSuccess;
+    int launches = 0;
+    for (int next = 0; next < n_tensors;) {
+        DenseAdamTable table{};
+        int n = 0;
+        uint32_t units = 0;
+        for (; next < n_tensors && n < ROW_TABLE_ENTRIES; next++) {
+            const StpDenseAdamTensor& t = tensors[next];
+            if (t.numel == 0) continue;
+            DenseAdamDesc& d = table.t[n++];
+            d.p = t.param; d.g = t.grad; d.m = t.exp_avg; d.v = t.exp_avg_sq;
+            d.numel = (uint32_t)t.numel;
+            d.first_unit = units;
+            d.wide = aligned16(t.param, t.grad, t.exp_avg, t.exp_avg_sq);
+            d.reg_kind = t.reg_kind;
+            d.c = {t.beta1, t.one_minus_beta1, t.beta2, t.one_minus_beta2, t.step_size, t.bias2_sqrt, t.eps, t.reg_coef};
+            units += (d.numel + ADAM_UNIT - 1) / ADAM_UNIT; // <= 2^19 per tensor
+        }
+        if (n == 0) break;
+        hipLaunchKernelGGL(dense_adam_kernel, dim3(units), dim3(ADAM_BLOCK), 0, st, table, n);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return launches; }
+        launches++;
+    }
+    return launches;
+}
 
 int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind, float beta1, float beta2,
                        hipStream_t st, hipError_t* err)

@@ -7,6 +7,7 @@
 // per-device helpers are created once behind a lock (here: the background-gradient scratch ring).
 #include "stp_internal.h"
 
+#include <cmath>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -420,6 +421,32 @@ int stp_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const vo
     hipError_t e;
     const int launches = launch_sparse_adam(n_tensors, tensors, N, visible, visible_kind, beta1, beta2, (hipStream_t)stream, &e);
     if (e != hipSuccess) return fail_hip(e, "sparse_adam launch");
+    return launches;
+}
+
+int stp_dense_adam(int n_tensors, const StpDenseAdamTensor* tensors, void* stream)
+{
+    // everything is checked before the first launch: a refused call has updated nothing
+    if (n_tensors < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_dense_adam: negative count");
+    if (n_tensors > 0 && !tensors) return fail(STP_ERR_INVALID_ARGUMENT, "stp_dense_adam: null tensor table");
+    bool any = false;
+    for (int k = 0; k < n_tensors; k++) {
+        const StpDenseAdamTensor& t = tensors[k];
+        const std::string which = "stp_dense_adam: tensor " + std::to_string(k);
+        if (t.numel < 0) return fail(STP_ERR_INVALID_ARGUMENT, which + ": negative numel");
+        if (t.numel >= (1ll << 31)) return fail(STP_ERR_INVALID_ARGUMENT, which + ": numel " + std::to_string(t.numel) + " >= 2^31");
+        if (t.numel == 0) continue; // (nothing of an entry without elements is looked at)
+        if (t.reg_kind < 0 || t.reg_kind > 2)
+            return fail(STP_ERR_INVALID_ARGUMENT, which + ": unknown reg_kind " + std::to_string(t.reg_kind) + " (0: none, 1: sigmoid, 2: exp)");
+        if (!(t.bias2_sqrt > 0.0f) || !std::isfinite(t.bias2_sqrt))
+            return fail(STP_ERR_INVALID_ARGUMENT, which + ": bias2_sqrt " + std::to_string(t.bias2_sqrt) + " is not a positive finite number");
+        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) return fail(STP_ERR_INVALID_ARGUMENT, which + ": null pointer");
+        any = true;
+    }
+    if (!any) return 0;
+    hipError_t e;
+    const int launches = launch_dense_adam(n_tensors, tensors, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "dense_adam launch");
     return launches;
 }
 

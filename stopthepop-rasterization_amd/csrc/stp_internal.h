@@ -291,6 +291,9 @@ hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmat
 // the launches made, *err = the launch error that ended them early (or hipSuccess)
 int launch_sparse_adam(int n_tensors, const StpAdamTensor* tensors, int N, const void* visible, int visible_kind, float beta1, float beta2,
                        hipStream_t st, hipError_t* err);
+// the fused dense, bias-corrected Adam step (stp_adam.hip: dense_adam_kernel) over tensors stp_dense_adam has validated: one launch per eight
+// tensors with elements; returns the launches made, *err = the launch error that ended them early (or hipSuccess)
+int launch_dense_adam(int n_tensors, const StpDenseAdamTensor* tensors, hipStream_t st, hipError_t* err);
 // the activated copies of a trainer's raw parameters (stp_activate.hip) over arguments stp_activate_params has validated (P in [1, 2^31 / 4)); any
 // of the three pairs may be nullptr together: one launch per pair given; returns the launches made, *err = the launch error (or hipSuccess)
 int launch_activate_params(int P, const float* scaling, const float* rotation, const float* opacity, float* scales, float* rotations, float* opacities,

@@ -58,6 +58,7 @@ _OPTIONAL_SYMBOLS = {
     "stp_geometry_buffer_size_stash": ([ctypes.c_int, ctypes.POINTER(StpSettings)], ctypes.c_size_t, "the SH stash"),
     "stp_sparse_adam": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
                         ctypes.c_int, "the sparse Adam step"),
+    "stp_dense_adam": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int, "the dense Adam step"),
     "stp_mcmc_relocation": ([ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3, ctypes.c_int, "the 3DGS-MCMC kernels"),
     "stp_mcmc_add_noise": ([ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_float] * 3 + [ctypes.c_int, ctypes.c_void_p], ctypes.c_int, "the 3DGS-MCMC kernels"),
     "stp_mcmc_relocate_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t, "the 3DGS-MCMC relocation kernels"),
@@ -505,6 +506,29 @@ def adamUpdate(param, grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps, N, M)
     if int(N) * int(M) != param.numel():
         raise RuntimeError(f"adamUpdate: param has {param.numel()} elements, N * M = {int(N) * int(M)}")
     sparse_adam([param], [grad], [exp_avg], [exp_avg_sq], visible, [lr], [eps], b1, b2, N)
+
+
+DENSE_ADAM_REG_KINDS = {None: 0, "sigmoid": 1, "exp": 2}   # StpDenseAdamTensor.reg_kind
+
+
+def dense_adam_coefficients(lr, beta1, beta2, eps, step, reg_weight=0.0, numel=1):
+    """The eight coefficients of one tensor of stp_dense_adam as float64 values, in StpDenseAdamTensor's order: beta1, 1 - beta1, beta2, 1 - beta2,
+    step_size = lr / (1 - beta1^step), bias2_sqrt = sqrt(1 - beta2^step), eps, reg_coef = reg_weight / numel.  Formed from the Python values as
+    torch.optim.Adam forms them (1 - beta from the unrounded beta); the binding rounds each to float32 once.  step: the count AFTER this step."""
+    beta1, beta2, step = float(beta1), float(beta2), float(step)
+    return (beta1, 1.0 - beta1, beta2, 1.0 - beta2, float(lr) / (1.0 - beta1 ** step), (1.0 - beta2 ** step) ** 0.5, float(eps),
+            float(reg_weight) / max(int(numel), 1))
+
+
+def dense_adam(params, grads, exp_avgs, exp_avg_sqs, coefs, reg_kinds) -> int:
+    """The fused dense Adam step (extension, include/stp_raster.h: stp_dense_adam) of all the quadruples (param, grad, exp_avg, exp_avg_sq) in
+    ONE library call on the current stream: every element takes  g' = g + r,  m <- b1 m + (1 - b1) g',  v <- b2 v + (1 - b2) g' g',
+    p <- p - step_size m / (sqrt(v) / bias2_sqrt + eps)  in place, with r = 0, reg_coef s (1 - s) (s = sigmoid(p)) or reg_coef exp(p).
+    coefs: one dense_adam_coefficients() tuple per tensor; reg_kinds: 0, 1 (sigmoid) or 2 (exp) per tensor.  grads are only read.  Returns the
+    kernel launches made (one per eight tensors with elements)."""
+    _require("stp_dense_adam")
+    flat = [float(x) for c in coefs for x in c]
+    return int((_host or _native()).dense_adam(list(params), list(grads), list(exp_avgs), list(exp_avg_sqs), flat, [int(k) for k in reg_kinds]))
 
 
 RELOCATION_N_MAX = 51   # upstream's N_max: N is clamped to [1, N_max - 1]

@@ -25,7 +25,7 @@ import torch.nn as nn
 from . import _C
 
 __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes", "SortSettings", "CullingSettings",
-           "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam",
+           "ExtendedSettings", "GaussianRasterizationSettings", "GaussianRasterizer", "SparseGaussianAdam", "GaussianAdam",
            "photometric_terms", "fused_ssim", "photometric_loss", "training_terms", "training_loss", "compute_relocation", "mcmc_add_noise_",
            "knn_mean_dist2", "distCUDA2", "dist_cuda2", "activate_params",
            "densification_stats_", "densify_plan", "densify_tensors", "densify_and_prune",
@@ -646,6 +646,140 @@ class SparseGaussianAdam(torch.optim.Adam):
             lrs.append(float(group["lr"]))
             epss.append(float(group["eps"]))
         self.last_launches = _C.sparse_adam(params, grads, exp_avgs, exp_avg_sqs, visibility, lrs, epss, betas[0], betas[1], N) if params else 0
+
+
+class GaussianAdam(torch.optim.Adam):
+    """torch.optim.Adam -- dense, bias-corrected, as the 3DGS trainer (optimizer_type "default") and every 3DGS-MCMC trainer construct it --
+    whose step is one fused kernel launch per eight tensors, with the two 3DGS-MCMC regularisers folded in (extension;
+    include/stp_raster.h: stp_dense_adam).  A trainer changes the class name only:
+
+        opt = GaussianAdam([{"params": [xyz], "lr": ..., "name": "xyz"}, ...], lr=0.0, eps=1e-15)
+        opt.set_regularizer("opacity", "sigmoid", opacity_reg)     # instead of  loss += opacity_reg * sigmoid(_opacity).abs().mean()
+        opt.set_regularizer("scaling", "exp", scale_reg)           # instead of  loss += scale_reg * exp(_scaling).abs().mean()
+        ...
+        opt.step()
+
+    For every tensor with a gradient, all groups in one call, every element in float32 (t = the tensor's step count after this step):
+        g' = g + r      m <- b1 m + (1 - b1) g'      v <- b2 v + (1 - b2) g' g'
+        p <- p - (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+    with r = 0, or for a group whose "reg" is ("sigmoid", w): r = (w / numel) s (1 - s), s = sigmoid(p) -- the gradient of w * sigmoid(p).mean()
+    -- or ("exp", w): r = (w / numel) exp(p), the gradient of w * exp(p).mean().  .grad is only read.  The regulariser's VALUE is not computed:
+    a trainer that logs it computes it itself.  Coefficients are formed in float64 from the Python values, as torch forms them, and rounded to
+    float32 once.  A group may hold any number of tensors; lr, eps, betas and "reg" are the group's, read at every step.
+    The state is non-capturable torch.optim.Adam's -- state[p]["step"] a CPU float32 scalar tensor, ["exp_avg"] and ["exp_avg_sq"] zeros_like(p),
+    created by the first step that finds a gradient -- so state_dict() / load_state_dict() (to and from a torch.optim.Adam), densify_and_prune,
+    mcmc_relocate_, mcmc_add_new and a trainer's own state surgery keep working.  No weight decay, amsgrad, maximize, capturable, differentiable,
+    fused or foreach option and no tensor lr (ValueError at construction).  A step is refused as a whole (RuntimeError naming the tensor, nothing
+    updated, no step counted) for a CPU tensor, a dtype other than float32, a sparse gradient, a non-contiguous param, grad or state, and tensors on
+    different devices.  `last_launches` holds the kernel launches of the latest step."""
+
+    _REFUSED = ("weight_decay", "amsgrad", "maximize", "capturable", "differentiable", "fused", "foreach")
+    _REG_KINDS = ("sigmoid", "exp")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, **options):
+        for name, value in options.items():
+            if name not in self._REFUSED:
+                raise TypeError(f"GaussianAdam got an unexpected option {name!r}")
+            self._refuse(name, value)
+        self._refuse_tensor_lr(lr)
+        super().__init__(params=params, lr=lr, betas=betas, eps=eps)
+        for group in self.param_groups:   # (options can also ride in a group's dict)
+            for name in self._REFUSED:
+                self._refuse(name, group.get(name))
+            self._refuse_tensor_lr(group["lr"])
+            self._reg_of(group)
+        self.last_launches = 0
+
+    @staticmethod
+    def _refuse(name, value):
+        if value is not None and value is not False and value != 0:
+            raise ValueError(f"GaussianAdam does not support {name} (got {name}={value!r}): the fused step is plain bias-corrected Adam")
+
+    @staticmethod
+    def _refuse_tensor_lr(lr):
+        if isinstance(lr, torch.Tensor):
+            raise ValueError("GaussianAdam does not support a tensor lr: the learning rate travels in the kernel arguments as a host number")
+
+    @classmethod
+    def _reg_of(cls, group):
+        """-> (reg_kind of the C ABI, weight) of a group's "reg": None or (kind, weight)"""
+        reg = group.get("reg")
+        if reg is None:
+            return 0, 0.0
+        if not (isinstance(reg, (tuple, list)) and len(reg) == 2 and reg[0] in cls._REG_KINDS):
+            raise ValueError(f"GaussianAdam: group {group.get('name', '?')!r}: reg must be None or (kind, weight) with kind in {cls._REG_KINDS}, got {reg!r}")
+        return _C.DENSE_ADAM_REG_KINDS[reg[0]], float(reg[1])
+
+    def set_regularizer(self, name, kind, weight=0.0):
+        """The group whose "name" is `name` gets "reg" = (kind, weight), kind in {"sigmoid", "exp"}, or None for kind None: from the next step on
+        the gradient of weight * mean(sigmoid(p)) or weight * mean(exp(p)) (the mean over each tensor's numel) is added to the tensor's inside the kernel."""
+        found = [g for g in self.param_groups if g.get("name") == name]
+        if len(found) != 1:
+            raise ValueError(f"GaussianAdam.set_regularizer: {len(found)} groups are named {name!r}")
+        old = found[0].get("reg")
+        found[0]["reg"] = None if kind is None else (kind, float(weight))
+        try:
+            self._reg_of(found[0])
+        except ValueError:
+            found[0]["reg"] = old
+            raise
+
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        # validate first ...
+        work, placed, device = [], [], None
+        for gi, group in enumerate(self.param_groups):
+            for name in self._REFUSED:
+                self._refuse(name, group.get(name))
+            self._refuse_tensor_lr(group["lr"])
+            kind, weight = self._reg_of(group)
+            beta1, beta2 = group["betas"]
+            for ti, param in enumerate(group["params"]):
+                grad = param.grad
+                if grad is None or param.numel() == 0:   # (nothing to step: no state is created, none is touched)
+                    continue
+                who = f"GaussianAdam.step: group {group.get('name', gi)!r} tensor {ti}"
+                state = self.state[param] if param in self.state else {}   # (no entry is created before the step is accepted)
+                if grad.is_sparse or grad.layout != torch.strided:
+                    raise RuntimeError(f"{who}: sparse gradients are not supported")
+                named = [("param", param), ("grad", grad)] + [(k, state[k]) for k in ("exp_avg", "exp_avg_sq") if len(state)]
+                for label, t in named:   # (what is wrong with the tensors themselves first, where they live last)
+                    if t.dtype != torch.float32:
+                        raise RuntimeError(f"{who}: {label}: expected float32, got {t.dtype}")
+                    if not t.is_contiguous():
+                        raise RuntimeError(f"{who}: {label} must be contiguous (it is updated in place)")
+                    if t.shape != param.shape:
+                        raise RuntimeError(f"{who}: {label} has shape {tuple(t.shape)}, param has {tuple(param.shape)}")
+                work.append((param, group, kind, weight, float(beta1), float(beta2)))
+                placed.append((who, named))
+        for who, named in placed:
+            for label, t in named:
+                if not t.is_cuda:
+                    raise RuntimeError(f"{who}: {label} is on {t.device}: there is no CPU path")
+                device = device or t.device
+                if t.device != device:
+                    raise RuntimeError(f"{who}: {label} is on {t.device}, earlier tensors on {device}: one step serves one device")
+        # ... count after
+        params, grads, exp_avgs, exp_avg_sqs, coefs, kinds = [], [], [], [], [], []
+        with torch.no_grad():
+            for param, group, kind, weight, beta1, beta2 in work:
+                state = self.state[param]
+                if len(state) == 0:   # created as non-capturable torch.optim.Adam creates it
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(param, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(param, memory_format=torch.preserve_format)
+                state["step"] += 1
+                params.append(param)
+                grads.append(param.grad)
+                exp_avgs.append(state["exp_avg"])
+                exp_avg_sqs.append(state["exp_avg_sq"])
+                coefs.append(_C.dense_adam_coefficients(group["lr"], beta1, beta2, group["eps"], float(state["step"]), weight, param.numel()))
+                kinds.append(kind)
+            self.last_launches = _C.dense_adam(params, grads, exp_avgs, exp_avg_sqs, coefs, kinds) if params else 0
+        return loss
 
 
 class _PhotometricTerms(torch.autograd.Function):
