@@ -3,7 +3,7 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam|gaussian_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--relocate torch|fused] [--cap-max N] [--split-sh] [--raw-params] [--init-scales scene|knn]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam|gaussian_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--relocate torch|fused] [--cap-max N] [--split-sh] [--raw-params] [--init-scales scene|knn] [--reorder N]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
@@ -25,7 +25,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "stopthepop-rasterization_amd"))
 from diff_gaussian_rasterization import (CullingSettings, ExtendedSettings, GaussianRasterizationSettings,  # noqa: E402
                                          GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, GaussianAdam, SparseGaussianAdam, compute_relocation,
-                                         densification_stats_, densify_and_prune, densify_plan, mcmc_add_new, mcmc_add_noise_, mcmc_relocate_, scenes, training_loss, training_terms)
+                                         densification_stats_, densify_and_prune, densify_plan, mcmc_add_new, mcmc_add_noise_, mcmc_relocate_, reorder_gaussians_, scenes, training_loss, training_terms)
 
 
 def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, scaling_modifier: float = 1.0,
@@ -203,6 +203,9 @@ def main(argv=None):
                     help="knn: the model's initial _scaling comes from the points alone, as the trainers' GaussianModel.create_from_pcd sets it: "
                          "log(sqrt(clamp_min(distCUDA2(xyz), 1e-7))) on all three axes, with `from simple_knn._C import distCUDA2` "
                          "(INTEGRATION.md section 3p)")
+    ap.add_argument("--reorder", type=int, default=0, metavar="N",
+                    help="every N iterations re-sort the model along the Morton curve of its positions: reorder_gaussians_ moves every tensor, both "
+                         "Adam moments and the densification statistics in one gather (INTEGRATION.md section 3u)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
@@ -237,7 +240,7 @@ def main(argv=None):
         opt = GaussianAdam([*model.feature_groups(2e-2), {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
                             {"params": [model._xyz], "lr": 0.0, "name": "xyz"}, {"params": [model._scaling], "lr": 0.0, "name": "scaling"},
                             {"params": [model._rotation], "lr": 0.0, "name": "rotation"}], lr=0.0, eps=1e-15)
-    elif (adc or fused_mcmc) and args.optimizer != "sparse_adam":   # densify_and_prune and mcmc_relocate_ want the trainers' layout: one named group per tensor
+    elif (adc or fused_mcmc or args.reorder > 0) and args.optimizer != "sparse_adam":   # densify_and_prune, mcmc_relocate_ and reorder_gaussians_ want the trainers' layout: one named group per tensor
         opt = torch.optim.Adam([*model.feature_groups(2e-2), {"params": [model._opacity], "lr": 5e-2, "name": "opacity"},
                                 {"params": [model._xyz], "lr": 0.0, "name": "xyz"}, {"params": [model._scaling], "lr": 0.0, "name": "scaling"},
                                 {"params": [model._rotation], "lr": 0.0, "name": "rotation"}], lr=0.0, eps=1e-15)
@@ -348,6 +351,15 @@ def main(argv=None):
                 relocations += 1
             # xyz += Sigma (randn * op_sigmoid(1 - opacity) * noise_lr * xyz_lr) in one kernel, from the raw parameters the step just moved
             mcmc_add_noise_(model._xyz, model._scaling, model._rotation, model._opacity, torch.randn_like(model._xyz), noise_scale, raw=True)
+        if args.reorder > 0 and it > 0 and it % args.reorder == 0:
+            # rows that densification appended or relocation rewrote lie anywhere: every so often the model goes back into the Morton order of its
+            # positions.  One gather moves every group's tensor, both Adam moments and the per-Gaussian statistics; the model takes the new
+            # Parameters as after densify_and_prune.  (`out` of this iteration indexes the old rows: it is not used below this point.)
+            new, order, (stat_signed, stat_abs, stat_denom, stat_radii, abs_denom) = reorder_gaussians_(
+                opt, extra=[stat_signed, stat_abs, stat_denom, stat_radii, abs_denom])
+            model.take_features(new)
+            model._opacity, model._xyz, model._scaling, model._rotation = (new[n] for n in ("opacity", "xyz", "scaling", "rotation"))
+            print(f"iter {it:3d}  reorder: {order.numel()} rows into Morton order")
         if adc and it > 0 and it % 10 == 0:
             # upstream's densify_and_prune: the decision as one byte per Gaussian, then one scan and one apply over every tensor and both
             # Adam moments; the optimizer's groups get the new Parameters and the model takes them from the returned dict

@@ -561,6 +561,41 @@ int stp_densify_apply(int P, const uint8_t* plan, const uint32_t* offsets, const
 size_t stp_knn_scratch_bytes(int P);
 int stp_knn_mean_dist2(int P, const float* points /* P x 3 */, void* scratch, size_t scratch_bytes, float* mean_dist2 /* P */, void* stream);
 
+/* Extension (not in the reference): the Morton order of a cloud, and the gather that moves a model into it (or into any other order).
+   Densification and 3DGS-MCMC growth append rows and relocation rewrites rows anywhere, so after some thousand iterations a row's index
+   says nothing about where its Gaussian lies; a trainer that wants neighbours in space to be neighbours in memory re-sorts every so often.
+   stp_spatial_order: order[s] is the index of the row of `xyz` (P x 3 contiguous float32 on the device) that moves to position s, and
+   codes[s] (where not null) the 30-bit code of that row.  It is the order stp_knn_mean_dist2 searches in (the same kernels), and it is
+   fixed to the bit.  Per axis a:
+       key_a(i) = the bits of xyz[i][a] as an unsigned integer of the same order (negative: ~bits, else bits | 2^31; -0 sorts below +0, the
+                  infinities lie at the ends)
+       sorted_a = the keys in ascending order          splitter_a[k - 1] = sorted_a[floor(k P / 1024)], k = 1 .. 1023
+       cell_a(i) = the number of splitters <= key_a(i), in 0 .. 1023
+   cells of equal COUNT, not of equal width: outliers take no cells from the rest, a cluster gets as many as it has points for.  Then
+       code(i) = spread10(cell_x) | spread10(cell_y) << 1 | spread10(cell_z) << 2          (spread10: bit b of 10 goes to bit 3 b)
+   and order is the STABLE ascending sort of (code, i): equal codes stay in index order.  The codes depend on the multiset of coordinates
+   only, so the order of an already ordered cloud is the identity.  P >= 1 is accepted.  The caller's stream only, no host synchronisation,
+   no atomics; `scratch` is stp_spatial_order_scratch_bytes(P) bytes of device memory, 16-byte aligned, free again when the kernels have run
+   (a function of P alone, 0 for P <= 0, non-decreasing in P, no overflow up to INT_MAX: 16 bytes per point and a little).  Returns the
+   number of launches made (a sort of the library counting as one; 0 for P == 0: nothing is touched), or a negative StpStatus with the
+   reason in the last-error text.  Refused BEFORE anything is launched (STP_ERR_INVALID_ARGUMENT): a negative P, a null xyz, order or
+   scratch, a scratch that is too small or misaligned.
+   stp_gather_rows: for each of n_tensors entries (an StpDensifyTensor by layout: row = 4-byte elements per row, role must be 0, exp_avg and
+   exp_avg_sq both given or both null, and then their outputs too) output row s, 0 <= s < M, of param_out, exp_avg_out and exp_avg_sq_out
+   is row index[s] of the P input rows, copied bit for bit: the elements are moved, never computed on, and may as well be int32 or NaN
+   payloads.  index may be a permutation (M == P), a subset, or hold repeats (M > P).  AN INDEX OUTSIDE [0, P) IS READ AS THE NEAREST VALID
+   ROW (0 or P - 1): the kernel never reads out of bounds, and never reports it.  Out of place only: an output that overlaps any input of
+   the call (a tensor, a moment or the index) is refused.  A tensor whose rows are multiples of 16 bytes and whose six pointers are all
+   16-byte aligned moves 16 bytes per lane, others one element at a time, with equal bits.  Up to eight entries go in one launch.  Returns
+   the number of launches made (0 for M == 0 or n_tensors == 0: nothing is touched) or a negative StpStatus.  Refused BEFORE anything is
+   launched (STP_ERR_INVALID_ARGUMENT): a negative P or M, M > 0 rows from P == 0, a null pointer, more than 64 entries, row <= 0,
+   max(P, M) * row >= 2^31, a role other than 0, one moment pointer without the other, an overlap. */
+typedef StpDensifyTensor StpGatherTensor;
+size_t stp_spatial_order_scratch_bytes(int P);
+int stp_spatial_order(int P, const float* xyz /* P x 3 */, void* scratch, size_t scratch_bytes, int32_t* order /* P */, uint32_t* codes /* P, may be null */,
+                      void* stream);
+int stp_gather_rows(int P, int M, const int32_t* index /* M */, int n_tensors, const StpGatherTensor* tensors, void* stream);
+
 /* Extension (not in the reference): the fused photometric loss of 3DGS trainers, (1 - lambda) * L1 + lambda * (1 - SSIM) -- upstream's
    l1_loss and ssim() with window_size = 11 and size_average = True, the pair the `fused-ssim` extension replaces.  `image` (x) and `target`
    (y) are `planes` contiguous float32 planes of H x W (a (C, H, W) or (B, C, H, W) tensor: planes = B * C), n = planes * H * W.  With

@@ -415,6 +415,102 @@ torch::Tensor knn_mean_dist2(const torch::Tensor& points_in)
     return out;
 }
 
+// == the Morton order of a cloud (extension, include/stp_raster.h: stp_spatial_order; spatial_order in __init__.py), on the caller's current stream:
+// -> (order int32 (P,), codes int32 (P,) or an undefined tensor).  The scratch comes from the caching allocator as knn_mean_dist2's does.  No host
+// synchronisation.
+std::tuple<torch::Tensor, torch::Tensor> spatial_order(const torch::Tensor& xyz_in, const bool return_codes)
+{
+    static const char* const who = "spatial_order";
+    need_library();
+    require(g_api.spatial_order, who);
+    require(g_api.spatial_order_scratch_bytes, who);
+    check_float(who, "xyz", xyz_in);
+    TORCH_CHECK(xyz_in.dim() == 2 && xyz_in.size(1) == 3, who, ": xyz must be (P, 3), got ", xyz_in.sizes());
+    const int64_t P = xyz_in.size(0);
+    TORCH_CHECK(P < (1ll << 31), who, ": xyz: ", P, " rows >= 2^31");
+    check_device(who, "xyz", xyz_in, xyz_in);
+    const torch::Tensor xyz = xyz_in.detach().contiguous();
+    const c10::hip::HIPGuard guard(xyz.device().index());
+    torch::Tensor order = torch::empty({P}, xyz.options().dtype(torch::kInt32)), codes;
+    if (return_codes) codes = torch::empty({P}, xyz.options().dtype(torch::kInt32));
+    if (P == 0) return {order, codes};
+    const size_t bytes = g_api.spatial_order_scratch_bytes((int)P);
+    torch::Tensor scratch = torch::empty({(int64_t)bytes}, xyz.options().dtype(torch::kByte));
+    checked(g_api.spatial_order((int)P, xyz.data_ptr<float>(), scratch.data_ptr(), bytes, order.data_ptr<int32_t>(),
+                                return_codes ? reinterpret_cast<uint32_t*>(codes.data_ptr<int32_t>()) : nullptr, current_stream(xyz.device())));
+    return {order, codes};
+}
+
+// == the gather of rows (extension, include/stp_raster.h: stp_gather_rows; gather_tensors and reorder_gaussians_ in __init__.py): -> (new tensors,
+// new exp_avgs, new exp_avg_sqs) of index.size(0) rows, lists as long as `tensors`, the moment lists holding None where none was given.  Tensor k is
+// float32 or int32 (P, ...) of any trailing shape -- the rows are moved as bits -- and its moments have its dtype and shape.  No host synchronisation.
+std::tuple<std::vector<torch::Tensor>, std::vector<c10::optional<torch::Tensor>>, std::vector<c10::optional<torch::Tensor>>>
+gather_rows(const torch::Tensor& index_in, const std::vector<torch::Tensor>& tensors, const std::vector<c10::optional<torch::Tensor>>& exp_avgs,
+            const std::vector<c10::optional<torch::Tensor>>& exp_avg_sqs)
+{
+    static const char* const who = "gather_tensors";
+    need_library();
+    require(g_api.gather_rows, who);
+    const size_t n = tensors.size();
+    TORCH_CHECK(index_in.defined() && index_in.scalar_type() == torch::kInt32, who, ": index: expected an int32 tensor");
+    TORCH_CHECK(index_in.dim() == 1, who, ": index must be (M,), got ", index_in.sizes());
+    TORCH_CHECK(exp_avgs.size() == n && exp_avg_sqs.size() == n, who, ": tensors, exp_avgs and exp_avg_sqs must have one entry per tensor");
+    TORCH_CHECK(n <= 64, who, ": ", n, " tensors, at most 64 in one call");
+    const int64_t M = index_in.size(0), P = n > 0 && tensors[0].defined() && tensors[0].dim() >= 1 ? tensors[0].size(0) : 0;
+    for (size_t k = 0; k < n; k++) {
+        const torch::Tensor& t = tensors[k];
+        TORCH_CHECK(t.defined(), who, ": tensor ", k, " is undefined");
+        TORCH_CHECK(t.scalar_type() == torch::kFloat32 || t.scalar_type() == torch::kInt32, who, ": tensor ", k, ": expected float32 or int32 tensor, got ", t.scalar_type());
+        TORCH_CHECK(t.dim() >= 1 && t.size(0) == P, who, ": tensor ", k, " must have ", P, " rows (tensor 0's), got ", t.sizes());
+        TORCH_CHECK(P == 0 || t.numel() > 0, who, ": tensor ", k, ": rows without elements, ", t.sizes());
+        TORCH_CHECK(exp_avgs[k].has_value() == exp_avg_sqs[k].has_value(), who, ": tensor ", k, ": exp_avg and exp_avg_sq must both be given or both be None");
+        if (exp_avgs[k].has_value())
+            for (const torch::Tensor* m : {&*exp_avgs[k], &*exp_avg_sqs[k]}) {
+                TORCH_CHECK(m->defined() && m->scalar_type() == t.scalar_type(), who, ": tensor ", k, ": moments: expected ", t.scalar_type(), " tensors");
+                TORCH_CHECK(m->sizes() == t.sizes(), who, ": tensor ", k, ": a moment has shape ", m->sizes(), ", the parameter has ", t.sizes());
+            }
+    }
+    TORCH_CHECK(P < (1ll << 31) && M < (1ll << 31), who, ": ", P, " rows, ", M, " indices: >= 2^31");
+    TORCH_CHECK(M == 0 || P > 0 || n == 0, who, ": ", M, " rows from tensors without rows");
+    check_on_gpu(who, "index", index_in);
+    for (size_t k = 0; k < n; k++) {
+        check_device(who, "a tensor", tensors[k], index_in);
+        if (exp_avgs[k].has_value()) {
+            check_device(who, "an exp_avg", *exp_avgs[k], index_in);
+            check_device(who, "an exp_avg_sq", *exp_avg_sqs[k], index_in);
+        }
+    }
+    const torch::Tensor index = index_in.contiguous();
+    const c10::hip::HIPGuard guard(index.device().index());
+    std::vector<torch::Tensor> held, out_p(n); // held: the contiguous inputs, alive until the launches are made
+    std::vector<c10::optional<torch::Tensor>> out_m(n), out_v(n);
+    std::vector<StpGatherTensor> table(n);
+    const auto ptr = [](const torch::Tensor& t) { return static_cast<float*>(t.data_ptr()); }; // (4-byte elements: moved, never computed on)
+    for (size_t k = 0; k < n; k++) {
+        std::vector<int64_t> shape = tensors[k].sizes().vec();
+        int64_t row = 1;
+        for (size_t d = 1; d < shape.size(); d++) row *= shape[d];
+        TORCH_CHECK(P == 0 || (row > 0 && std::max(P, M) * row < (1ll << 31)), who, ": tensor ", k, ": ", std::max(P, M), " rows of ", row, " elements: outside (0, 2^31)");
+        shape[0] = M;
+        held.push_back(tensors[k].detach().contiguous());
+        out_p[k] = torch::empty(shape, held.back().options());
+        table[k] = StpGatherTensor{ptr(held.back()), nullptr, nullptr, ptr(out_p[k]), nullptr, nullptr, (int32_t)row, 0};
+        if (exp_avgs[k].has_value()) {
+            held.push_back(exp_avgs[k]->detach().contiguous());
+            table[k].exp_avg = ptr(held.back());
+            held.push_back(exp_avg_sqs[k]->detach().contiguous());
+            table[k].exp_avg_sq = ptr(held.back());
+            out_m[k] = torch::empty(shape, held.back().options());
+            out_v[k] = torch::empty(shape, held.back().options());
+            table[k].exp_avg_out = ptr(*out_m[k]);
+            table[k].exp_avg_sq_out = ptr(*out_v[k]);
+        }
+    }
+    if (M == 0 || n == 0 || P == 0) return {out_p, out_m, out_v};
+    checked(g_api.gather_rows((int)P, (int)M, index.data_ptr<int32_t>(), (int)n, table.data(), current_stream(index.device())));
+    return {out_p, out_m, out_v};
+}
+
 // == densification (extension, include/stp_raster.h: stp_densify_stats / _plan / _scan / _apply; densification_stats_, densify_plan,
 // densify_tensors and densify_and_prune in __init__.py).  Only densify_scan synchronises with the host (inside the library: the new row count).
 void densify_check_column(const char* who, const char* name, const torch::Tensor& t, const int64_t P)

@@ -49,6 +49,9 @@
     X(mcmc_add_apply, false, "the 3DGS-MCMC relocation kernels")                           \
     X(knn_scratch_bytes, false, "the nearest-neighbour kernels")                           \
     X(knn_mean_dist2, false, "the nearest-neighbour kernels")                              \
+    X(spatial_order_scratch_bytes, false, "the spatial order kernels")                     \
+    X(spatial_order, false, "the spatial order kernels")                                   \
+    X(gather_rows, false, "the spatial order kernels")                                     \
     X(densify_stats, false, "the densification kernels")                                   \
     X(densify_plan, false, "the densification kernels")                                    \
     X(densify_scratch_bytes, false, "the densification kernels")                           \

@@ -30,6 +30,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("mcmc_add_apply", &mcmc_add_apply);
     m.def("activate_params", &activate_params);
     m.def("knn_mean_dist2", &knn_mean_dist2);
+    m.def("spatial_order", &spatial_order);
+    m.def("gather_rows", &gather_rows);
     m.def("densify_stats", &densify_stats);
     m.def("densify_plan", &densify_plan);
     m.def("densify_scan", &densify_scan);

@@ -11,6 +11,7 @@
 #include <mutex>
 #include <string>
 #include <utility>
+#include <vector>
 
 namespace stp {
 
@@ -570,6 +571,66 @@ int stp_knn_mean_dist2(int P, const float* points, void* scratch, size_t scratch
     hipError_t e;
     const int launches = launch_knn_mean_dist2(P, points, scratch, mean_dist2, (hipStream_t)stream, &e);
     if (e != hipSuccess) return fail_hip(e, "knn_mean_dist2");
+    return launches;
+}
+
+size_t stp_spatial_order_scratch_bytes(int P) { return spatial_order_scratch_bytes(P); }
+
+int stp_spatial_order(int P, const float* xyz, void* scratch, size_t scratch_bytes, int32_t* order, uint32_t* codes, void* stream)
+{
+    // everything is checked before the first launch
+    if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_spatial_order: negative P");
+    if (P == 0) return 0;
+    if (!xyz) return fail(STP_ERR_INVALID_ARGUMENT, "stp_spatial_order: null pointer (xyz)");
+    if (!order) return fail(STP_ERR_INVALID_ARGUMENT, "stp_spatial_order: null pointer (order)");
+    if (!scratch) return fail(STP_ERR_INVALID_ARGUMENT, "stp_spatial_order: null pointer (scratch)");
+    if (const int rc = check_scratch("stp_spatial_order", scratch, scratch_bytes, spatial_order_scratch_bytes(P), 16, "stp_spatial_order_scratch_bytes")) return rc;
+    hipError_t e;
+    const int launches = launch_spatial_order(P, xyz, scratch, order, codes, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "spatial_order");
+    return launches;
+}
+
+// ---- the gather of rows (stp_reorder.hip): everything is checked before the first launch
+static const int GATHER_ROLE_ROWS[1] = {0};
+static const RowRoles GATHER_ROLES = {0, nullptr, GATHER_ROLE_ROWS, "(0 plain: a gather has no other)", "max(P, M)", nullptr};
+
+int stp_gather_rows(int P, int M, const int32_t* index, int n_tensors, const StpGatherTensor* tensors, void* stream)
+{
+    static const char* const who = "stp_gather_rows";
+    if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative P");
+    if (M < 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": negative M");
+    // (the work is flattened over the M output rows, and a source offset is below P * row)
+    if (const int rc = check_row_tensors(who, n_tensors, tensors, P > M ? P : M, GATHER_ROLES, false, M > 0, false)) return rc;
+    if (M == 0 || n_tensors == 0) return 0;
+    if (P == 0) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(M) + " rows from P = 0 rows");
+    if (!index) return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer (index)");
+    // out of place only: no output may overlap an input of the call (a tensor or a moment of ANY entry, or the index)
+    struct Span { uintptr_t lo, hi; int tensor; const char* what; };
+    std::vector<Span> in, out;
+    in.push_back({reinterpret_cast<uintptr_t>(index), reinterpret_cast<uintptr_t>(index) + (uintptr_t)M * sizeof(int32_t), -1, "index"});
+    for (int k = 0; k < n_tensors; k++) {
+        const StpGatherTensor& t = tensors[k];
+        const uintptr_t nin = (uintptr_t)P * t.row * sizeof(float), nout = (uintptr_t)M * t.row * sizeof(float);
+        const auto span = [k](const void* p, uintptr_t n, const char* what) { return Span{reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + n, k, what}; };
+        in.push_back(span(t.param, nin, "param"));
+        out.push_back(span(t.param_out, nout, "param_out"));
+        if (t.exp_avg) {
+            in.push_back(span(t.exp_avg, nin, "exp_avg"));
+            in.push_back(span(t.exp_avg_sq, nin, "exp_avg_sq"));
+            out.push_back(span(t.exp_avg_out, nout, "exp_avg_out"));
+            out.push_back(span(t.exp_avg_sq_out, nout, "exp_avg_sq_out"));
+        }
+    }
+    for (const Span& o : out)
+        for (const Span& i : in)
+            if (o.lo < i.hi && i.lo < o.hi)
+                return fail(STP_ERR_INVALID_ARGUMENT, std::string(who) + ": tensor " + std::to_string(o.tensor) + ": " + o.what + " overlaps " +
+                                                          (i.tensor < 0 ? std::string("the index") : i.what + std::string(" of tensor ") + std::to_string(i.tensor)) +
+                                                          ": the call is out of place only");
+    hipError_t e;
+    const int launches = launch_gather_rows(P, M, index, n_tensors, tensors, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "gather_rows launch");
     return launches;
 }
 

@@ -350,6 +350,14 @@ int launch_training_loss_backward(int planes, int H, int W, const float* image, 
 // them early (or hipSuccess).  knn_scratch_bytes: 0 for P <= 0, non-decreasing in P, no overflow up to INT_MAX.
 size_t knn_scratch_bytes(int P);
 int launch_knn_mean_dist2(int P, const float* points, void* scratch, float* mean_dist2, hipStream_t st, hipError_t* err);
+// the Morton order of a cloud (stp_knn.hip: steps 1-3 of the search above, shared with it) over arguments stp_spatial_order has validated (P in
+// [1, 2^31), a scratch of spatial_order_scratch_bytes(P) bytes, 16-byte aligned; codes may be nullptr): returns the launches made, *err as
+// above.  spatial_order_scratch_bytes: 0 for P <= 0, non-decreasing in P, no overflow up to INT_MAX.
+size_t spatial_order_scratch_bytes(int P);
+int launch_spatial_order(int P, const float* xyz, void* scratch, int32_t* order, uint32_t* codes, hipStream_t st, hipError_t* err);
+// the gather of rows (stp_reorder.hip) over arguments stp_gather_rows has validated (P, M >= 1, P * row and M * row < 2^31, outputs that
+// overlap no input): one launch per eight tensors through launch_row_tables; returns the launches made, *err = the launch error (or hipSuccess)
+int launch_gather_rows(int P, int M, const int32_t* index, int n_tensors, const StpGatherTensor* tensors, hipStream_t st, hipError_t* err);
 
 uint32_t higher_msb(uint32_t n);
 

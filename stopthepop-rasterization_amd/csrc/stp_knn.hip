@@ -28,6 +28,10 @@
 //      shrinks early -- 256 boxes per step, one box-to-box test per lane against the workgroup's largest b2.  The boxes that pass are taken
 //      in order: tested once more against the largest b2 of now (the same value in every lane: no divergence), staged in LDS, and scanned by
 //      every lane whose own point-to-box bound does not exceed its b2.  The result goes to out[original index].
+//
+// stp_spatial_order is steps 1-3 by themselves (launch_morton_order, the one function both calls run) and one kernel that hands the sorted
+// indices -- and, where asked, the sorted codes -- to the caller: the order a trainer re-sorts its model into (stp_reorder.hip moves the rows).
+// There the code IS the result, so include/stp_raster.h fixes it to the bit; it takes clouds from one point on.
 #include "stp_internal.h"
 
 #include <rocprim/rocprim.hpp>
@@ -142,6 +146,16 @@ __global__ void __launch_bounds__(KNN_BLOCK) knn_morton_kernel(const uint32_t P,
     }
     keys[i] = code;
     values[i] = i;
+}
+
+// the result of stp_spatial_order leaves the scratch: order[s] = the row that moves to position s, codes[s] = its code (where asked)
+__global__ void __launch_bounds__(KNN_BLOCK) spatial_order_emit_kernel(const uint32_t P, const uint32_t* __restrict__ sorted_values, const uint32_t* __restrict__ sorted_keys,
+                                                                       int32_t* __restrict__ order, uint32_t* __restrict__ codes)
+{
+    const uint32_t s = blockIdx.x * (uint32_t)KNN_BLOCK + threadIdx.x; // (< 2^31 + 256)
+    if (s >= P) return;
+    order[s] = (int32_t)sorted_values[s];                             // (< P < 2^31)
+    if (codes) codes[s] = sorted_keys[s];
 }
 
 // workgroup b: the records of sorted positions [b * KNN_BOX, ...) and their AABB
@@ -308,17 +322,23 @@ size_t knn_sort_reserve(int P)
     return most;
 }
 
-struct KnnScratch {
+// what steps 1-3 work in: the head of the knn call's scratch, and the whole of stp_spatial_order's
+struct MortonScratch {
     uint32_t* splitters; // 3 x KNN_CELLS
     uint32_t *keys[2], *values[2];
-    f32x4 *records, *box_lo, *box_hi;
     char* sort_temp;
-    size_t sort_temp_bytes, total;
+    size_t sort_temp_bytes;
+};
+struct KnnScratch {
+    MortonScratch m;
+    f32x4 *records, *box_lo, *box_hi;
+    size_t total;
 };
 
-KnnScratch knn_carve(char* base, int P) // P >= 1
+// with_boxes: the records and boxes of the search lie between the sort's buffers and rocPRIM's temporary storage
+KnnScratch knn_carve(char* base, int P, bool with_boxes) // P >= 1
 {
-    KnnScratch s;
+    KnnScratch s{};
     size_t off = 0;
     const auto take = [&](size_t bytes) {
         char* const p = base ? base + off : nullptr;
@@ -326,27 +346,30 @@ KnnScratch knn_carve(char* base, int P) // P >= 1
         return p;
     };
     const size_t n = (size_t)P, boxes = knn_boxes(P);
-    s.splitters = reinterpret_cast<uint32_t*>(take(3 * KNN_CELLS * sizeof(uint32_t)));
-    for (int k = 0; k < 2; k++) s.keys[k] = reinterpret_cast<uint32_t*>(take(n * sizeof(uint32_t)));
-    for (int k = 0; k < 2; k++) s.values[k] = reinterpret_cast<uint32_t*>(take(n * sizeof(uint32_t)));
-    s.records = reinterpret_cast<f32x4*>(take(n * sizeof(f32x4)));
-    s.box_lo = reinterpret_cast<f32x4*>(take(boxes * sizeof(f32x4)));
-    s.box_hi = reinterpret_cast<f32x4*>(take(boxes * sizeof(f32x4)));
-    s.sort_temp_bytes = knn_sort_reserve(P);
-    s.sort_temp = take(s.sort_temp_bytes);
+    s.m.splitters = reinterpret_cast<uint32_t*>(take(3 * KNN_CELLS * sizeof(uint32_t)));
+    for (int k = 0; k < 2; k++) s.m.keys[k] = reinterpret_cast<uint32_t*>(take(n * sizeof(uint32_t)));
+    for (int k = 0; k < 2; k++) s.m.values[k] = reinterpret_cast<uint32_t*>(take(n * sizeof(uint32_t)));
+    if (with_boxes) {
+        s.records = reinterpret_cast<f32x4*>(take(n * sizeof(f32x4)));
+        s.box_lo = reinterpret_cast<f32x4*>(take(boxes * sizeof(f32x4)));
+        s.box_hi = reinterpret_cast<f32x4*>(take(boxes * sizeof(f32x4)));
+    }
+    s.m.sort_temp_bytes = knn_sort_reserve(P);
+    s.m.sort_temp = take(s.m.sort_temp_bytes);
     s.total = off;
     return s;
 }
 
-} // namespace
-
-size_t knn_scratch_bytes(int P) { return P <= 0 ? 0 : knn_carve(nullptr, P).total; }
-
-int launch_knn_mean_dist2(int P, const float* points, void* scratch, float* mean_dist2, hipStream_t st, hipError_t* err)
+// Steps 1-3 of the pipeline above, THE Morton order of a cloud of n >= 1 points (include/stp_raster.h: stp_spatial_order states it): *codes and
+// *order are the buffers of s that hold the sorted codes and, beside them, the original indices -- rocPRIM's radix sort is stable and the
+// values start as 0 .. n - 1, so equal codes stay in index order.  Returns the launches made (a sort of the library counting as one), *err =
+// the error that ended them early (or hipSuccess).
+int launch_morton_order(const uint32_t n, const float* points, const MortonScratch& s, hipStream_t st, hipError_t* err, const uint32_t** codes,
+                        const uint32_t** order)
 {
-    const KnnScratch s = knn_carve(static_cast<char*>(scratch), P);
-    const uint32_t n = (uint32_t)P, boxes = knn_boxes(P), blocks = (n + KNN_BLOCK - 1) / KNN_BLOCK;
+    const uint32_t blocks = (n + KNN_BLOCK - 1) / KNN_BLOCK;
     *err = hipSuccess;
+    *codes = *order = nullptr;
     if (knn_sort_temp((size_t)n) > s.sort_temp_bytes) { // (rocPRIM wants more at P than at the powers of two around it: refuse in front of the first launch)
         *err = hipErrorInvalidValue;
         return 0;
@@ -371,10 +394,41 @@ int launch_knn_mean_dist2(int P, const float* points, void* scratch, float* mean
     size_t bytes = s.sort_temp_bytes;
     if ((*err = rocprim::radix_sort_pairs(s.sort_temp, bytes, keys, values, (size_t)n, 0u, KNN_SORT_BITS, st)) != hipSuccess) return launches;
     launches++;
-    hipLaunchKernelGGL(knn_boxes_kernel, dim3(boxes), dim3(KNN_BOX), 0, st, n, points, values.current(), s.records, s.box_lo, s.box_hi);
+    *codes = keys.current();
+    *order = values.current();
+    return launches;
+}
+
+} // namespace
+
+size_t knn_scratch_bytes(int P) { return P <= 0 ? 0 : knn_carve(nullptr, P, true).total; }
+
+int launch_knn_mean_dist2(int P, const float* points, void* scratch, float* mean_dist2, hipStream_t st, hipError_t* err)
+{
+    const KnnScratch s = knn_carve(static_cast<char*>(scratch), P, true);
+    const uint32_t n = (uint32_t)P, boxes = knn_boxes(P);
+    const uint32_t *codes, *order;
+    int launches = launch_morton_order(n, points, s.m, st, err, &codes, &order);
+    if (*err != hipSuccess) return launches;
+    hipLaunchKernelGGL(knn_boxes_kernel, dim3(boxes), dim3(KNN_BOX), 0, st, n, points, order, s.records, s.box_lo, s.box_hi);
     if ((*err = hipGetLastError()) != hipSuccess) return launches;
     launches++;
     hipLaunchKernelGGL(knn_search_kernel, dim3(boxes), dim3(KNN_BOX), 0, st, n, boxes, s.records, s.box_lo, s.box_hi, mean_dist2);
+    if ((*err = hipGetLastError()) != hipSuccess) return launches;
+    launches++;
+    return launches;
+}
+
+size_t spatial_order_scratch_bytes(int P) { return P <= 0 ? 0 : knn_carve(nullptr, P, false).total; }
+
+int launch_spatial_order(int P, const float* xyz, void* scratch, int32_t* order_out, uint32_t* codes_out, hipStream_t st, hipError_t* err)
+{
+    const KnnScratch s = knn_carve(static_cast<char*>(scratch), P, false);
+    const uint32_t n = (uint32_t)P;
+    const uint32_t *codes, *order;
+    int launches = launch_morton_order(n, xyz, s.m, st, err, &codes, &order);
+    if (*err != hipSuccess) return launches;
+    hipLaunchKernelGGL(spatial_order_emit_kernel, dim3((n + KNN_BLOCK - 1) / KNN_BLOCK), dim3(KNN_BLOCK), 0, st, n, order, codes, order_out, codes_out);
     if ((*err = hipGetLastError()) != hipSuccess) return launches;
     launches++;
     return launches;

@@ -1,5 +1,5 @@
-// stp_row_table.h -- what the training-side kernels beside the rasterizer share (stp_adam.hip, stp_densify.hip, stp_mcmc_relocate.hip; stp_mcmc.hip
-// takes f32x4 and aligned16 only): a launch that serves up to ROW_TABLE_ENTRIES tensors through a table of descriptors passed by value, and the
+// stp_row_table.h -- what the training-side kernels beside the rasterizer share (stp_adam.hip, stp_densify.hip, stp_mcmc_relocate.hip, stp_reorder.hip;
+// stp_mcmc.hip takes f32x4 and aligned16 only): a launch that serves up to ROW_TABLE_ENTRIES tensors through a table of descriptors passed by value, and the
 // workgroup scan of the two tile-sum prefixes.
 //
 // Row table.  A tensor owns consecutive work units of a launch, a workgroup is one unit and finds its tensor by a wave-uniform search for the

@@ -70,6 +70,9 @@ _OPTIONAL_SYMBOLS = {
                            ctypes.c_int, "the 3DGS-MCMC relocation kernels"),
     "stp_knn_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t, "the nearest-neighbour kernels"),
     "stp_knn_mean_dist2": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2, ctypes.c_int, "the nearest-neighbour kernels"),
+    "stp_spatial_order_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t, "the spatial order kernels"),
+    "stp_spatial_order": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3, ctypes.c_int, "the spatial order kernels"),
+    "stp_gather_rows": ([ctypes.c_int] * 2 + [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 2, ctypes.c_int, "the spatial order kernels"),
     "stp_densify_stats": ([ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int, "the densification kernels"),
     "stp_densify_plan": ([ctypes.c_int] + [ctypes.c_void_p] * 8, ctypes.c_int, "the densification kernels"),
     "stp_densify_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t, "the densification kernels"),
@@ -626,6 +629,36 @@ def knn_mean_dist2(points):
     is refused (there are no three neighbours)."""
     _require("stp_knn_mean_dist2")
     return (_host or _native()).knn_mean_dist2(points)
+
+
+def spatial_order_scratch_bytes(P: int) -> int:
+    """Bytes of device scratch stp_spatial_order needs for P points (include/stp_raster.h): a function of P alone, non-decreasing in P."""
+    return int(_require("stp_spatial_order_scratch_bytes")(int(P)))
+
+
+def spatial_order(xyz, return_codes=False):
+    """The Morton order of a cloud (extension, include/stp_raster.h: stp_spatial_order), on the current stream, without host synchronisation:
+    xyz (P, 3) float32 on a GPU -> (order, codes): order int32 (P,), order[s] the row that moves to position s; codes int32 (P,), the 30-bit
+    code of the row at position s, or None when not asked for."""
+    _require("stp_spatial_order")
+    _require("stp_spatial_order_scratch_bytes")
+    order, codes = (_host or _native()).spatial_order(xyz, bool(return_codes))
+    return order, (codes if return_codes else None)
+
+
+class StpGatherTensor(ctypes.Structure):
+    """include/stp_raster.h: StpGatherTensor == StpDensifyTensor (for callers of the C ABI through ctypes; the native module builds its own)"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("param", "exp_avg", "exp_avg_sq", "param_out", "exp_avg_out", "exp_avg_sq_out")] + \
+               [("row", ctypes.c_int32), ("role", ctypes.c_int32)]
+
+
+def gather_rows(index, tensors, exp_avgs, exp_avg_sqs):
+    """Output row s of every tensor and moment is input row index[s], bit for bit (extension, include/stp_raster.h: stp_gather_rows) ->
+    (new_tensors, new_exp_avgs, new_exp_avg_sqs), lists as long as `tensors`; exp_avgs / exp_avg_sqs hold None where a tensor has no moments,
+    and so do the results.  index: int32 (M,).  No host synchronisation."""
+    _require("stp_gather_rows")
+    out = (_host or _native()).gather_rows(index, list(tensors), list(exp_avgs), list(exp_avg_sqs))
+    return list(out[0]), list(out[1]), list(out[2])
 
 
 class StpDensifyRule(ctypes.Structure):

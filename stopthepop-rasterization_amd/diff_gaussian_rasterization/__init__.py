@@ -29,7 +29,8 @@ __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes
            "photometric_terms", "fused_ssim", "photometric_loss", "training_terms", "training_loss", "compute_relocation", "mcmc_add_noise_",
            "knn_mean_dist2", "distCUDA2", "dist_cuda2", "activate_params",
            "densification_stats_", "densify_plan", "densify_tensors", "densify_and_prune",
-           "mcmc_relocation_plan", "mcmc_relocate_tensors_", "mcmc_relocate_", "mcmc_add_plan", "mcmc_add_tensors", "mcmc_add_new"]
+           "mcmc_relocation_plan", "mcmc_relocate_tensors_", "mcmc_relocate_", "mcmc_add_plan", "mcmc_add_tensors", "mcmc_add_new",
+           "spatial_order", "gather_tensors", "reorder_gaussians_"]
 
 
 def enum_dict_factory(data):
@@ -1134,3 +1135,54 @@ def mcmc_add_new(optimizer, cap_max: int, uniforms: Optional[torch.Tensor] = Non
     plan = mcmc_add_plan(opacity, uniforms, raw=raw)
     new_t, new_m, new_v = mcmc_add_tensors(plan, params, roles, ms, vs, min_opacity=min_opacity, raw=raw)
     return _replace_group_tensors(optimizer, groups, params, new_t, new_m, new_v)
+
+
+def spatial_order(xyz: torch.Tensor, return_codes: bool = False):
+    """The Morton order of a cloud (extension; include/stp_raster.h: stp_spatial_order): for xyz (P, 3) float32 on a GPU, the int32 (P,)
+    tensor whose entry s is the index of the row that moves to position s -- `xyz[order]` is the cloud sorted along the curve -- and, with
+    return_codes, (order, codes) with the int32 30-bit code of the row at every position.  It is the order knn_mean_dist2 searches in, fixed
+    to the bit: per axis the coordinates become order-preserving integers (-0 below +0, the infinities at the ends), 1023 splitters cut their
+    sorted sequence into 1024 runs of equal length (splitter[k - 1] = sorted[k P // 1024]), a point's cell is the number of splitters <= its
+    coordinate, the code interleaves the three 10-bit cells (x lowest), and the order is the stable ascending sort of (code, index).  Cells
+    of equal count survive outliers and clusters; the codes depend on the multiset of coordinates only, so the order of an ordered cloud is
+    arange(P).  On the current stream, without host synchronisation and without atomics: equal inputs give equal bits.  xyz is detached, a
+    non-contiguous view is made contiguous, P == 0 gives empty tensors.  Refused with a RuntimeError naming the argument: another dtype
+    ("xyz: expected float32"), another shape ("xyz must be (P, 3)"), a CPU tensor ("no CPU path")."""
+    order, codes = _C.spatial_order(xyz.detach(), return_codes)
+    return (order, codes) if return_codes else order
+
+
+def gather_tensors(index: torch.Tensor, tensors, exp_avgs=None, exp_avg_sqs=None):
+    """Row s of every output is row index[s] of its input, bit for bit, for every tensor and both Adam moments, in one launch per eight
+    tensors and without host synchronisation (extension; include/stp_raster.h: stp_gather_rows) -> (new_tensors, new_exp_avgs,
+    new_exp_avg_sqs), lists as long as `tensors` with None where there are no moments.  index: int32 (M,) (an int64 index is converted) --
+    a permutation such as spatial_order's, a subset, or a list with repeats; tensors: float32 or int32 (P, ...) of any trailing shape on
+    index's GPU; exp_avgs / exp_avg_sqs: the moments per tensor, None where there are none (None: no moments at all).  The rows are moved,
+    never computed on: NaN payloads and -0 keep their bits.  AN INDEX OUTSIDE [0, P) IS READ AS THE NEAREST VALID ROW (nothing is read out
+    of bounds, nothing is reported).  The inputs are not modified; non-contiguous ones are made contiguous."""
+    if isinstance(index, torch.Tensor) and index.dtype == torch.int64:
+        index = index.to(torch.int32)
+    tensors, _, exp_avgs, exp_avg_sqs = _row_lists(tensors, None, None, exp_avgs, exp_avg_sqs)
+    return _C.gather_rows(index, tensors, exp_avgs, exp_avg_sqs)
+
+
+def reorder_gaussians_(optimizer, order: Optional[torch.Tensor] = None, *, xyz: str = "xyz", extra=()):
+    """Re-sort a model along the Morton curve (or by any `order`) on its optimizer (extension) -> (new_params, order, new_extra).
+    `optimizer`: a torch.optim.Adam, SparseGaussianAdam or GaussianAdam whose groups hold one tensor each and carry "name", as
+    densify_and_prune takes it.  order=None computes spatial_order of the group named `xyz`; otherwise order is an int32 (P,) permutation,
+    order[s] the row that moves to position s.  Every group's tensor, both moments and the tensors of `extra` -- the trainer's per-Gaussian
+    side buffers (xyz_gradient_accum, denom, max_radii2D, ...: float32 or int32 (P, ...)) -- go through ONE gather_tensors call.  Each group
+    gets a new nn.Parameter in group["params"][0], optimizer.state moves onto it with the new exp_avg and exp_avg_sq exactly as
+    densify_and_prune moves it (a group whose state is still empty stays empty; "step" and every group option are kept); new_params =
+    {name: new Parameter} is for the model to take, new_extra the permuted side buffers in the order given.  No host synchronisation.
+    What indexes rows and is not handed in (a visibility mask of the last render, cached activations) is stale afterwards."""
+    groups, params, _, ms, vs = _named_groups("reorder_gaussians_", optimizer, {})
+    extra = list(extra)
+    if order is None:
+        named = [p for g, p in zip(groups, params) if g["name"] == xyz]
+        if len(named) != 1:
+            raise ValueError(f"reorder_gaussians_: the optimizer needs exactly one group named {xyz!r} to order by (or pass order=)")
+        order = spatial_order(named[0])
+    n = len(params)
+    new_t, new_m, new_v = gather_tensors(order, list(params) + extra, list(ms) + [None] * len(extra), list(vs) + [None] * len(extra))
+    return _replace_group_tensors(optimizer, groups, params, new_t[:n], new_m[:n], new_v[:n]), order, new_t[n:]
