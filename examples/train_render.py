@@ -3,13 +3,14 @@
 `gaussian_renderer/__init__.py`), written against this package, plus a tiny optimisation
 loop on a synthetic scene that shows the forward + backward of the hot path in its natural habitat.
 
-    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam|gaussian_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--relocate torch|fused] [--cap-max N] [--split-sh] [--raw-params] [--init-scales scene|knn] [--reorder N]
+    PYTHONPATH=stopthepop-rasterization_amd python examples/train_render.py [--iters 30] [--config full|min|kbuffer|global] [--absgrad] [--prune-views N] [--mask-weight W] [--depth-weight W] [--optimizer adam|sparse_adam|gaussian_adam] [--loss l1|l1_ssim] [--strategy none|mcmc|adc] [--relocate torch|fused] [--cap-max N] [--split-sh] [--raw-params] [--init-scales scene|knn] [--reorder N] [--filter-3d]
 
 `render()` takes the trainer's usual objects by duck typing:
   camera : image_width, image_height, FoVx, FoVy, world_view_transform, full_proj_transform, camera_center
   model  : get_xyz, get_opacity, get_scaling, get_rotation, get_features, active_sh_degree
            (a model with `split_sh` set also has get_features_dc and get_features_rest, which are then passed as they are;
-            a model with `raw_params` set hands over _scaling, _rotation and _opacity, its stored parameters, to GaussianRasterizer(..., raw=True))
+            a model with `raw_params` set hands over _scaling, _rotation and _opacity, its stored parameters, to GaussianRasterizer(..., raw=True);
+            a model whose `filter_3d` is a tensor renders from filtered_activations(_scaling, _opacity, filter_3d), Mip-Splatting's 3D filter)
 and returns the trainer's usual dict (render, viewspace_points, visibility_filter, radii; "alpha" and "invdepth" too when asked for).
 """
 from __future__ import annotations
@@ -25,7 +26,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "stopthepop-rasterization_amd"))
 from diff_gaussian_rasterization import (CullingSettings, ExtendedSettings, GaussianRasterizationSettings,  # noqa: E402
                                          GaussianRasterizer, GlobalSortOrder, SortMode, SortQueueSizes, SortSettings, GaussianAdam, SparseGaussianAdam, compute_relocation,
-                                         densification_stats_, densify_and_prune, densify_plan, mcmc_add_new, mcmc_add_noise_, mcmc_relocate_, reorder_gaussians_, scenes, training_loss, training_terms)
+                                         compute_3d_filter, densification_stats_, densify_and_prune, densify_plan, filtered_activations, mcmc_add_new, mcmc_add_noise_, mcmc_relocate_, reorder_gaussians_, scenes, training_loss, training_terms)
 
 
 def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, scaling_modifier: float = 1.0,
@@ -40,7 +41,9 @@ def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, 
     A model with `split_sh` hands its two SH parameters over as they are -- dc=_features_dc, shs=_features_rest -- where a trainer
     otherwise concatenates them every step.  A model with `raw_params` hands over its stored _opacity (logit),
     _scaling (log) and _rotation (unnormalised) to a rasterizer made with raw=True: sigmoid, exp and normalize run inside the rasterizer's kernels, and the
-    gradients arrive on the three leaves without an activated copy in between."""
+    gradients arrive on the three leaves without an activated copy in between.  A model with a `filter_3d` buffer
+    (Mip-Splatting; compute_3d_filter over the training cameras) renders from filtered_activations(_scaling, _opacity, filter_3d): one kernel in
+    place of get_scaling_with_3D_filter and get_opacity_with_3D_filter, the gradients arriving on _scaling and _opacity."""
     screenspace_points = torch.zeros_like(model.get_xyz, requires_grad=True)
     raster_settings = GaussianRasterizationSettings(
         image_height=int(camera.image_height), image_width=int(camera.image_width),
@@ -57,8 +60,12 @@ def render(camera, model, bg_color: torch.Tensor, splat_args: ExtendedSettings, 
         image, radii, *extra = rasterizer(means3D=model.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors,
                                           opacities=model._opacity, scales=model._scaling, rotations=model._rotation, dc=dc)
     else:
+        if getattr(model, "filter_3d", None) is not None:
+            scales, opacities = filtered_activations(model._scaling, model._opacity, model.filter_3d)
+        else:
+            scales, opacities = model.get_scaling, model.get_opacity
         image, radii, *extra = rasterizer(means3D=model.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors,
-                                          opacities=model.get_opacity, scales=model.get_scaling, rotations=model.get_rotation, dc=dc)
+                                          opacities=opacities, scales=scales, rotations=model.get_rotation, dc=dc)
     out = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
     if getattr(splat_args, "_alpha", False):      # (the extra outputs in their order: alpha, then the inverse depth)
         out["alpha"] = extra.pop(0)
@@ -98,6 +105,7 @@ class ToyGaussians(torch.nn.Module):
         else:
             self._features = t(sc.shs)
         self.active_sh_degree = sc.sh_degree
+        self.filter_3d = None   # --filter-3d: Mip-Splatting's buffer, (P, 1), no gradient
 
     get_xyz = property(lambda s: s._xyz)
     get_scaling = property(lambda s: torch.exp(s._scaling))
@@ -129,6 +137,15 @@ def camera_of(sc: scenes.Scene, device):
     t = lambda a: torch.tensor(a, device=device)
     return SimpleNamespace(image_width=sc.W, image_height=sc.H, FoVx=2 * math.atan(sc.tanfovx), FoVy=2 * math.atan(sc.tanfovy),
                            world_view_transform=t(sc.viewmatrix), full_proj_transform=t(sc.projmatrix), camera_center=t(sc.campos))
+
+
+def update_filter_3d(model: ToyGaussians, cameras) -> None:
+    """Mip-Splatting's GaussianModel.compute_3D_filter(cameras): one fused pass over all cameras, no host synchronisation.  A trainer calls it once
+    after loading and again after every step that changes the rows (densification, growth, a reordering) or resets opacities."""
+    views = torch.stack([c.world_view_transform for c in cameras])
+    intrinsics = torch.tensor([[c.image_width / (2.0 * math.tan(c.FoVx * 0.5)), c.image_height / (2.0 * math.tan(c.FoVy * 0.5)), c.image_width, c.image_height]
+                               for c in cameras], dtype=torch.float32, device=views.device)
+    model.filter_3d = compute_3d_filter(model.get_xyz, views, intrinsics)
 
 
 def relocate_dead(model: ToyGaussians, opt: torch.optim.Optimizer, min_opacity: float = 0.005) -> int:
@@ -206,7 +223,13 @@ def main(argv=None):
     ap.add_argument("--reorder", type=int, default=0, metavar="N",
                     help="every N iterations re-sort the model along the Morton curve of its positions: reorder_gaussians_ moves every tensor, both "
                          "Adam moments and the densification statistics in one gather (INTEGRATION.md section 3u)")
+    ap.add_argument("--filter-3d", action="store_true",
+                    help="Mip-Splatting's 3D smoothing filter: compute_3d_filter over the example's camera once and again after every densification, growth "
+                         "or reordering, and the render from filtered_activations(_scaling, _opacity, filter_3d) (INTEGRATION.md section 3v)")
     args = ap.parse_args(argv)
+    if args.filter_3d and args.raw_params:
+        raise SystemExit("--filter-3d cannot be combined with --raw-params: raw=True makes the rasterizer's kernels activate the stored parameters "
+                         "themselves, and they do not read filter_3d; the filtered activations feed the ordinary scales= / opacities= call")
     if not torch.cuda.is_available():
         raise SystemExit("this example needs a GPU (the rasterizer has no CPU path)")
     dev = torch.device("cuda:0")
@@ -233,6 +256,9 @@ def main(argv=None):
             dist2 = torch.clamp_min(distCUDA2(model._xyz.detach().float()), 0.0000001)
             model._scaling.copy_(torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3))
             print(f"initial scales from distCUDA2 over {dist2.numel()} points: mean 3-NN distance {float(torch.sqrt(dist2).mean()):.4f}")
+    if args.filter_3d:
+        update_filter_3d(model, [cam])
+        print(f"filter_3d over 1 camera: {float(model.filter_3d.min()):.5f} .. {float(model.filter_3d.max()):.5f}")
     adc = args.strategy == "adc"
     fused_mcmc = args.strategy == "mcmc" and args.relocate == "fused"
     cap_max = args.cap_max if args.cap_max is not None else (115 * args.points) // 100
@@ -349,6 +375,8 @@ def main(argv=None):
             elif it > 0 and it % 10 == 0:
                 relocated += relocate_dead(model, opt)
                 relocations += 1
+            if args.filter_3d and it > 0 and it % 10 == 0:   # (relocated rows sit elsewhere now, and new rows have no entry yet)
+                update_filter_3d(model, [cam])
             # xyz += Sigma (randn * op_sigmoid(1 - opacity) * noise_lr * xyz_lr) in one kernel, from the raw parameters the step just moved
             mcmc_add_noise_(model._xyz, model._scaling, model._rotation, model._opacity, torch.randn_like(model._xyz), noise_scale, raw=True)
         if args.reorder > 0 and it > 0 and it % args.reorder == 0:
@@ -359,6 +387,8 @@ def main(argv=None):
                 opt, extra=[stat_signed, stat_abs, stat_denom, stat_radii, abs_denom])
             model.take_features(new)
             model._opacity, model._xyz, model._scaling, model._rotation = (new[n] for n in ("opacity", "xyz", "scaling", "rotation"))
+            if args.filter_3d:   # (the rows moved)
+                update_filter_3d(model, [cam])
             print(f"iter {it:3d}  reorder: {order.numel()} rows into Morton order")
         if adc and it > 0 and it % 10 == 0:
             # upstream's densify_and_prune: the decision as one byte per Gaussian, then one scan and one apply over every tensor and both
@@ -369,6 +399,8 @@ def main(argv=None):
             model.take_features(new)
             model._opacity, model._xyz, model._scaling, model._rotation = (new[n] for n in ("opacity", "xyz", "scaling", "rotation"))
             after = model.get_xyz.shape[0]
+            if args.filter_3d:
+                update_filter_3d(model, [cam])
             kept, cloned, split = (int(((plan >> b) & 1).sum()) for b in range(3))
             grown, pruned = grown + cloned + 2 * split, pruned + before - kept
             print(f"iter {it:3d}  adc: {before} rows -> {after} (kept {kept}, cloned {cloned}, split {split} into {2 * split})")

@@ -442,6 +442,39 @@ int stp_mcmc_relocation(int n, const float* opacity_old, const float* scale_old,
 int stp_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise,
                        float noise_scale, float k, float x0, int raw, void* stream);
 
+/* Extension (not in the reference): Mip-Splatting's 3D smoothing filter ("Mip-Splatting: Alias-free 3D Gaussian Splatting"), the half of that
+   method that lives outside the rasterizer (the 2D filter is proper_ewa_scaling).
+   stp_mip_filter_3d is that project's compute_3D_filter over all C training cameras in one pass.  xyz: P x 3 floats; world_view_transforms:
+   C x 16 floats, camera c's world-view matrix M in row-vector layout, p_cam = [p, 1] @ M (only M[:3, :3] and M[3, :3] are read); intrinsics:
+   C x 4 floats (focal_x, focal_y, image_width, image_height); filter_3d: P floats; workspace: 4 bytes of device memory, 4-byte aligned, the
+   call's own until the kernels have run.  With (x, y, z) = p_cam, for every Gaussian i and camera c:
+       valid = z > 0.2  and  -0.15 W <= x / max(z, 0.001) * focal_x + W / 2 <= 1.15 W  and  -0.15 H <= y / max(z, 0.001) * focal_y + H / 2 <= 1.15 H
+       distance[i] = min over the valid cameras of z (100000 before any)
+   a row without a valid camera takes the largest distance of the rows that have one; where no row has one, every row keeps 100000 (upstream
+   raises there: that needs a read-back, which this call never does).  filter_3d = distance / max_c(focal_x) * sqrt(0.2), the maximum over ALL
+   cameras.  In float32, p_cam by a fixed chain of fmas and the screen test in its division-free form |x focal_x| <= (0.65 W) z
+   (csrc/stp_mip_filter.hip); on inputs 1e-4 (relative to 0.2, W and H) away from every threshold each decision is that of a float64
+   evaluation.  A NaN coordinate is never valid.  The maximum over rows is an integer maximum on the floats' bits: equal inputs give equal bits.
+   Two kernel launches behind a 4-byte fill.
+   stp_mip_activations_forward / _backward are get_scaling_with_3D_filter and get_opacity_with_3D_filter and their chain rule, one kernel each.
+   scaling: P x 3 stored log-scales; opacity: P stored logits; filter_3d: P.  With e_j = exp(scaling_j), f = filter_3d, sig = 1 / (1 + exp(-opacity)):
+       scales_j = sqrt(e_j^2 + f^2)      r_j = e_j^2 / (e_j^2 + f^2)      opacities = sig * sqrt(r_0 r_1 r_2)
+       grad_scaling_j = grad_scales_j * e_j^2 / scales_j + grad_opacities * opacities * (1 - r_j)
+       grad_opacity   = grad_opacities * sqrt(r_0 r_1 r_2) * sig * (1 - sig)
+   (upstream's sqrt(prod e^2 / prod (e^2 + f^2)) without the two determinants, which leave the normal range for small scales).  The backward
+   recomputes from the three inputs; grad_scales (P x 3) or grad_opacities (P) may be NULL and then counts as zero; filter_3d gets no gradient.
+   Where all pointers are 16-byte aligned the streams move 16 bytes per lane, otherwise one float per access; the arithmetic is the same.
+   No atomics: equal inputs give equal bits.
+   Each call returns the number of kernel launches made (2, 1, 1; 0 for P == 0: nothing is touched), or a negative StpStatus with the reason in
+   the last-error text.  Refused BEFORE anything is launched (STP_ERR_INVALID_ARGUMENT): a negative count, C == 0, C >= 2^24, a null pointer
+   (but the two optional gradients; both NULL is refused).  Plain calls: no host synchronisation, no allocation, no per-thread request state.
+   All pointers are device pointers to contiguous data. */
+int stp_mip_filter_3d(int P, int C, const float* xyz, const float* world_view_transforms, const float* intrinsics, void* workspace, float* filter_3d,
+                      void* stream);
+int stp_mip_activations_forward(int P, const float* scaling, const float* opacity, const float* filter_3d, float* scales, float* opacities, void* stream);
+int stp_mip_activations_backward(int P, const float* scaling, const float* opacity, const float* filter_3d, const float* grad_scales,
+                                 const float* grad_opacities, float* grad_scaling, float* grad_opacity, void* stream);
+
 /* Extension (not in the reference): the rest of a 3DGS-MCMC trainer's relocate_gs and add_new_gs around stp_mcmc_relocation -- the multinomial
    draw of the sources and the rewrite of every parameter and both Adam moments -- in three calls.  All tensors are float32, all pointers are
    device pointers to contiguous data, every call runs on the caller's stream, allocates nothing and NEVER synchronises with the host; no float

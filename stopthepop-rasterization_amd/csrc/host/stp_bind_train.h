@@ -1,4 +1,4 @@
-// stp_bind_train.h -- the training kernels beside the rasterizer: sparse Adam, 3DGS-MCMC, nearest neighbours, densification, the photometric and the training loss.
+// stp_bind_train.h -- the training kernels beside the rasterizer: sparse Adam, 3DGS-MCMC, Mip-Splatting's 3D filter, nearest neighbours, densification, the photometric and the training loss.
 // All run on the caller's current stream.  What is wrong with the tensors themselves is refused first, where they live last (stp_tensor_checks.h).
 #pragma once
 
@@ -352,6 +352,109 @@ mcmc_add_apply(const torch::Tensor& src_in, const torch::Tensor& count_in, const
     checked(g_api.mcmc_add_apply((int)P, (int)n_new, src.data_ptr<int32_t>(), count.data_ptr<int32_t>(), (int)r.table.size(), r.table.data(), (float)min_opacity, raw ? 1 : 0,
                                  scratch.data_ptr(), bytes, current_stream(count.device())));
     return {r.out_p, r.out_m, r.out_v};
+}
+
+// == Mip-Splatting's 3D filter (extension, include/stp_raster.h: stp_mip_filter_3d / stp_mip_activations_forward / _backward; compute_3d_filter and
+// filtered_activations in __init__.py).  No host synchronisation; the 4-byte workspace is a torch tensor of the caching allocator.
+// -> filter_3d (P, 1).  xyz is made contiguous, and so are the two camera tensors.
+torch::Tensor compute_3d_filter(const torch::Tensor& xyz_in, const torch::Tensor& views_in, const torch::Tensor& intrinsics_in)
+{
+    static const char* const who = "compute_3d_filter";
+    need_library();
+    require(g_api.mip_filter_3d, who);
+    check_float(who, "xyz", xyz_in);
+    check_float(who, "world_view_transforms", views_in);
+    check_float(who, "intrinsics", intrinsics_in);
+    TORCH_CHECK(xyz_in.dim() == 2 && xyz_in.size(1) == 3, who, ": xyz must be (P, 3), got ", xyz_in.sizes());
+    const int64_t P = xyz_in.size(0);
+    TORCH_CHECK(P < (1ll << 31), who, ": xyz: ", P, " rows >= 2^31");
+    TORCH_CHECK(views_in.dim() == 3 && views_in.size(1) == 4 && views_in.size(2) == 4, who, ": world_view_transforms must be (C, 4, 4), got ", views_in.sizes());
+    const int64_t C = views_in.size(0);
+    TORCH_CHECK(C > 0, who, ": world_view_transforms: C == 0: the filter needs at least one camera");
+    TORCH_CHECK(C < (1ll << 24), who, ": world_view_transforms: ", C, " cameras >= 2^24");
+    check_rows(who, "intrinsics", intrinsics_in, C, 4);
+    check_device(who, "world_view_transforms", views_in, xyz_in);
+    check_device(who, "intrinsics", intrinsics_in, xyz_in);
+    check_device(who, "xyz", xyz_in, xyz_in);
+    const torch::Tensor xyz = xyz_in.detach().contiguous(), views = views_in.detach().contiguous(), intrinsics = intrinsics_in.detach().contiguous();
+    const c10::hip::HIPGuard guard(xyz.device().index());
+    torch::Tensor out = torch::empty({P, 1}, xyz.options());
+    if (P == 0) return out;
+    torch::Tensor workspace = torch::empty({1}, xyz.options().dtype(torch::kInt32));
+    checked(g_api.mip_filter_3d((int)P, (int)C, xyz.data_ptr<float>(), views.data_ptr<float>(), intrinsics.data_ptr<float>(), workspace.data_ptr(), out.data_ptr<float>(),
+                                current_stream(xyz.device())));
+    return out;
+}
+
+// what the two activation calls ask of (scaling, opacity, filter_3d); -> P
+int64_t mip_check_inputs(const char* who, const torch::Tensor& scaling, const torch::Tensor& opacity, const torch::Tensor& filter_3d)
+{
+    check_float(who, "scaling", scaling);
+    check_float(who, "opacity", opacity);
+    check_float(who, "filter_3d", filter_3d);
+    TORCH_CHECK(scaling.dim() == 2 && scaling.size(1) == 3, who, ": scaling must be (P, 3), got ", scaling.sizes());
+    const int64_t P = scaling.size(0);
+    TORCH_CHECK(P < (1ll << 31), who, ": scaling: ", P, " rows >= 2^31");
+    check_column(who, "opacity", opacity);
+    TORCH_CHECK(opacity.size(0) == P, who, ": opacity has ", opacity.size(0), " rows, scaling has ", P);
+    check_column(who, "filter_3d", filter_3d);
+    TORCH_CHECK(filter_3d.size(0) == P, who, ": filter_3d has ", filter_3d.size(0), " rows, scaling has ", P);
+    return P;
+}
+
+// -> (scales (P, 3), opacities of opacity's shape)
+std::tuple<torch::Tensor, torch::Tensor> mip_activations(const torch::Tensor& scaling_in, const torch::Tensor& opacity_in, const torch::Tensor& filter_in)
+{
+    static const char* const who = "filtered_activations";
+    need_library();
+    require(g_api.mip_activations_forward, who);
+    const int64_t P = mip_check_inputs(who, scaling_in, opacity_in, filter_in);
+    check_device(who, "opacity", opacity_in, scaling_in);
+    check_device(who, "filter_3d", filter_in, scaling_in);
+    check_device(who, "scaling", scaling_in, scaling_in);
+    const torch::Tensor scaling = scaling_in.detach().contiguous(), opacity = opacity_in.detach().contiguous(), filter = filter_in.detach().contiguous();
+    const c10::hip::HIPGuard guard(scaling.device().index());
+    torch::Tensor scales = torch::empty(scaling.sizes(), scaling.options()), opacities = torch::empty(opacity.sizes(), opacity.options());
+    if (P == 0) return {scales, opacities};
+    checked(g_api.mip_activations_forward((int)P, scaling.data_ptr<float>(), opacity.data_ptr<float>(), filter.data_ptr<float>(), scales.data_ptr<float>(),
+                                          opacities.data_ptr<float>(), current_stream(scaling.device())));
+    return {scales, opacities};
+}
+
+// -> (grad_scaling (P, 3), grad_opacity of opacity's shape); either upstream gradient may be None (zeros), not both
+std::tuple<torch::Tensor, torch::Tensor> mip_activations_backward(const torch::Tensor& scaling_in, const torch::Tensor& opacity_in, const torch::Tensor& filter_in,
+                                                                  const c10::optional<torch::Tensor>& grad_scales_in, const c10::optional<torch::Tensor>& grad_opacities_in)
+{
+    static const char* const who = "filtered_activations (backward)";
+    need_library();
+    require(g_api.mip_activations_backward, who);
+    const int64_t P = mip_check_inputs(who, scaling_in, opacity_in, filter_in);
+    TORCH_CHECK(grad_scales_in.has_value() || grad_opacities_in.has_value(), who, ": grad_scales and grad_opacities are both None");
+    if (grad_scales_in.has_value()) {
+        check_float(who, "grad_scales", *grad_scales_in);
+        check_rows(who, "grad_scales", *grad_scales_in, P, 3);
+    }
+    if (grad_opacities_in.has_value()) {
+        check_float(who, "grad_opacities", *grad_opacities_in);
+        check_column(who, "grad_opacities", *grad_opacities_in);
+        TORCH_CHECK(grad_opacities_in->size(0) == P, who, ": grad_opacities has ", grad_opacities_in->size(0), " rows, scaling has ", P);
+    }
+    check_device(who, "opacity", opacity_in, scaling_in);
+    check_device(who, "filter_3d", filter_in, scaling_in);
+    if (grad_scales_in.has_value()) check_device(who, "grad_scales", *grad_scales_in, scaling_in);
+    if (grad_opacities_in.has_value()) check_device(who, "grad_opacities", *grad_opacities_in, scaling_in);
+    check_device(who, "scaling", scaling_in, scaling_in);
+    const torch::Tensor scaling = scaling_in.detach().contiguous(), opacity = opacity_in.detach().contiguous(), filter = filter_in.detach().contiguous();
+    torch::Tensor gs, go;
+    if (grad_scales_in.has_value()) gs = grad_scales_in->contiguous();
+    if (grad_opacities_in.has_value()) go = grad_opacities_in->contiguous();
+    const c10::hip::HIPGuard guard(scaling.device().index());
+    torch::Tensor g_scaling = torch::empty(scaling.sizes(), scaling.options()), g_opacity = torch::empty(opacity.sizes(), opacity.options());
+    if (P == 0) return {g_scaling, g_opacity};
+    checked(g_api.mip_activations_backward((int)P, scaling.data_ptr<float>(), opacity.data_ptr<float>(), filter.data_ptr<float>(), gs.defined() ? gs.data_ptr<float>() : nullptr,
+                                           go.defined() ? go.data_ptr<float>() : nullptr, g_scaling.data_ptr<float>(), g_opacity.data_ptr<float>(),
+                                           current_stream(scaling.device())));
+    return {g_scaling, g_opacity};
 }
 
 // == the activated copies of a trainer's raw parameters (extension, include/stp_raster.h: stp_activate_params; activate_params in __init__.py): the

@@ -47,6 +47,9 @@
     X(mcmc_sample, false, "the 3DGS-MCMC relocation kernels")                              \
     X(mcmc_relocate_apply, false, "the 3DGS-MCMC relocation kernels")                      \
     X(mcmc_add_apply, false, "the 3DGS-MCMC relocation kernels")                           \
+    X(mip_filter_3d, false, "the Mip-Splatting 3D filter")                                 \
+    X(mip_activations_forward, false, "the Mip-Splatting 3D filter")                       \
+    X(mip_activations_backward, false, "the Mip-Splatting 3D filter")                      \
     X(knn_scratch_bytes, false, "the nearest-neighbour kernels")                           \
     X(knn_mean_dist2, false, "the nearest-neighbour kernels")                              \
     X(spatial_order_scratch_bytes, false, "the spatial order kernels")                     \

@@ -28,6 +28,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("mcmc_sample", &mcmc_sample);
     m.def("mcmc_relocate_apply", &mcmc_relocate_apply);
     m.def("mcmc_add_apply", &mcmc_add_apply);
+    m.def("compute_3d_filter", &compute_3d_filter);
+    m.def("mip_activations", &mip_activations);
+    m.def("mip_activations_backward", &mip_activations_backward);
     m.def("activate_params", &activate_params);
     m.def("knn_mean_dist2", &knn_mean_dist2);
     m.def("spatial_order", &spatial_order);

@@ -481,6 +481,46 @@ int stp_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rota
     return launches;
 }
 
+// ---- Mip-Splatting's 3D filter (stp_mip_filter.hip): everything is checked before the first launch
+int stp_mip_filter_3d(int P, int C, const float* xyz, const float* world_view_transforms, const float* intrinsics, void* workspace, float* filter_3d, void* stream)
+{
+    if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mip_filter_3d: negative P");
+    if (C < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mip_filter_3d: negative C");
+    if (C == 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mip_filter_3d: C == 0: the filter needs at least one camera");
+    if (C >= (1 << 24)) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mip_filter_3d: C must be below 2^24");
+    if (P == 0) return 0;
+    if (!xyz || !world_view_transforms || !intrinsics || !workspace || !filter_3d) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mip_filter_3d: null pointer");
+    hipError_t e;
+    const int launches = launch_mip_filter_3d(P, C, xyz, world_view_transforms, intrinsics, workspace, filter_3d, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "mip_filter_3d launch");
+    return launches;
+}
+
+int stp_mip_activations_forward(int P, const float* scaling, const float* opacity, const float* filter_3d, float* scales, float* opacities, void* stream)
+{
+    if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mip_activations_forward: negative P");
+    if (P == 0) return 0;
+    if (!scaling || !opacity || !filter_3d || !scales || !opacities) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mip_activations_forward: null pointer");
+    hipError_t e;
+    const int launches = launch_mip_activations_forward(P, scaling, opacity, filter_3d, scales, opacities, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "mip_activations_forward launch");
+    return launches;
+}
+
+int stp_mip_activations_backward(int P, const float* scaling, const float* opacity, const float* filter_3d, const float* grad_scales, const float* grad_opacities,
+                                 float* grad_scaling, float* grad_opacity, void* stream)
+{
+    if (P < 0) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mip_activations_backward: negative P");
+    if (P == 0) return 0;
+    if (!scaling || !opacity || !filter_3d || !grad_scaling || !grad_opacity) return fail(STP_ERR_INVALID_ARGUMENT, "stp_mip_activations_backward: null pointer");
+    if (!grad_scales && !grad_opacities)
+        return fail(STP_ERR_INVALID_ARGUMENT, "stp_mip_activations_backward: null pointer: grad_scales and grad_opacities are both absent");
+    hipError_t e;
+    const int launches = launch_mip_activations_backward(P, scaling, opacity, filter_3d, grad_scales, grad_opacities, grad_scaling, grad_opacity, (hipStream_t)stream, &e);
+    if (e != hipSuccess) return fail_hip(e, "mip_activations_backward launch");
+    return launches;
+}
+
 // ---- the 3DGS-MCMC relocation and growth (stp_mcmc_relocate.hip): everything is checked before the first launch
 static constexpr int MCMC_RELOCATE_MAX_P = 1 << 28;
 static const char* const MCMC_ROLE_NAMES[3] = {"", "1 (opacity, row 1)", "2 (scaling, row 3)"};

@@ -304,6 +304,13 @@ int launch_mcmc_relocation(int n, const float* opacity_old, const float* scale_o
                            float* scale_new, hipStream_t st, hipError_t* err);
 int launch_mcmc_add_noise(int P, float* xyz, const float* scales, const float* rotations, const float* opacities, const float* noise, float noise_scale,
                           float k, float x0, int raw, hipStream_t st, hipError_t* err);
+// Mip-Splatting's 3D filter (stp_mip_filter.hip) over arguments stp_mip_filter_3d / stp_mip_activations_forward / _backward have validated (P in
+// [1, 2^31), C in [1, 2^24)); each returns the launches made, *err = the launch error (or hipSuccess)
+int launch_mip_filter_3d(int P, int C, const float* xyz, const float* views, const float* intrinsics, void* workspace, float* filter_3d, hipStream_t st, hipError_t* err);
+int launch_mip_activations_forward(int P, const float* scaling, const float* opacity, const float* filter_3d, float* scales, float* opacities, hipStream_t st,
+                                   hipError_t* err);
+int launch_mip_activations_backward(int P, const float* scaling, const float* opacity, const float* filter_3d, const float* grad_scales, const float* grad_opacities,
+                                    float* grad_scaling, float* grad_opacity, hipStream_t st, hipError_t* err);
 // the 3DGS-MCMC relocation and growth (stp_mcmc_relocate.hip) over arguments stp_mcmc_sample / stp_mcmc_relocate_apply / stp_mcmc_add_apply have
 // validated (P in [1, 2^28], every written row count times row < 2^31, exactly one tensor of each of the roles 1 and 2, a scratch of
 // mcmc_relocate_scratch_bytes(P) bytes, 16-byte aligned): each returns the launches made, *err = the launch error that ended it early (or

@@ -68,6 +68,9 @@ _OPTIONAL_SYMBOLS = {
                                  ctypes.c_void_p], ctypes.c_int, "the 3DGS-MCMC relocation kernels"),
     "stp_mcmc_add_apply": ([ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
                            ctypes.c_int, "the 3DGS-MCMC relocation kernels"),
+    "stp_mip_filter_3d": ([ctypes.c_int] * 2 + [ctypes.c_void_p] * 6, ctypes.c_int, "the Mip-Splatting 3D filter"),
+    "stp_mip_activations_forward": ([ctypes.c_int] + [ctypes.c_void_p] * 6, ctypes.c_int, "the Mip-Splatting 3D filter"),
+    "stp_mip_activations_backward": ([ctypes.c_int] + [ctypes.c_void_p] * 8, ctypes.c_int, "the Mip-Splatting 3D filter"),
     "stp_knn_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t, "the nearest-neighbour kernels"),
     "stp_knn_mean_dist2": ([ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2, ctypes.c_int, "the nearest-neighbour kernels"),
     "stp_spatial_order_scratch_bytes": ([ctypes.c_int], ctypes.c_size_t, "the spatial order kernels"),
@@ -612,6 +615,28 @@ def activate_params(scaling=None, rotation=None, opacity=None):
     _require("stp_activate_params")
     out = (_host or _native()).activate_params(scaling, rotation, opacity)
     return tuple(o if given is not None else None for o, given in zip(out, (scaling, rotation, opacity)))
+
+
+def compute_3d_filter(xyz, world_view_transforms, intrinsics):
+    """Mip-Splatting's 3D filter over all cameras in one pass (extension, include/stp_raster.h: stp_mip_filter_3d), on the current stream, without
+    host synchronisation: xyz (P, 3), world_view_transforms (C, 4, 4) in row-vector layout, intrinsics (C, 4) = (focal_x, focal_y, width,
+    height), float32 on one GPU -> filter_3d (P, 1) float32.  P == 0 gives an empty tensor; C == 0 is refused."""
+    _require("stp_mip_filter_3d")
+    return (_host or _native()).compute_3d_filter(xyz, world_view_transforms, intrinsics)
+
+
+def mip_activations(scaling, opacity, filter_3d):
+    """(scales, opacities) of Mip-Splatting's filtered activations (extension, include/stp_raster.h: stp_mip_activations_forward): one launch on
+    the current stream.  scaling (P, 3), opacity and filter_3d (P,) or (P, 1), float32 on one GPU; opacities has opacity's shape."""
+    _require("stp_mip_activations_forward")
+    return tuple((_host or _native()).mip_activations(scaling, opacity, filter_3d))
+
+
+def mip_activations_backward(scaling, opacity, filter_3d, grad_scales, grad_opacities):
+    """(grad_scaling, grad_opacity) of mip_activations (extension, include/stp_raster.h: stp_mip_activations_backward), recomputed from the three
+    inputs: one launch.  grad_scales (P, 3) or grad_opacities (opacity's rows) may be None (zeros), not both."""
+    _require("stp_mip_activations_backward")
+    return tuple((_host or _native()).mip_activations_backward(scaling, opacity, filter_3d, grad_scales, grad_opacities))
 
 
 KNN_BOX = 256   # == STP_KNN_BOX (include/stp_raster.h): points per box of the search, and lanes per workgroup

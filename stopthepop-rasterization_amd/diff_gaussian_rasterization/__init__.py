@@ -30,7 +30,7 @@ __all__ = ["rasterize_gaussians", "SortMode", "GlobalSortOrder", "SortQueueSizes
            "knn_mean_dist2", "distCUDA2", "dist_cuda2", "activate_params",
            "densification_stats_", "densify_plan", "densify_tensors", "densify_and_prune",
            "mcmc_relocation_plan", "mcmc_relocate_tensors_", "mcmc_relocate_", "mcmc_add_plan", "mcmc_add_tensors", "mcmc_add_new",
-           "spatial_order", "gather_tensors", "reorder_gaussians_"]
+           "spatial_order", "gather_tensors", "reorder_gaussians_", "compute_3d_filter", "filtered_activations"]
 
 
 def enum_dict_factory(data):
@@ -912,6 +912,52 @@ def mcmc_add_noise_(xyz: torch.Tensor, scales: torch.Tensor, rotations: torch.Te
     on different devices, an xyz that is not contiguous."""
     _C.mcmc_add_noise(xyz.detach(), scales.detach(), rotations.detach(), opacities.detach(), noise.detach(), noise_scale, k, x0, raw)
     return xyz
+
+
+def compute_3d_filter(xyz: torch.Tensor, world_view_transforms: torch.Tensor, intrinsics: torch.Tensor) -> torch.Tensor:
+    """Mip-Splatting's 3D smoothing filter over ALL training cameras in one pass (extension; include/stp_raster.h: stp_mip_filter_3d; that
+    trainer's GaussianModel.compute_3D_filter) -> filter_3d, (P, 1) float32, never requiring grad, on the current
+    stream without host synchronisation.  xyz: (P, 3); world_view_transforms: (C, 4, 4), every camera's world_view_transform (row-vector
+    layout, p_cam = [p, 1] @ M; only M[:3, :3] and M[3, :3] are read); intrinsics: (C, 4) = (focal_x, focal_y, image_width, image_height);
+    float32 on one GPU, made contiguous where they are not.  With (x, y, z) = p_cam, per Gaussian and camera:
+        valid = z > 0.2  and  -0.15 W <= x / max(z, 0.001) * focal_x + W / 2 <= 1.15 W  and the same in y with focal_y and H
+        distance = min over the valid cameras of z;   a row no camera sees takes the largest distance of the rows that are seen
+        filter_3d = distance / max_c(focal_x) * sqrt(0.2)                                       (the maximum over all cameras)
+    Where NO row is seen every row keeps the distance 100000 (upstream raises there, which needs a read-back).  A NaN coordinate is never valid.
+    Equal inputs give equal bits.  P == 0 gives an empty (0, 1) tensor; C == 0 is refused.  Refused with a RuntimeError naming the argument: CPU
+    tensors ("no CPU path"), other dtypes than float32, shapes or row counts that do not match, tensors on different devices."""
+    return _C.compute_3d_filter(xyz.detach(), world_view_transforms.detach(), intrinsics.detach())
+
+
+class _FilteredActivations(torch.autograd.Function):
+    """(scaling, opacity, filter_3d) -> (scales, opacities): one kernel forward, one backward that recomputes from the three inputs."""
+
+    @staticmethod
+    def forward(ctx, scaling, opacity, filter_3d):
+        ctx.save_for_backward(scaling, opacity, filter_3d)
+        ctx.set_materialize_grads(False)   # (an output the loss did not use arrives as None: the kernel then skips its stream)
+        return _C.mip_activations(scaling, opacity, filter_3d)
+
+    @staticmethod
+    def backward(ctx, grad_scales, grad_opacities):
+        if grad_scales is None and grad_opacities is None:
+            return None, None, None
+        scaling, opacity, filter_3d = ctx.saved_tensors
+        g_scaling, g_opacity = _C.mip_activations_backward(scaling, opacity, filter_3d, grad_scales, grad_opacities)
+        return g_scaling, g_opacity, None
+
+
+def filtered_activations(scaling: torch.Tensor, opacity: torch.Tensor, filter_3d: torch.Tensor):
+    """Mip-Splatting's get_scaling_with_3D_filter and get_opacity_with_3D_filter in one kernel, differentiable (extension; include/stp_raster.h:
+    stp_mip_activations_forward / _backward) -> (scales (P, 3), opacities of opacity's shape), the `scales=` and
+    `opacities=` of the ordinary (non-raw) GaussianRasterizer call.  scaling: (P, 3) stored log-scales; opacity: (P,) or (P, 1) stored logits;
+    filter_3d: (P,) or (P, 1), compute_3d_filter's buffer -- it gets NO gradient (None).  With e_j = exp(scaling_j), f = filter_3d:
+        scales_j = sqrt(e_j^2 + f^2)      r_j = e_j^2 / (e_j^2 + f^2)      opacities = sigmoid(opacity) * sqrt(r_0 r_1 r_2)
+    which is upstream's sqrt(prod e^2 / prod (e^2 + f^2)) without the determinants that leave float32's normal range for small scales.  The
+    backward saves nothing but the three inputs; either output may go unused.  Deterministic: equal inputs give equal bits, forward and
+    backward.  Refused with a RuntimeError naming the argument: CPU tensors ("no CPU path"), other dtypes than float32, shapes or row counts
+    that do not match, tensors on different devices."""
+    return _FilteredActivations.apply(scaling, opacity, filter_3d)
 
 
 def knn_mean_dist2(points: torch.Tensor) -> torch.Tensor:
