@@ -781,6 +781,32 @@ PhotometricShape photometric_check(const char* who, const torch::Tensor& image, 
     photometric_tensor_check(who, image, target);
     return photometric_shape(who, image);
 }
+// the outputs of a loss forward on the (contiguous) image: n_terms floats and, with want_maps, the maps (3, *image.shape).  An empty image:
+// NaN terms (the means of nothing, as torch's) and (3, 0) maps -- the caller returns them as they are
+struct LossOutputs { torch::Tensor terms, maps; };
+LossOutputs loss_outputs(const torch::Tensor& image, const int64_t n_terms, const bool want_maps)
+{
+    const auto opt = image.options();
+    LossOutputs o{torch::empty({n_terms}, opt), torch::Tensor()};
+    if (image.numel() == 0) o.terms.fill_(std::numeric_limits<float>::quiet_NaN());
+    if (want_maps) {
+        std::vector<int64_t> shape{3};
+        if (image.numel() == 0) shape.push_back(0);
+        else shape.insert(shape.end(), image.sizes().begin(), image.sizes().end());
+        o.maps = torch::empty(shape, opt);
+    }
+    return o;
+}
+// what a loss backward with n_terms terms asks of maps and of grad_out = dL/dterms -> grad_out as contiguous float32
+torch::Tensor loss_backward_check(const char* who, const torch::Tensor& image, const torch::Tensor& maps, const torch::Tensor& grad_out, const int64_t n_terms)
+{
+    TORCH_CHECK(maps.defined() && maps.is_cuda() && maps.device() == image.device() && maps.scalar_type() == torch::kFloat32 && maps.is_contiguous() &&
+                    maps.numel() == 3 * image.numel(),
+                who, ": maps must be the contiguous float32 tensor of 3 * image.numel() elements a forward with want_maps returned");
+    TORCH_CHECK(grad_out.defined() && grad_out.is_cuda() && grad_out.device() == image.device() && grad_out.numel() == n_terms,
+                who, ": grad_out", n_terms, " must hold ", n_terms == 2 ? "two" : "three", " elements on the device of image");
+    return grad_out.to(torch::kFloat32).contiguous();
+}
 
 // -> (out2 = [mean |image - target|, mean SSIM], the three derivative maps (3, *image.shape) or an undefined tensor)
 std::tuple<torch::Tensor, torch::Tensor> photometric_forward(const torch::Tensor& image_in, const torch::Tensor& target_in, const bool want_maps)
@@ -788,23 +814,13 @@ std::tuple<torch::Tensor, torch::Tensor> photometric_forward(const torch::Tensor
     need_library();
     const PhotometricShape s = photometric_check("photometric_forward", image_in, target_in);
     const torch::Tensor image = image_in.contiguous(), target = target_in.contiguous();
-    const auto opt = image.options();
     const c10::hip::HIPGuard guard(image.device().index());
-    torch::Tensor out2 = torch::empty({2}, opt), maps;
-    if (image.numel() == 0) { // the mean of nothing, as torch's
-        out2.fill_(std::numeric_limits<float>::quiet_NaN());
-        if (want_maps) maps = torch::empty({3, 0}, opt);
-        return {out2, maps};
-    }
-    if (want_maps) {
-        std::vector<int64_t> shape{3};
-        for (const int64_t d : image.sizes()) shape.push_back(d);
-        maps = torch::empty(shape, opt);
-    }
-    torch::Tensor workspace = torch::empty({(int64_t)g_api.photometric_workspace_floats(s.planes, s.H, s.W)}, opt);
-    checked(g_api.photometric_forward(s.planes, s.H, s.W, image.data_ptr<float>(), target.data_ptr<float>(), out2.data_ptr<float>(),
-                                      want_maps ? maps.data_ptr<float>() : nullptr, workspace.data_ptr<float>(), current_stream(image.device())));
-    return {out2, maps};
+    const LossOutputs o = loss_outputs(image, 2, want_maps);
+    if (image.numel() == 0) return {o.terms, o.maps};
+    torch::Tensor workspace = torch::empty({(int64_t)g_api.photometric_workspace_floats(s.planes, s.H, s.W)}, image.options());
+    checked(g_api.photometric_forward(s.planes, s.H, s.W, image.data_ptr<float>(), target.data_ptr<float>(), o.terms.data_ptr<float>(),
+                                      want_maps ? o.maps.data_ptr<float>() : nullptr, workspace.data_ptr<float>(), current_stream(image.device())));
+    return {o.terms, o.maps};
 }
 
 // -> dL/dimage (image's shape); grad_out2 = dL/dout2, two floats on the device (read there: no host synchronisation)
@@ -813,12 +829,7 @@ torch::Tensor photometric_backward(const torch::Tensor& image_in, const torch::T
     need_library();
     const PhotometricShape s = photometric_check("photometric_backward", image_in, target_in);
     const torch::Tensor image = image_in.contiguous(), target = target_in.contiguous();
-    TORCH_CHECK(maps.defined() && maps.is_cuda() && maps.device() == image.device() && maps.scalar_type() == torch::kFloat32 && maps.is_contiguous() &&
-                    maps.numel() == 3 * image.numel(),
-                "photometric_backward: maps must be the contiguous float32 tensor of 3 * image.numel() elements a forward with want_maps returned");
-    TORCH_CHECK(grad_out2_in.defined() && grad_out2_in.is_cuda() && grad_out2_in.device() == image.device() && grad_out2_in.numel() == 2,
-                "photometric_backward: grad_out2 must hold two elements on the device of image");
-    const torch::Tensor grad_out2 = grad_out2_in.to(torch::kFloat32).contiguous();
+    const torch::Tensor grad_out2 = loss_backward_check("photometric_backward", image, maps, grad_out2_in, 2);
     const c10::hip::HIPGuard guard(image.device().index());
     torch::Tensor dL_dimage = torch::empty(image.sizes(), image.options());
     if (image.numel() == 0) return dL_dimage;
@@ -913,23 +924,13 @@ std::tuple<torch::Tensor, torch::Tensor> training_loss_forward(const torch::Tens
     static const char* const who = "training_loss_forward";
     const TrainingExtras x = training_check(who, image_in, target_in, exposure, clamp, alpha_mask, invdepth, mono_invdepth, depth_mask);
     const torch::Tensor image = image_in.contiguous(), target = target_in.contiguous();
-    const auto opt = image.options();
     const c10::hip::HIPGuard guard(image.device().index());
-    torch::Tensor out3 = torch::empty({3}, opt), maps;
-    if (image.numel() == 0) { // the means of nothing, as torch's
-        out3.fill_(std::numeric_limits<float>::quiet_NaN());
-        if (want_maps) maps = torch::empty({3, 0}, opt);
-        return {out3, maps};
-    }
-    if (want_maps) {
-        std::vector<int64_t> shape{3};
-        for (const int64_t d : image.sizes()) shape.push_back(d);
-        maps = torch::empty(shape, opt);
-    }
-    torch::Tensor workspace = torch::empty({(int64_t)g_api.training_loss_workspace_floats(x.s.planes, x.s.H, x.s.W, x.pod.depth_planes)}, opt);
-    checked(g_api.training_loss_forward(x.s.planes, x.s.H, x.s.W, image.data_ptr<float>(), target.data_ptr<float>(), &x.pod, out3.data_ptr<float>(),
-                                        want_maps ? maps.data_ptr<float>() : nullptr, workspace.data_ptr<float>(), current_stream(image.device())));
-    return {out3, maps};
+    const LossOutputs o = loss_outputs(image, 3, want_maps);
+    if (image.numel() == 0) return {o.terms, o.maps};
+    torch::Tensor workspace = torch::empty({(int64_t)g_api.training_loss_workspace_floats(x.s.planes, x.s.H, x.s.W, x.pod.depth_planes)}, image.options());
+    checked(g_api.training_loss_forward(x.s.planes, x.s.H, x.s.W, image.data_ptr<float>(), target.data_ptr<float>(), &x.pod, o.terms.data_ptr<float>(),
+                                        want_maps ? o.maps.data_ptr<float>() : nullptr, workspace.data_ptr<float>(), current_stream(image.device())));
+    return {o.terms, o.maps};
 }
 
 // -> (dL/dimage, dL/dexposure (exposure's shape) or undefined, dL/dinvdepth (invdepth's shape) or undefined); grad_out3: three floats on the device
@@ -942,14 +943,9 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> training_loss_backward(c
     static const char* const who = "training_loss_backward";
     const TrainingExtras x = training_check(who, image_in, target_in, exposure, clamp, alpha_mask, invdepth, mono_invdepth, depth_mask);
     const torch::Tensor image = image_in.contiguous(), target = target_in.contiguous();
-    TORCH_CHECK(maps.defined() && maps.is_cuda() && maps.device() == image.device() && maps.scalar_type() == torch::kFloat32 && maps.is_contiguous() &&
-                    maps.numel() == 3 * image.numel(),
-                who, ": maps must be the contiguous float32 tensor of 3 * image.numel() elements a forward with want_maps returned");
-    TORCH_CHECK(grad_out3_in.defined() && grad_out3_in.is_cuda() && grad_out3_in.device() == image.device() && grad_out3_in.numel() == 3,
-                who, ": grad_out3 must hold three elements on the device of image");
+    const torch::Tensor grad_out3 = loss_backward_check(who, image, maps, grad_out3_in, 3);
     TORCH_CHECK(!want_exposure || x.exposure.defined(), who, ": a gradient for an exposure that was not given");
     TORCH_CHECK(!want_invdepth || x.invdepth.defined(), who, ": a gradient for an invdepth that was not given");
-    const torch::Tensor grad_out3 = grad_out3_in.to(torch::kFloat32).contiguous();
     const c10::hip::HIPGuard guard(image.device().index());
     torch::Tensor dL_dimage = torch::empty(image.sizes(), image.options()), dL_dexposure, dL_dinvdepth, workspace;
     if (want_exposure) dL_dexposure = torch::empty(x.exposure.sizes(), image.options());

@@ -30,9 +30,12 @@
 // same tree after that, and divides by n.  Equal inputs give equal bits.
 //
 // The training loss (stp_training_loss_forward / _backward) is the same pair with the trainer's exposure, clamp, alpha mask and depth term:
-// variants of these kernels further down, under a comment of their own that states the colour transform's fixed chain
+// kernels of its own further down, under a comment that states the colour transform's fixed chain
 //     v_j = fma(E[2][j], x_2, fma(E[1][j], x_1, fma(E[0][j], x_0, E[j][3])))
-// The three kernels of the plain call are not touched by them.
+// Both pairs are their own staging around ONE copy of the numerics, the __device__ __forceinline__ pieces ssim_tile, blur_maps,
+// photometric_gradient, rows_sum / photometric_means and loss_tile_at.  Every fused operation of a piece is an explicit __fmaf_rn,
+// so it is the same arithmetic in a caller under `fp contract(off)` and in one without.  What holds the bits of both pairs in place is
+// tests/test_gpu_loss_bits.py: outputs recorded from the kernels as they were before the pieces were shared.
 #include "stp_internal.h"
 
 namespace stp {
@@ -76,14 +79,15 @@ __device__ __forceinline__ float block_sum(float v, float* s_wave)
 }
 
 struct LossTile { int plane, x0, y0; };
-// blockIdx.x -> (plane, tile): wave-uniform, scalar code
-__device__ __forceinline__ LossTile loss_tile(const int tiles_x, const int tiles_y)
+// entry idx of the flat (plane, tile row, tile column) list: wave-uniform, scalar code
+__device__ __forceinline__ LossTile loss_tile_at(const uint32_t idx, const int tiles_x, const int tiles_y)
 {
     const uint32_t per_plane = (uint32_t)tiles_x * (uint32_t)tiles_y;
-    const uint32_t plane = blockIdx.x / per_plane, t = blockIdx.x - plane * per_plane;
+    const uint32_t plane = idx / per_plane, t = idx - plane * per_plane;
     const uint32_t ty = t / (uint32_t)tiles_x, tx = t - ty * (uint32_t)tiles_x;
     return LossTile{(int)plane, (int)tx * LOSS_TW, (int)ty * LOSS_TH};
 }
+__device__ __forceinline__ LossTile loss_tile(const int tiles_x, const int tiles_y) { return loss_tile_at(blockIdx.x, tiles_x, tiles_y); }
 
 // the 74 x 26 halo tile of one plane into LDS, scaled; zeros outside the image
 __device__ __forceinline__ void stage_halo(float (*dst)[LOSS_HW], const float* __restrict__ src, const int x0, const int y0, const int H, const int W,
@@ -98,20 +102,14 @@ __device__ __forceinline__ void stage_halo(float (*dst)[LOSS_HW], const float* _
     }
 }
 
+// The forward of one tile from its staged halo tiles s_x, s_y (the staging's barrier included): the two passes of the window, the SSIM of the
+// thread's four pixels, with MAPS the three derivative maps at plane_off, and the tile's sums of |x - y| and of m into row[0], row[1]
 template <bool MAPS>
-__global__ void __launch_bounds__(LOSS_BLOCK) photometric_forward_kernel(const float* __restrict__ image, const float* __restrict__ target, const int H, const int W,
-                                                                         const int tiles_x, const int tiles_y, const size_t n, float* __restrict__ maps,
-                                                                         float* __restrict__ partials)
+__device__ __forceinline__ void ssim_tile(const float (&s_x)[LOSS_HH][LOSS_HW], const float (&s_y)[LOSS_HH][LOSS_HW], float (&s_h)[5][LOSS_HH][LOSS_TW],
+                                          float (&s_wave)[LOSS_BLOCK / 64], const LossTile t, const size_t plane_off, const int H, const int W, const size_t n,
+                                          float* __restrict__ maps, float* __restrict__ row)
 {
-    __shared__ float s_x[LOSS_HH][LOSS_HW], s_y[LOSS_HH][LOSS_HW];
-    __shared__ float s_h[5][LOSS_HH][LOSS_TW];
-    __shared__ float s_wave[LOSS_BLOCK / 64];
-    const LossTile t = loss_tile(tiles_x, tiles_y);
-    const size_t plane_off = (size_t)t.plane * H * W;
-    stage_halo(s_x, image + plane_off, t.x0, t.y0, H, W, 1.0f);
-    stage_halo(s_y, target + plane_off, t.x0, t.y0, H, W, 1.0f);
     __syncthreads();
-
     const int col = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // horizontal pass: rows wave, wave + 4, ... of the 26
     for (int r = wave; r < LOSS_HH; r += LOSS_BLOCK / 64) {
@@ -169,22 +167,84 @@ __global__ void __launch_bounds__(LOSS_BLOCK) photometric_forward_kernel(const f
     const float bl1 = block_sum(sum_l1, s_wave);
     const float bm = block_sum(sum_m, s_wave);
     if (threadIdx.x == 0) {
-        partials[2 * (size_t)blockIdx.x] = bl1;
-        partials[2 * (size_t)blockIdx.x + 1] = bm;
+        row[0] = bl1;
+        row[1] = bm;
     }
 }
 
-// one workgroup: the `groups` partial rows, thread t rows t, t + 256, ... in order, then the workgroup's sum, divided by n
+template <bool MAPS>
+__global__ void __launch_bounds__(LOSS_BLOCK) photometric_forward_kernel(const float* __restrict__ image, const float* __restrict__ target, const int H, const int W,
+                                                                         const int tiles_x, const int tiles_y, const size_t n, float* __restrict__ maps,
+                                                                         float* __restrict__ partials)
+{
+    __shared__ float s_x[LOSS_HH][LOSS_HW], s_y[LOSS_HH][LOSS_HW];
+    __shared__ float s_h[5][LOSS_HH][LOSS_TW];
+    __shared__ float s_wave[LOSS_BLOCK / 64];
+    const LossTile t = loss_tile(tiles_x, tiles_y);
+    const size_t plane_off = (size_t)t.plane * H * W;
+    stage_halo(s_x, image + plane_off, t.x0, t.y0, H, W, 1.0f);
+    stage_halo(s_y, target + plane_off, t.x0, t.y0, H, W, 1.0f);
+    ssim_tile<MAPS>(s_x, s_y, s_h, s_wave, t, plane_off, H, W, n, maps, partials + 2 * (size_t)blockIdx.x);
+}
+
+// the workgroup's sum of column k of `rows` rows of `stride` floats, in every thread: thread t adds the rows t, t + 256, ... in order, then block_sum
+__device__ __forceinline__ float rows_sum(const float* __restrict__ partials, const size_t first, const uint32_t rows, const int stride, const int k, float* s_wave)
+{
+    float acc = 0.0f;
+    for (uint32_t r = threadIdx.x; r < rows; r += LOSS_BLOCK) acc += partials[stride * (first + r) + k];
+    return block_sum(acc, s_wave);
+}
+
+// out2[0 .. 1] = the two columns of the `groups` partial rows, each summed and then divided by n once
+__device__ __forceinline__ void photometric_means(const float* __restrict__ partials, const uint32_t groups, const float n, float* __restrict__ out2, float* s_wave)
+{
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const float s = rows_sum(partials, 0, groups, 2, k, s_wave);
+        if (threadIdx.x == 0) out2[k] = s / n;
+    }
+}
+
+// one workgroup: the means of the `groups` partial rows
 __global__ void __launch_bounds__(LOSS_BLOCK) photometric_sum_kernel(const float* __restrict__ partials, const uint32_t groups, const float n, float* __restrict__ out2)
 {
     __shared__ float s_wave[LOSS_BLOCK / 64];
+    photometric_means(partials, groups, n, out2, s_wave);
+}
+
+// The backward's blur of the three staged maps s_d (the staging's barrier included): b[k][o] = blur(s_d[k]) at the thread's pixel o.  Behind
+// the second barrier nobody reads s_d, and s_h is read only before the caller's next barrier
+__device__ __forceinline__ void blur_maps(const float (&s_d)[3][LOSS_HH][LOSS_HW], float (&s_h)[3][LOSS_HH][LOSS_TW], float (&b)[3][LOSS_ROWS])
+{
+    __syncthreads();
+    const int col = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = wave; r < LOSS_HH; r += LOSS_BLOCK / 64) {
 #pragma unroll
-    for (int k = 0; k < 2; k++) {
-        float acc = 0.0f;
-        for (uint32_t r = threadIdx.x; r < groups; r += LOSS_BLOCK) acc += partials[2 * (size_t)r + k];
-        const float s = block_sum(acc, s_wave);
-        if (threadIdx.x == 0) out2[k] = s / n;
+        for (int k = 0; k < 3; k++) {
+            float v[11];
+#pragma unroll
+            for (int j = 0; j < 11; j++) v[j] = s_d[k][r][col + j];
+            s_h[k][r][col] = window11(v);
+        }
     }
+    __syncthreads();
+
+    const int r0 = wave * LOSS_ROWS;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float v[LOSS_ROWS + 10];
+#pragma unroll
+        for (int j = 0; j < LOSS_ROWS + 10; j++) v[j] = s_h[k][r0 + j][col];
+#pragma unroll
+        for (int o = 0; o < LOSS_ROWS; o++) b[k][o] = window11(v + o);
+    }
+}
+
+// dL/dx of a pixel from its three blurred maps b0, b1, b2 and l1w = g0 / n:  b0 + 2 x b1 + y b2 + l1w sign(x - y)
+__device__ __forceinline__ float photometric_gradient(const float x, const float y, const float b0, const float b1, const float b2, const float l1w)
+{
+    const float sgn = x > y ? l1w : (x < y ? -l1w : 0.0f); // (a NaN pixel: 0)
+    return __fmaf_rn(y, b2, __fmaf_rn(2.0f * x, b1, b0)) + sgn;
 }
 
 __global__ void __launch_bounds__(LOSS_BLOCK) photometric_backward_kernel(const float* __restrict__ image, const float* __restrict__ target, const float* __restrict__ maps,
@@ -198,46 +258,21 @@ __global__ void __launch_bounds__(LOSS_BLOCK) photometric_backward_kernel(const 
     const float l1w = dL_dout2[0] / nf, s = dL_dout2[1] / nf;
 #pragma unroll
     for (int k = 0; k < 3; k++) stage_halo(s_d[k], maps + (size_t)k * n + plane_off, t.x0, t.y0, H, W, s);
-    __syncthreads();
-
-    const int col = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int r = wave; r < LOSS_HH; r += LOSS_BLOCK / 64) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float v[11];
-#pragma unroll
-            for (int j = 0; j < 11; j++) v[j] = s_d[k][r][col + j];
-            s_h[k][r][col] = window11(v);
-        }
-    }
-    __syncthreads();
-
     float b[3][LOSS_ROWS];
-    const int r0 = wave * LOSS_ROWS;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        float v[LOSS_ROWS + 10];
-#pragma unroll
-        for (int j = 0; j < LOSS_ROWS + 10; j++) v[j] = s_h[k][r0 + j][col];
-#pragma unroll
-        for (int o = 0; o < LOSS_ROWS; o++) b[k][o] = window11(v + o);
-    }
-    const int gx = t.x0 + col;
+    blur_maps(s_d, s_h, b);
+    const int col = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * LOSS_ROWS, gx = t.x0 + col;
 #pragma unroll
     for (int o = 0; o < LOSS_ROWS; o++) {
         const int gy = t.y0 + r0 + o;
         if (gx < W && gy < H) {
             const size_t e = plane_off + (size_t)gy * W + gx;
-            const float x = image[e], y = target[e];
-            const float sgn = x > y ? l1w : (x < y ? -l1w : 0.0f); // (a NaN pixel: 0)
-            dL_dimage[e] = __fmaf_rn(y, b[2][o], __fmaf_rn(2.0f * x, b[1][o], b[0][o])) + sgn;
+            dL_dimage[e] = photometric_gradient(image[e], target[e], b[0][o], b[1][o], b[2][o], l1w);
         }
     }
 }
 
 // ---- the training loss: the same tiles with the colour transform, the clamp and the alpha mask in the staging, the depth term in the same
-// launch.  The kernels above are not touched (their registers, LDS and code are those of the plain photometric call); these are their
-// variants, and everything they add to the arithmetic is written with explicit fused multiply-adds and is never contracted.
+// launch.  Everything these kernels add to the arithmetic of the pieces above is written with explicit fused multiply-adds and is never contracted.
 //     v_j = fma(E[2][j], x_2, fma(E[1][j], x_1, fma(E[0][j], x_0, E[j][3])))       (E row-major 3 x 4; the row index is the INPUT channel)
 //     clamp: v < 0 ? 0 : v > 1 ? 1 : v (a NaN stays)        x''_j = v_j * alpha_mask       a halo pixel outside the image: 0
 // Backward: a workgroup owns an (image, tile) and loops over the image's channels j with the same LDS; g''_j is the expression of
@@ -253,14 +288,6 @@ struct LossColour {
     size_t mask_stride;
 };
 struct LossDepth { const float *invdepth, *mono, *mask; };
-
-__device__ __forceinline__ LossTile loss_tile_at(const uint32_t idx, const int tiles_x, const int tiles_y)
-{
-    const uint32_t per_plane = (uint32_t)tiles_x * (uint32_t)tiles_y;
-    const uint32_t plane = idx / per_plane, t = idx - plane * per_plane;
-    const uint32_t ty = t / (uint32_t)tiles_x, tx = t - ty * (uint32_t)tiles_x;
-    return LossTile{(int)plane, (int)tx * LOSS_TW, (int)ty * LOSS_TH};
-}
 
 __device__ __forceinline__ float clamp01(const float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
 
@@ -332,67 +359,7 @@ __global__ void __launch_bounds__(LOSS_BLOCK) training_forward_kernel(const floa
         }
     }
     stage_halo(s_y, target + plane_off, t.x0, t.y0, H, W, 1.0f);
-    __syncthreads();
-
-    // from here on: photometric_forward_kernel on s_x = x''
-    const int col = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int r = wave; r < LOSS_HH; r += LOSS_BLOCK / 64) {
-        float x[11], y[11], xx[11], yy[11], xy[11];
-#pragma unroll
-        for (int j = 0; j < 11; j++) {
-            x[j] = s_x[r][col + j];
-            y[j] = s_y[r][col + j];
-            xx[j] = x[j] * x[j];
-            yy[j] = y[j] * y[j];
-            xy[j] = x[j] * y[j];
-        }
-        s_h[0][r][col] = window11(x);
-        s_h[1][r][col] = window11(y);
-        s_h[2][r][col] = window11(xx);
-        s_h[3][r][col] = window11(yy);
-        s_h[4][r][col] = window11(xy);
-    }
-    __syncthreads();
-
-    float st[5][LOSS_ROWS];
-    const int r0 = wave * LOSS_ROWS;
-#pragma unroll
-    for (int q = 0; q < 5; q++) {
-        float v[LOSS_ROWS + 10];
-#pragma unroll
-        for (int j = 0; j < LOSS_ROWS + 10; j++) v[j] = s_h[q][r0 + j][col];
-#pragma unroll
-        for (int o = 0; o < LOSS_ROWS; o++) st[q][o] = window11(v + o);
-    }
-
-    float sum_l1 = 0.0f, sum_m = 0.0f;
-    const int gx = t.x0 + col;
-#pragma unroll
-    for (int o = 0; o < LOSS_ROWS; o++) {
-        const int gy = t.y0 + r0 + o;
-        if (gx < W && gy < H) {
-            const float mu1 = st[0][o], mu2 = st[1][o];
-            const float s1 = __fmaf_rn(-mu1, mu1, st[2][o]), s2 = __fmaf_rn(-mu2, mu2, st[3][o]), s12 = __fmaf_rn(-mu1, mu2, st[4][o]);
-            const float A = __fmaf_rn(2.0f * mu1, mu2, LOSS_C1), B = __fmaf_rn(2.0f, s12, LOSS_C2);
-            const float Cc = __fmaf_rn(mu1, mu1, __fmaf_rn(mu2, mu2, LOSS_C1)), D = (s1 + s2) + LOSS_C2;
-            const float rcd = 1.0f / (Cc * D);
-            const float m = (A * B) * rcd;
-            sum_m += m;
-            sum_l1 += fabsf(s_x[r0 + o + LOSS_R][col + LOSS_R] - s_y[r0 + o + LOSS_R][col + LOSS_R]);
-            if constexpr (MAPS) {
-                const size_t e = plane_off + (size_t)gy * W + gx;
-                maps[e] = 2.0f * __fmaf_rn(mu2, B - A, (mu1 * m) * (Cc - D)) * rcd;
-                maps[n + e] = -m / D;
-                maps[2 * n + e] = (2.0f * A) * rcd;
-            }
-        }
-    }
-    const float bl1 = block_sum(sum_l1, s_wave);
-    const float bm = block_sum(sum_m, s_wave);
-    if (threadIdx.x == 0) {
-        partials[2 * (size_t)blockIdx.x] = bl1;
-        partials[2 * (size_t)blockIdx.x + 1] = bm;
-    }
+    ssim_tile<MAPS>(s_x, s_y, s_h, s_wave, t, plane_off, H, W, n, maps, partials + 2 * (size_t)blockIdx.x); // the plain forward on s_x = x''
 }
 
 // photometric_sum_kernel with the depth term's column: out3[0 .. 1] by the same additions, out3[2] = the depth rows' sum / n_d (0 without rows)
@@ -400,16 +367,8 @@ __global__ void __launch_bounds__(LOSS_BLOCK) training_sum_kernel(const float* _
                                                                   const float n_d, float* __restrict__ out3)
 {
     __shared__ float s_wave[LOSS_BLOCK / 64];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        float acc = 0.0f;
-        for (uint32_t r = threadIdx.x; r < groups; r += LOSS_BLOCK) acc += partials[2 * (size_t)r + k];
-        const float s = block_sum(acc, s_wave);
-        if (threadIdx.x == 0) out3[k] = s / n;
-    }
-    float acc = 0.0f;
-    for (uint32_t r = threadIdx.x; r < depth_groups; r += LOSS_BLOCK) acc += partials[2 * (size_t)groups + r];
-    const float s = block_sum(acc, s_wave);
+    photometric_means(partials, groups, n, out3, s_wave);
+    const float s = rows_sum(partials, 2 * (size_t)groups, depth_groups, 1, 0, s_wave);
     if (threadIdx.x == 0) out3[2] = depth_groups ? s / n_d : 0.0f;
 }
 
@@ -424,7 +383,7 @@ __global__ void __launch_bounds__(LOSS_BLOCK) training_backward_kernel(const flo
     __shared__ float s_d[3][LOSS_HH][LOSS_HW];
     __shared__ float s_h[3][LOSS_HH][LOSS_TW];
     __shared__ float s_wave[LOSS_BLOCK / 64];
-    const int col = threadIdx.x & 63, wave = threadIdx.x >> 6, r0 = wave * LOSS_ROWS;
+    const int col = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * LOSS_ROWS;
     const size_t hw = (size_t)H * W;
     if (blockIdx.x >= image_groups) { // (workgroup-uniform) a depth tile
         const LossTile t = loss_tile_at(blockIdx.x - image_groups, tiles_x, tiles_y);
@@ -462,26 +421,8 @@ __global__ void __launch_bounds__(LOSS_BLOCK) training_backward_kernel(const flo
         const size_t plane_off = ((size_t)t.plane * c.channels + j) * hw;
 #pragma unroll
         for (int k = 0; k < 3; k++) stage_halo(s_d[k], maps + (size_t)k * n + plane_off, t.x0, t.y0, H, W, s);
-        __syncthreads();
-        for (int r = wave; r < LOSS_HH; r += LOSS_BLOCK / 64) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                float v[11];
-#pragma unroll
-                for (int q = 0; q < 11; q++) v[q] = s_d[k][r][col + q];
-                s_h[k][r][col] = window11(v);
-            }
-        }
-        __syncthreads();
         float b[3][LOSS_ROWS];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float v[LOSS_ROWS + 10];
-#pragma unroll
-            for (int q = 0; q < LOSS_ROWS + 10; q++) v[q] = s_h[k][r0 + q][col];
-#pragma unroll
-            for (int o = 0; o < LOSS_ROWS; o++) b[k][o] = window11(v + o);
-        }
+        blur_maps(s_d, s_h, b);
         float pe[4] = {0.0f, 0.0f, 0.0f, 0.0f}; // the thread's sums of x_0 g', x_1 g', x_2 g', g' of channel j
 #pragma unroll
         for (int o = 0; o < LOSS_ROWS; o++) {
@@ -496,9 +437,7 @@ __global__ void __launch_bounds__(LOSS_BLOCK) training_backward_kernel(const flo
                     mk = mk_plane[pix];
                     x = x * mk;
                 }
-                const float y = target[plane_off + pix];
-                const float sgn = x > y ? l1w : (x < y ? -l1w : 0.0f); // (a NaN pixel: 0)
-                float g = __fmaf_rn(y, b[2][o], __fmaf_rn(2.0f * x, b[1][o], b[0][o])) + sgn; // g'': photometric_backward_kernel's expression
+                float g = photometric_gradient(x, target[plane_off + pix], b[0][o], b[1][o], b[2][o], l1w); // g''
                 if (mk_plane) g = g * mk;
                 if (!pass) g = 0.0f;
                 if (E) {
@@ -542,33 +481,47 @@ __global__ void __launch_bounds__(LOSS_BLOCK) exposure_sum_kernel(const float* _
     __shared__ float s_wave[LOSS_BLOCK / 64];
     for (uint32_t e = 0; e < n_out; e++) {
         for (int k = 0; k < 12; k++) {
-            float acc = 0.0f;
-            for (uint32_t r = threadIdx.x; r < rows_per; r += LOSS_BLOCK) acc += partials[12 * ((size_t)e * rows_per + r) + k];
-            const float s = block_sum(acc, s_wave);
+            const float s = rows_sum(partials, (size_t)e * rows_per, rows_per, 12, k, s_wave);
             if (threadIdx.x == 0) out[12 * (size_t)e + k] = s;
         }
     }
 }
 
+// the tiling of `planes` (H, W) planes: tiles per plane, workgroups of a tile kernel (one per (plane, tile)), elements
+struct LossGrid {
+    int tiles_x, tiles_y;
+    uint32_t groups; // <= planes * H * W < 2^31
+    size_t n;
+    LossGrid(int planes, int H, int W)
+        : tiles_x((W + LOSS_TW - 1) / LOSS_TW), tiles_y((H + LOSS_TH - 1) / LOSS_TH), groups((uint32_t)((uint64_t)planes * tiles_y * tiles_x)), n((size_t)planes * H * W) {}
+};
+
+// the plain forward's tile kernel over grid g
+void launch_photometric_tiles(const LossGrid& g, int H, int W, const float* image, const float* target, float* maps, float* workspace, hipStream_t st)
+{
+    if (maps) hipLaunchKernelGGL(photometric_forward_kernel<true>, dim3(g.groups), dim3(LOSS_BLOCK), 0, st, image, target, H, W, g.tiles_x, g.tiles_y, g.n, maps, workspace);
+    else hipLaunchKernelGGL(photometric_forward_kernel<false>, dim3(g.groups), dim3(LOSS_BLOCK), 0, st, image, target, H, W, g.tiles_x, g.tiles_y, g.n, maps, workspace);
+}
+
+bool has_colour_extras(const StpTrainingLoss& x) { return x.exposure || x.alpha_mask || x.clamp; }
+
+LossColour loss_colour(const StpTrainingLoss& x, int H, int W)
+{
+    return LossColour{x.exposure, x.alpha_mask, x.exposure_batched ? 12 : 0, x.clamp, x.channels, x.alpha_mask_batched ? (size_t)H * W : 0};
+}
+
 } // namespace
 
-uint32_t photometric_groups(int planes, int H, int W)
-{
-    const uint64_t g = (uint64_t)planes * ((H + LOSS_TH - 1) / LOSS_TH) * ((W + LOSS_TW - 1) / LOSS_TW); // <= planes * H * W < 2^31
-    return (uint32_t)g;
-}
+uint32_t photometric_groups(int planes, int H, int W) { return LossGrid(planes, H, W).groups; }
 
 int launch_photometric_forward(int planes, int H, int W, const float* image, const float* target, float* out2, float* maps, float* workspace,
                                hipStream_t st, hipError_t* err)
 {
-    const int tiles_x = (W + LOSS_TW - 1) / LOSS_TW, tiles_y = (H + LOSS_TH - 1) / LOSS_TH;
-    const uint32_t groups = photometric_groups(planes, H, W);
-    const size_t n = (size_t)planes * H * W;
+    const LossGrid g(planes, H, W);
     *err = hipSuccess;
-    if (maps) hipLaunchKernelGGL(photometric_forward_kernel<true>, dim3(groups), dim3(LOSS_BLOCK), 0, st, image, target, H, W, tiles_x, tiles_y, n, maps, workspace);
-    else hipLaunchKernelGGL(photometric_forward_kernel<false>, dim3(groups), dim3(LOSS_BLOCK), 0, st, image, target, H, W, tiles_x, tiles_y, n, maps, workspace);
+    launch_photometric_tiles(g, H, W, image, target, maps, workspace, st);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 0; }
-    hipLaunchKernelGGL(photometric_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, groups, (float)n, out2);
+    hipLaunchKernelGGL(photometric_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, g.groups, (float)g.n, out2);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 1; }
     return 2;
 }
@@ -576,17 +529,13 @@ int launch_photometric_forward(int planes, int H, int W, const float* image, con
 int launch_photometric_backward(int planes, int H, int W, const float* image, const float* target, const float* maps, const float* dL_dout2,
                                 float* dL_dimage, hipStream_t st, hipError_t* err)
 {
-    const int tiles_x = (W + LOSS_TW - 1) / LOSS_TW, tiles_y = (H + LOSS_TH - 1) / LOSS_TH;
-    const size_t n = (size_t)planes * H * W;
+    const LossGrid g(planes, H, W);
     *err = hipSuccess;
-    hipLaunchKernelGGL(photometric_backward_kernel, dim3(photometric_groups(planes, H, W)), dim3(LOSS_BLOCK), 0, st, image, target, maps, dL_dout2, H, W,
-                       tiles_x, tiles_y, n, (float)n, dL_dimage);
+    hipLaunchKernelGGL(photometric_backward_kernel, dim3(g.groups), dim3(LOSS_BLOCK), 0, st, image, target, maps, dL_dout2, H, W, g.tiles_x, g.tiles_y, g.n,
+                       (float)g.n, dL_dimage);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 0; }
     return 1;
 }
-
-static uint32_t image_groups(int planes, int channels, int H, int W) { return photometric_groups(planes / channels, H, W); }
-static bool has_colour_extras(const StpTrainingLoss& x) { return x.exposure || x.alpha_mask || x.clamp; }
 
 size_t training_loss_workspace_floats(int planes, int H, int W, int depth_planes)
 {
@@ -595,29 +544,21 @@ size_t training_loss_workspace_floats(int planes, int H, int W, int depth_planes
     return forward > backward ? forward : backward;
 }
 
-static LossColour loss_colour(const StpTrainingLoss& x, int H, int W)
-{
-    return LossColour{x.exposure, x.alpha_mask, x.exposure_batched ? 12 : 0, x.clamp, x.channels, x.alpha_mask_batched ? (size_t)H * W : 0};
-}
-
 int launch_training_loss_forward(int planes, int H, int W, const float* image, const float* target, const StpTrainingLoss& x, float* out3, float* maps,
                                  float* workspace, hipStream_t st, hipError_t* err)
 {
-    const int tiles_x = (W + LOSS_TW - 1) / LOSS_TW, tiles_y = (H + LOSS_TH - 1) / LOSS_TH;
-    const uint32_t groups = photometric_groups(planes, H, W), depth_groups = x.invdepth ? photometric_groups(x.depth_planes, H, W) : 0;
-    const size_t n = (size_t)planes * H * W, n_d = (size_t)x.depth_planes * H * W;
+    const LossGrid g(planes, H, W), gd(x.invdepth ? x.depth_planes : 0, H, W); // colour planes, depth planes
     *err = hipSuccess;
-    if (!has_colour_extras(x) && !depth_groups) { // the plain call's tile kernel, instantiation for instantiation
-        if (maps) hipLaunchKernelGGL(photometric_forward_kernel<true>, dim3(groups), dim3(LOSS_BLOCK), 0, st, image, target, H, W, tiles_x, tiles_y, n, maps, workspace);
-        else hipLaunchKernelGGL(photometric_forward_kernel<false>, dim3(groups), dim3(LOSS_BLOCK), 0, st, image, target, H, W, tiles_x, tiles_y, n, maps, workspace);
+    if (!has_colour_extras(x) && !gd.groups) { // the plain call's tile kernel, instantiation for instantiation
+        launch_photometric_tiles(g, H, W, image, target, maps, workspace, st);
     } else {
         const LossColour c = loss_colour(x, H, W);
         const LossDepth d{x.invdepth, x.mono_invdepth, x.depth_mask};
-        if (maps) hipLaunchKernelGGL(training_forward_kernel<true>, dim3(groups + depth_groups), dim3(LOSS_BLOCK), 0, st, image, target, c, d, H, W, tiles_x, tiles_y, groups, n, maps, workspace);
-        else hipLaunchKernelGGL(training_forward_kernel<false>, dim3(groups + depth_groups), dim3(LOSS_BLOCK), 0, st, image, target, c, d, H, W, tiles_x, tiles_y, groups, n, maps, workspace);
+        if (maps) hipLaunchKernelGGL(training_forward_kernel<true>, dim3(g.groups + gd.groups), dim3(LOSS_BLOCK), 0, st, image, target, c, d, H, W, g.tiles_x, g.tiles_y, g.groups, g.n, maps, workspace);
+        else hipLaunchKernelGGL(training_forward_kernel<false>, dim3(g.groups + gd.groups), dim3(LOSS_BLOCK), 0, st, image, target, c, d, H, W, g.tiles_x, g.tiles_y, g.groups, g.n, maps, workspace);
     }
     if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 0; }
-    hipLaunchKernelGGL(training_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, groups, (float)n, depth_groups, (float)n_d, out3);
+    hipLaunchKernelGGL(training_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, g.groups, (float)g.n, gd.groups, (float)gd.n, out3);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 1; }
     return 2;
 }
@@ -626,22 +567,22 @@ int launch_training_loss_backward(int planes, int H, int W, const float* image, 
                                   const float* dL_dout3, float* dL_dimage, float* dL_dexposure, float* dL_dinvdepth, float* workspace, hipStream_t st,
                                   hipError_t* err)
 {
-    const int tiles_x = (W + LOSS_TW - 1) / LOSS_TW, tiles_y = (H + LOSS_TH - 1) / LOSS_TH;
-    const size_t n = (size_t)planes * H * W, n_d = (size_t)x.depth_planes * H * W;
     *err = hipSuccess;
     if (!has_colour_extras(x) && !dL_dinvdepth) // (dL_dout3[0 .. 1] are the plain call's two)
         return launch_photometric_backward(planes, H, W, image, target, maps, dL_dout3, dL_dimage, st, err);
-    const uint32_t groups = image_groups(planes, x.channels, H, W), depth_groups = dL_dinvdepth ? photometric_groups(x.depth_planes, H, W) : 0;
-    const uint32_t tiles = (uint32_t)tiles_x * (uint32_t)tiles_y;
-    hipLaunchKernelGGL(training_backward_kernel, dim3(groups + depth_groups), dim3(LOSS_BLOCK), 0, st, image, target, maps, dL_dout3, loss_colour(x, H, W),
-                       LossDepth{x.invdepth, x.mono_invdepth, x.depth_mask}, H, W, tiles_x, tiles_y, groups, n, (float)n, (float)n_d, dL_dimage, dL_dinvdepth,
+    const LossGrid gi(planes / x.channels, H, W), gd(dL_dinvdepth ? x.depth_planes : 0, H, W); // a workgroup per (image, tile), then the depth planes' tiles
+    const size_t n = (size_t)planes * H * W;
+    const uint32_t tiles = (uint32_t)gi.tiles_x * (uint32_t)gi.tiles_y;
+    hipLaunchKernelGGL(training_backward_kernel, dim3(gi.groups + gd.groups), dim3(LOSS_BLOCK), 0, st, image, target, maps, dL_dout3, loss_colour(x, H, W),
+                       LossDepth{x.invdepth, x.mono_invdepth, x.depth_mask}, H, W, gi.tiles_x, gi.tiles_y, gi.groups, n, (float)n, (float)gd.n, dL_dimage, dL_dinvdepth,
                        dL_dexposure ? workspace : nullptr);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 0; }
     if (!dL_dexposure) return 1;
-    if (x.exposure_batched) hipLaunchKernelGGL(exposure_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, tiles, groups / tiles, dL_dexposure);
-    else hipLaunchKernelGGL(exposure_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, groups, 1u, dL_dexposure);
+    if (x.exposure_batched) hipLaunchKernelGGL(exposure_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, tiles, gi.groups / tiles, dL_dexposure);
+    else hipLaunchKernelGGL(exposure_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, st, workspace, gi.groups, 1u, dL_dexposure);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) { *err = e; return 1; }
     return 2;
 }
 
 } // namespace stp
+

@@ -17,8 +17,8 @@ With --training two more cases, the full loss of upstream's step (per-image expo
 to dL/dimage, dL/dexposure and dL/dinvdepth), alternating like the others:
   around_fused     today's way: the torch lines (permute / matmul, clamp, mask, the depth L1) around photometric_loss
   training_loss    training_loss: the same in the fused kernels
-With --ab-lib PATH one more pair: photometric_loss alone on the default library and on the library at PATH, alternating (has the plain
-call moved?)."""
+With --ab-lib PATH two more pairs: photometric_loss alone, and training_loss with the extras above, each on the default library and on the
+library at PATH, alternating (has either pair of kernels moved?)."""
 import argparse
 import os
 import statistics
@@ -40,7 +40,7 @@ ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--variant", default="full")
 ap.add_argument("--training", action="store_true", help="also time the extended loss: torch lines around photometric_loss against training_loss")
-ap.add_argument("--ab-lib", default=None, help="also time photometric_loss alone on the default library and on this one, alternating")
+ap.add_argument("--ab-lib", default=None, help="also time photometric_loss and training_loss on the default library and on this one, alternating")
 ap.add_argument("--no-raster", action="store_true", help="do not build the workload's scene: synthetic images, no raster_step")
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -155,10 +155,11 @@ def workload(name):
     faster = all(f < t for f, t in zip(ms["fused_loss"], ms["torch_loss"]))
     print(f"  torch_loss / fused_loss = {med['torch_loss'] / med['fused_loss']:.2f} (per round: {', '.join('%.2f' % (t / f) for f, t in zip(ms['fused_loss'], ms['torch_loss']))}); "
           f"fused_loss faster in every round: {faster}")
+    extras = training_extras(image, gen) if args.training or args.ab_lib else None
     if args.training:
-        training_cases(name, image, target, gen)
+        training_cases(name, image, target, extras)
     if args.ab_lib:
-        library_cases(name, image, target)
+        library_cases(name, image, target, extras)
     return moved / (med["fused_loss"] * 1e-3) / 1e12
 
 
@@ -173,14 +174,25 @@ def report(name, cases, a, b):
           f"{b} faster in every round: {all(f < t for f, t in zip(ms[b], ms[a]))}")
 
 
-def training_cases(name, image, target, gen):
-    """the full loss of upstream's step: (a) torch ops around photometric_loss, (b) training_loss"""
+def training_extras(image, gen):
+    """the extras of upstream's full step on image's frame: (exposure, alpha_mask, invdepth, mono_invdepth, depth_mask); exposure and invdepth are leaves"""
     H, W = image.shape[-2:]
     exposure = (torch.eye(3, 4, device=dev) + 0.05 * torch.randn(3, 4, device=dev, generator=gen)).requires_grad_(True)
     alpha_mask = (torch.rand(1, H, W, device=dev, generator=gen) > 0.1).float()
     invdepth = torch.rand(1, H, W, device=dev, generator=gen).requires_grad_(True)
     mono = torch.rand(1, H, W, device=dev, generator=gen)
     depth_mask = (torch.rand(1, H, W, device=dev, generator=gen) > 0.2).float()
+    return exposure, alpha_mask, invdepth, mono, depth_mask
+
+
+def fused_training_loss(image, target, extras):
+    exposure, alpha_mask, invdepth, mono, depth_mask = extras
+    return dgr.training_loss(image, target, 0.2, 0.5, exposure=exposure, clamp=True, alpha_mask=alpha_mask, invdepth=invdepth, mono_invdepth=mono, depth_mask=depth_mask)
+
+
+def training_cases(name, image, target, extras):
+    """the full loss of upstream's step: (a) torch ops around photometric_loss, (b) training_loss"""
+    exposure, alpha_mask, invdepth, mono, depth_mask = extras
 
     def around():
         x = torch.matmul(image.permute(1, 2, 0), exposure[:3, :3]).permute(2, 0, 1) + exposure[:3, 3, None, None]
@@ -188,7 +200,7 @@ def training_cases(name, image, target, gen):
         return dgr.photometric_loss(x, target) + 0.5 * ((invdepth - mono) * depth_mask).abs().mean()
 
     def fused():
-        return dgr.training_loss(image, target, 0.2, 0.5, exposure=exposure, clamp=True, alpha_mask=alpha_mask, invdepth=invdepth, mono_invdepth=mono, depth_mask=depth_mask)
+        return fused_training_loss(image, target, extras)
 
     def step_of(loss_fn):
         def step():
@@ -205,21 +217,33 @@ def training_cases(name, image, target, gen):
     report(name, {"around_fused": step_of(around), "training_loss": step_of(fused)}, "around_fused", "training_loss")
 
 
-def library_cases(name, image, target):
-    """photometric_loss alone, the default library against args.ab_lib, alternating"""
-    def step():
+def library_cases(name, image, target, extras):
+    """photometric_loss alone and training_loss with every extra, the default library against args.ab_lib, alternating"""
+    exposure, _, invdepth, _, _ = extras
+
+    def plain():
         dgr.photometric_loss(image, target).backward()
         image.grad = None
 
-    ms = {"default_lib": [], "other_lib": []}
+    def training():
+        fused_training_loss(image, target, extras).backward()
+        image.grad = exposure.grad = invdepth.grad = None
+
+    steps = {"photometric_loss": plain, "training_loss": training}
+    ms = {(fn, lib): [] for fn in steps for lib in ("default_lib", "other_lib")}
     for _ in range(args.rounds):
-        for n, path in (("default_lib", None), ("other_lib", args.ab_lib)):
+        for lib, path in (("default_lib", None), ("other_lib", args.ab_lib)):
             _C.use_library(path)   # (the next call loads it)
-            ms[n].append(timed(step, args.steps))
+            for fn, step in steps.items():
+                ms[fn, lib].append(timed(step, args.steps))
     _C.use_library(None)
-    print(f"{name} photometric_loss alone, the default library against {args.ab_lib}:")
-    for n, v in ms.items():
-        print(f"  {n:13s} {statistics.median(v):.4f} [{min(v):.4f} .. {max(v):.4f}]  {args.steps} steps per round")
+    for fn in steps:
+        print(f"{name} {fn} alone, the default library against {args.ab_lib}:")
+        for lib in ("default_lib", "other_lib"):
+            v = ms[fn, lib]
+            print(f"  {lib:13s} {statistics.median(v):.4f} [{min(v):.4f} .. {max(v):.4f}]  {args.steps} steps per round")
+        other = ms[fn, "other_lib"]
+        print(f"  default_lib's median within or below other_lib's range: {statistics.median(ms[fn, 'default_lib']) <= max(other)}")
 
 
 print(f"stp_hbm_probe copy, 1 GiB, this box, this run: {(rate := copy_rate()):.2f} TB/s")
